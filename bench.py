@@ -3,7 +3,7 @@
 targets on (">= 70 % of the HBM roofline on the J-build kernel and >= 10x PySCF-CPU wall-clock on benzene/cc-pVTZ RHF") --
 on N MI355X, with the J/K digestion kernel's achieved bandwidth against the HBM roofline and a CPU baseline.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 A step is one SCF cycle exactly as `SCF.kernel` runs it (`SCF._step`): Fock = h + J - K/2 from the HBM-resident ERI tiles
@@ -176,6 +176,23 @@ def time_steps(mf, st, steps, warmup, barrier):
     return time.perf_counter() - t0
 
 
+def dump_outputs(out_dir, st):
+    """What the last timed step computed, float64 (benzene/cc-pVTZ: 2 x 0.56 MB): `fock` and `e_tot`, the AO Fock matrix and
+    total energy of the density the step consumed, and `dm`, the AO density the step produced.  In the pipelined loop that
+    density is the head of the next cycle (purified from this step's CDIIS-extrapolated Fock matrix; `st["front"]`, whose
+    graphed form also backs `st["dm"]`), otherwise the step's own purification; in a converged loop the two agree to rounding.
+    The orbital-gradient norm is left out: in the converged loop it is ~6e-14, i.e. it measures only the rounding of the
+    atomic J/K sums and differs by 10-20 % from run to run, while the density, Fock matrix and energy agree to rounding."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    front = st.get("front")
+    dm = front["dm"] if front is not None else st["dm"]
+    arrays = {"dm": dm.detach().cpu().numpy(), "fock": st["fock"].detach().cpu().numpy(),
+              "e_tot": np.array([st["e_tot"]])}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def pmc_traffic(label, alg_bytes, variant="J+K"):
     """HBM bytes per launch from the committed rocprofv3 PMC passes (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE, separate
     --pmc runs as the guide prescribes).  PMC needs the profiler, so this is NOT measured by this process: `traffic_source`
@@ -260,6 +277,10 @@ def main():
                     help="torch.distributed backend; 'gloo' only for rehearsing N>1 ranks on a 1-GPU box")
     ap.add_argument("--no-wall-clock", action="store_true", help="skip the cold-process wall-clock leg (N = 1 only)")
     ap.add_argument("--no-scale-leg", action="store_true", help="skip the ibuprofen RHF/def2-TZVP cycle leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the AO density it produced, the AO Fock matrix and total energy "
+                         "of the density it consumed) as "
+                         "DIR/<name>.npy in float64, for comparing two builds output for output")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -337,6 +358,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st)
 
     # roofline leg: the J/K digestion kernel alone, HIP events on the launch stream (this rank's share of the tiles)
     label = args.molecule + "/" + args.basis

@@ -1,48 +1,24 @@
 """The reference templates' import surface resolves against the drop-in packages (`pyscf`, `gpu4pyscf`, `cupy`, `rdkit`
-stand-ins) -- checked STATICALLY: the scripts under /root/reference/templates are parsed with `ast` (read as text, never
-imported or executed, nothing is written next to them), every `import` / `from ... import ...` and every dotted attribute
+stand-ins) -- checked STATICALLY: every `import` / `from ... import ...` of the template scripts and every dotted attribute
 chain rooted at an imported chemistry module (`gto.Mole`, `scf.hf.RHF`, `gpu4pyscf.dft.rks.RKS`, `Chem.AddHs`, ...) is
-collected and resolved against this repo's packages.  Runs here (CPU container, reference mounted); skipped on the GPU box
-where /root/reference does not exist.  The call sequences themselves are replayed on the GPU in
-tests/test_gpu_template_flow.py."""
-import ast
+resolved against this repo's packages.  The surface is stored in tests/golden/template_surface.json (names only, extracted
+from the scripts with `ast` by tests/golden/make_template_surface.py), so the check needs nothing outside the repository.
+The call sequences themselves are replayed on the GPU in tests/test_gpu_template_flow.py."""
 import importlib
+import json
 import os
 
 import numpy as np
 import pytest
 
-TEMPLATES = "/root/reference/templates"
-pytestmark = pytest.mark.skipif(not os.path.isdir(TEMPLATES), reason="reference not mounted")
-
-OURS = ("pyscf", "gpu4pyscf", "cupy", "rdkit")   # top-level packages this repo stands in for
+with open(os.path.join(os.path.dirname(__file__), "golden", "template_surface.json")) as _fh:
+    SURFACE = json.load(_fh)
 
 
 def _surface(name):
-    """-> (imports, chains): imports = [(module, symbol|None)], chains = dotted names rooted at an alias of one of OURS."""
-    with open(os.path.join(TEMPLATES, name + ".py"), "r", encoding="utf-8") as fh:
-        tree = ast.parse(fh.read())
-    imports, alias = [], {}
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Import):
-            for a in node.names:
-                if a.name.split(".")[0] in OURS:
-                    imports.append((a.name, None))
-                    alias[a.asname or a.name.split(".")[0]] = a.name if a.asname else a.name.split(".")[0]
-        elif isinstance(node, ast.ImportFrom) and node.module and node.module.split(".")[0] in OURS:
-            for a in node.names:
-                imports.append((node.module, a.name))
-                alias[a.asname or a.name] = node.module + "." + a.name
-    chains = set()
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Attribute):
-            parts, cur = [], node
-            while isinstance(cur, ast.Attribute):
-                parts.append(cur.attr)
-                cur = cur.value
-            if isinstance(cur, ast.Name) and cur.id in alias:
-                chains.add((alias[cur.id], tuple(reversed(parts))))
-    return imports, chains
+    """-> (imports, chains): imports = [(module, symbol|None)], chains = dotted names rooted at an alias of a stood-in package."""
+    s = SURFACE[name]
+    return [tuple(x) for x in s["imports"]], {(root, tuple(attrs)) for root, attrs in s["chains"]}
 
 
 def _resolve(dotted):
