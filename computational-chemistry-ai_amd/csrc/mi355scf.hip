@@ -5017,7 +5017,10 @@ __global__ __launch_bounds__(256) void xc_aow_kernel(const double *ao, const dou
 
 extern "C" int mi_xc_aow(mi_ctx *c, const double *d_ao, const double *d_wv, int64_t ng, int gga, double *d_aow, void *stream)
 {
-    if (!c || !d_ao || !d_wv || !d_aow) return fail("mi_xc_aow: null argument");
+    if (!c) return fail("mi_xc_aow: null context");
+    if (ng < 0) return fail("mi_xc_aow: negative number of grid points");
+    if (ng == 0) return 0;   // nothing to write (a zero-sized grid would be a launch error)
+    if (!d_ao || !d_wv || !d_aow) return fail("mi_xc_aow: null argument");
     dim3 grid((unsigned)((ng + 255) / 256), (unsigned)std::min(c->nao, 64));
     hipLaunchKernelGGL(xc_aow_kernel, grid, dim3(256), 0, (hipStream_t)stream, d_ao, d_wv, c->nao, ng, gga, d_aow);
     HIPCHK(hipGetLastError());
@@ -7461,7 +7464,10 @@ __global__ __launch_bounds__(256) void xc_vmat_kernel(const double *__restrict__
 
 extern "C" int mi_xc_vmat(mi_ctx *c, const double *d_ao0, const double *d_aow, int64_t ng, double *d_vmat, void *stream)
 {
-    if (!c || !d_ao0 || !d_aow || !d_vmat) return fail("mi_xc_vmat: null argument");
+    if (!c) return fail("mi_xc_vmat: null context");
+    if (ng < 0) return fail("mi_xc_vmat: negative number of grid points");
+    if (ng == 0) return 0;   // C += A W^T over no points; the split arithmetic below would divide by a zero chunk
+    if (!d_ao0 || !d_aow || !d_vmat) return fail("mi_xc_vmat: null argument");
     const int nt = (c->nao + VM_T - 1) / VM_T;
     // Split over the grid points: nt^2 x nsplit workgroups, two of which fit a CU (68 KB of LDS each), i.e. 512 run at a time.
     // Round 1 rounded nsplit UP to reach 1024 -- 1025 workgroups for benzene/cc-pVTZ, 1053 for ibuprofen/def2-TZVP: a third,
@@ -7621,7 +7627,10 @@ static int launch_vmat_fold(mi_ctx *c, const double *d_ao, const double *d_wv, i
 // (as mi_xc_aow takes them), gga = 0: LDA (component 0 only).  d_vmat += ao_0 . (sum_c wv_c ao_c)^T, unsymmetrised.
 extern "C" int mi_xc_vmat_fold(mi_ctx *c, const double *d_ao, const double *d_wv, int64_t ng, int gga, double *d_vmat, void *stream)
 {
-    if (!c || !d_ao || !d_wv || !d_vmat) return fail("mi_xc_vmat_fold: null argument");
+    if (!c) return fail("mi_xc_vmat_fold: null context");
+    if (ng < 0) return fail("mi_xc_vmat_fold: negative number of grid points");
+    if (ng == 0) return 0;   // as mi_xc_vmat: no points, no launch
+    if (!d_ao || !d_wv || !d_vmat) return fail("mi_xc_vmat_fold: null argument");
     hipStream_t st = (hipStream_t)stream;
     const int nt = (c->nao + 63) / 64;                 // 64-row tiles of the matrix
     const int cap = std::max(1, std::min(5, c->opt_vmat_fold_mt));

@@ -280,7 +280,7 @@ int mi_xc_eval(const int32_t *kinds, const double *coefs, int nterms, const doub
 int mi_xc_eval_spin(const int32_t *kinds, const double *coefs, int nterms, const double *d_rhoa, const double *d_rhob,
                     const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wva, double *d_wvb, void *stream);
 
-/* d_aow[nao][ng] = sum_c d_ao[c] * d_wv[c]; Vxc = ao0 @ aow^T + transpose is then one DGEMM. */
+/* d_aow[nao][ng] = sum_c d_ao[c] * d_wv[c]; Vxc = ao0 @ aow^T + transpose is then one DGEMM.  ng == 0: no-op. */
 int mi_xc_aow(mi_ctx *ctx, const double *d_ao, const double *d_wv, int64_t ng, int gga, double *d_aow,
               void *stream);
 
@@ -317,7 +317,8 @@ int mi_xc_eval_mgga_spin(const int32_t *kinds, const double *coefs, int nterms, 
                          double *d_wvb, void *stream);
 
 /* d_vmat[nao][nao] += ao0 . aow^T over the grid block (split-K FP64 MFMA kernel; rocBLAS has no split-K for
- * this tiny-M,N / huge-K shape and runs it at < 1 TFLOP/s).  The caller symmetrises (Vxc = vmat + vmat^T). */
+ * this tiny-M,N / huge-K shape and runs it at < 1 TFLOP/s).  The caller symmetrises (Vxc = vmat + vmat^T).  ng == 0 (here and
+ * in mi_xc_vmat_fold): d_vmat is left untouched; ng < 0 is an error. */
 int mi_xc_vmat(mi_ctx *ctx, const double *d_ao0, const double *d_aow, int64_t ng, double *d_vmat, void *stream);
 /* Round 3: the same accumulation with the weighted AOs formed on the fly from the AO values and the weights x potential that
  * mi_xc_aow would take (d_ao [1|4][nao][ng], d_wv [1|4][ng], gga = 0: LDA): d_vmat += ao_0 . (sum_c wv_c ao_c)^T.  Replaces the
