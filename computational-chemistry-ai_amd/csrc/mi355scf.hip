@@ -393,6 +393,8 @@ struct mi_ctx {
     // J/K work buffers
     double *d_Dpad = nullptr, *d_Jacc = nullptr, *d_Kacc = nullptr;
     int ldp = 0;
+    // mi_build_jk_multi: padded densities and accumulators of one batch (JKM_BATCH of each), allocated on first use
+    double *d_mDpad = nullptr, *d_mJacc = nullptr, *d_mKacc = nullptr;
     double *d_red = nullptr;
     mi_eri_stats stats{};
     int64_t mem_need_bytes = 0, mem_free_bytes = 0; // of the last mi_eri_prepare (also when it returned MI_ERR_NOMEM)
@@ -405,6 +407,7 @@ struct mi_ctx {
     int opt_xf_mfma_min = 300; // transform kernel: MFMA tiles only when the spherical block has at least this many elements
     double opt_tpq_maxprim = 32.0; // thread-per-quartet kernels only when the mean primitive quartets per shell quartet stay below this
     int opt_eri_tpq = 1;     // thread-per-quartet fused ERI kernels for the low angular classes (0: wave-per-quartet pair everywhere)
+    int opt_jk_multi_batch = 8;  // mi_build_jk_multi: densities per launch (1..JKM_BATCH); 8 measured faster per density than 16
     int opt_jk_pair = -1;    // n_dm = 2: one pass with two waves per work item (-1: for stores > 16 GB, 0: one pass per density, 1: always)
     int opt_tri_tiles = 1;   // block-diagonal tiles store triangular rows (0: the full-row layout of round 1); next mi_eri_prepare
     int tri = 1;             // layout of the current store
@@ -717,7 +720,8 @@ extern "C" void mi_ctx_destroy(mi_ctx *c)
     hipSetDevice(c->device);
     free_eri(c);
     void *ptrs[] = {c->d_env, c->d_bas, c->d_atm, c->d_shell_ao, c->d_c2s, c->d_rys_cheb, c->d_herm_r, c->d_herm_w,
-                    c->d_Dpad, c->d_Jacc, c->d_Kacc, c->d_red, c->d_shell_xyz, c->d_sp2_bar, c->d_xt_scratch, c->d_perm, c->d_iperm};
+                    c->d_Dpad, c->d_Jacc, c->d_Kacc, c->d_red, c->d_shell_xyz, c->d_sp2_bar, c->d_xt_scratch, c->d_perm, c->d_iperm,
+                    c->d_mDpad, c->d_mJacc, c->d_mKacc};
     for (void *p : ptrs) if (p) dev_free(p);
     // the large host vectors of the context (pair records and gradient matrices, tile directory: several hundred MB for
     // ibuprofen/def2-TZVP) are handed to the next context on this device instead of being unmapped here (~40 ms) and faulted
@@ -751,6 +755,7 @@ extern "C" int mi_set_option(mi_ctx *c, const char *key, double value)
     else if (k == "grad_rows_g32") g_rows_g32 = (int)value;
     else if (k == "jk_cache_mb") c->opt_jk_cache_mb = (int)value;
     else if (k == "jk_pair") c->opt_jk_pair = (int)value;
+    else if (k == "jk_multi_batch") c->opt_jk_multi_batch = (int)value;
     else if (k == "sp2_persist") c->opt_sp2_persist = (int)value;
     else if (k == "vmat_wgs") c->opt_vmat_wgs = (int)value;
     else if (k == "vmat_xcd") c->opt_vmat_xcd = (int)value;
@@ -3662,6 +3667,272 @@ extern "C" int mi_build_jk(mi_ctx *c, const double *d_D, int n_dm, double *d_J, 
         if (launch_jk(c, d_J != nullptr, d_K != nullptr, st)) return -1;
         hipLaunchKernelGGL(finalize_jk_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, c->d_Jacc, c->d_Kacc,
                            d_J ? d_J + m * nn : nullptr, d_K ? d_K + m * nn : nullptr, c->nao, c->ldp, c->d_perm);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+// =================================================================================================
+// Batched J/K: n densities per pass over the resident tiles (mi_build_jk_multi; linear response, many trial densities).
+//
+// A workgroup of two waves digests one work item.  Each tile is read from HBM once, expanded to a full 8x8x8x8 block in LDS
+// (triangular rows and ragged edges zero-filled), and contracted against every density of the batch: wave w owns densities
+// w, w+2, ...  The six contractions are the three index pairings of the tile read as a 64x64 matrix, each used directly and
+// transposed; lane (a, b) produces one output element per pairing and density (a 64-term dot product with the density block,
+// whose rows are wave-uniform scalar loads).  Per-tile outputs (J_IJ, K_IK, K_IL) are added with one FP64 atomic per lane and
+// density; the run-wide ones (J_KL, K_JL, K_JK) stay in NPW registers each until the run ends.
+//
+// LDS image: element (i,j,k,l) at JKM_SI*i + JKM_SJ*j + JKM_SK*k + l (4292 doubles).  The strides are purely additive, so every
+// read of a pairing is the lane's base plus an immediate offset; with the lane orientations used below the 32 lanes of a
+// ds_read_b64 half hit at most two addresses per bank (three pairings conflict-free, three 2-way).
+//
+// Accumulated contributions.  A stored value x = w (ij|kl) adds x D_jl to K_ik, x D_jk to K_il, x D_ik to K_jl and x D_il to K_jk:
+// the four index permutations that keep the bra on the left.  The other four permutations of the quartet, (kl|ij) and its
+// swaps, are exactly these four with both sides of the density and of K transposed, so for any D
+//   K[D] = Kacc[D] + (Kacc[D^T])^T,
+// which is Kacc + Kacc^T for a symmetric and Kacc - Kacc^T for an antisymmetric density.  The set of four is invariant under
+// i <-> j and under k <-> l, so the tiles' halved block diagonals (only i >= j stored on I == J, k >= l on K == L, doubled
+// weight) give the same Kacc as the full tiles for any density.  J of an antisymmetric density is zero and is not produced.
+// =================================================================================================
+constexpr int JKM_BATCH = 16;                  // densities per launch: 2 waves x 8
+constexpr int JKM_SI = 537, JKM_SJ = 67, JKM_SK = 8;
+constexpr int JKM_LDS = 7 * JKM_SI + 7 * JKM_SJ + 7 * JKM_SK + 8;
+
+struct JkmArgs {
+    const double *tiles;
+    const int64_t *tile_off;
+    const int *tile_I;
+    const RunRec *runs;
+    const int *wave_seg;
+    const double *D;           // [n][ld][ld] padded densities in tile order
+    double *Jacc, *Kacc;       // [n][ld][ld]
+    size_t pp;                 // ld * ld
+    int ld, nao, n, jmask;     // jmask bit m: density m is symmetric (J wanted)
+    int withk;                 // 0: J only (pure functionals)
+    int n_cached, tri;
+};
+
+// acc[q] += sum_{c,d} T[base + sc*c + sd*d] * Dq[c*ld + d]  (Dq: the 8x8 density block of density slot q, wave-uniform)
+template <int NPW>
+__device__ __forceinline__ void jkm_contract(const double *__restrict__ Tl, const int base, const int sc, const int sd,
+                                             const MI_CONST_AS double *const (&Dq)[NPW], const int ld, double (&acc)[NPW])
+{
+#pragma unroll 2
+    for (int c = 0; c < 8; c++) {
+        double x[8];
+#pragma unroll
+        for (int d = 0; d < 8; d++) x[d] = Tl[base + sc * c + sd * d];
+#pragma unroll
+        for (int q = 0; q < NPW; q++) {
+            const MI_CONST_AS double *row = Dq[q] + (size_t)c * ld;
+#pragma unroll
+            for (int d = 0; d < 8; d++) acc[q] = fma(x[d], row[d], acc[q]);
+        }
+    }
+}
+
+template <bool NT, int NPW>
+__device__ __forceinline__ void jkm_load_tile(const JkmArgs &A, double *__restrict__ Tl, const int64_t toff, const int bi, const int bk,
+                                              const bool dij, const bool dkl)
+{
+    const d2_t *__restrict__ T = reinterpret_cast<const d2_t *>(A.tiles + toff);
+    // 2048 chunks {T[i,j,k,2m], T[i,j,k,2m+1]} in the store's order (row (j, m), then lanes (i, k)): 16 per thread
+    d2_t v[16];
+#pragma unroll
+    for (int s = 0; s < 16; s++) {
+        const int c2 = threadIdx.x + 128 * s;
+        const int j = c2 >> 8, m = (c2 >> 6) & 3, i = (c2 >> 3) & 7, k = c2 & 7;
+        const int ch = (i < bi && k < bk) ? tile_chunk(dij, dkl, bi, bk, i, j, k, m) : -1;
+        d2_t x = {0.0, 0.0};
+        if (ch >= 0) x = NT ? __builtin_nontemporal_load(T + ch) : T[ch];
+        v[s] = x;
+    }
+#pragma unroll
+    for (int s = 0; s < 16; s++) {
+        const int c2 = threadIdx.x + 128 * s;
+        const int j = c2 >> 8, m = (c2 >> 6) & 3, i = (c2 >> 3) & 7, k = c2 & 7;
+        const int a = JKM_SI * i + JKM_SJ * j + JKM_SK * k + 2 * m;
+        Tl[a] = v[s].x;
+        Tl[a + 1] = v[s].y;
+    }
+}
+
+template <bool NT, int NPW>
+__device__ __forceinline__ void jkm_segment(const JkmArgs &A, double *__restrict__ Tl, const int seg)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int a = lane >> 3, b = lane & 7;
+    const MI_CONST_AS RunRec *rr = as_const(A.runs) + seg;
+    const RunRec R{rr->J, rr->K, rr->L, rr->first, rr->count};
+    const int J0 = R.J * BLK, K0 = R.K * BLK, L0 = R.L * BLK;
+    const int ld = A.ld;
+    const int bk = min(BLK, A.nao - K0);
+    const bool dkl = A.tri && R.K == R.L;
+    // density slots of this wave: m = 2q + wave; slots beyond n repeat density 0 and add nothing
+    int mq[NPW];
+    bool live[NPW], wantj[NPW];
+    bool anyj = false;
+#pragma unroll
+    for (int q = 0; q < NPW; q++) {
+        const int m = 2 * q + wave;
+        live[q] = m < A.n;
+        mq[q] = live[q] ? m : 0;
+        wantj[q] = live[q] && ((A.jmask >> m) & 1);
+        anyj |= wantj[q];
+    }
+    const MI_CONST_AS double *Dc = as_const(A.D);
+    double jkl[NPW], kjl[NPW], kjk[NPW];
+#pragma unroll
+    for (int q = 0; q < NPW; q++) { jkl[q] = 0.0; kjl[q] = 0.0; kjk[q] = 0.0; }
+    const MI_CONST_AS int *tile_I = as_const(A.tile_I);
+    const MI_CONST_AS int64_t *tile_off = as_const(A.tile_off);
+    for (int t = 0; t < R.count; t++) {
+        const int I = tile_I[R.first + t];
+        const int64_t toff = tile_off[R.first + t];
+        const int I0 = I * BLK;
+        const int bi = min(BLK, A.nao - I0);
+        __syncthreads();   // the previous tile's image is no longer read
+        jkm_load_tile<NT, NPW>(A, Tl, toff, bi, bk, A.tri && I == R.J, dkl);
+        __syncthreads();
+        const MI_CONST_AS double *Dq[NPW];
+        double acc[NPW];
+        // J_IJ (lanes i = a, j = b) and J_KL (run-wide; lanes k = a, l = b)
+        if (anyj) {
+#pragma unroll
+            for (int q = 0; q < NPW; q++) { Dq[q] = Dc + mq[q] * A.pp + (size_t)K0 * ld + L0; acc[q] = 0.0; }
+            jkm_contract<NPW>(Tl, JKM_SI * a + JKM_SJ * b, JKM_SK, 1, Dq, ld, acc);
+#pragma unroll
+            for (int q = 0; q < NPW; q++)
+                if (wantj[q]) atomicAdd(&A.Jacc[mq[q] * A.pp + (size_t)(I0 + a) * ld + J0 + b], acc[q]);
+#pragma unroll
+            for (int q = 0; q < NPW; q++) Dq[q] = Dc + mq[q] * A.pp + (size_t)I0 * ld + J0;
+            jkm_contract<NPW>(Tl, JKM_SK * a + b, JKM_SI, JKM_SJ, Dq, ld, jkl);
+        }
+        if (!A.withk) continue;
+        // K_IK (lanes k = a, i = b): sum over j, l of T D_JL
+#pragma unroll
+        for (int q = 0; q < NPW; q++) { Dq[q] = Dc + mq[q] * A.pp + (size_t)J0 * ld + L0; acc[q] = 0.0; }
+        jkm_contract<NPW>(Tl, JKM_SK * a + JKM_SI * b, JKM_SJ, 1, Dq, ld, acc);
+#pragma unroll
+        for (int q = 0; q < NPW; q++)
+            if (live[q]) atomicAdd(&A.Kacc[mq[q] * A.pp + (size_t)(I0 + b) * ld + K0 + a], acc[q]);
+        // K_IL (lanes i = a, l = b): sum over j, k of T D_JK
+#pragma unroll
+        for (int q = 0; q < NPW; q++) { Dq[q] = Dc + mq[q] * A.pp + (size_t)J0 * ld + K0; acc[q] = 0.0; }
+        jkm_contract<NPW>(Tl, JKM_SI * a + b, JKM_SJ, JKM_SK, Dq, ld, acc);
+#pragma unroll
+        for (int q = 0; q < NPW; q++)
+            if (live[q]) atomicAdd(&A.Kacc[mq[q] * A.pp + (size_t)(I0 + a) * ld + L0 + b], acc[q]);
+        // K_JL (run-wide; lanes l = a, j = b): sum over i, k of T D_IK
+#pragma unroll
+        for (int q = 0; q < NPW; q++) Dq[q] = Dc + mq[q] * A.pp + (size_t)I0 * ld + K0;
+        jkm_contract<NPW>(Tl, a + JKM_SJ * b, JKM_SI, JKM_SK, Dq, ld, kjl);
+        // K_JK (run-wide; lanes k = a, j = b): sum over i, l of T D_IL
+#pragma unroll
+        for (int q = 0; q < NPW; q++) Dq[q] = Dc + mq[q] * A.pp + (size_t)I0 * ld + L0;
+        jkm_contract<NPW>(Tl, JKM_SK * a + JKM_SJ * b, JKM_SI, 1, Dq, ld, kjk);
+    }
+#pragma unroll
+    for (int q = 0; q < NPW; q++) {
+        if (!live[q]) continue;
+        const size_t o = mq[q] * A.pp;
+        if (wantj[q]) atomicAdd(&A.Jacc[o + (size_t)(K0 + a) * ld + L0 + b], jkl[q]);
+        if (!A.withk) continue;
+        atomicAdd(&A.Kacc[o + (size_t)(J0 + b) * ld + L0 + a], kjl[q]);
+        atomicAdd(&A.Kacc[o + (size_t)(J0 + b) * ld + K0 + a], kjk[q]);
+    }
+}
+
+template <bool NT, int NPW>
+__global__ __launch_bounds__(128) void jk_multi_kernel(JkmArgs A)
+{
+    __shared__ double Tl[JKM_LDS];
+    const MI_CONST_AS int *wave_seg = as_const(A.wave_seg);
+    const int seg_end = wave_seg[blockIdx.x + 1];
+    for (int seg = wave_seg[blockIdx.x]; seg < seg_end; seg++) {
+        if (NT && seg < A.n_cached) jkm_segment<false, NPW>(A, Tl, seg);
+        else jkm_segment<NT, NPW>(A, Tl, seg);
+    }
+}
+
+// n densities -> zero-padded [ld][ld] copies in tile order, their accumulators cleared
+__global__ void pad_density_multi_kernel(const double *D, double *Dp, double *Jacc, double *Kacc, int n, int nao, int ld,
+                                         const int *__restrict__ iperm)
+{
+    const size_t pp = (size_t)ld * ld;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= pp * n) return;
+    const int m = (int)(idx / pp);
+    const int64_t e = (int64_t)(idx - (size_t)m * pp);
+    const int r = (int)(e / ld), c = (int)(e - (int64_t)r * ld);
+    Dp[idx] = (r < nao && c < nao) ? D[(size_t)m * nao * nao + (size_t)iperm[r] * nao + iperm[c]] : 0.0;
+    Jacc[idx] = 0.0;
+    Kacc[idx] = 0.0;
+}
+
+struct JkmSigns { int s[JKM_BATCH]; };
+// K = Kacc + s Kacc^T; J = 2 (Jacc + Jacc^T) for s = +1 and 0 for s = -1 (caller's AO order; either output may be NULL)
+__global__ void finalize_jk_multi_kernel(const double *Jacc, const double *Kacc, double *J, double *K, int n, int nao, int ld,
+                                         const int *__restrict__ perm, JkmSigns sg)
+{
+    const size_t nn = (size_t)nao * nao, pp = (size_t)ld * ld;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nn * n) return;
+    const int m = (int)(idx / nn);
+    const int64_t e = (int64_t)(idx - (size_t)m * nn);
+    const int r = perm[e / nao], c = perm[e % nao];
+    const size_t o = (size_t)m * pp;
+    const double s = (double)sg.s[m];
+    if (K) K[idx] = Kacc[o + (size_t)r * ld + c] + s * Kacc[o + (size_t)c * ld + r];
+    if (J) J[idx] = sg.s[m] > 0 ? 2.0 * (Jacc[o + (size_t)r * ld + c] + Jacc[o + (size_t)c * ld + r]) : 0.0;
+}
+
+extern "C" int mi_build_jk_multi(mi_ctx *c, const double *d_D, int n_dm, const int *sym, double *d_J, double *d_K, void *stream)
+{
+    if (!c || !d_D || !sym || (!d_J && !d_K) || n_dm < 0) return fail("mi_build_jk_multi: null argument");
+    if (!c->eri_ready) return fail("mi_build_jk_multi: call mi_eri_prepare first");
+    for (int m = 0; m < n_dm; m++)
+        if (sym[m] != 1 && sym[m] != -1) return fail("mi_build_jk_multi: sym[m] must be +1 or -1");
+    if (n_dm == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nn = (size_t)c->nao * c->nao, pp = (size_t)c->ldp * c->ldp;
+    if (!c->d_mDpad) {
+        HIPCHK(dev_malloc(&c->d_mDpad, sizeof(double) * JKM_BATCH * pp));
+        HIPCHK(dev_malloc(&c->d_mJacc, sizeof(double) * JKM_BATCH * pp));
+        HIPCHK(dev_malloc(&c->d_mKacc, sizeof(double) * JKM_BATCH * pp));
+    }
+    const int batch = std::max(1, std::min(JKM_BATCH, c->opt_jk_multi_batch));
+    const bool nt = c->opt_jk_nt != 0 && (c->opt_jk_nt > 1 || c->tile_doubles * 8 > ((int64_t)256 << 20));
+    for (int m0 = 0; m0 < n_dm; m0 += batch) {
+        const int n = std::min(batch, n_dm - m0);
+        JkmSigns sg{};
+        int jmask = 0;
+        for (int m = 0; m < n; m++) { sg.s[m] = sym[m0 + m]; if (sg.s[m] > 0) jmask |= 1 << m; }
+        if (!d_K && !jmask) {   // J only, and every density antisymmetric: J is zero
+            HIPCHK(hipMemsetAsync(d_J + m0 * nn, 0, sizeof(double) * nn * n, st));
+            continue;
+        }
+        hipLaunchKernelGGL(pad_density_multi_kernel, dim3((unsigned)((pp * n + 255) / 256)), dim3(256), 0, st, d_D + m0 * nn, c->d_mDpad,
+                           c->d_mJacc, c->d_mKacc, n, c->nao, c->ldp, c->d_iperm);
+        HIPCHK(hipGetLastError());
+        if (c->n_tiles > 0) {
+            JkmArgs A{c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg, c->d_mDpad, c->d_mJacc, c->d_mKacc, pp,
+                      c->ldp, c->nao, n, d_J ? jmask : 0, d_K ? 1 : 0, c->n_jk_cached, c->tri};
+            dim3 g(c->n_jk_waves), b(128);
+            const int npw = (n + 1) / 2;
+#define JKM_LAUNCH(P) do { if (nt) hipLaunchKernelGGL((jk_multi_kernel<true, P>), g, b, 0, st, A); \
+                           else hipLaunchKernelGGL((jk_multi_kernel<false, P>), g, b, 0, st, A); } while (0)
+            if (npw <= 1) JKM_LAUNCH(1);
+            else if (npw <= 2) JKM_LAUNCH(2);
+            else if (npw <= 4) JKM_LAUNCH(4);
+            else JKM_LAUNCH(8);
+#undef JKM_LAUNCH
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(finalize_jk_multi_kernel, dim3((unsigned)((nn * n + 255) / 256)), dim3(256), 0, st, c->d_mJacc, c->d_mKacc,
+                           d_J ? d_J + m0 * nn : nullptr, d_K ? d_K + m0 * nn : nullptr, n, c->nao, c->ldp, c->d_perm, sg);
         HIPCHK(hipGetLastError());
     }
     return 0;

@@ -67,6 +67,7 @@ def lib():
         L.mi_eri_prepare.argtypes = [vp, ctypes.c_double, ctypes.c_int, ctypes.c_int, vp]
         L.mi_eri_get_stats.argtypes = [vp, ctypes.POINTER(_Stats)]
         L.mi_build_jk.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
+        L.mi_build_jk_multi.argtypes = [vp, vp, ctypes.c_int, ip, vp, vp, vp]
         L.mi_eri_unpack.argtypes = [vp, vp, vp]
         L.mi_time_jk_kernel.argtypes = [vp, vp, ctypes.c_int, dp, vp]
         L.mi_time_jk_variant.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, vp]
@@ -290,6 +291,30 @@ class Engine:
         if squeeze:
             J = J[0] if with_j else None
             K = K[0] if with_k else None
+        return J, K
+
+    def get_jk_multi(self, dms, sym, with_j=True, with_k=True):
+        """J, K of a stack [n, N, N] of densities that are each symmetric (sym[m] = +1) or antisymmetric (-1), every resident
+        tile read once per launch of up to `jk_multi_batch` densities (mi_build_jk_multi; default 8, at most 16).  J of an
+        antisymmetric member is zero.  J / K is None when `with_j` / `with_k` is False (J only skips the exchange
+        contractions).  Sharded engines return this rank's partial sums."""
+        if not self.eri_ready:
+            self.prepare_eri()
+        dms = torch.as_tensor(dms, dtype=torch.float64, device=self.device).contiguous()
+        assert dms.dim() == 3 and dms.shape[1] == dms.shape[2] == self.nao
+        n = dms.shape[0]
+        sym = [int(s) for s in sym]
+        assert len(sym) == n and all(s in (1, -1) for s in sym), "sym: +1 or -1 per density"
+        assert with_j or with_k
+        J = torch.empty_like(dms) if with_j else None
+        K = torch.empty_like(dms) if with_k else None
+        if n == 0:
+            return J, K
+        s = (ctypes.c_int32 * n)(*sym)
+        with torch.cuda.device(self.device):
+            _check(lib().mi_build_jk_multi(self._h, dms.data_ptr(), n, s, J.data_ptr() if with_j else None,
+                                           K.data_ptr() if with_k else None,
+                                           self._stream()))
         return J, K
 
     def df_build(self, aux_engine, int3c, int2c):

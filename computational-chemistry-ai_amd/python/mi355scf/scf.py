@@ -466,8 +466,53 @@ class SCF:
         if dm is None:
             dm = self.make_rdm1()
         self._setup_once()   # integrals + resident ERI tiles (or the direct-mode fallback when the store does not fit)
-        J, K = self._jk(dm, with_j, with_k)
+        if hermi == 0:
+            J, K = self._jk_general(dm, with_j, with_k)
+        else:
+            J, K = self._jk(dm, with_j, with_k)
         return (J.cpu().numpy() if with_j else None), (K.cpu().numpy() if with_k else None)
+
+    def _jk_general(self, dm, with_j=True, with_k=True):
+        """J, K of one [N,N] or a stack [n,N,N] of densities without symmetry (hermi=0): each is split into its symmetric and
+        antisymmetric parts, whose J/K come from one batched pass over the resident tiles (J of the antisymmetric part is zero)."""
+        d = torch.as_tensor(np.asarray(dm) if not torch.is_tensor(dm) else dm, dtype=torch.float64, device=self.engine.device)
+        df = getattr(self, "with_df", None)
+        if df is not None:
+            # fitted integrals: the symmetric part through the SCF's fitted build (its K routes assume D = D^T), the
+            # antisymmetric part's K = (B D_a) B^T as two dense GEMMs on this rank's slice of B (J of it is zero)
+            ds = 0.5 * (d + d.transpose(-1, -2))
+            J, K = self._jk(ds, with_j, with_k)
+            if with_k:
+                da = 0.5 * (d - d.transpose(-1, -2))
+                B = df._B
+                n, na, _ = B.shape
+                Bf = B.reshape(n, na * n)
+                das = da.unsqueeze(0) if da.dim() == 2 else da
+                Ka = torch.stack([torch.matmul(B.reshape(n * na, n), a).reshape(n, na * n) @ Bf.T for a in das])
+                if self._nranks > 1:
+                    from . import parallel
+                    parallel.all_reduce_sum(Ka, self._pg)
+                K = K + (Ka[0] if da.dim() == 2 else Ka)
+            return J, K
+        if self._stream_groups > 1:
+            if torch.equal(d, d.transpose(-1, -2)):
+                return self._jk(d, with_j, with_k)   # symmetric after all: the direct-mode build is exact
+            raise NotImplementedError("J/K of non-symmetric densities in direct mode (the ERI store does not fit)")
+        squeeze = d.dim() == 2
+        if squeeze:
+            d = d.unsqueeze(0)
+        n = d.shape[0]
+        parts = torch.cat([0.5 * (d + d.transpose(1, 2)), 0.5 * (d - d.transpose(1, 2))])
+        Jp, Kp = self.engine.get_jk_multi(parts, [1] * n + [-1] * n, with_j=with_j)
+        if self._nranks > 1:
+            from . import parallel
+            parallel.all_reduce_fused([x for x in (Jp, Kp) if x is not None], self._pg)
+        J = Jp[:n] if with_j else None
+        K = Kp[:n] + Kp[n:]
+        if squeeze:
+            J = J[0] if with_j else None
+            K = K[0]
+        return J, (K if with_k else None)
 
     def _veff(self, dm):
         """Returns (vhf, e_two_electron) on device.  RHF: vhf = J - K/2, E2 = 1/2 tr(D vhf)."""
@@ -1228,6 +1273,17 @@ class SCF:
     def nuc_grad_method(self):
         from . import grad
         return grad.Gradients(self)
+
+    # --- linear response (tdscf.py) ---
+    def TDA(self):
+        from . import tdscf
+        return tdscf.TDA(self)
+
+    def TDHF(self):
+        from . import tdscf
+        return tdscf.TDHF(self)
+
+    TDDFT = TDHF
 
     Gradients = nuc_grad_method
 

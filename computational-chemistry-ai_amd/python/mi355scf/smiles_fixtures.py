@@ -89,6 +89,26 @@ def _benzene(rcc=1.3915, rch=1.0800):
     return b.result()
 
 
+def _benzoquinone(rco=1.222, rc1c2=1.477, rcc=1.337, rch=1.087, ring=117.8):
+    """p-benzoquinone, D2h in the xy plane with C=O along x (UV template's documented example)."""
+    half = math.radians(ring / 2.0)
+    x2, y2 = rcc / 2.0, rc1c2 * math.sin(half)
+    x1 = x2 + rc1c2 * math.cos(half)
+    # C-H along the exterior bisector at C2 (unit vectors towards C1 and C3 summed, reversed)
+    u = (math.cos(half) - 1.0, -math.sin(half))
+    n = math.hypot(*u)
+    hx, hy = x2 - rch * u[0] / n, y2 - rch * u[1] / n
+    b = _Builder()
+    for sx in (1.0, -1.0):
+        b.add("C", (sx * x1, 0.0, 0.0))
+        b.add("O", (sx * (x1 + rco), 0.0, 0.0))
+    for sx, sy in ((1, 1), (-1, 1), (-1, -1), (1, -1)):
+        b.add("C", (sx * x2, sy * y2, 0.0))
+    for sx, sy in ((1, 1), (-1, 1), (-1, -1), (1, -1)):
+        b.add("H", (sx * hx, sy * hy, 0.0))
+    return b.result()
+
+
 def _ibuprofen():
     """CC(C)Cc1ccc(cc1)C(C)C(=O)O  -> C13H18O2, 33 atoms."""
     b = _Builder()
@@ -144,6 +164,7 @@ TABLE = {
     "CCO": _ethanol, "OCC": _ethanol,
     "CC(=O)O": _acetic_acid, "CC(O)=O": _acetic_acid,
     "c1ccccc1": _benzene, "C1=CC=CC=C1": _benzene,
+    "O=C1C=CC(=O)C=C1": _benzoquinone, "C1=CC(=O)C=CC1=O": _benzoquinone,
     "CC(C)Cc1ccc(cc1)C(C)C(=O)O": _ibuprofen, "CC(C)CC1=CC=C(C=C1)C(C)C(=O)O": _ibuprofen,
     "C60": _c60, _C60_SMILES: _c60,
 }

@@ -1,0 +1,1 @@
+from mi355scf.tdscf import TDA, TDDFT  # noqa: F401

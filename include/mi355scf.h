@@ -147,6 +147,13 @@ int mi_eri_get_stats(const mi_ctx *ctx, mi_eri_stats *out);
  * RYS_build_jk [MEM], reached from get_jk / get_veff inside mf.kernel(). */
 int mi_build_jk(mi_ctx *ctx, const double *d_D, int n_dm, double *d_J, double *d_K, void *stream);
 
+/* J and K of n_dm densities that are each symmetric or antisymmetric, with every resident tile read once per batch
+ * (linear response: many trial densities against one store).  sym: host array [n_dm], sym[m] = +1 (symmetric: J and K) or
+ * -1 (antisymmetric: K; J[m] is written as zero, J of an antisymmetric density vanishes).  d_D, d_J, d_K: [n_dm][nao][nao]
+ * device arrays; either d_J or d_K may be NULL (J only: the exchange contractions are skipped).  Requests beyond the per-launch batch (option "jk_multi_batch": default 8, at most 16)
+ * run as several launches.  Sharded contexts return this rank's partial sums, as mi_build_jk does. */
+int mi_build_jk_multi(mi_ctx *ctx, const double *d_D, int n_dm, const int *sym, double *d_J, double *d_K, void *stream);
+
 /* Dense [nao^4] copy of the resident ERIs (chemists' notation (ij|kl), all eight symmetry images) for post-SCF methods on
  * small molecules: `mp.MP2(mf).kernel()` in templates/calculate_interaction.py:116-120.  Unsharded contexts only. */
 int mi_eri_unpack(mi_ctx *ctx, double *d_out, void *stream);
