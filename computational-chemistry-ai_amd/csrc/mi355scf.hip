@@ -443,6 +443,8 @@ struct mi_ctx {
     int opt_vmat_wgs = 0;    // xc_vmat: workgroups aimed at by the split over the grid points (0: 1024 = two per CU; -1: round-1 formula)
     int opt_sp2_persist = 0; // planned purification as ONE resident launch with grid barriers (1: release/acquire fences, 2: write-through
                              // stores + L2-bypassing loads) -- measured SLOWER than one launch per pass (0), see sp2_plan_persist_kernel
+    int opt_sp2_direct = 0;  // planned purification, one launch per pass: 1 = sp2_direct_kernel (MFMA operands loaded straight into
+                             // registers, N <= 320), 0 = sp2_plan_kernel (row panels staged in LDS)
     unsigned *d_sp2_bar = nullptr; // [0] arrival counter (monotonic), [1] abort tag
     double *d_xt_scratch = nullptr; // xc_tail_kernel: per-workgroup partials + ticket
     unsigned sp2_bar_base = 0, sp2_tag = 0;
@@ -757,6 +759,7 @@ extern "C" int mi_set_option(mi_ctx *c, const char *key, double value)
     else if (k == "jk_pair") c->opt_jk_pair = (int)value;
     else if (k == "jk_multi_batch") c->opt_jk_multi_batch = (int)value;
     else if (k == "sp2_persist") c->opt_sp2_persist = (int)value;
+    else if (k == "sp2_direct") c->opt_sp2_direct = (int)value;
     else if (k == "vmat_wgs") c->opt_vmat_wgs = (int)value;
     else if (k == "vmat_xcd") c->opt_vmat_xcd = (int)value;
     else if (k == "tri_tiles") c->opt_tri_tiles = (int)value;       // takes effect at the next mi_eri_prepare
@@ -7295,6 +7298,88 @@ __global__ __launch_bounds__(256) void sp2_plan_kernel(const double *__restrict_
     sp2_plan_pass<MAXM, false>(Xin, n, kpad, b_in, c_in, Xout, trc, nx, bI, bJ, lds);
 }
 
+// The same planned pass with the MFMA operands loaded straight into registers (option sp2_direct, N <= 16 MAXS).
+// X_k is symmetric, so row i of X_k is also its column i: the A operand of v_mfma_f64_16x16x4f64 (lane l: row i0 + l % 16,
+// k = 4 s + l / 16 of step s) is read as X_k[k][i0 + l % 16], and each load instruction of a wave covers four whole 128-byte
+// row segments -- the coalescing of the LDS-staged panel loads without the staging, its barrier and the dependent LDS reads in
+// front of every MFMA.  Each wave keeps the K-quarter of sp2_plan_kernel (k = wave kq + 4 s + l / 16) on two interleaved
+// accumulators; LDS holds only the 4-way K reduction, and the epilogue is spread over the four waves (wave w: rows 4w..4w+3
+// of the tile, the C/D rows of the q = w register).  The element and mirror of X_k that the next-pass polynomial needs are
+// loaded with the operands.  Summation order fixed per build, no atomics: the traces repeat bit for bit from run to run.
+// Pass 0 of a Fock matrix that is symmetric only to rounding reads its columns where sp2_plan_kernel read its rows.
+template <int MAXS>
+__global__ __launch_bounds__(256) void sp2_direct_kernel(const double *__restrict__ Xin, int n, int S, double b_in, double c_in,
+                                                         double *__restrict__ Xout, double *__restrict__ trc, Sp2Coef nx)
+{
+    __shared__ double red[4 * 256];
+    __shared__ double trs[4][2];
+    int bI, bJ;
+    sp2_tile_of_block((int)blockIdx.x, bI, bJ);
+    const bool diag = bI == bJ;
+    const int i0 = bI * 16, j0 = bJ * 16;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
+    const int ia = i0 + col, jb = j0 + col;
+    const int kw = wave * 4 * S + g;            // k of step s: kw + 4 s
+    // epilogue element (gi, gj) of this lane and the input elements the polynomial reads, issued with the operand loads
+    const int gi = i0 + g + 4 * wave, gj = j0 + col;
+    const bool own = gi < n && gj < n;
+    const int ci = min(gi, n - 1), cj = min(gj, n - 1);
+    const double xt = Xin[(size_t)ci * n + cj], xm = Xin[(size_t)cj * n + ci];
+    // unconditional loads from clamped (in-bounds) addresses, out-of-range values dropped below: no branch around every load
+    const int ca = min(ia, n - 1), cb = min(jb, n - 1);
+    double a[MAXS], b[MAXS];
+#pragma unroll
+    for (int s = 0; s < MAXS; s++) {
+        const size_t row = (size_t)min(kw + 4 * s, n - 1) * n;
+        a[s] = Xin[row + ca];
+        b[s] = Xin[row + cb];
+    }
+    // pass 0: X_0 = b_in F + c_in I on the real elements; the zero padding stays zero
+#pragma unroll
+    for (int s = 0; s < MAXS; s++) {
+        const int k = kw + 4 * s;
+        const bool in = s < S && k < n;
+        a[s] = (in && ia < n) ? fma(b_in, a[s], k == ia ? c_in : 0.0) : 0.0;
+        b[s] = diag ? a[s] : ((in && jb < n) ? fma(b_in, b[s], k == jb ? c_in : 0.0) : 0.0);
+    }
+    d4_t acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < MAXS; s += 2) {
+        if (s < S) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[s], acc0, 0, 0, 0);
+        if (s + 1 < MAXS && s + 1 < S) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s + 1], b[s + 1], acc1, 0, 0, 0);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) red[wave * 256 + q * 64 + lane] = acc0[q] + acc1[q];
+    __syncthreads();
+    const int e = wave * 64 + lane;             // C/D register q = wave: row g + 4 wave, column col
+    const double v = (red[e] + red[256 + e]) + (red[512 + e] + red[768 + e]);
+    double tr1 = 0.0, tr2 = 0.0;
+    if (own) {
+        const double xc = fma(b_in, xt, gi == gj ? c_in : 0.0);
+        Xout[(size_t)gi * n + gj] = fma(nx.a, v, fma(nx.b, xc, gi == gj ? nx.c : 0.0));
+        if (!diag) Xout[(size_t)gj * n + gi] = fma(nx.a, v, nx.b * fma(b_in, xm, 0.0));
+        if (gi == gj) { tr1 = xc; tr2 = v; }
+    }
+    if (diag) {   // uniform over the workgroup
+        for (int o = 32; o > 0; o >>= 1) { tr1 += __shfl_xor(tr1, o); tr2 += __shfl_xor(tr2, o); }
+        if (lane == 0) { trs[wave][0] = tr1; trs[wave][1] = tr2; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            trc[2 * bI] = (trs[0][0] + trs[1][0]) + (trs[2][0] + trs[3][0]);
+            trc[2 * bI + 1] = (trs[0][1] + trs[1][1]) + (trs[2][1] + trs[3][1]);
+        }
+    }
+}
+#define SP2_DIRECT_MAXS 20   /* N <= 320 */
+typedef void (*sp2_direct_fn)(const double *, int, int, double, double, double *, double *, Sp2Coef);
+static sp2_direct_fn sp2_direct_for(int S)
+{
+    if (S <= 8) return sp2_direct_kernel<8>;
+    if (S <= 12) return sp2_direct_kernel<12>;
+    if (S <= 16) return sp2_direct_kernel<16>;
+    return sp2_direct_kernel<SP2_DIRECT_MAXS>;
+}
+
 // The whole planned sequence in ONE launch (option sp2_persist, OFF by default): the grid of nb(nb+1)/2 <= #CU workgroups stays
 // resident and the passes are separated by a grid barrier on a counter in device memory instead of a kernel boundary.  Same
 // per-pass code (sp2_plan_pass), hence bit-identical matrices and traces (tests/test_gpu_sp2_persist.py).
@@ -7515,6 +7600,19 @@ extern "C" int mi_sp2_iterate_planned(mi_ctx *c, const double *d_F, double *d_A,
             *d_res = (nit % 2 == 0) ? d_A : d_B;   // pass k writes A for even k, B for odd k
             return 0;
         }
+    }
+    if (c->opt_sp2_direct && kpad / 16 <= SP2_DIRECT_MAXS) {
+        const int S = kpad / 16;   // MFMA steps per wave (K-quarter kpad / 4)
+        const sp2_direct_fn dk = sp2_direct_for(S);
+        hipLaunchKernelGGL(dk, grid, block, 0, st, d_F, n, S, coef[1], coef[2], cur, d_tr, next_coef(0));
+        for (int it = 1; it <= nit; it++) {
+            hipLaunchKernelGGL(dk, grid, block, 0, st, cur, n, S, 1.0, 0.0, nxt, d_tr + TS * it, next_coef(it));
+            std::swap(cur, nxt);
+        }
+        HIPCHK(hipGetLastError());
+        *d_tr_out = d_tr + TS * nit;
+        *d_res = cur;
+        return 0;
     }
     hipLaunchKernelGGL(kern, grid, block, shm, st, d_F, n, kpad, coef[1], coef[2], cur, d_tr, next_coef(0));
     for (int it = 1; it <= nit; it++) {

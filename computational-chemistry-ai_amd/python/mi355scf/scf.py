@@ -9,6 +9,7 @@ returning a Python float, `converged` reporting non-convergence (never an except
 All N x N algebra runs on the GPU: J/K from the resident-ERI HIP kernels, DIIS through the HIP
 helpers, `eigh`/GEMM through torch (hipSOLVER / rocBLAS).  There is no CPU path.
 """
+import os
 import sys
 import time
 
@@ -685,12 +686,19 @@ class SCF:
         if ws is None or ws["n"] != n:
             mk = lambda *s: torch.empty(*s, dtype=torch.float64, device=fo.device)
             ws = self._sp2p = dict(n=n, scal=mk(self._HEAD_MAX + 64 * 80), pp=(mk(2, n, n), mk(2, n, n)))
+        want = int(bool(self.sp2_direct))
+        if getattr(eng, "_sp2_direct", None) != want:
+            eng.set_option("sp2_direct", want)
+            eng._sp2_direct = want
         coef = self._sp2_plan[:self._sp2_plan_len + 1]
         tr = ws["scal"][self._HEAD_MAX:]
         res, off = eng.sp2_iterate_planned(fo.contiguous(), ws["pp"][0], ws["pp"][1], coef, tr, out_scale=scale)
         self._sp2_hist_shape = (coef.shape[0], (n + 15) // 16)
         return res[0], tr[:off + 64]   # a view of the ping-pong buffers: consumed by this cycle's Fock build, before the next pass
 
+    # planned passes with the MFMA operands loaded straight into registers (engine option sp2_direct, N <= 320); MI355_SP2_DIRECT=0
+    # selects the LDS-staged sp2_plan_kernel instead, so that the two can be compared on one box
+    sp2_direct = os.environ.get("MI355_SP2_DIRECT", "1") != "0"
     sp2_plan_gnorm = 2e-3      # make the purification plan only once the previous cycle's |g| is below this
     # A diagonalisation made only to obtain the plan's bounds (7 ms at N = 264, 40 ms at 573) is never earned back inside one
     # SCF: the planned path saves 0.3 ms per cycle at N = 264 (0.5 ms at 573).  So by default a cold object runs the
