@@ -64,3 +64,33 @@ def jk(j3, j2, dm):
     J = np.einsum("pij,p->ij", B, rho)
     K = np.einsum("pij,jl,pkl->ik", B, dm, B)
     return J, K
+
+
+def grad(mol, auxmol, z3=None, z2=None):
+    """d/dR [natm, 3] of sum_{ab,P} Z3[a, b, P] (ab|P) + sum_{PQ} Z2[P, Q] (P|Q) (what mi_df_grad adds) with Z3 symmetric in ab
+    and Z2 symmetric, from the oracle's derivative integrals `orc_eri_ip1_shell` on the combined shell list.  The unit function
+    has exponent 0, so its derivative vanishes; the auxiliary centre's derivative is minus the sum of the others (translational
+    invariance of each integral).  Symmetry of Z3 / Z2 gives the second orbital / auxiliary centre as twice the first."""
+    cm = _Combined(mol, auxmol)
+    o = orc.Oracle(cm)
+    lo = mol.ao_loc_nr()
+    la = auxmol.ao_loc_nr()
+    ob, u = cm.nbas_orb, cm.nbas_orb + cm.nbas_aux
+    atom = cm._bas[:, 0] % mol.natm      # the auxiliary shells sit on copies of the atoms (indices natm..2 natm-1)
+    g = np.zeros((mol.natm, 3))
+    if z3 is not None:
+        for i in range(mol.nbas):
+            for j in range(mol.nbas):
+                for p in range(auxmol.nbas):
+                    blk = o.eri_ip1_shell(i, j, ob + p, u)[..., 0]
+                    v = 2.0 * np.einsum("xabp,abp->x", blk, z3[lo[i]:lo[i + 1], lo[j]:lo[j + 1], la[p]:la[p + 1]])
+                    g[atom[i]] += v
+                    g[atom[ob + p]] -= v
+    if z2 is not None:
+        for p in range(auxmol.nbas):
+            for q in range(auxmol.nbas):
+                blk = o.eri_ip1_shell(ob + p, u, ob + q, u)[:, :, 0, :, 0]
+                v = np.einsum("xpq,pq->x", blk, z2[la[p]:la[p + 1], la[q]:la[q + 1]])
+                g[atom[ob + p]] += v
+                g[atom[ob + q]] -= v
+    return g

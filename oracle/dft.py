@@ -14,6 +14,8 @@ B3LYP = 0.2 HF + 0.08 Slater + 0.72 B88 + 0.19 VWN-RPA + 0.81 LYP (libxc HYB_GGA
 """
 import ctypes
 
+import math
+
 import numpy as np
 
 from . import oracle as orc
@@ -116,11 +118,13 @@ def _c2s(l):
 
 
 def eval_ao(mol, coords, deriv=1):
-    """ao[4 or 1][ng][nao]: values and d/dx, d/dy, d/dz of the real-spherical contracted AOs."""
+    """ao[1, 4 or 10][ng][nao]: values, d/dx, d/dy, d/dz (deriv >= 1) and the second derivatives xx, xy, xz, yy, yz, zz
+    (deriv = 2) of the real-spherical contracted AOs -- the component order of mi_eval_ao."""
     ng = len(coords)
     nao = mol.nao
-    out = np.zeros((4 if deriv else 1, ng, nao))
+    out = np.zeros(({0: 1, 1: 4, 2: 10}[int(deriv)], ng, nao))
     loc = mol.ao_loc_nr()
+    pairs = [(i, j) for i in range(3) for j in range(i, 3)]
     for ish in range(mol.nbas):
         ia, l, npr, _, _, pe, pc, _ = mol._bas[ish]
         exps, cs = mol._env[pe:pe + npr], mol._env[pc:pc + npr]
@@ -128,29 +132,36 @@ def eval_ao(mol, coords, deriv=1):
         r2 = (d * d).sum(axis=1)
         e = np.exp(-np.outer(r2, exps))
         rad = e @ cs
-        drad = e @ (-2.0 * exps * cs)
+        drad = e @ (-2.0 * exps * cs)          # (1/r) dR/dr: d_i R = drad x_i
+        d2rad = e @ (4.0 * exps * exps * cs)   # d_i d_j R = d2rad x_i x_j + delta_ij drad
         c2s = _c2s(l)
-        x, y, z = d.T
-        k = 0
-        poly = np.zeros((ng, c2s.shape[0]))
-        dpoly = np.zeros((3, ng, c2s.shape[0]))
-        for lx in range(l, -1, -1):
-            for ly in range(l - lx, -1, -1):
-                lz = l - lx - ly
-                poly[:, k] = x ** lx * y ** ly * z ** lz
-                if lx:
-                    dpoly[0, :, k] = lx * x ** (lx - 1) * y ** ly * z ** lz
-                if ly:
-                    dpoly[1, :, k] = ly * x ** lx * y ** (ly - 1) * z ** lz
-                if lz:
-                    dpoly[2, :, k] = lz * x ** lx * y ** ly * z ** (lz - 1)
-                k += 1
-        s = poly @ c2s
+        pw = [(lx, ly, l - lx - ly) for lx in range(l, -1, -1) for ly in range(l - lx, -1, -1)]
+
+        def mono(k):       # d^k (x^lx y^ly z^lz) for the multi-index k = (kx, ky, kz), every cartesian component
+            cols = np.zeros((ng, len(pw)))
+            for c, p in enumerate(pw):
+                f = np.ones(ng)
+                for q in range(3):
+                    if k[q] > p[q]:
+                        f = None
+                        break
+                    f = f * math.perm(p[q], k[q]) * d[:, q] ** (p[q] - k[q])
+                if f is not None:
+                    cols[:, c] = f
+            return cols @ c2s
+        s = mono((0, 0, 0))
         sl = slice(loc[ish], loc[ish + 1])
         out[0][:, sl] = rad[:, None] * s
-        if deriv:
+        if deriv >= 1:
+            s1 = [mono(tuple(int(q == c) for q in range(3))) for c in range(3)]
             for c in range(3):
-                out[1 + c][:, sl] = (drad * d[:, c])[:, None] * s + rad[:, None] * (dpoly[c] @ c2s)
+                out[1 + c][:, sl] = (drad * d[:, c])[:, None] * s + rad[:, None] * s1[c]
+        if deriv >= 2:
+            for m, (i, j) in enumerate(pairs):
+                s2 = mono(tuple(int(q == i) + int(q == j) for q in range(3)))
+                rij = d2rad * d[:, i] * d[:, j] + (drad if i == j else 0.0)
+                out[4 + m][:, sl] = (rij[:, None] * s + (drad * d[:, i])[:, None] * s1[j] + (drad * d[:, j])[:, None] * s1[i]
+                                     + rad[:, None] * s2)
     return out
 
 

@@ -23,6 +23,8 @@
  *   orc_eri_full     -> mol.intor('int2e')                                       (test helper)
  *   orc_incore_*     -> mol.intor('int2e', aosym='s8') cached by the SCF object, and
  *   orc_jk_incore    -> libcvhf CVHFnrs8_incore_drv (PySCF's in-core J/K)        (rows a5, a6)
+ *   orc_eri_ip1_shell, orc_grad_eri -> libcint int2e_ip1 + the J/K gradient contraction  (row a15)
+ *   orc_int1e_ip     -> libcint int1e_ipovlp / int1e_ipkin / int1e_ipnuc per nucleus  (row a15)
  *
  * Basis arrays follow the libcint atm/bas/env convention (include/mi355scf.h); nctr must be 1.
  */
@@ -47,9 +49,10 @@
 
 #define LMAX 4            /* g (auxiliary density-fitting shells; orbital tables stop at f) */
 #define LMAX1 (LMAX + 1)
-#define NCART_MAX 15
+/* Internal tables reach l = LMAX + 1: a derivative integral raises the differentiated shell by one (orc_eri_ip1_shell). */
+#define NCART_MAX 21
 #define NSPH_MAX 9
-#define TMAX (4 * LMAX + 1) /* Hermite order range for an ERI: 0..16 */
+#define TMAX (4 * LMAX + 2) /* Hermite order range for a derivative ERI: 0..17 */
 
 static const double PI = 3.14159265358979323846;
 
@@ -144,8 +147,8 @@ void orc_boys(int mmax, double T, double *F)
 /* ---------- Hermite expansion coefficients ----------------------------------------------------- */
 
 /* E[i][j][t], 0<=i<=imax, 0<=j<=jmax, 0<=t<=i+j; includes exp(-mu X^2) in E[0][0][0]. */
-#define EI (LMAX + 3)      /* room for l+2 (kinetic) */
-#define ET (2 * LMAX + 5)
+#define EI (LMAX + 4)      /* room for (l+1)+2 (kinetic of a differentiated shell) */
+#define ET (2 * LMAX + 8)
 typedef double etab_t[EI][EI][ET];
 
 static void hermite_E(int imax, int jmax, double a, double b, double XAB, etab_t E)
@@ -408,7 +411,7 @@ static void eri_cart(const pair_t *ab, const pair_t *cd, double *out)
     cart_powers(la, pa); cart_powers(lb, pb); cart_powers(lc, pc); cart_powers(ld, pd);
     memset(out, 0, sizeof(double) * nab * ncdn);
     int H = Lab + 1;
-    static __thread double G[(2 * LMAX + 1) * (2 * LMAX + 1) * (2 * LMAX + 1)];
+    static __thread double G[(2 * LMAX + 2) * (2 * LMAX + 2) * (2 * LMAX + 2)];
     rtab_t R;
     int tab = la + lb + 1, tcd = lc + ld + 1;
     for (int n1 = 0; n1 < ab->npp; n1++) {
@@ -915,6 +918,295 @@ void orc_jk_shellblock(const int *atm, int natm, const int *bas, int nbas, const
     free(loc);
 }
 
+/* ---------- derivative integrals (nuclear gradients) -------------------------------------------- */
+/* For a primitive cartesian Gaussian x^lx y^ly z^lz exp(-a r^2) about A:  d/dA_x = 2a (l + 1_x) - lx (l - 1_x).  A contracted
+ * shell's derivative is therefore a shell of l+1 with coefficients 2a c and a shell of l-1 with coefficients c; the existing
+ * cartesian integrals of those two shells are combined component by component and then transformed with the c2s of l. */
+
+/* position of the cartesian component (lx, ly, lz) in cart_powers order (lx is implied by l) */
+static int cart_index(int ly, int lz)
+{
+    int m = ly + lz;
+    return m * (m + 1) / 2 + lz;
+}
+
+typedef struct {
+    shell_t up, dn; /* l+1 with coefficients 2a c; l-1 with c (meaningless for l = 0) */
+    double *cup;
+} dshell_t;
+
+static void deriv_shells(const shell_t *A, dshell_t *d)
+{
+    d->cup = (double *)malloc(sizeof(double) * A->nprim);
+    for (int p = 0; p < A->nprim; p++) d->cup[p] = 2.0 * A->exps[p] * A->coef[p];
+    d->up = *A; d->up.l = A->l + 1; d->up.coef = d->cup;
+    d->dn = *A; d->dn.l = A->l - 1;
+}
+
+/* out[x][nc(la)][rest] = plus[a + 1_x][rest] - a_x minus[a - 1_x][rest]  (plus: [nc(la+1)][rest], minus: [nc(la-1)][rest]) */
+static void deriv_combine(int la, size_t rest, const double *plus, const double *minus, double *out)
+{
+    int pw[NCART_MAX][3];
+    cart_powers(la, pw);
+    int nca = ncart_of(la);
+    for (int x = 0; x < 3; x++)
+        for (int a = 0; a < nca; a++) {
+            int p[3] = {pw[a][0], pw[a][1], pw[a][2]};
+            double *o = out + ((size_t)x * nca + a) * rest;
+            p[x]++;
+            const double *src = plus + (size_t)cart_index(p[1], p[2]) * rest;
+            for (size_t r = 0; r < rest; r++) o[r] = src[r];
+            if (pw[a][x] > 0) {
+                p[x] -= 2;
+                const double *sm = minus + (size_t)cart_index(p[1], p[2]) * rest;
+                const double f = pw[a][x];
+                for (size_t r = 0; r < rest; r++) o[r] -= f * sm[r];
+            }
+        }
+}
+
+/* d/dA (ab|cd), derivative on the first shell (angular momentum la): out[3][nsa][nsb][nsc][nsd].
+ * abp / abm: pairs of the raised / lowered first shell with b (abm unused for la = 0).  work: 4 * QBUF doubles. */
+static void eri_ip1_pairs(int la, const pair_t *abp, const pair_t *abm, const pair_t *cd, double *out, double *work)
+{
+    int lb = abp->lb, lc = cd->la, ld = cd->lb;
+    size_t rest = (size_t)ncart_of(lb) * ncart_of(lc) * ncart_of(ld), nca = ncart_of(la);
+    size_t nsph = (size_t)(2 * la + 1) * (2 * lb + 1) * (2 * lc + 1) * (2 * ld + 1);
+    double *cp = work, *cm = work + QBUF, *dc = work + 2 * QBUF, *tmp = work + 3 * QBUF;
+    eri_cart(abp, cd, cp);
+    if (la > 0) eri_cart(abm, cd, cm);
+    deriv_combine(la, rest, cp, cm, dc);
+    for (int x = 0; x < 3; x++) c2s_quartet(la, lb, lc, ld, dc + x * nca * rest, out + x * nsph, tmp);
+}
+
+/* d/dA_i (ij|kl) spherical block, A_i the centre of shell i: out[3][di][dj][dk][dl] (libcint int2e_ip1 up to its sign
+ * convention: this is the derivative with respect to the nuclear coordinate) */
+void orc_eri_ip1_shell(const int *atm, int natm, const int *bas, int nbas, const double *env,
+                       int i, int j, int k, int l, double *out)
+{
+    shell_t A = get_shell(atm, bas, env, i), B = get_shell(atm, bas, env, j);
+    shell_t C = get_shell(atm, bas, env, k), D = get_shell(atm, bas, env, l);
+    dshell_t dA;
+    deriv_shells(&A, &dA);
+    pair_t abp, abm, cd;
+    build_pair(&dA.up, &B, &abp);
+    if (A.l > 0) build_pair(&dA.dn, &B, &abm);
+    build_pair(&C, &D, &cd);
+    double *work = (double *)malloc(sizeof(double) * QBUF * 4);
+    eri_ip1_pairs(A.l, &abp, A.l > 0 ? &abm : NULL, &cd, out, work);
+    free(work);
+    free_pair(&abp); if (A.l > 0) free_pair(&abm); free_pair(&cd);
+    free(dA.cup);
+}
+
+/* weight of (IJ|KL) in E2 summed over ALL ordered AO quartets: 1/2 D_IJ D_KL - hyb/8 (D_IK D_JL + D_IL D_JK + M_IK M_JL + M_IL M_JK);
+ * symmetric under the 8 index permutations of the integral for symmetric D, M */
+static double gamma_eri(const double *D, const double *M, double hyb, size_t n, size_t I, size_t J, size_t K, size_t L)
+{
+    double x = D[I * n + K] * D[J * n + L] + D[I * n + L] * D[J * n + K];
+    if (M) x += M[I * n + K] * M[J * n + L] + M[I * n + L] * M[J * n + K];
+    return 0.5 * D[I * n + J] * D[K * n + L] - 0.125 * hyb * x;
+}
+
+/* grad[natm][3] = dE2/dR of E2 = 1/2 sum (ij|kl) D_ij D_kl - hyb/4 sum (ij|kl) (D_ik D_jl + M_ik M_jl) (the energy of
+ * mi_grad_eri_spin; M may be NULL), over ALL unique shell quartets without screening.  grad_small (may be NULL) receives the
+ * part of the quartets with q_ij q_kl < qtol (Schwarz factors of orc_schwarz): what a Schwarz threshold qtol drops.
+ * Each unique bra pair accumulates into its own row, the rows are summed in a fixed order: the result does not depend on the
+ * number of threads or the schedule. */
+void orc_grad_eri(const int *atm, int natm, const int *bas, int nbas, const double *env, const double *D, const double *M,
+                  double hyb, double qtol, double *grad, double *grad_small)
+{
+    int nao = orc_nao(bas, nbas);
+    int *loc = (int *)malloc(sizeof(int) * (nbas + 1));
+    ao_offsets(bas, nbas, loc);
+    double *q = NULL;
+    if (grad_small) {
+        q = (double *)malloc(sizeof(double) * nbas * nbas);
+        orc_schwarz(atm, natm, bas, nbas, env, q);
+    }
+    /* every ordered shell pair: plain, and with its first shell raised / lowered */
+    size_t nsq = (size_t)nbas * nbas;
+    pair_t *pp = (pair_t *)calloc(3 * nsq, sizeof(pair_t)), *pplus = pp + nsq, *pminus = pp + 2 * nsq;
+    dshell_t *ds = (dshell_t *)malloc(sizeof(dshell_t) * nbas);
+    for (int i = 0; i < nbas; i++) {
+        shell_t A = get_shell(atm, bas, env, i);
+        deriv_shells(&A, ds + i);
+    }
+#pragma omp parallel for schedule(dynamic)
+    for (int i = 0; i < nbas; i++)
+        for (int j = 0; j < nbas; j++) {
+            shell_t A = get_shell(atm, bas, env, i), B = get_shell(atm, bas, env, j);
+            build_pair(&A, &B, pp + (size_t)i * nbas + j);
+            build_pair(&ds[i].up, &B, pplus + (size_t)i * nbas + j);
+            if (A.l > 0) build_pair(&ds[i].dn, &B, pminus + (size_t)i * nbas + j);
+        }
+    int npair = nbas * (nbas + 1) / 2, n3 = natm * 3;
+    double *rows = (double *)calloc((size_t)npair * 2 * n3, sizeof(double));
+#pragma omp parallel
+    {
+        double *work = (double *)malloc(sizeof(double) * QBUF * 4);
+        double *blk = (double *)malloc(sizeof(double) * 3 * NSPH_MAX * NSPH_MAX * NSPH_MAX * NSPH_MAX);
+#pragma omp for schedule(dynamic, 1)
+        for (int ij = npair - 1; ij >= 0; ij--) {
+            int i = (int)((sqrt(8.0 * ij + 1) - 1) / 2);
+            while ((i + 1) * (i + 2) / 2 <= ij) i++;
+            while (i * (i + 1) / 2 > ij) i--;
+            int j = ij - i * (i + 1) / 2;
+            for (int kl = 0; kl <= ij; kl++) {
+                int k = (int)((sqrt(8.0 * kl + 1) - 1) / 2);
+                while ((k + 1) * (k + 2) / 2 <= kl) k++;
+                while (k * (k + 1) / 2 > kl) k--;
+                int l = kl - k * (k + 1) / 2;
+                int sh[4] = {i, j, k, l}, at[4];
+                for (int c = 0; c < 4; c++) at[c] = bas[sh[c] * BAS_SLOTS + ATOM_OF];
+                if (at[0] == at[3] && at[1] == at[3] && at[2] == at[3]) continue;
+                double deg = (i != j ? 2.0 : 1.0) * (k != l ? 2.0 : 1.0) * (ij != kl ? 2.0 : 1.0);
+                double *row = rows + ((size_t)ij * 2 + ((q && q[i * nbas + j] * q[k * nbas + l] < qtol) ? 1 : 0)) * n3;
+                /* centres i, j, k by their own derivative integrals (shell c first), centre l by translational invariance */
+                static const int ord[3][4] = {{0, 1, 2, 3}, {1, 0, 2, 3}, {2, 3, 0, 1}};
+                for (int c = 0; c < 3; c++) {
+                    if (at[c] == at[3]) continue;
+                    int s1 = sh[ord[c][0]], s2 = sh[ord[c][1]], s3 = sh[ord[c][2]], s4 = sh[ord[c][3]];
+                    int l1 = bas[s1 * BAS_SLOTS + ANG_OF];
+                    eri_ip1_pairs(l1, pplus + (size_t)s1 * nbas + s2, pminus + (size_t)s1 * nbas + s2, pp + (size_t)s3 * nbas + s4, blk, work);
+                    int d1 = 2 * l1 + 1, d2 = loc[s2 + 1] - loc[s2], d3 = loc[s3 + 1] - loc[s3], d4 = loc[s4 + 1] - loc[s4];
+                    size_t nsph = (size_t)d1 * d2 * d3 * d4;
+                    double g[3] = {0, 0, 0};
+                    for (int a = 0; a < d1; a++)
+                        for (int b = 0; b < d2; b++)
+                            for (int e = 0; e < d3; e++)
+                                for (int f = 0; f < d4; f++) {
+                                    size_t o = ((size_t)(a * d2 + b) * d3 + e) * d4 + f;
+                                    double w = gamma_eri(D, M, hyb, nao, loc[s1] + a, loc[s2] + b, loc[s3] + e, loc[s4] + f);
+                                    g[0] += blk[o] * w; g[1] += blk[nsph + o] * w; g[2] += blk[2 * nsph + o] * w;
+                                }
+                    for (int x = 0; x < 3; x++) {
+                        row[at[c] * 3 + x] += deg * g[x];
+                        row[at[3] * 3 + x] -= deg * g[x];
+                    }
+                }
+            }
+        }
+        free(blk); free(work);
+    }
+    for (int n = 0; n < n3; n++) {
+        grad[n] = 0.0;
+        if (grad_small) grad_small[n] = 0.0;
+    }
+    for (int ij = 0; ij < npair; ij++)
+        for (int n = 0; n < n3; n++) {
+            double full = rows[(size_t)ij * 2 * n3 + n], small = rows[((size_t)ij * 2 + 1) * n3 + n];
+            grad[n] += full + small;
+            if (grad_small) grad_small[n] += small;
+        }
+    free(rows);
+    for (size_t n = 0; n < nsq; n++) {
+        free_pair(pp + n); free_pair(pplus + n);
+        if (pminus[n].p) free_pair(pminus + n);
+    }
+    free(pp);
+    for (int i = 0; i < nbas; i++) free(ds[i].cup);
+    free(ds); free(q); free(loc);
+}
+
+/* cartesian <a|b>, <a|-1/2 nabla^2|b> and, per nucleus C, <a|-Z_C/|r-C||b> (0 for charge 0): cs, ct [nca*ncb], cv [natm][nca*ncb] */
+static void int1e_cart(const shell_t *A, const shell_t *B, const int *atm, int natm, const double *env, double *cs, double *ct,
+                       double *cv)
+{
+    int la = A->l, lb = B->l, nca = ncart_of(la), ncb = ncart_of(lb), nab = nca * ncb;
+    int pa[NCART_MAX][3], pb[NCART_MAX][3];
+    cart_powers(la, pa); cart_powers(lb, pb);
+    memset(cs, 0, sizeof(double) * nab); memset(ct, 0, sizeof(double) * nab); memset(cv, 0, sizeof(double) * nab * natm);
+    etab_t Ex, Ey, Ez;
+    rtab_t R;
+    etab_t *E[3] = {&Ex, &Ey, &Ez};
+    for (int ip = 0; ip < A->nprim; ip++)
+        for (int jp = 0; jp < B->nprim; jp++) {
+            double a = A->exps[ip], b = B->exps[jp], p = a + b, cc = A->coef[ip] * B->coef[jp];
+            double P[3];
+            for (int d = 0; d < 3; d++) P[d] = (a * A->r[d] + b * B->r[d]) / p;
+            for (int d = 0; d < 3; d++) hermite_E(la, lb + 2, a, b, A->r[d] - B->r[d], *E[d]);
+            double pref = pow(PI / p, 1.5) * cc;
+            for (int ia = 0; ia < nca; ia++)
+                for (int ib = 0; ib < ncb; ib++) {
+                    double s1[3], t1[3];
+                    for (int d = 0; d < 3; d++) {
+                        int i = pa[ia][d], j = pb[ib][d];
+                        double sij = (*E[d])[i][j][0];
+                        double tij = -2.0 * b * (2 * j + 1) * sij + 4.0 * b * b * (*E[d])[i][j + 2][0];
+                        if (j >= 2) tij += j * (j - 1) * (*E[d])[i][j - 2][0];
+                        s1[d] = sij; t1[d] = -0.5 * tij;
+                    }
+                    cs[ia * ncb + ib] += pref * s1[0] * s1[1] * s1[2];
+                    ct[ia * ncb + ib] += pref * (t1[0] * s1[1] * s1[2] + s1[0] * t1[1] * s1[2] + s1[0] * s1[1] * t1[2]);
+                }
+            for (int ic = 0; ic < natm; ic++) {
+                double Z = atm[ic * ATM_SLOTS + CHARGE_OF];
+                if (Z == 0) continue;
+                const double *C = env + atm[ic * ATM_SLOTS + PTR_COORD];
+                double PC[3] = {P[0] - C[0], P[1] - C[1], P[2] - C[2]};
+                hermite_R(la + lb, p, PC, R);
+                double pv = -Z * 2.0 * PI / p * cc;
+                for (int ia = 0; ia < nca; ia++)
+                    for (int ib = 0; ib < ncb; ib++) {
+                        double s = 0;
+                        for (int t = 0; t <= pa[ia][0] + pb[ib][0]; t++)
+                            for (int u = 0; u <= pa[ia][1] + pb[ib][1]; u++)
+                                for (int v = 0; v <= pa[ia][2] + pb[ib][2]; v++)
+                                    s += Ex[pa[ia][0]][pb[ib][0]][t] * Ey[pa[ia][1]][pb[ib][1]][u] * Ez[pa[ia][2]][pb[ib][2]][v] * R[t][u][v];
+                        cv[(size_t)ic * nab + ia * ncb + ib] += pv * s;
+                    }
+            }
+        }
+}
+
+/* Bra-centre derivatives of the one-electron integrals, d/dA_x of the bra function mu (A its centre):
+ *   dS[3][nao][nao] = <d mu|nu>,  dT[3][nao][nao] = <d mu|-1/2 nabla^2|nu>,  dV[natm][3][nao][nao] = <d mu|-Z_C/|r-C||nu>.
+ * The derivative of <mu|V_C|nu> with respect to the nucleus C itself is -(dV_C + dV_C^T) (translational invariance). */
+void orc_int1e_ip(const int *atm, int natm, const int *bas, int nbas, const double *env, double *dS, double *dT, double *dV)
+{
+    int nao = orc_nao(bas, nbas);
+    size_t nn = (size_t)nao * nao;
+    int *loc = (int *)malloc(sizeof(int) * (nbas + 1));
+    ao_offsets(bas, nbas, loc);
+#pragma omp parallel
+    {
+        size_t blk = NCART_MAX * NCART_MAX;
+        double *buf = (double *)malloc(sizeof(double) * blk * (natm + 2) * 5);
+        double *sp = buf, *tp = sp + blk, *vp = tp + blk;                                  /* l+1 */
+        double *sm = vp + natm * blk, *tm = sm + blk, *vm = tm + blk;                      /* l-1 */
+        double *dc = vm + natm * blk;                                                      /* [3][nc(l)][ncb] */
+        double sph[NSPH_MAX * NSPH_MAX];
+#pragma omp for schedule(dynamic)
+        for (int ish = 0; ish < nbas; ish++) {
+            shell_t A = get_shell(atm, bas, env, ish);
+            dshell_t dA;
+            deriv_shells(&A, &dA);
+            for (int jsh = 0; jsh < nbas; jsh++) {
+                shell_t B = get_shell(atm, bas, env, jsh);
+                int la = A.l, lb = B.l, ncb = ncart_of(lb), nca = ncart_of(la), nsa = 2 * la + 1, nsb = 2 * lb + 1;
+                int nabp = ncart_of(la + 1) * ncb, nabm = la > 0 ? ncart_of(la - 1) * ncb : 0;
+                int1e_cart(&dA.up, &B, atm, natm, env, sp, tp, vp);
+                if (la > 0) int1e_cart(&dA.dn, &B, atm, natm, env, sm, tm, vm);
+                for (int m = 0; m < 2 + natm; m++) {
+                    const double *plus = m == 0 ? sp : m == 1 ? tp : vp + (size_t)(m - 2) * nabp;
+                    const double *minus = m == 0 ? sm : m == 1 ? tm : vm + (size_t)(m - 2) * nabm;
+                    double *dst = m == 0 ? dS : m == 1 ? dT : dV + (size_t)(m - 2) * 3 * nn;
+                    deriv_combine(la, ncb, plus, minus, dc);
+                    for (int x = 0; x < 3; x++) {
+                        c2s_pair(la, lb, dc + (size_t)x * nca * ncb, sph);
+                        for (int a = 0; a < nsa; a++)
+                            for (int b = 0; b < nsb; b++) dst[x * nn + (size_t)(loc[ish] + a) * nao + loc[jsh] + b] = sph[a * nsb + b];
+                    }
+                }
+            }
+            free(dA.cup);
+        }
+        free(buf);
+    }
+    free(loc);
+}
+
 /* number of OpenMP threads the following calls use (bench.py: the CPU share the container really has, cgroup cpu.max) */
 void orc_set_num_threads(int n)
 {
@@ -934,10 +1226,10 @@ int orc_num_threads(void)
 #endif
 }
 
-/* c2s table for tests and the numpy AO evaluator: out[NCART_MAX = 15][NSPH_MAX = 9] */
+/* c2s table for tests and the numpy AO evaluator: out[15][NSPH_MAX = 9] (the cartesian rows of l <= LMAX) */
 void orc_c2s(int l, double *out)
 {
     double c[NCART_MAX][NSPH_MAX];
     c2s_matrix(l, c);
-    memcpy(out, c, sizeof(c));
+    memcpy(out, c, sizeof(double) * 15 * NSPH_MAX);
 }

@@ -34,6 +34,8 @@ def lib():
         _LIB.orc_jk_direct.restype = ctypes.c_long
         _LIB.orc_incore_layout.restype = ctypes.c_long
         _LIB.orc_incore_fill.restype = ctypes.c_long
+        for f in ("orc_eri_ip1_shell", "orc_grad_eri", "orc_int1e_ip"):
+            getattr(_LIB, f).restype = None
     return _LIB
 
 
@@ -81,6 +83,41 @@ class Oracle:
         out = np.zeros(d)
         lib().orc_eri_shell(*self._args(), int(i), int(j), int(k), int(l), _p(out))
         return out
+
+    def eri_ip1_shell(self, i, j, k, l):
+        """d/dA_i (ij|kl), A_i the centre of shell i (nuclear-coordinate derivative): [3, di, dj, dk, dl]."""
+        d = [2 * int(self.bas[s, 1]) + 1 for s in (i, j, k, l)]
+        out = np.zeros([3] + d)
+        lib().orc_eri_ip1_shell(*self._args(), int(i), int(j), int(k), int(l), _p(out))
+        return out
+
+    def grad_eri(self, dm, spin_density=None, hyb=1.0, qtol=None):
+        """dE2/dR [natm, 3] of E2 = 1/2 D.J[D] - hyb/4 (D.K[D] + M.K[M]) (M = spin_density, None: closed shell) over every
+        unique shell quartet.  With `qtol`: (gradient, part of it from the quartets with q_ij q_kl < qtol)."""
+        dm = np.ascontiguousarray(dm, dtype=np.float64)
+        M = None if spin_density is None else np.ascontiguousarray(spin_density, dtype=np.float64)
+        g, gs = np.zeros((self.natm, 3)), np.zeros((self.natm, 3))
+        lib().orc_grad_eri(*self._args(), _p(dm), _p(M) if M is not None else None, ctypes.c_double(hyb),
+                           ctypes.c_double(qtol or 0.0), _p(g), _p(gs) if qtol is not None else None)
+        return g if qtol is None else (g, gs)
+
+    def int1e_ip(self):
+        """Bra-centre derivatives d/dA_x of mu: (<d mu|nu> [3, n, n], <d mu|T|nu> [3, n, n], <d mu|V_C|nu> [natm, 3, n, n])."""
+        n = self.nao
+        dS, dT, dV = np.zeros((3, n, n)), np.zeros((3, n, n)), np.zeros((self.natm, 3, n, n))
+        lib().orc_int1e_ip(*self._args(), _p(dS), _p(dT), _p(dV))
+        return dS, dT, dV
+
+    def grad_1e(self, dm, W):
+        """d/dR [natm, 3] of sum D (T + V) - sum W S at fixed D, W (symmetric): basis-function motion plus the
+        Hellmann-Feynman term of every charged nucleus (what mi_grad_1e adds)."""
+        dS, dT, dV = self.int1e_ip()
+        aoatm = np.repeat(self.bas[:, 0], 2 * self.bas[:, 1] + 1)
+        per_ao = 2 * np.einsum("xij,ij->xi", dT + dV.sum(axis=0), dm) - 2 * np.einsum("xij,ij->xi", dS, W)
+        g = np.zeros((self.natm, 3))
+        np.add.at(g, aoatm, per_ao.T)
+        g -= 2 * np.einsum("cxij,ij->cx", dV, dm)
+        return g
 
     def jk(self, dm, tol=1e-13):
         if getattr(self, "_incore", None) is not None:

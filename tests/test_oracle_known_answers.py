@@ -242,3 +242,185 @@ def test_oracle_uhf_and_spin_functionals_known_answers():
             e_p = np.real(fn(np.array([r / 2 + 0j]), np.array([r / 2 + 0j]), 0, 0, 0))[0] / r
             e_f = np.real(fn(np.array([r * (1 - 1e-12) + 0j]), np.array([r * 1e-12 + 0j]), 0, 0, 0))[0] / r
             assert abs(e_p - para) < 4e-4 and abs(e_f - ferro) < 4e-4
+
+
+# ------------------------------------------------------------------------------------------------
+# Derivative integrals of the oracle (the exact references of the GPU gradient tests, test_gpu_grad_oracle.py), pinned to
+# fourth-order central differences of the oracle's own integrals and energies.
+# ------------------------------------------------------------------------------------------------
+
+def _fd4(f, h):
+    """(-f(2h) + 8 f(h) - 8 f(-h) + f(-2h)) / 12h of a function of the step."""
+    return (-f(2 * h) + 8 * f(h) - 8 * f(-h) + f(-2 * h)) / (12 * h)
+
+
+def _displaced(mol, ia, x, h):
+    R = mol.atom_coords().copy()
+    R[ia, x] += h
+    return mol.set_geom_(R, unit="Bohr", inplace=False)
+
+
+def _one_shell_per_l(lmax):
+    """Four atoms (He, Be, C, O: even electron count), each carrying one two-primitive shell of every l <= lmax; the exponents
+    differ per atom.  Shell index of (atom a, l) = a * (lmax + 1) + l."""
+    basis = {}
+    for a, el in enumerate(("He", "Be", "C", "O")):
+        basis[el] = [[l, [1.3 + 0.2 * a + 0.1 * l, 0.6], [0.45 + 0.05 * a, 0.5]] for l in range(lmax + 1)]
+    atom = "He 0 0 0; Be 0.3 1.1 -0.4; C -0.9 0.2 0.8; O 0.5 -0.7 0.6"
+    return _mol(atom, basis, unit="Bohr")
+
+
+def test_eri_ip1_matches_finite_differences_all_classes_to_f():
+    """orc_eri_ip1_shell for every (l1 l2|l3 l4) class up to f: shell i is the only shell of the quartet on atom 0, so moving atom 0
+    moves exactly the differentiated shell.  The four centre derivatives sum to zero (translational invariance)."""
+    from oracle import oracle as orc
+    mol = _one_shell_per_l(3)
+    o = orc.Oracle(mol)
+    classes = [(a, b, c, d) for a in range(4) for b in range(4) for c in range(4) for d in range(4)]
+    quart = {cl: (cl[0], 4 + cl[1], 8 + cl[2], 12 + cl[3]) for cl in classes}
+    ana = {cl: o.eri_ip1_shell(*q) for cl, q in quart.items()}
+    h = 1e-3
+    worst = 0.0
+    for x in range(3):
+        blocks = {s: {cl: orc.Oracle(_displaced(mol, 0, x, s)).eri_shell(*q) for cl, q in quart.items()} for s in (2 * h, h, -h, -2 * h)}
+        for cl in classes:
+            fd = _fd4(lambda s: blocks[s][cl], h)
+            err = np.abs(ana[cl][x] - fd).max() / max(1.0, np.abs(fd).max())
+            worst = max(worst, err)
+            assert err < 1e-8, (cl, x, err)
+    for cl, (i, j, k, l) in quart.items():
+        tot = (ana[cl] + o.eri_ip1_shell(j, i, k, l).transpose(0, 2, 1, 3, 4) + o.eri_ip1_shell(k, l, i, j).transpose(0, 3, 4, 1, 2)
+               + o.eri_ip1_shell(l, k, i, j).transpose(0, 3, 4, 2, 1))
+        assert np.abs(tot).max() < 1e-12 * max(1.0, np.abs(ana[cl]).max()), cl
+
+
+def test_eri_ip1_g_shell_three_and_two_centre():
+    """A g shell in the differentiated and in the plain positions of (ij|P 1) and (P 1|Q 1) with the exponent-0 unit function --
+    how oracle/df.py uses it: l = 5 inside the derivative.  Also: the unit function's own derivative is exactly zero."""
+    import math
+    from oracle import oracle as orc
+    basis = {"He": [[4, [1.1, 1.0]], [2, [0.8, 1.0]]], "Be": [[3, [0.9, 1.0]], [4, [0.7, 0.5], [2.1, 0.5]]]}
+
+    def with_unit(m):
+        class P:
+            pass
+        p = P()
+        env = np.concatenate([m._env, [0.0, math.sqrt(4 * math.pi)]])
+        p._atm, p._env, p.nao = m._atm, env, m.nao + 1
+        p._bas = np.vstack([m._bas, [[0, 0, 1, 1, 0, len(m._env), len(m._env) + 1, 0]]]).astype(np.int32)
+        return p
+    mol = _mol("He 0 0 0; Be 0.4 -0.9 1.2", basis, unit="Bohr")
+    u = mol.nbas
+    sh = {(int(b[0]), int(b[1])): n for n, b in enumerate(mol._bas)}
+    hg, hd, bf, bg = sh[0, 4], sh[0, 2], sh[1, 3], sh[1, 4]
+    cases = [(hg, bf, bg, u), (bf, hg, hd, u), (bg, u, hg, u), (hg, u, bf, u), (hd, bg, bf, u), (bg, hd, hg, u)]
+    o = orc.Oracle(with_unit(mol))
+    h = 1e-3
+    for (i, j, k, l) in cases:
+        ana = o.eri_ip1_shell(i, j, k, l)
+        ia = int(mol._bas[i, 0])
+        assert all(int(mol._bas[s, 0]) != ia for s in (j, k) if s < u), "the moved atom must carry only shell i of the quartet"
+        for x in range(3):
+            fd = _fd4(lambda s: orc.Oracle(with_unit(_displaced(mol, ia, x, s))).eri_shell(i, j, k, l), h)
+            assert np.abs(ana[x] - fd).max() < 1e-8 * max(1.0, np.abs(fd).max()), ((i, j, k, l), x)
+    assert np.abs(o.eri_ip1_shell(u, 0, 3, u)).max() == 0.0
+
+
+def test_df_gradient_oracle_matches_finite_differences():
+    """oracle/df.py grad (Z3 and Z2 together) against differences of oracle/df.py integrals, water/6-31G(d): its generated
+    auxiliary set reaches g."""
+    from mi355scf import df
+    from mi355scf.mole import Mole
+    from oracle import df as odf
+    mol = _mol(MOLECULES["h2o"], "6-31g(d)")
+
+    def aux(m):
+        return Mole(atom=[(s_, xyz) for s_, xyz in m._atom], basis=df.even_tempered_aux(m), unit="Bohr", verbose=0).build()
+    am = aux(mol)
+    assert am._bas[:, 1].max() == 4
+    n, na = mol.nao, am.nao
+    rng = np.random.default_rng(21)
+    z3 = rng.standard_normal((n, n, na))
+    z3 = 0.5 * (z3 + z3.transpose(1, 0, 2))
+    a = rng.standard_normal((na, na))
+    z2 = 0.5 * (a + a.T)
+    g = odf.grad(mol, am, z3, z2)
+    assert np.abs(g.sum(axis=0)).max() < 1e-10 * np.abs(g).max()
+
+    def F(m):
+        j3, j2 = odf.integrals(m, aux(m))
+        return float((z3 * j3).sum() + (z2 * j2).sum())
+    for x in range(3):   # the oxygen: orbital, auxiliary and g shells all move
+        fd = _fd4(lambda s: F(_displaced(mol, 0, x, s)), 1e-3)
+        assert abs(g[0, x] - fd) < 1e-8 * max(1.0, np.abs(g).max()), (x, g[0, x], fd)
+
+
+def test_grad_eri_oracle_matches_finite_differences():
+    """orc_grad_eri against differences of the oracle's own J/K energy 1/2 D.J[D] - hyb/4 (D.K[D] + M.K[M]), water/6-31G(d),
+    random non-idempotent D and M, hyb 0 and 1, with and without M."""
+    from oracle import oracle as orc
+    mol = _mol(MOLECULES["h2o"], "6-31g(d)")
+    n = mol.nao
+    rng = np.random.default_rng(5)
+    a, b = rng.standard_normal((n, n)), rng.standard_normal((n, n))
+    D, M = a + a.T, b + b.T
+    o = orc.Oracle(mol)
+
+    def parts(m):
+        om = orc.Oracle(m)
+        J, K = om.jk(D, tol=0.0)
+        _, KM = om.jk(M, tol=0.0)
+        return np.array([0.5 * np.sum(D * J), -0.25 * np.sum(D * K), -0.25 * np.sum(M * KM)])
+    fd = np.zeros((mol.natm, 3, 3))
+    for ia in range(mol.natm):
+        for x in range(3):
+            fd[ia, x] = _fd4(lambda s: parts(_displaced(mol, ia, x, s)), 1e-3)
+    for hyb in (0.0, 1.0):
+        for spin in (None, M):
+            g = o.grad_eri(D, spin, hyb=hyb)
+            ref = fd[..., 0] + hyb * fd[..., 1] + (hyb * fd[..., 2] if spin is not None else 0.0)
+            assert np.abs(g - ref).max() < 1e-8 * max(1.0, np.abs(ref).max()), (hyb, spin is not None, np.abs(g - ref).max())
+            assert np.abs(g.sum(axis=0)).max() < 1e-11 * max(1.0, np.abs(g).max())
+    # what a Schwarz threshold drops is reported separately and is part of the whole
+    g, gs = o.grad_eri(D, M, hyb=1.0, qtol=1e-3)
+    assert np.abs(gs).max() > 0 and np.abs(g - o.grad_eri(D, M, hyb=1.0)).max() == 0.0
+
+
+def test_grad_1e_oracle_matches_finite_differences_with_ghost_atoms():
+    """orc_int1e_ip contracted like mi_grad_1e (basis motion + Hellmann-Feynman term) against differences of orc_int1e, water with
+    a ghost water: the ghost nuclei carry no charge but their basis functions move."""
+    from oracle import oracle as orc
+    mol = _mol("O 0 0 0; H 0 -0.757 0.587; H 0 0.757 0.587; Ghost:O 0.1 0.2 2.9; Ghost:H 0.7 0 3.5; Ghost:H -0.7 0.1 3.6",
+               "6-31g(d)")
+    assert list(mol._atm[:, 0]) == [8, 1, 1, 0, 0, 0]
+    n = mol.nao
+    rng = np.random.default_rng(6)
+    a, b = rng.standard_normal((n, n)), rng.standard_normal((n, n))
+    D, W = a + a.T, b + b.T
+    g = orc.Oracle(mol).grad_1e(D, W)
+
+    def E(m):
+        S, T, V, _ = orc.Oracle(m).int1e()
+        return float(np.sum(D * (T + V)) - np.sum(W * S))
+    ref = np.array([[_fd4(lambda s: E(_displaced(mol, ia, x, s)), 1e-3) for x in range(3)] for ia in range(mol.natm)])
+    assert np.abs(g - ref).max() < 1e-8 * max(1.0, np.abs(ref).max()), np.abs(g - ref).max()
+    assert np.abs(g[3:]).max() > 1.0      # the ghost atoms' basis functions do feel forces
+    assert np.abs(g.sum(axis=0)).max() < 1e-11 * np.abs(g).max()
+
+
+def test_eval_ao_second_derivatives_match_finite_differences():
+    """oracle/dft.py eval_ao(deriv=2) (xx, xy, xz, yy, yz, zz after value and gradient) against differences of deriv=1, and
+    deriv=2's first four components equal deriv=1 exactly; water/cc-pVTZ (f shells)."""
+    from oracle import dft as odft
+    mol = _mol(MOLECULES["h2o"], "cc-pvtz")
+    coords = np.random.default_rng(7).normal(size=(40, 3)) * 1.5
+    a2 = odft.eval_ao(mol, coords, 2)
+    assert a2.shape == (10, 40, mol.nao)
+    assert np.array_equal(a2[:4], odft.eval_ao(mol, coords, 1))
+    for m, (i, j) in enumerate([(0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)]):
+        def d1(s):
+            c = coords.copy()
+            c[:, j] += s
+            return odft.eval_ao(mol, c, 1)[1 + i]
+        fd = _fd4(d1, 1e-4)
+        assert np.abs(a2[4 + m] - fd).max() < 1e-8 * max(1.0, np.abs(fd).max()), (i, j)
