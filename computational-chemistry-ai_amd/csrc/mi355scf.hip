@@ -8,6 +8,7 @@
 //   schwarz_diag_kernel     q_ab = sqrt(max (ab|ab))                      (row a3)
 //   jk_tiles_kernel         one-pass J+K digestion of the HBM-resident tiles (rows a5, a6)
 //   pad/finalize, DIIS helpers                                             (row a10)
+//   pcm_* kernels           C-PCM surface-charge integrals, their two per-cycle passes and gradient (pcm.py)
 // Written for gfx950 only: 64-lane waves are assumed throughout.
 
 #include <hip/hip_runtime.h>
@@ -8013,4 +8014,427 @@ extern "C" int mi_xc_vmat_fold(mi_ctx *c, const double *d_ao, const double *d_wv
     case 4: return launch_vmat_fold<4>(c, d_ao, d_wv, ncomp, ng, nrb, d_vmat, st);
     default: return launch_vmat_fold<5>(c, d_ao, d_wv, ncomp, ng, nrb, d_vmat, st);
     }
+}
+
+// =================================================================================================
+// C-PCM implicit solvation (mi355scf/pcm.py): one-electron integrals against the Gaussian surface charges of the cavity.
+//
+//   B[g, mn] = int phi_m phi_n erf(zeta_g |r - s_g|) / |r - s_g| dr,   rows g = surface points, columns mn = packed spherical
+//   AO pairs m >= n (caller's AO order, column m (m + 1) / 2 + n), row stride ld >= nao (nao + 1) / 2 (padding columns zero).
+//
+// The attenuated nuclear attraction by Rys quadrature: with eta = zeta^2 and rho = p eta / (p + eta) the Boys argument is
+// rho |PC|^2, the prefactor gains sqrt(rho / p) and the roots are scaled by rho / p before the usual 1-D recurrences.
+// Every launch holds shell pairs of ONE angular class (template arguments: fixed-size register arrays, no per-thread blocks
+// sized for the largest class); a workgroup is (one shell pair, up to 64 surface points of one owning atom).
+//   pcm_int_kernel<LA,LB>       B (once per geometry)
+//   pcm_potential_kernel        v[g] = vn[g] - sum_c B[g,c] d[c]     (per cycle; one workgroup per row, fixed-order sums)
+//   pcm_fock_partial_kernel     part[k][c] = sum_{g in chunk k} q[g] B[g,c]   (per cycle; column-streaming, no atomics)
+//   pcm_fock_finalize_kernel    V[m,n] (+)= scale sum_k part[k][c(m,n)]        (chunks added in index order)
+//   pcm_grad_kernel<LA,LB>      -2 sum_g q_g sum_{m in A, n} D_mn <d_A m|erf/r|n> per (ordered pair, point block)
+// =================================================================================================
+struct PcmArgs {
+    const int32_t *atm, *bas;
+    const double *env;
+    const int *shell_ao;
+    const double *c2s;
+    int c2s_off[LMAX + 2];
+    RysDev rys;
+    int nao;
+    const int *pairs;     // [n][2] shell pairs of one class (la, lb) = template arguments
+    const double *pts;    // [npts][4]: x, y, z, zeta
+    const int *blk;       // [nblk][3]: first point, count (1..64), owning atom
+    int nblk;
+    int64_t ld;
+    double *B;
+    const double *D, *q;  // gradient: density [nao][nao], surface charges [npts]
+    double *part;         // gradient: [n][nblk][3] (rows of the launch's class at its offset)
+};
+
+__device__ inline int pcm_cart(int l, int idx, int d)   // exponent of direction d of cartesian component idx of shell l
+{
+    int x = 0, y = 0, z = 0;
+    cart_pow(l, idx, x, y, z);
+    return d == 0 ? x : (d == 1 ? y : z);
+}
+
+template <int LA, int LB>
+__global__ __launch_bounds__(64) void pcm_int_kernel(PcmArgs A)
+{
+    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2, NSA = 2 * LA + 1, NSB = 2 * LB + 1;
+    constexpr int NR = (LA + LB) / 2 + 1, NI = LA + LB + 1;
+    const int pidx = blockIdx.x / A.nblk, b = blockIdx.x - pidx * A.nblk;
+    const int *bk = A.blk + 3 * b;
+    if ((int)threadIdx.x >= bk[1]) return;
+    const int g = bk[0] + threadIdx.x;
+    const int ish = A.pairs[2 * pidx], jsh = A.pairs[2 * pidx + 1];
+    const int32_t *bi = A.bas + ish * BAS_SLOTS, *bj = A.bas + jsh * BAS_SLOTS;
+    const double *ra = A.env + A.atm[bi[0] * ATM_SLOTS + 1], *rb = A.env + A.atm[bj[0] * ATM_SLOTS + 1];
+    const double C[3] = {A.pts[4 * g], A.pts[4 * g + 1], A.pts[4 * g + 2]};
+    const double eta = A.pts[4 * g + 3] * A.pts[4 * g + 3];
+    const double AB[3] = {ra[0] - rb[0], ra[1] - rb[1], ra[2] - rb[2]};
+    double acc[NCA * NCB];
+#pragma unroll
+    for (int k = 0; k < NCA * NCB; k++) acc[k] = 0.0;
+    for (int ip = 0; ip < bi[2]; ip++)
+        for (int jp = 0; jp < bj[2]; jp++) {
+            const double a = A.env[bi[5] + ip], bb = A.env[bj[5] + jp];
+            const double cc = A.env[bi[6] + ip] * A.env[bj[6] + jp];
+            const double p = a + bb, h = 0.5 / p;
+            const double ex = exp(-a * bb / p * (AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2]));
+            const double theta = eta / (p + eta);          // rho / p
+            double PA[3], PC[3];
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                const double P = (a * ra[d] + bb * rb[d]) / p;
+                PA[d] = P - ra[d];
+                PC[d] = P - C[d];
+            }
+            const double x = p * theta * (PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2]);
+            const double pv = cc * ex * 2.0 * M_PI / p * sqrt(theta);
+#pragma unroll
+            for (int r = 0; r < NR; r++) {
+                const double u = rys_eval(A.rys, NR, r, x) * theta, w = rys_eval(A.rys, NR, NR + r, x);
+                const double b10 = (1.0 - u) * h;
+                double gt[3][NI][LB + 1];
+#pragma unroll
+                for (int d = 0; d < 3; d++) {
+                    const double c00 = PA[d] - u * PC[d];
+                    gt[d][0][0] = 1.0;
+#pragma unroll
+                    for (int i = 0; i + 1 < NI; i++) gt[d][i + 1][0] = c00 * gt[d][i][0] + (i > 0 ? i * b10 * gt[d][i - 1][0] : 0.0);
+#pragma unroll
+                    for (int j = 0; j < LB; j++)
+#pragma unroll
+                        for (int i = 0; i < NI - j - 1; i++) gt[d][i][j + 1] = gt[d][i + 1][j] + AB[d] * gt[d][i][j];
+                }
+                const double f = pv * w;
+#pragma unroll
+                for (int ia = 0; ia < NCA; ia++)
+#pragma unroll
+                    for (int ib = 0; ib < NCB; ib++)
+                        acc[ia * NCB + ib] += f * gt[0][pcm_cart(LA, ia, 0)][pcm_cart(LB, ib, 0)] *
+                                              gt[1][pcm_cart(LA, ia, 1)][pcm_cart(LB, ib, 1)] *
+                                              gt[2][pcm_cart(LA, ia, 2)][pcm_cart(LB, ib, 2)];
+            }
+        }
+    const double *ca = A.c2s + A.c2s_off[LA], *cb = A.c2s + A.c2s_off[LB];
+    const int ao_i = A.shell_ao[ish], ao_j = A.shell_ao[jsh];
+    double *row = A.B + (size_t)g * A.ld;
+    for (int i = 0; i < NSA; i++)
+        for (int j = 0; j < NSB; j++) {
+            int m = ao_i + i, n = ao_j + j;
+            if (ish == jsh && n > m) continue;
+            double v = 0.0;
+#pragma unroll
+            for (int ia = 0; ia < NCA; ia++) {
+                double t = 0.0;
+#pragma unroll
+                for (int ib = 0; ib < NCB; ib++) t += acc[ia * NCB + ib] * cb[ib * NSB + j];
+                v += ca[ia * NSA + i] * t;
+            }
+            if (m < n) { const int s_ = m; m = n; n = s_; }
+            row[(size_t)m * (m + 1) / 2 + n] = v;
+        }
+}
+
+template <int LA, int LB>
+__global__ __launch_bounds__(64) void pcm_grad_kernel(PcmArgs A)
+{
+    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2, NSA = 2 * LA + 1, NSB = 2 * LB + 1;
+    constexpr int NR = (LA + LB + 1) / 2 + 1, NI = LA + LB + 2;
+    __shared__ double Dc[NCA * NCB];
+    const int pidx = blockIdx.x / A.nblk, b = blockIdx.x - pidx * A.nblk;
+    const int *bk = A.blk + 3 * b;
+    const int ish = A.pairs[2 * pidx], jsh = A.pairs[2 * pidx + 1];
+    const int32_t *bi = A.bas + ish * BAS_SLOTS, *bj = A.bas + jsh * BAS_SLOTS;
+    const int ao_i = A.shell_ao[ish], ao_j = A.shell_ao[jsh];
+    const double *ca = A.c2s + A.c2s_off[LA], *cb = A.c2s + A.c2s_off[LB];
+    for (int k = threadIdx.x; k < NCA * NCB; k += 64) {   // density block back-transformed to cartesian components, once per workgroup
+        const int ia = k / NCB, ib = k - ia * NCB;
+        double s = 0.0;
+        for (int i = 0; i < NSA; i++) {
+            double t = 0.0;
+            for (int j = 0; j < NSB; j++) t += A.D[(size_t)(ao_i + i) * A.nao + ao_j + j] * cb[ib * NSB + j];
+            s += ca[ia * NSA + i] * t;
+        }
+        Dc[k] = s;
+    }
+    __syncthreads();
+    double gc[3] = {0.0, 0.0, 0.0};
+    if ((int)threadIdx.x < bk[1]) {
+        const int g = bk[0] + threadIdx.x;
+        const double *ra = A.env + A.atm[bi[0] * ATM_SLOTS + 1], *rb = A.env + A.atm[bj[0] * ATM_SLOTS + 1];
+        const double C[3] = {A.pts[4 * g], A.pts[4 * g + 1], A.pts[4 * g + 2]};
+        const double eta = A.pts[4 * g + 3] * A.pts[4 * g + 3];
+        const double qg = A.q[g];
+        const double AB[3] = {ra[0] - rb[0], ra[1] - rb[1], ra[2] - rb[2]};
+        for (int ip = 0; ip < bi[2]; ip++)
+            for (int jp = 0; jp < bj[2]; jp++) {
+                const double a = A.env[bi[5] + ip], bb = A.env[bj[5] + jp];
+                const double cc = A.env[bi[6] + ip] * A.env[bj[6] + jp];
+                const double p = a + bb, h = 0.5 / p;
+                const double ex = exp(-a * bb / p * (AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2]));
+                const double theta = eta / (p + eta);
+                double PA[3], PC[3];
+#pragma unroll
+                for (int d = 0; d < 3; d++) {
+                    const double P = (a * ra[d] + bb * rb[d]) / p;
+                    PA[d] = P - ra[d];
+                    PC[d] = P - C[d];
+                }
+                const double x = p * theta * (PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2]);
+                const double pv = qg * cc * ex * 2.0 * M_PI / p * sqrt(theta);
+#pragma unroll
+                for (int r = 0; r < NR; r++) {
+                    const double u = rys_eval(A.rys, NR, r, x) * theta, w = rys_eval(A.rys, NR, NR + r, x);
+                    const double b10 = (1.0 - u) * h;
+                    double gt[3][NI][LB + 1];
+#pragma unroll
+                    for (int d = 0; d < 3; d++) {
+                        const double c00 = PA[d] - u * PC[d];
+                        gt[d][0][0] = 1.0;
+#pragma unroll
+                        for (int i = 0; i + 1 < NI; i++) gt[d][i + 1][0] = c00 * gt[d][i][0] + (i > 0 ? i * b10 * gt[d][i - 1][0] : 0.0);
+#pragma unroll
+                        for (int j = 0; j < LB; j++)
+#pragma unroll
+                            for (int i = 0; i < NI - j - 1; i++) gt[d][i][j + 1] = gt[d][i + 1][j] + AB[d] * gt[d][i][j];
+                    }
+                    const double f = pv * w;
+#pragma unroll
+                    for (int ia = 0; ia < NCA; ia++)
+#pragma unroll
+                        for (int ib = 0; ib < NCB; ib++) {
+                            double v0[3], vd[3];
+#pragma unroll
+                            for (int d = 0; d < 3; d++) {
+                                const int i = pcm_cart(LA, ia, d), j = pcm_cart(LB, ib, d);
+                                v0[d] = gt[d][i][j];
+                                vd[d] = 2.0 * a * gt[d][i + 1][j] - (i > 0 ? i * gt[d][i > 0 ? i - 1 : 0][j] : 0.0);
+                            }
+                            const double dc = f * Dc[ia * NCB + ib];
+                            gc[0] += dc * vd[0] * v0[1] * v0[2];
+                            gc[1] += dc * v0[0] * vd[1] * v0[2];
+                            gc[2] += dc * v0[0] * v0[1] * vd[2];
+                        }
+                }
+            }
+    }
+    // butterfly over the wave: every lane ends with the same fixed-order sum (no atomics)
+#pragma unroll
+    for (int d = 0; d < 3; d++)
+        for (int o = 32; o > 0; o >>= 1) gc[d] += __shfl_xor(gc[d], o);
+    if (threadIdx.x == 0)
+        for (int d = 0; d < 3; d++) A.part[((size_t)pidx * A.nblk + b) * 3 + d] = -2.0 * gc[d];
+}
+
+__global__ __launch_bounds__(256) void pcm_pack_kernel(const double *D, int nao, double *d)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)nao * nao) return;
+    const int m = (int)(idx / nao), n = (int)(idx - (size_t)m * nao);
+    if (n > m) return;
+    d[(size_t)m * (m + 1) / 2 + n] = m == n ? D[idx] : D[idx] + D[(size_t)n * nao + m];
+}
+
+__global__ __launch_bounds__(256) void pcm_potential_kernel(const double *B, int64_t ld, const double *d, const double *vn, double *v)
+{
+    __shared__ double sh[4];
+    const int64_t g = blockIdx.x;
+    const d2_t *row = reinterpret_cast<const d2_t *>(B + g * ld);
+    const d2_t *d2 = reinterpret_cast<const d2_t *>(d);
+    const int64_t n2 = ld / 2;
+    double s0 = 0.0, s1 = 0.0;
+    int64_t c = threadIdx.x;
+    for (; c + 256 < n2; c += 512) {
+        const d2_t b0 = __builtin_nontemporal_load(row + c), b1 = __builtin_nontemporal_load(row + c + 256);
+        const d2_t e0 = d2[c], e1 = d2[c + 256];
+        s0 += b0.x * e0.x + b0.y * e0.y;
+        s1 += b1.x * e1.x + b1.y * e1.y;
+    }
+    if (c < n2) {
+        const d2_t b0 = __builtin_nontemporal_load(row + c), e0 = d2[c];
+        s0 += b0.x * e0.x + b0.y * e0.y;
+    }
+    double s = s0 + s1;
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double t = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+        v[g] = vn ? vn[g] - t : t;
+    }
+}
+
+__global__ __launch_bounds__(256) void pcm_fock_partial_kernel(const double *B, int64_t ld, int npts, int rows_per, const double *q, double *part)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ld / 2) return;
+    const int g0 = blockIdx.y * rows_per, g1 = min(npts, g0 + rows_per);
+    double ax = 0.0, ay = 0.0, bx = 0.0, by = 0.0;
+    int g = g0;
+    for (; g + 1 < g1; g += 2) {
+        const d2_t b0 = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(B + (int64_t)g * ld) + c);
+        const d2_t b1 = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(B + (int64_t)(g + 1) * ld) + c);
+        const double q0 = q[g], q1 = q[g + 1];
+        ax += q0 * b0.x; ay += q0 * b0.y;
+        bx += q1 * b1.x; by += q1 * b1.y;
+    }
+    if (g < g1) {
+        const d2_t b0 = __builtin_nontemporal_load(reinterpret_cast<const d2_t *>(B + (int64_t)g * ld) + c);
+        ax += q[g] * b0.x; ay += q[g] * b0.y;
+    }
+    d2_t out;
+    out.x = ax + bx;
+    out.y = ay + by;
+    reinterpret_cast<d2_t *>(part + (int64_t)blockIdx.y * ld)[c] = out;
+}
+
+__global__ __launch_bounds__(256) void pcm_fock_finalize_kernel(const double *part, int nchunk, int64_t ld, int nao, double scale, int accumulate,
+                                                                double *V)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)nao * nao) return;
+    const int m = (int)(idx / nao), n = (int)(idx - (size_t)m * nao);
+    const int64_t c = m >= n ? (int64_t)m * (m + 1) / 2 + n : (int64_t)n * (n + 1) / 2 + m;
+    double s = 0.0;
+    for (int k = 0; k < nchunk; k++) s += part[(int64_t)k * ld + c];
+    V[idx] = (accumulate ? V[idx] : 0.0) + scale * s;
+}
+
+// Shell pairs of the PCM launches, grouped by angular class: ordered = 0: i >= j with l_i >= l_j (B), 1: all (i, j) (gradient,
+// derivative on i).  class_start[k] .. class_start[k + 1] is class k = la * 4 + lb.
+static void pcm_pair_list(const mi_ctx *c, int ordered, std::vector<int> &pairs, std::vector<int> &class_start)
+{
+    std::vector<std::vector<int>> by(16);
+    for (int i = 0; i < c->nbas; i++)
+        for (int j = 0; j < (ordered ? c->nbas : i + 1); j++) {
+            int a = i, b = j;
+            if (!ordered && c->shells[a].l < c->shells[b].l) std::swap(a, b);
+            by[c->shells[a].l * 4 + c->shells[b].l].push_back(a);
+            by[c->shells[a].l * 4 + c->shells[b].l].push_back(b);
+        }
+    pairs.clear();
+    class_start.assign(17, 0);
+    for (int k = 0; k < 16; k++) {
+        class_start[k] = (int)pairs.size() / 2;
+        pairs.insert(pairs.end(), by[k].begin(), by[k].end());
+    }
+    class_start[16] = (int)pairs.size() / 2;
+}
+
+extern "C" int mi_pcm_pairs(mi_ctx *c, int ordered, int32_t *out)
+{
+    if (!c) return fail("mi_pcm_pairs: null context");
+    std::vector<int> pairs, cs;
+    pcm_pair_list(c, ordered, pairs, cs);
+    if (out) std::copy(pairs.begin(), pairs.end(), out);
+    return (int)(pairs.size() / 2);
+}
+
+template <int LA, int LB>
+static void pcm_launch(bool grad, const PcmArgs &A0, const int *d_pairs, int first, int count, hipStream_t st)
+{
+    if (count <= 0) return;
+    PcmArgs A = A0;
+    A.pairs = d_pairs + 2 * first;
+    if (grad) A.part = A0.part + (size_t)first * A0.nblk * 3;
+    const dim3 grid((unsigned)((int64_t)count * A.nblk));
+    if (grad) hipLaunchKernelGGL((pcm_grad_kernel<LA, LB>), grid, dim3(64), 0, st, A);
+    else hipLaunchKernelGGL((pcm_int_kernel<LA, LB>), grid, dim3(64), 0, st, A);
+}
+
+static int pcm_dispatch(mi_ctx *c, bool grad, PcmArgs &A, int npts, hipStream_t st)
+{
+    std::vector<int> pairs, cs;
+    pcm_pair_list(c, grad ? 1 : 0, pairs, cs);
+    const int n = cs[16];
+    if ((int64_t)n * A.nblk >= (int64_t)1 << 31) return fail("mi_pcm: %d shell pairs x %d point blocks exceed one launch", n, A.nblk);
+    int *d_pairs = nullptr;
+    HIPCHK(dev_malloc(&d_pairs, sizeof(int) * std::max<size_t>(pairs.size(), 2)));
+    HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(int) * pairs.size(), hipMemcpyHostToDevice, st));
+    A.atm = c->d_atm; A.bas = c->d_bas; A.env = c->d_env; A.shell_ao = c->d_shell_ao; A.c2s = c->d_c2s;
+    for (int i = 0; i <= LMAX + 1; i++) A.c2s_off[i] = c->c2s_off[i];
+    A.rys = c->rys; A.nao = c->nao;
+#define PCM_CASE(a, b) pcm_launch<a, b>(grad, A, d_pairs, cs[(a) * 4 + (b)], cs[(a) * 4 + (b) + 1] - cs[(a) * 4 + (b)], st)
+    PCM_CASE(0, 0); PCM_CASE(1, 0); PCM_CASE(1, 1); PCM_CASE(2, 0); PCM_CASE(2, 1); PCM_CASE(2, 2);
+    PCM_CASE(3, 0); PCM_CASE(3, 1); PCM_CASE(3, 2); PCM_CASE(3, 3);
+    if (grad) { PCM_CASE(0, 1); PCM_CASE(0, 2); PCM_CASE(0, 3); PCM_CASE(1, 2); PCM_CASE(1, 3); PCM_CASE(2, 3); }
+#undef PCM_CASE
+    hipError_t e = hipGetLastError();
+    // the pair list is read by the launches above: the pool's dev_free synchronises the device before parking the block
+    HIPCHK(hipStreamSynchronize(st));
+    dev_free(d_pairs);
+    if (e != hipSuccess) return fail("mi_pcm: launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+static int pcm_check_points(const mi_ctx *c, const char *who, const double *d_pts, int npts, const int32_t *d_blk, int nblk)
+{
+    if (!c || !d_pts || !d_blk) return fail("%s: null argument", who);
+    if (check_orbital_lmax(c, who)) return -1;
+    if (npts <= 0 || nblk <= 0) return fail("%s: no surface points", who);
+    return 0;
+}
+
+extern "C" int mi_pcm_eval(mi_ctx *c, const double *d_pts, int npts, const int32_t *d_blk, int nblk, int64_t ld, double *d_B, void *stream)
+{
+    if (pcm_check_points(c, "mi_pcm_eval", d_pts, npts, d_blk, nblk)) return -1;
+    if (!d_B) return fail("mi_pcm_eval: null B");
+    if (ld < (int64_t)c->nao * (c->nao + 1) / 2 || (ld & 1)) return fail("mi_pcm_eval: ld = %lld must be even and >= nao (nao + 1) / 2", (long long)ld);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(d_B, 0, sizeof(double) * (size_t)npts * ld, st));
+    PcmArgs A{};
+    A.pts = d_pts; A.blk = d_blk; A.nblk = nblk; A.ld = ld; A.B = d_B;
+    return pcm_dispatch(c, false, A, npts, st);
+}
+
+extern "C" int mi_pcm_grad(mi_ctx *c, const double *d_pts, int npts, const int32_t *d_blk, int nblk, const double *d_D, const double *d_q,
+                           double *d_part, void *stream)
+{
+    if (pcm_check_points(c, "mi_pcm_grad", d_pts, npts, d_blk, nblk)) return -1;
+    if (!d_D || !d_q || !d_part) return fail("mi_pcm_grad: null argument");
+    HIPCHK(hipSetDevice(c->device));
+    PcmArgs A{};
+    A.pts = d_pts; A.blk = d_blk; A.nblk = nblk; A.D = d_D; A.q = d_q; A.part = d_part;
+    return pcm_dispatch(c, true, A, npts, (hipStream_t)stream);
+}
+
+extern "C" int mi_pcm_potential(mi_ctx *c, const double *d_B, int npts, int64_t ld, const double *d_D, double *d_dpack, const double *d_vn,
+                                double *d_v, void *stream)
+{
+    if (!c || !d_B || !d_D || !d_dpack || !d_v) return fail("mi_pcm_potential: null argument");
+    if (npts <= 0 || ld < (int64_t)c->nao * (c->nao + 1) / 2 || (ld & 1)) return fail("mi_pcm_potential: bad sizes");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nn = (size_t)c->nao * c->nao;
+    hipLaunchKernelGGL(pcm_pack_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, d_D, c->nao, d_dpack);
+    hipLaunchKernelGGL(pcm_potential_kernel, dim3((unsigned)npts), dim3(256), 0, st, d_B, ld, d_dpack, d_vn, d_v);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mi_pcm_fock_chunks(int npts, int64_t ld)
+{
+    const int64_t colblk = (ld / 2 + 255) / 256;
+    int64_t k = (2048 + colblk - 1) / colblk;
+    k = std::max<int64_t>(1, std::min<int64_t>({k, 64, (int64_t)std::max(npts, 1)}));
+    return (int)k;
+}
+
+extern "C" int mi_pcm_fock(mi_ctx *c, const double *d_B, int npts, int64_t ld, const double *d_q, double scale, int accumulate, double *d_part,
+                           double *d_V, void *stream)
+{
+    if (!c || !d_B || !d_q || !d_part || !d_V) return fail("mi_pcm_fock: null argument");
+    if (npts <= 0 || ld < (int64_t)c->nao * (c->nao + 1) / 2 || (ld & 1)) return fail("mi_pcm_fock: bad sizes");
+    hipStream_t st = (hipStream_t)stream;
+    const int nchunk = mi_pcm_fock_chunks(npts, ld);
+    const int rows_per = (npts + nchunk - 1) / nchunk;
+    hipLaunchKernelGGL(pcm_fock_partial_kernel, dim3((unsigned)((ld / 2 + 255) / 256), (unsigned)nchunk), dim3(256), 0, st, d_B, ld, npts, rows_per,
+                       d_q, d_part);
+    const size_t nn = (size_t)c->nao * c->nao;
+    hipLaunchKernelGGL(pcm_fock_finalize_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, d_part, nchunk, ld, c->nao, scale,
+                       accumulate, d_V);
+    HIPCHK(hipGetLastError());
+    return 0;
 }

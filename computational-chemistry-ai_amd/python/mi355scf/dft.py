@@ -280,6 +280,10 @@ class RKS(RHF):
             V, tail = buf[:nn].view(n, n), buf[nn:]
             self._nr_rks_raw(dm, V, tail)
             self._nelec_grid = tail[0]
+            ws = getattr(self, "with_solvent", None)
+            if ws is not None:      # PCM: 1/2 V_pcm joins the unsymmetrised XC matrix, E_pcm the last entry of the tail
+                e = ws.fock_energy(dm, V, -0.5, accumulate=True)
+                tail = torch.cat([tail[0:1], tail[1:2] + e])
             F = eng.build_fock(dm, self._h1, 0.5 * hyb, torch.empty_like(dm), part, with_k=with_k, vxc_unsym=V)
             return F, tail[0:2]
         nmat = 3 if with_k else 2
@@ -295,6 +299,10 @@ class RKS(RHF):
             parallel.all_reduce_sum(buf, self._pg)
         vxc = V + V.T
         self._nelec_grid = tail[0]
+        ws = getattr(self, "with_solvent", None)
+        if ws is not None:
+            e = ws.fock_energy(dm, vxc, -1.0, accumulate=True)
+            tail = torch.cat([tail[0:1], tail[1:2] + e])
         F = torch.empty_like(J)
         eng.fock_energy(self._h1, J, K, vxc, dm, 0.5 * hyb, F, part)
         return F, tail[0:2]      # [N_elec, E_xc]: the last entry is added to the energy, the first validates the quadrature

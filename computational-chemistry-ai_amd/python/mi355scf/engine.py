@@ -120,6 +120,12 @@ def lib():
         L.mi_commutator_norm.argtypes = [vp, vp, vp, vp, vp]
         L.mi_c2s_table.argtypes = [ctypes.c_int, dp]
         L.mi_rys_roots_host.argtypes = [ctypes.c_int, ctypes.c_double, dp, dp]
+        L.mi_pcm_pairs.argtypes = [vp, ctypes.c_int, ip]
+        L.mi_pcm_eval.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, i64, vp, vp]
+        L.mi_pcm_grad.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp]
+        L.mi_pcm_potential.argtypes = [vp, vp, ctypes.c_int, i64, vp, vp, vp, vp, vp]
+        L.mi_pcm_fock_chunks.argtypes = [ctypes.c_int, i64]
+        L.mi_pcm_fock.argtypes = [vp, vp, ctypes.c_int, i64, vp, ctypes.c_double, ctypes.c_int, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -505,6 +511,62 @@ class Engine:
             self.prepare_eri()
         _check(lib().mi_grad_eri_sharded(self._h, D.data_ptr(), spin_density.data_ptr() if spin_density is not None else None,
                                          float(hyb), grad.data_ptr(), int(rank), int(nranks), self._stream()))
+
+    # --- C-PCM (pcm.py): surface-charge integrals and the two per-cycle passes over them -----------------------------------
+    def pcm_pairs(self, ordered=False):
+        """Shell pairs [n, 2] in the order of the rows of `pcm_grad`'s output (ordered: derivative on the first shell)."""
+        n = lib().mi_pcm_pairs(self._h, int(bool(ordered)), None)
+        _check(0 if n >= 0 else n)
+        out = np.zeros((max(n, 1), 2), dtype=np.int32)
+        lib().mi_pcm_pairs(self._h, int(bool(ordered)), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        return out[:n]
+
+    @staticmethod
+    def _pcm_points(pts, blk):
+        assert pts.is_contiguous() and pts.dtype == torch.float64 and pts.dim() == 2 and pts.shape[1] == 4
+        assert blk.is_contiguous() and blk.dtype == torch.int32 and blk.dim() == 2 and blk.shape[1] == 3
+        b = blk.cpu().numpy()
+        assert b.shape[0] > 0 and (b[:, 1] >= 1).all() and (b[:, 1] <= 64).all() and (b[:, 0] >= 0).all() \
+            and (b[:, 0] + b[:, 1] <= pts.shape[0]).all(), "point blocks must lie inside the point list (1..64 points each)"
+
+    def pcm_eval(self, pts, blk, ld, B):
+        """B[g, m(m+1)/2 + n] = (mn | erf(zeta_g r) / r at s_g) for pts [n, 4] = (x, y, z, zeta), blocks [nblk, 3]."""
+        self._pcm_points(pts, blk)
+        assert B.is_contiguous() and B.shape == (pts.shape[0], ld) and ld % 2 == 0 and ld >= self.nao * (self.nao + 1) // 2
+        with torch.cuda.device(self.device):
+            _check(lib().mi_pcm_eval(self._h, pts.data_ptr(), pts.shape[0], blk.data_ptr(), blk.shape[0], int(ld), B.data_ptr(),
+                                     self._stream()))
+
+    def pcm_grad(self, pts, blk, D, q, part):
+        """part[pair, block, 3] = -2 sum_g q_g sum D_mn <d m|erf/r|n> (pairs of `pcm_pairs(ordered=True)`)."""
+        self._pcm_points(pts, blk)
+        assert D.is_contiguous() and D.shape == (self.nao, self.nao) and q.is_contiguous() and q.numel() == pts.shape[0]
+        assert part.is_contiguous() and part.numel() == len(self.pcm_pairs(True)) * blk.shape[0] * 3
+        with torch.cuda.device(self.device):
+            _check(lib().mi_pcm_grad(self._h, pts.data_ptr(), pts.shape[0], blk.data_ptr(), blk.shape[0], D.data_ptr(), q.data_ptr(),
+                                     part.data_ptr(), self._stream()))
+
+    def pcm_potential(self, B, ld, D, dpack, vn, v):
+        """v = vn - B d (vn None: v = B d), d = D packed (m >= n, off-diagonals D_mn + D_nm) into `dpack` [ld]."""
+        n = B.shape[0]
+        assert B.is_contiguous() and B.shape[1] == ld and ld % 2 == 0 and ld >= self.nao * (self.nao + 1) // 2
+        assert D.is_contiguous() and D.shape == (self.nao, self.nao) and dpack.numel() == ld and v.numel() == n
+        assert vn is None or vn.numel() == n
+        _check(lib().mi_pcm_potential(self._h, B.data_ptr(), n, int(ld), D.data_ptr(), dpack.data_ptr(),
+                                      vn.data_ptr() if vn is not None else None, v.data_ptr(), self._stream()))
+
+    @staticmethod
+    def pcm_fock_chunks(npts, ld):
+        return int(lib().mi_pcm_fock_chunks(int(npts), int(ld)))
+
+    def pcm_fock(self, B, ld, q, scale, accumulate, part, V):
+        """V (+)= scale sum_g q_g B_g unpacked to [nao, nao]; `part`: pcm_fock_chunks(npts, ld) * ld doubles of scratch."""
+        n = B.shape[0]
+        assert B.is_contiguous() and B.shape[1] == ld and ld % 2 == 0 and ld >= self.nao * (self.nao + 1) // 2
+        assert q.is_contiguous() and q.numel() == n and V.is_contiguous() and V.shape == (self.nao, self.nao)
+        assert part.numel() >= self.pcm_fock_chunks(n, ld) * ld
+        _check(lib().mi_pcm_fock(self._h, B.data_ptr(), n, int(ld), q.data_ptr(), float(scale), int(bool(accumulate)),
+                                 part.data_ptr(), V.data_ptr(), self._stream()))
 
     # --- row a11: SP2 purification helpers ------------------------------------------------------
     def sp2_init(self, f_orth, X, work):

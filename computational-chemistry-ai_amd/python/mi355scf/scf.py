@@ -525,12 +525,21 @@ class SCF:
         """F = h + veff(D) on device; `part` receives the fixed-order partial sums of E_elec(D) (fused kernel).  Returns
         (F, extra): `extra` is None or a device tensor whose LAST element is added to the energy (E_xc); RKS passes
         [N_elec on the grid, E_xc] so that the host can also validate the quadrature of the cycle.  Overridden by RKS."""
+        ws = getattr(self, "with_solvent", None)   # PCM (pcm.py): V_pcm enters F through the V input, E_pcm through `extra`
         if self._fused_fock_ok(dm):
-            return self.engine.build_fock(dm, self._h1, 0.5, torch.empty_like(dm), part), None
+            if ws is None:
+                return self.engine.build_fock(dm, self._h1, 0.5, torch.empty_like(dm), part), None
+            V = torch.empty_like(dm)
+            e = ws.fock_energy(dm, V, -0.5)          # the fused epilogue adds V + V^T
+            return self.engine.build_fock(dm, self._h1, 0.5, torch.empty_like(dm), part, vxc_unsym=V), e
         J, K = self._jk(dm)
+        V = e = None
+        if ws is not None:
+            V = torch.empty_like(J)
+            e = ws.fock_energy(dm, V, -1.0)
         F = torch.empty_like(J)
-        self.engine.fock_energy(self._h1, J, K, None, dm, 0.5, F, part)
-        return F, None
+        self.engine.fock_energy(self._h1, J, K, V, dm, 0.5, F, part)
+        return F, e
 
     fused_fock = True   # single rank, resident tiles: F and the energy partials straight from the J/K accumulators (mi_build_fock)
 
@@ -1281,6 +1290,11 @@ class SCF:
     def nuc_grad_method(self):
         from . import grad
         return grad.Gradients(self)
+
+    def PCM(self):
+        """`mf.PCM()`: this object wrapped for C-PCM solvation (pcm.PCM)."""
+        from . import pcm
+        return pcm.PCM(self)
 
     # --- linear response (tdscf.py) ---
     def TDA(self):

@@ -6,6 +6,8 @@ from . import rhf, rks  # noqa: F401
 def _check(mf):
     if not getattr(mf, "_spin_restricted", True):
         raise NotImplementedError("tdscf: UHF/UKS references are not supported (closed-shell RHF/RKS only)")
+    if getattr(mf, "_pcm", False):
+        raise NotImplementedError("tdscf: excited states with PCM solvation are not implemented")
     return mf
 
 

@@ -341,6 +341,29 @@ int mi_c2s_table(int l, double *out);
 /* Rys roots/weights as evaluated by the device tables, for tests: roots[n], weights[n] (host). */
 int mi_rys_roots_host(int nroots, double x, double *roots, double *weights);
 
+/* ---- C-PCM implicit solvation (additions; ABI version unchanged) ----------------------------------------------------------
+ * Surface points d_pts[npts][4] = (x, y, z, zeta) in Bohr; point blocks d_blk[nblk][3] = (first point, count 1..64, owning
+ * atom), every block inside the point list.  The store B[npts][ld], ld even and >= nao (nao + 1) / 2, holds
+ *   B[g][m (m + 1) / 2 + n] = int phi_m phi_n erf(zeta_g |r - s_g|) / |r - s_g| dr   (m >= n, caller's AO order; padding 0).
+ * mi_pcm_eval:      B, once per geometry (Rys quadrature with the erf attenuation; one launch per angular class).
+ * mi_pcm_potential: d_dpack[ld] = D packed (off-diagonals D_mn + D_nm), d_v[g] = d_vn[g] - (B d)[g] (d_vn NULL: + (B d)[g]);
+ *                   one workgroup per row, fixed-order sums.
+ * mi_pcm_fock:      d_V[nao][nao] (accumulate ? += : =) scale * sum_g q_g B[g] unpacked symmetric; d_part holds
+ *                   mi_pcm_fock_chunks(npts, ld) * ld doubles of per-chunk column sums (added in index order, no atomics).
+ * mi_pcm_pairs:     the shell pairs of the launches (ordered = 1: all (i, j), the gradient's rows); returns their number,
+ *                   fills out[n][2] when out is not NULL.
+ * mi_pcm_grad:      d_part[n_ordered_pairs][nblk][3] = -2 sum_{g in block} q_g sum_{m in i, n in j} D_mn d/dA_i B[g]_mn:
+ *                   the share of the atom of shell i; the block's owning atom takes minus it (translational invariance). */
+int mi_pcm_pairs(mi_ctx *ctx, int ordered, int32_t *out);
+int mi_pcm_eval(mi_ctx *ctx, const double *d_pts, int npts, const int32_t *d_blk, int nblk, int64_t ld, double *d_B, void *stream);
+int mi_pcm_potential(mi_ctx *ctx, const double *d_B, int npts, int64_t ld, const double *d_D, double *d_dpack, const double *d_vn,
+                     double *d_v, void *stream);
+int mi_pcm_fock_chunks(int npts, int64_t ld);
+int mi_pcm_fock(mi_ctx *ctx, const double *d_B, int npts, int64_t ld, const double *d_q, double scale, int accumulate, double *d_part,
+                double *d_V, void *stream);
+int mi_pcm_grad(mi_ctx *ctx, const double *d_pts, int npts, const int32_t *d_blk, int nblk, const double *d_D, const double *d_q,
+                double *d_part, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
