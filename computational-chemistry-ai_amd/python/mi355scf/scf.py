@@ -18,6 +18,7 @@ import torch
 
 from . import engine as _engine
 from .mole import Mole
+from .purify import HEAD_MAX, Purifier
 
 AU2DEBYE = 2.541746473  # e*a0 -> Debye [MEM: pyscf.data.nist.AU2DEBYE]
 
@@ -142,9 +143,6 @@ class SCF:
     eig_method = "sp2"
     sp2_tol = 1e-11
     sp2_margin = 2     # purification steps kept beyond the first one that met sp2_tol in the previous cycle
-    sp2_fused = True   # small N: one fused HIP launch per SP2 step instead of rocBLAS DGEMM + update kernel
-    _sp2_iters = 24
-    _sp2_validated = False   # True once an iteration count has passed the checked path for this Fock spectrum
     sp2_fused_max = 320  # one fused launch per purification step up to here (single-batch panel loads), rocBLAS DGEMM + update above
     # Planned purification (sp2plan.py): the sequence of quadratics is fixed from bounds of the spectrum and of the HOMO/LUMO
     # taken at the last diagonalisation -- about half the steps of trace-correcting SP2.  The result is validated every cycle;
@@ -152,7 +150,6 @@ class SCF:
     sp2_planned = True
     sp2_inner_margin = 0.15   # Hartree the HOMO / LUMO may move towards the gap before the plan fails
     sp2_outer_margin = 2.0    # Hartree the extreme eigenvalues may move outwards
-    _sp2_plan = None
     _spin_restricted = True
     # Sharded runs: every rank decides redo / convergence / loop exit from its own replicated algebra.  The own kernels are free
     # of atomics (fixed-order partial sums) and `parallel.blas_atomics_off()` forbids atomics in rocBLAS, so those scalars are
@@ -547,12 +544,6 @@ class SCF:
         return (self.fused_fock and self._nranks == 1 and self._stream_groups <= 1 and getattr(self, "with_df", None) is None
                 and dm.dim() == 2 and dm.is_contiguous())
 
-    @staticmethod
-    def _sp2_traces(tr_host):
-        """(tr X, tr X^2) from the interleaved partial traces of the fused SP2 kernel (or a plain pair), added in index order."""
-        t = np.asarray(tr_host, dtype=np.float64).reshape(-1, 2)
-        return float(t[:, 0].sum()), float(t[:, 1].sum())
-
     def get_veff(self, mol=None, dm=None, **kw):
         if dm is None:
             dm = self.make_rdm1()
@@ -565,145 +556,15 @@ class SCF:
         e, c = torch.linalg.eigh(Li @ f @ Li.T)
         return e, Li.T @ c
 
-    def _density_sp2(self, f, nocc, orth=False):
-        """2 P_occ(F) without diagonalisation: D' in the orthonormal basis if `orth` (then `f` is F'), else
-        the AO density.  Returns None if the purification does not converge (e.g. vanishing HOMO-LUMO gap);
-        the caller then falls back to `eigh`."""
-        Li = self._Linv
-        self._sp2_orth = orth
-        fo = f if orth else Li @ f @ Li.T
-        n = fo.shape[0]
-        if nocc == 0 or nocc >= n:
-            return None
-        eng = self.engine
-        if n <= self.sp2_fused_max and self.sp2_fused:
-            return self._density_sp2_fused(fo, nocc)
-        buf = getattr(self, "_sp2_buf", None)
-        if buf is None or buf[0].numel() != 2 + n * n:
-            buf = [torch.empty(2 + n * n, dtype=torch.float64, device=fo.device) for _ in range(2)]
-            self._sp2_buf = buf
-            self._sp2_x2 = torch.empty(n, n, dtype=torch.float64, device=fo.device)
-        cur = 0
-        X = buf[cur][2:].view(n, n)
-        eng.sp2_init(fo.contiguous(), X, buf[1 - cur])
-        X2 = self._sp2_x2
-        nit = getattr(self, "_sp2_iters", 24)
-        target = float(nocc)
-        done = 0
-        for attempt in range(6):
-            for _ in range(nit - done):
-                torch.matmul(X, X, out=X2)
-                eng.sp2_update(X, X2, target, buf[1 - cur])   # one fused launch: traces, branch, update
-                cur = 1 - cur
-                X = buf[cur][2:].view(n, n)
-            done = nit
-            torch.matmul(X, X, out=X2)
-            tr = torch.stack([torch.trace(X), torch.trace(X2)]).cpu()
-            err = float(tr[0] - tr[1])          # = sum lambda (1 - lambda) >= 0
-            if abs(err) < self.sp2_tol and abs(float(tr[0]) - target) < 1e-8:
-                self._sp2_iters = nit
-                self._sp2_validated = True
-                Xs = X + X.T                       # exactly symmetric 2 X (see _sp2_planned_gemm)
-                return Xs if self._sp2_orth else Li.T @ Xs @ Li
-            nit += 8
-        return None
-
-    def _density_sp2_fused(self, fo, nocc):
-        """Same SP2 recursion, one fused HIP launch per step (`sp2_fused_kernel`, FP64 MFMA)."""
-        eng, Li = self.engine, self._Linv
-        n = fo.shape[0]
-        ws = getattr(self, "_sp2f", None)
-        if ws is None or ws["X"].shape[0] != n:
-            mk = lambda *s: torch.empty(*s, dtype=torch.float64, device=fo.device)
-            ws = self._sp2f = dict(X=mk(n, n), X2=mk(n, n), work=mk(2 * n * n), tr=mk(64 * 80), b=mk(2 * n))
-        nit = min(getattr(self, "_sp2_iters", 24), 72)
-        target = float(nocc)
-        nbd = (n + 15) // 16
-        for attempt in range(5):
-            eng.sp2_init(fo.contiguous(), ws["X"], ws["b"])
-            off = eng.sp2_iterate(ws["X"], ws["X2"], nit, target, ws["work"], ws["tr"])
-            tr = self._sp2_traces(ws["tr"][off:off + 2 * nbd].cpu().numpy())
-            err = float(tr[0] - tr[1])
-            if abs(err) < self.sp2_tol and abs(float(tr[0]) - target) < 1e-8:
-                self._sp2_iters = nit
-                self._sp2_validated = True
-                if (self.sp2_trace_plan and self.sp2_planned and self._sp2_plan is None and self._sp2_plannable(n)
-                        and off == 64 * nit):
-                    # cold object: the history of this checked run and the Gershgorin discs give the bounds for a plan
-                    # (one more small copy in a path that waits for the device anyway; see _plan_from_traces)
-                    h = torch.cat([ws["tr"][:off + 64], ws["b"][:2 * n]]).cpu().numpy()
-                    hh = h[:off + 64].reshape(nit + 1, 32, 2)[:, :nbd, :]
-                    self._trace_bounds = (hh[:, :, 0].sum(axis=1), hh[:, :, 1].sum(axis=1), float(h[off + 64:off + 64 + n].min()),
-                                          float(h[off + 64 + n:].max()), -1)
-                return 2.0 * ws["X"] if self._sp2_orth else 2.0 * (Li.T @ ws["X"] @ Li)
-            nit = min(nit + 8, 76)
-        return None
-
-    def _sp2_fused_async(self, fo, nocc):
-        """Optimistic SP2: enqueue the purification with the iteration count that worked last cycle and return
-        (D', device traces) WITHOUT a host sync; the caller validates tr(X - X^2) together with the cycle's other
-        scalars and redoes the cycle through the checked path if the count was too small."""
-        eng = self.engine
-        n = fo.shape[0]
-        ws = getattr(self, "_sp2f", None)
-        if ws is None or ws["X"].shape[0] != n:
-            mk = lambda *s: torch.empty(*s, dtype=torch.float64, device=fo.device)
-            ws = self._sp2f = dict(X=mk(n, n), X2=mk(n, n), work=mk(2 * n * n), tr=mk(64 * 80), b=mk(2 * n))
-        nit = min(self._sp2_iters, 76)
-        if n <= self.sp2_fused_max and self.sp2_fused:
-            pp = ws.get("pp")
-            if pp is None:   # two [X | X2] buffers: the passes ping-pong between them and the result is read where it lands
-                pp = ws["pp"] = (torch.empty(2, n, n, dtype=torch.float64, device=fo.device),
-                                 torch.empty(2, n, n, dtype=torch.float64, device=fo.device))
-            eng.sp2_init(fo.contiguous(), pp[0][0], ws["b"])
-            res, off = eng.sp2_iterate_pingpong(pp[0], pp[1], nit, float(nocc), ws["tr"])
-            # the partial traces of EVERY step (64 slots per step, 2 ceil(n/16) used): the host validates the last step and
-            # reads off the first step at which the projector was already converged (-> iteration count of the next cycle)
-            self._sp2_hist_shape = (nit + 1, (n + 15) // 16)
-            if self.sp2_trace_plan and self.sp2_planned and self._sp2_plan is None and self._sp2_plannable(n):
-                # cold object: the Gershgorin discs of this F' (already on the device for X_0) travel with the traces, so that the
-                # host can read spectral bounds for a purification PLAN off this run (sp2plan.bounds_from_traces)
-                self._sp2_hist_shape = (nit + 1, (n + 15) // 16, 2 * n)
-                return 2.0 * res[0], torch.cat([ws["tr"][:off + 64], ws["b"][:2 * n]])
-            return 2.0 * res[0], ws["tr"][:off + 64]
-        eng.sp2_init(fo.contiguous(), ws["X"], ws["b"])
-        # larger N: rocBLAS DGEMM + fused update kernel per step, still without a host sync
-        buf = getattr(self, "_sp2_buf", None)
-        if buf is None or buf[0].numel() != 2 + n * n:
-            buf = self._sp2_buf = [torch.empty(2 + n * n, dtype=torch.float64, device=fo.device) for _ in range(2)]
-        X, X2, cur = ws["X"], ws["X2"], 0
-        for _ in range(nit):
-            torch.matmul(X, X, out=X2)
-            eng.sp2_update(X, X2, float(nocc), buf[cur])
-            X = buf[cur][2:].view(n, n)
-            cur = 1 - cur
-        torch.matmul(X, X, out=X2)
-        return X + X.T, torch.stack([torch.trace(X), torch.trace(X2)])   # exactly symmetric 2 X (see _sp2_planned_gemm)
+    @property
+    def _purifier(self):
+        """The purification state of the density step (purify.Purifier)."""
+        p = self.__dict__.get("_pur")
+        if p is None or p.mf is not self:
+            p = self._pur = Purifier(self) if p is None else p.rebind(self)
+        return p
 
     xc_nelec_rtol = 2e-4   # relative error of the grid electron count a low-rank-factor cycle may show (level-3 grids: ~1e-5)
-    _HEAD_MAX = 4096   # doubles reserved in front of the planned-path trace history for [E partials | |g|^2 partials | extra]
-
-    def _sp2_planned_async(self, fo, nocc, scale=2.0):
-        """Planned purification, no host sync: (D' = 2 X, partial traces of every pass) -- validated by the caller like the
-        optimistic SP2 path.  The traces land behind `_HEAD_MAX` doubles of one persistent buffer whose head the Fock build
-        fills afterwards, so the cycle's scalars leave the device as ONE contiguous copy without a gather kernel."""
-        eng = self.engine
-        n = fo.shape[0]
-        if not (n <= self.sp2_fused_max and self.sp2_fused):
-            return self._sp2_planned_gemm(fo, nocc, scale)
-        ws = getattr(self, "_sp2p", None)
-        if ws is None or ws["n"] != n:
-            mk = lambda *s: torch.empty(*s, dtype=torch.float64, device=fo.device)
-            ws = self._sp2p = dict(n=n, scal=mk(self._HEAD_MAX + 64 * 80), pp=(mk(2, n, n), mk(2, n, n)))
-        want = int(bool(self.sp2_direct))
-        if getattr(eng, "_sp2_direct", None) != want:
-            eng.set_option("sp2_direct", want)
-            eng._sp2_direct = want
-        coef = self._sp2_plan[:self._sp2_plan_len + 1]
-        tr = ws["scal"][self._HEAD_MAX:]
-        res, off = eng.sp2_iterate_planned(fo.contiguous(), ws["pp"][0], ws["pp"][1], coef, tr, out_scale=scale)
-        self._sp2_hist_shape = (coef.shape[0], (n + 15) // 16)
-        return res[0], tr[:off + 64]   # a view of the ping-pong buffers: consumed by this cycle's Fock build, before the next pass
 
     # planned passes with the MFMA operands loaded straight into registers (engine option sp2_direct, N <= 320); MI355_SP2_DIRECT=0
     # selects the LDS-staged sp2_plan_kernel instead, so that the two can be compared on one box
@@ -715,41 +576,6 @@ class SCF:
     # plan, and every later kernel() of the object -- geometry steps, scans, restarts -- is planned and pipelined from its first
     # cycle.  True: also plan inside the first SCF, once it has settled (long SCFs).
     sp2_plan_inloop = False
-    sp2_planned_gemm = True   # N > sp2_fused_max: the same planned sequence with one rocBLAS DGEMM (addmm) per pass
-
-    def _sp2_plannable(self, n):
-        return (n <= self.sp2_fused_max and self.sp2_fused) or self.sp2_planned_gemm
-
-    def _sp2_planned_gemm(self, fo, nocc, scale=2.0):
-        """Planned purification for matrices beyond the fused kernel (ibuprofen N = 573, C60 N = 840): X_{k+1} = a X_k^2 + b X_k
-        + c I as ONE `addmm` (rocBLAS DGEMM with beta) plus a diagonal shift per pass -- half the passes of the trace-
-        correcting recursion of `_sp2_fused_async`, and no branch decisions on the device.  Only the last pass is checked:
-        tr X and tr X^2 = |X|_F^2 (X is symmetric) travel to the host with the cycle's other scalars."""
-        n = fo.shape[0]
-        coef = self._sp2_plan[:self._sp2_plan_len + 1]
-        buf = getattr(self, "_sp2g", None)
-        if buf is None or buf[0].shape[0] != n:
-            buf = self._sp2g = [torch.empty(n, n, dtype=torch.float64, device=fo.device) for _ in range(3)]
-        X = torch.mul(fo, float(coef[0, 1]), out=buf[0])
-        X.diagonal().add_(float(coef[0, 2]))
-        cur, nit = 0, coef.shape[0] - 1
-        for k in range(1, nit + 1):
-            a, b, c = (float(v) for v in coef[k])
-            Y = torch.addmm(X, X, X, beta=b, alpha=a, out=buf[(cur + 1) % 3])
-            cur = (cur + 1) % 3
-            if c != 0.0:
-                Y.diagonal().add_(c)
-            if k % 4 == 0 or k == nit:
-                # a library GEMM does not return X.X exactly symmetric, and the antisymmetric part A obeys A <- a (SA + AS) + b A:
-                # it can double per pass while the gap is being opened (1e-16 -> 1e-12 over 20 passes, measured).  The J/K kernel
-                # reads one triangle of D, so an asymmetric D shows up as 1e-9 Ha cycle-to-cycle jitter of a 650 Ha energy
-                # (tools/noise_check.py; the fused kernel's mirror stores keep X exactly symmetric)
-                Y = torch.add(Y, Y.T, out=buf[(cur + 1) % 3]).mul_(0.5)
-                cur = (cur + 1) % 3
-            X = Y
-        self._sp2_hist_shape = None
-        tr = torch.stack([torch.trace(X), torch.sum(X * X)])
-        return scale * X, tr
 
     # Cold object (round 3): the trace-correcting purification of a cycle leaves, for free, an interval inside the HOMO-LUMO gap
     # (sp2plan.gap_from_traces) and Gershgorin bounds outside; once |g| is below `sp2_trace_plan_gnorm` a plan is made from them
@@ -758,34 +584,6 @@ class SCF:
     sp2_trace_plan = True
     sp2_first_passes = 48     # passes of the very first (optimistic) purification of an object; 0: checked path
     sp2_trace_plan_gnorm = 2e-2
-    _trace_bounds = None
-    _sp2_plan_from_traces = False
-
-    def _plan_from_traces(self, nocc):
-        from . import sp2plan
-        tx, tx2, emin, emax, _cycle = self._trace_bounds
-        self._trace_bounds = None
-        b = sp2plan.bounds_from_traces(tx, tx2, emin, emax, self.sp2_inner_margin)
-        plan = sp2plan.plan(*b) if b is not None else None
-        if plan is not None:
-            self._sp2_plan = plan
-            self._sp2_plan_len = plan.shape[0] - 1
-            self._sp2_plan_gen = getattr(self, "_sp2_plan_gen", 0) + 1
-            self._sp2_plan_from_traces = True
-            self.path_counts["plan_from_traces"] = self.path_counts.get("plan_from_traces", 0) + 1
-
-    def _sp2_replan(self, mo_e, nocc):
-        """New plan from the eigenvalues of the (orthonormal-basis) Fock matrix just diagonalised."""
-        from . import sp2plan
-        e = mo_e.cpu().numpy() if torch.is_tensor(mo_e) else np.asarray(mo_e)
-        self._sp2_plan = None
-        self._sp2_plan_from_traces = False
-        self._sp2_plan_gen = getattr(self, "_sp2_plan_gen", 0) + 1
-        if self.sp2_planned and self.eig_method == "sp2" and 0 < nocc < len(e) and self._sp2_plannable(len(e)):
-            b = sp2plan.bounds_from_spectrum(e, nocc, self.sp2_inner_margin, self.sp2_outer_margin)
-            self._sp2_plan = sp2plan.plan(*b)
-            if self._sp2_plan is not None:
-                self._sp2_plan_len = self._sp2_plan.shape[0] - 1
 
     def make_rdm1(self, mo_coeff=None, mo_occ=None):
         if mo_coeff is None:
@@ -839,7 +637,7 @@ class SCF:
         mol = self.mol
         self._setup_once()
         eng = self.engine
-        self._trace_bounds = None
+        self._purifier.trace_bounds = None
         t0 = time.time()
         if dm0 is None:
             dm0 = self.get_init_guess()
@@ -849,25 +647,25 @@ class SCF:
         if self._nranks > 1:   # one-off: identical starting density on every rank (the atomic guess is built with atomics per rank)
             from . import parallel
             parallel.broadcast0(dm, self._pg)
-        self._fgraph = self._fgraph_seen = None     # a captured head belongs to one SCF (its CDIIS history buffers)
+        self._fgraph = self._fgraph_seen = None     # captured heads belong to one SCF (its CDIIS history buffers)
         st = {"nocc": mol.nelectron // 2, "enuc": mol.energy_nuc(), "cycle": 0, "diis": DeviceDIIS(eng, self.diis_space)}
         st["dmo"] = self._L.T @ dm @ self._L
         self._after_density(st, dm, e_last=None, next_cycle=0)
         self.timing["first_fock_seconds"] = time.time() - t0
         return st
 
-    def _after_density(self, st, dm, e_last, next_cycle, sp2_tr=None, nocc=0, hist_shape=None):
+    def _after_density(self, st, dm, e_last, next_cycle, sp2_tr=None, nocc=0, layout=None):
         """J/K(+XC) for `dm`, new Fock in the orthonormal basis, commutator error, energy, |g|; pushes
         (F', e) into the DIIS history and fetches all scalars of the cycle with ONE device-to-host copy."""
-        ctx = self._after_density_launch(st, dm, next_cycle, sp2_tr, hist_shape)
+        ctx = self._after_density_launch(st, dm, next_cycle, sp2_tr, layout)
         return self._after_density_finish(st, ctx, e_last, nocc)
 
     _PIN_DOUBLES = 16384
 
-    def _after_density_launch(self, st, dm, next_cycle, sp2_tr=None, hist_shape=None, projector=False):
+    def _after_density_launch(self, st, dm, next_cycle, sp2_tr=None, layout=None, projector=False):
         """Device part of `_after_density`: everything is queued, the scalars of the cycle are on their way to pinned host
         memory (asynchronous copy + event) when this returns -- the caller may queue more work before `_after_density_finish`
-        waits for them."""
+        waits for them.  `sp2_tr`, `layout`: the purification's device traces and their purify.Layout."""
         Li = self._Linv
         dm = dm.contiguous()
         # `projector`: dm = L^-T (2 X) L^-1 with X (= st["dmo"] / 2) an idempotent of rank n_occ -- lets the XC quadrature of
@@ -875,12 +673,11 @@ class SCF:
         self._xc_projector = (dm, st["dmo"], st["nocc"]) if projector else None
         nb = self.engine.reduce_blocks
         self.n_fock_builds = getattr(self, "n_fock_builds", 0) + 1
-        # partial sums of [E_elec | |[F',D']|^2]: on the planned path they go right in front of the trace history
-        ws = getattr(self, "_sp2p", None)
-        inplace = (sp2_tr is not None and ws is not None and 2 * nb <= self._HEAD_MAX
-                   and sp2_tr.data_ptr() == ws["scal"].data_ptr() + 8 * self._HEAD_MAX)
-        if inplace:
-            part = ws["scal"][self._HEAD_MAX - 2 * nb:self._HEAD_MAX]
+        # partial sums of [E_elec | |[F',D']|^2]: on the planned path they go right in front of the trace history, into the
+        # head of the buffer the traces sit in
+        head = layout.head if layout is not None and 2 * nb <= HEAD_MAX else None
+        if head is not None:
+            part = head[HEAD_MAX - 2 * nb:HEAD_MAX]
         else:
             part = torch.empty(2 * nb, dtype=torch.float64, device=dm.device)
         fock, extra = self._fock_energy(dm, part[:nb])
@@ -901,8 +698,8 @@ class SCF:
         self.engine.commutator_norm(m, eo, part[nb:])  # eo = [F', D'] and the partial sums of its squared norm
         if keep:
             diis.push_inplace()
-        if inplace and extra is None:
-            packed = ws["scal"][self._HEAD_MAX - 2 * nb:self._HEAD_MAX + sp2_tr.numel()]   # already contiguous: no gather kernel
+        if head is not None and extra is None:
+            packed = head[HEAD_MAX - 2 * nb:HEAD_MAX + sp2_tr.numel()]   # already contiguous: no gather kernel
         else:
             parts = [part] + ([extra.reshape(-1)] if extra is not None else []) + ([sp2_tr] if sp2_tr is not None else [])
             packed = torch.cat(parts) if len(parts) > 1 else part
@@ -913,7 +710,7 @@ class SCF:
             from . import parallel
             parallel.broadcast0(packed, self._pg)
         ctx = dict(dm=dm, fock=fock, fo=fo, nb=nb, n_extra=0 if extra is None else extra.numel(), has_tr=sp2_tr is not None,
-                   hist_shape=hist_shape, lowrank=self._xc_projector is not None,
+                   layout=layout, lowrank=self._xc_projector is not None,
                    packed=packed, event=None)
         k = packed.numel()
         if k <= self._PIN_DOUBLES:
@@ -949,31 +746,8 @@ class SCF:
                     return False
             e_el += float(vals[pos + ne - 1])
             pos += ne
-        if ctx["has_tr"]:
-            hist = vals[pos:]
-            shape = ctx["hist_shape"]
-            discs = None
-            if shape is not None and len(shape) > 2 and shape[2] and hist.size == shape[0] * 64 + shape[2]:
-                discs, hist = hist[-shape[2]:], hist[:-shape[2]]
-            if shape is not None and hist.size == shape[0] * 64:
-                h = hist.reshape(shape[0], 32, 2)[:, :shape[1], :]
-                tx, tx2 = h[:, :, 0].sum(axis=1), h[:, :, 1].sum(axis=1)     # per step, partials added in index order
-                ok = (np.abs(tx - tx2) < self.sp2_tol) & (np.abs(tx - nocc) < 1e-8)
-                if not ok[-1]:
-                    return False
-                self._sp2_validated = True
-                first_ok = int(np.argmax(ok))            # steps beyond it were not needed for this Fock matrix
-                if getattr(self, "_sp2_planned_pass", False):
-                    self._sp2_plan_len = min(self._sp2_plan.shape[0] - 1, max(first_ok + 1, 4))
-                else:
-                    self._sp2_iters = max(first_ok + self.sp2_margin, 4)
-                    if discs is not None:      # trace-correcting run of a cold object: keep what a plan needs (made in _step)
-                        nd = discs.size // 2
-                        self._trace_bounds = (tx.copy(), tx2.copy(), float(discs[:nd].min()), float(discs[nd:].max()), st["cycle"])
-            else:
-                trx, trx2 = self._sp2_traces(hist)
-                if not (abs(trx - trx2) < self.sp2_tol and abs(trx - nocc) < 1e-8):
-                    return False
+        if ctx["has_tr"] and not self._purifier.accept(vals[pos:], ctx["layout"], nocc):
+            return False
         e_tot = e_el + st["enuc"]
         n = ctx["fo"].shape[0]
         nvo = max((n - st["nocc"]) * st["nocc"], 1)
@@ -987,76 +761,129 @@ class SCF:
     cold_margin = 6        # extra purification passes queued while |g| > sp2_plan_gnorm (the needed count still moves)
     pipeline = True   # queue the device-only head of cycle k+1 (extrapolation, purification, density) before waiting for cycle k's scalars
 
-    def _front(self, st):
-        """Device-only head of the NEXT cycle, queued speculatively: CDIIS-extrapolated F' (coefficients solved on the device)
-        -> planned purification -> AO density.  The GPU works on it while the host reads back and checks the scalars of the
-        cycle that just finished; the caller drops it when that cycle turns out converged or invalid.  None when the next
-        cycle cannot take the planned path."""
-        nocc = st["nocc"]
-        n = self._Linv.shape[0]
-        if not (self.pipeline and self.eig_method == "sp2" and 0 < nocc < n and not self.level_shift
-                and st["cycle"] + 1 >= self.diis_start_cycle and st["diis"].count > 0):
-            return None
-        use_gnorm = self.sp2_trace_plan_gnorm if self._sp2_plan_from_traces else self.sp2_plan_gnorm
-        planned = (self.sp2_planned and self._sp2_plannable(n) and self._sp2_plan is not None
-                   and st.get("gnorm", 0.0) <= use_gnorm)
+    def _route(self, st, head=False, want_mo=False, redo_of=None):
+        """How the next density step obtains the occupied projector: (route, path_counts key or None, passes).  route is a
+        purify.Purifier route ('planned', 'optimistic', 'checked') or 'eigh'; passes is the pass count of 'optimistic'.
+        `head`: for the speculative head of the NEXT cycle (None when it cannot be queued); `redo_of`: the route of a cycle
+        whose result failed its check."""
+        if redo_of is not None:       # planned: the spectrum left the planned bounds -- diagonalise, which also gives new ones
+            return ("eigh", None, 0) if redo_of == "planned" else ("checked", None, 0)
+        pur = self._purifier
+        nocc, n, g = st["nocc"], self._Linv.shape[0], st.get("gnorm", 0.0)
+        sp2 = self.eig_method == "sp2" and not want_mo
+        planned_ok = sp2 and self.sp2_planned and 0 < nocc < n and not self.level_shift
+        settled = g <= (self.sp2_trace_plan_gnorm if pur.from_traces else self.sp2_plan_gnorm)
         # a COLD object (first kernel() of the object: no plan yet, see `sp2_plan_inloop`) pipelines too: the trace-correcting
         # purification needs no spectral bounds, only a pass count -- the one the previous cycle needed plus a margin that is
-        # generous while the spectrum still moves (a pass costs 7 us, a redone cycle a whole Fock build)
-        cold = (not planned and self.cold_pipeline and (self._sp2_validated or self.sp2_first_passes) and n <= self.sp2_fused_max and self.sp2_fused
-                and (self._sp2_plan is None or st.get("gnorm", 0.0) > use_gnorm))
-        if not (planned or cold):
+        # generous while the spectrum still moves (a pass costs 7 us, a redone cycle a whole Fock build).  The very first
+        # purification of an object has no count yet: `sp2_first_passes` in one go instead of the checked path's 24 / 32 / 40
+        # with a host round trip each (benzene/cc-pVTZ needs 34); too few -> a redo
+        cold_ok = self.cold_pipeline and (pur.validated or self.sp2_first_passes) and n <= self.sp2_fused_max
+        cold_passes = (min(pur.iters + (self.cold_margin if g > self.sp2_plan_gnorm else 0), 72) if pur.validated
+                       else self.sp2_first_passes)
+        if head:
+            if not (self.pipeline and sp2 and 0 < nocc < n and not self.level_shift
+                    and st["cycle"] + 1 >= self.diis_start_cycle and st["diis"].count > 0):
+                return None
+            if self.sp2_planned and pur.plan is not None and settled:
+                return "planned", "front_planned", 0
+            if cold_ok and (pur.plan is None or not settled):
+                return "optimistic", "front_cold", cold_passes
             return None
-        if planned and self.graph_front:
-            out = self._front_graphed(st, nocc)
+        # A plan needs spectral bounds, i.e. one diagonalisation (7 ms at N = 264, 40 ms at 573), and holds while HOMO / LUMO
+        # move by less than its margins.  From a superposition-of-atoms guess the spectrum moves more than that in the
+        # first two or three cycles (measured: a plan made at cycle 1 failed its trace check at cycles 2 and 3, each costing
+        # another diagonalisation and a second Fock build), so while the orbital gradient of the previous cycle is above
+        # `sp2_plan_gnorm` the trace-correcting purification runs instead -- it needs no bounds -- and the plan is made once,
+        # when the SCF has settled; warm starts (dm0 from a nearby geometry) plan at their first cycle.
+        if planned_ok and pur.plan is not None:
+            # not settled: a plan exists (seeded by an earlier SCF of this object) but this SCF is still far from its solution
+            # -- e.g. kernel() from the atomic guess again: the spectrum is not the planned one yet (measured: three redo
+            # cycles, each a diagonalisation and a second Fock build).  Checked purification until the SCF has settled.
+            return ("planned", "planned_nofront", 0) if settled else ("checked", "checked_unsettled_with_plan", 0)
+        if planned_ok and (g > self.sp2_plan_gnorm or not self.sp2_plan_inloop):     # no plan on this object yet
+            if g > self.sp2_plan_gnorm:
+                # optimistic with a generous margin, validated with the cycle's scalars (no host sync here)
+                return ("optimistic", None, cold_passes) if cold_ok else ("checked", None, 0)
+            # settled, but no plan on this object yet (see sp2_plan_inloop)
+            return ("optimistic", "optimistic_noplan", pur.iters) if pur.validated else ("checked", None, 0)
+        if planned_ok:
+            # no plan yet: diagonalise, which also yields the bounds for one.  (Bounds from ~130 Lanczos steps on the projected
+            # Fock matrix instead -- HOMO, LUMO with residual bounds, Gershgorin outside -- were tried: as torch vector ops they
+            # cost as much as rocSOLVER's syevd at N = 264, 7 ms, and needed redo cycles when a Ritz value had not converged;
+            # the plan survives on the object across kernel() calls, so warm starts pay nothing.)
+            return "eigh", None, 0
+        if sp2 and 0 < nocc < n:
+            return ("optimistic", None, pur.iters) if pur.validated else ("checked", None, 0)
+        return "eigh", None, 0
+
+    def _purify(self, route, fo, nocc, passes):
+        """(D', device traces or None, layout) by a purify.Purifier route; D' is None when the checked route failed."""
+        pur = self._purifier
+        if route == "planned":
+            return pur.planned(fo, nocc)
+        if route == "optimistic":
+            return pur.optimistic(fo, nocc, passes)
+        return pur.checked(fo, nocc), None, None
+
+    def _front(self, st):
+        """Device-only head of the NEXT cycle, queued speculatively: CDIIS-extrapolated F' (coefficients solved on the device)
+        -> purification -> AO density.  The GPU works on it while the host reads back and checks the scalars of the cycle that
+        just finished; the caller drops it when that cycle turns out converged or invalid.  None when the next cycle cannot
+        take a head."""
+        r = self._route(st, head=True)
+        if r is None:
+            return None
+        route, label, passes = r
+        if route == "planned" and self.graph_front:
+            out = self._front_graphed(st, st["nocc"])
             if out is not None:
                 return out
         fo = st["diis"].extrapolate()
-        if planned:
-            dmo, tr_dev = self._sp2_planned_async(fo, nocc)
-        else:
-            keep = self._sp2_iters
-            self._sp2_iters = min(keep + (self.cold_margin if st.get("gnorm", 0.0) > self.sp2_plan_gnorm else 0), 72)
-            if not self._sp2_validated:      # head of cycle 2, queued before cycle 1's first purification has been validated
-                self._sp2_iters = self.sp2_first_passes
-            dmo, tr_dev = self._sp2_fused_async(fo, nocc)
-            self._sp2_iters = keep
-        shape, self._sp2_hist_shape = self._sp2_hist_shape, None
+        dmo, tr_dev, layout = self._purify(route, fo, st["nocc"], passes)
         dm = (self._Linv.T @ dmo @ self._Linv).contiguous()
-        return dict(fo=fo, dmo=dmo, dm=dm, tr=tr_dev, shape=shape, planned=planned)
+        return dict(fo=fo, dmo=dmo, dm=dm, tr=tr_dev, layout=layout, route=route, label=label)
 
     # The planned head of a cycle is ~26 small launches (CDIIS combination, ~21 purification passes, 2-3 GEMMs) queued by the host
     # between the wait for cycle k's scalars and the J/K launch of cycle k+1.  On a loaded host (measured on boxes of the pool:
     # host time per cycle 0.26 ms or 0.6 ms from one run to the next) the device then waits for the host: 1.07 vs 1.25-1.5 ms per
-    # cycle.  Once the plan and the CDIIS history length are stable the head is captured ONCE as a HIP graph (torch.cuda.CUDAGraph:
+    # cycle.  Once the plan and the CDIIS history length are stable the head is captured as a HIP graph (torch.cuda.CUDAGraph:
     # our ctypes launches go to torch's current stream, which is the capturing one) and replayed with a single launch call.
+    # It is captured TWICE, into two output sets (F', projector, AO density, purification buffers, traces), and the two are
+    # replayed alternately: the head of cycle k+1 is queued before cycle k has been validated, and must not overwrite what
+    # cycle k still owns (its F' for a redo, its density for `st["dm"]`).
     graph_front = True
     _GRAPH_STABLE = 3   # cycles with an unchanged (plan, history length) before the head is captured
 
     def _front_graphed(self, st, nocc):
         """Replay (or capture) the planned head as a HIP graph; None = not available this cycle (the caller queues it eagerly)."""
         diis = st["diis"]
+        pur = self._purifier
         m = min(diis.count, diis.space)
-        key = (id(diis), m, self._sp2_plan_len, getattr(self, "_sp2_plan_gen", 0), self._Linv.data_ptr())
+        key = (id(diis), m, pur.plan_len, pur.plan_gen, self._Linv.data_ptr())
         g = self.__dict__.get("_fgraph")
-        if g is not None and g["key"] == key and g["diis"] is diis:   # (the graph holds `diis` alive: its address cannot be reused)
-            g["graph"].replay()
-            self._sp2_hist_shape = None
-            return dict(fo=g["fo"], dmo=g["dmo"], dm=g["dm"], tr=g["tr"], shape=g["shape"], planned=True)
-        seen = self.__dict__.get("_fgraph_seen")
-        if seen is None or seen[0] != key:
-            self._fgraph_seen = [key, 1]
-            return None
-        seen[1] += 1
-        if seen[1] < self._GRAPH_STABLE or m < diis.space:
-            return None
+        if g is None or g["key"] != key or g["diis"] is not diis:   # (the graph holds `diis` alive: its address cannot be reused)
+            seen = self.__dict__.get("_fgraph_seen")
+            if seen is None or seen[0] != key:
+                self._fgraph_seen = [key, 1]
+                return None
+            seen[1] += 1
+            if seen[1] < self._GRAPH_STABLE or m < diis.space:
+                return None
+            g = self._fgraph = dict(key=key, diis=diis, heads=[], turn=0)
+        i, g["turn"] = g["turn"], 1 - g["turn"]
+        if i < len(g["heads"]):
+            head = g["heads"][i]
+            head["graph"].replay()
+            return head["out"]
         try:
+            # head i uses purification buffers 1 - i: the first captured head must not touch those of the eager head (0), whose
+            # cycle is still in flight.  The second head is captured one cycle later, when buffers 0 are free again.
             def body():
                 fo = diis.extrapolate()
-                dmo, tr_dev = self._sp2_planned_async(fo, nocc)
-                shape, self._sp2_hist_shape = self._sp2_hist_shape, None
+                dmo, tr_dev, layout = pur.planned(fo, nocc, slot=1 - i)
                 dm = torch.matmul(self._Linv.T @ dmo, self._Linv)
-                return fo, dmo, dm, tr_dev, shape
+                return dict(fo=fo, dmo=dmo, dm=dm, tr=tr_dev, layout=layout, route="planned", label="front_planned")
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream()
             side.wait_stream(cur)
@@ -1065,10 +892,10 @@ class SCF:
             cur.wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                fo, dmo, dm, tr_dev, shape = body()
+                out = body()
             graph.replay()                   # the capture itself executes nothing
-            self._fgraph = dict(key=key, diis=diis, graph=graph, fo=fo, dmo=dmo, dm=dm, tr=tr_dev, shape=shape)
-            return dict(fo=fo, dmo=dmo, dm=dm, tr=tr_dev, shape=shape, planned=True)
+            g["heads"].append(dict(graph=graph, out=out))
+            return out
         except Exception as e:   # capture not possible on this stack: stay eager for good
             self.graph_front = False
             self._fgraph = None
@@ -1080,6 +907,7 @@ class SCF:
         energy, orbital gradient.  This is the unit bench.py times ("SCF iteration").  With `pipeline` the first three
         stages of a cycle are queued on the device by the PREVIOUS call, before it waited for its own scalars."""
         nocc, Li = st["nocc"], self._Linv
+        pur = self._purifier
         front = st.pop("front", None)
         if want_mo or not use_diis:
             front = None                                 # final cycle: plain diagonalisation of the last Fock matrix
@@ -1087,13 +915,14 @@ class SCF:
 
         def took(name):
             paths[name] = paths.get(name, 0) + 1
-        tr_dev, hist_shape = None, None
-        self._sp2_planned_pass = False
+
+        def eigh(fo):
+            e, c = torch.linalg.eigh(fo)
+            co = c[:, :nocc]
+            return e, c, 2.0 * co @ co.T
         if front is not None:
-            fo, dmo, tr_dev, hist_shape, dm = front["fo"], front["dmo"], front["tr"], front["shape"], front["dm"]
-            self._sp2_planned_pass = bool(front.get("planned", True))
-            took("front_planned" if self._sp2_planned_pass else "front_cold")
-            planned_ok = True
+            fo, dmo, tr_dev, layout, dm, route = (front[k] for k in ("fo", "dmo", "tr", "layout", "dm", "route"))
+            took(front["label"])
             st.pop("mo_e", None)
         else:
             if use_diis and st["cycle"] >= self.diis_start_cycle:
@@ -1104,78 +933,30 @@ class SCF:
                 # PySCF `level_shift`: raise the virtual space of the matrix the new orbitals come from, F' + s (1 - D'/2), D' the
                 # current projector x 2; it leaves a converged solution unchanged and is not applied to the final (extra) cycle
                 fo = fo + self.level_shift * (torch.eye(fo.shape[0], dtype=fo.dtype, device=fo.device) - 0.5 * st["dmo"])
-            use_sp2 = self.eig_method == "sp2" and not want_mo
-            n = fo.shape[0]
-            planned_ok = (use_sp2 and self.sp2_planned and self._sp2_plannable(n) and 0 < nocc < n and not self.level_shift)
-            dmo = None
-            # A plan needs spectral bounds, i.e. one diagonalisation (7 ms at N = 264, 40 ms at 573), and holds while HOMO / LUMO
-            # move by less than its margins.  From a superposition-of-atoms guess the spectrum moves more than that in the
-            # first two or three cycles (measured: a plan made at cycle 1 failed its trace check at cycles 2 and 3, each costing
-            # another diagonalisation and a second Fock build), so while the orbital gradient of the previous cycle is above
-            # `sp2_plan_gnorm` the trace-correcting purification runs instead -- it needs no bounds -- and the plan is made once,
-            # when the SCF has settled; warm starts (dm0 from a nearby geometry) plan at their first cycle.
-            early = planned_ok and self._sp2_plan is None and (st.get("gnorm", 0.0) > self.sp2_plan_gnorm or not self.sp2_plan_inloop)
-            settled = st.get("gnorm", 0.0) <= (self.sp2_trace_plan_gnorm if self._sp2_plan_from_traces else self.sp2_plan_gnorm)
-            if planned_ok and self._sp2_plan is not None and settled and not st.get("_redo"):
-                dmo, tr_dev = self._sp2_planned_async(fo, nocc)
-                self._sp2_planned_pass = True
-                took("planned_nofront")
-            elif planned_ok and self._sp2_plan is not None and not settled:
-                # a plan exists (seeded by an earlier SCF of this object) but this SCF is still far from its solution -- e.g.
-                # kernel() from the atomic guess again: the spectrum is not the planned one yet (measured: three redo cycles,
-                # each a diagonalisation and a second Fock build).  Checked purification until the SCF has settled.
-                dmo = self._density_sp2(fo, nocc, orth=True)
-                took("checked_unsettled_with_plan")
-            elif early and st.get("gnorm", 0.0) > self.sp2_plan_gnorm:
-                if (self.cold_pipeline and (self._sp2_validated or self.sp2_first_passes) and not st.get("_redo")
-                        and n <= self.sp2_fused_max and self.sp2_fused):
-                    # optimistic: last count + a generous margin, validated with the cycle's scalars (no host sync here).  The
-                    # very first purification of an object has no count yet: `sp2_first_passes` in one go instead of the checked
-                    # path's 24 / 32 / 40 with a host round trip each (benzene/cc-pVTZ needs 34); too few -> the redo below
-                    keep = self._sp2_iters
-                    self._sp2_iters = min(keep + self.cold_margin, 72) if self._sp2_validated else self.sp2_first_passes
-                    dmo, tr_dev = self._sp2_fused_async(fo, nocc)
-                    self._sp2_iters = keep
-                else:
-                    # checked purification (validated on the host inside, iteration count adapted there)
-                    dmo = self._density_sp2(fo, nocc, orth=True)
-            elif early and self._sp2_validated and not st.get("_redo"):
-                dmo, tr_dev = self._sp2_fused_async(fo, nocc)     # settled, but no plan on this object yet (see sp2_plan_inloop)
-                took("optimistic_noplan")
-            elif early:
-                dmo = self._density_sp2(fo, nocc, orth=True)
-            elif planned_ok:
-                # no plan yet: diagonalise below, which also yields the bounds for one.  (Bounds from ~130 Lanczos steps on the
-                # projected Fock matrix instead -- HOMO, LUMO with residual bounds, Gershgorin outside -- were tried: as torch
-                # vector ops they cost as much as rocSOLVER's syevd at N = 264, 7 ms, and needed redo cycles when a Ritz value
-                # had not converged; the plan survives on the object across kernel() calls, so warm starts pay nothing.)
-                pass
-            elif use_sp2 and self._sp2_validated and 0 < nocc < n and not st.get("_redo"):
-                dmo, tr_dev = self._sp2_fused_async(fo, nocc)
-            elif use_sp2:
-                dmo = self._density_sp2(fo, nocc, orth=True)
-            hist_shape, self._sp2_hist_shape = getattr(self, "_sp2_hist_shape", None), None
+            route, label, passes = self._route(st, want_mo=want_mo)
+            if label:
+                took(label)
+            dmo, tr_dev, layout = (None, None, None) if route == "eigh" else self._purify(route, fo, nocc, passes)
             if dmo is None:
                 took("eigh")
-                e, c = torch.linalg.eigh(fo)
-                co = c[:, :nocc]
-                dmo = 2.0 * co @ co.T
+                e, c, dmo = eigh(fo)
                 st.update(mo_e=e, mo_c=Li.T @ c)
-                if planned_ok or (want_mo and self.eig_method == "sp2" and not self.level_shift):
-                    self._sp2_replan(e, nocc)        # (final cycle: the orbital energies seed the plan of the NEXT kernel())
+                if self.eig_method == "sp2" and not self.level_shift and (want_mo or (self.sp2_planned and 0 < nocc < fo.shape[0])):
+                    pur.replan(e, nocc)        # (final cycle: the orbital energies seed the plan of the NEXT kernel())
             else:
                 st.pop("mo_e", None)
             dm = Li.T @ dmo @ Li
         saved = (st["dmo"], st["diis"].count)
         st["dmo"] = dmo
         e_prev = st["e_tot"]
-        ctx = self._after_density_launch(st, dm, st["cycle"] + 1, sp2_tr=tr_dev, hist_shape=hist_shape, projector=True)
+        ctx = self._after_density_launch(st, dm, st["cycle"] + 1, sp2_tr=tr_dev, layout=layout, projector=True)
         nxt = self._front(st) if (use_diis and not want_mo) else None
-        if (self.sp2_trace_plan and self._sp2_plan is None and self._trace_bounds is not None and use_diis and not want_mo
+        if (self.sp2_trace_plan and pur.plan is None and pur.trace_bounds is not None and use_diis and not want_mo
                 and st.get("gnorm", 1.0) <= self.sp2_trace_plan_gnorm):
             # cold object, SCF settling: the plan for the cycles to come is made HERE, from the traces of the last checked
             # purification, while the device is busy with this cycle's Fock build and the head of the next (1 ms of host time)
-            self._plan_from_traces(st["nocc"])
+            if pur.plan_from_traces():
+                took("plan_from_traces")
         ok = self._after_density_finish(st, ctx, e_prev, nocc)
         if not ok:
             # the optimistic purification had not converged (planned path: the spectrum left the planned bounds): roll the DIIS
@@ -1184,20 +965,15 @@ class SCF:
             self.n_redo = getattr(self, "n_redo", 0) + 1       # diagnostics (bench.py reports it: 0 in a settled loop)
             st["dmo"], st["diis"].count = saved
             st["e_tot"] = e_prev
-            self._sp2_validated = False
-            st["_redo"] = True
-            try:
-                dmo = None if self._sp2_planned_pass else self._density_sp2(fo, nocc, orth=True)
-                if dmo is None:
-                    e, c = torch.linalg.eigh(fo)
-                    co = c[:, :nocc]
-                    dmo = 2.0 * co @ co.T
-                    if self._sp2_planned_pass:
-                        self._sp2_replan(e, nocc)
-                st["dmo"] = dmo
-                self._after_density(st, Li.T @ dmo @ Li, e_last=e_prev, next_cycle=st["cycle"] + 1)
-            finally:
-                st.pop("_redo", None)
+            pur.validated = False
+            redo, _, _ = self._route(st, redo_of=route)
+            dmo = pur.checked(fo, nocc) if redo == "checked" else None
+            if dmo is None:
+                e, _c, dmo = eigh(fo)
+                if redo == "eigh":
+                    pur.replan(e, nocc)
+            st["dmo"] = dmo
+            self._after_density(st, Li.T @ dmo @ Li, e_last=e_prev, next_cycle=st["cycle"] + 1)
         if nxt is not None:
             st["front"] = nxt
         st["cycle"] += 1
@@ -1229,7 +1005,7 @@ class SCF:
             e_, c_ = torch.linalg.eigh(st["fo"])
             st["mo_e"], st["mo_c"] = e_, self._Linv.T @ c_
             if self.eig_method == "sp2" and not self.level_shift:
-                self._sp2_replan(e_, st["nocc"])
+                self._purifier.replan(e_, st["nocc"])
         self._dm, self._vhf = st["dm"], st["fock"] - self._h1
         self.e_tot = float(st["e_tot"])
         self.mo_energy = st["mo_e"].cpu().numpy()

@@ -12,6 +12,7 @@ import time
 import numpy as np
 import torch
 
+from .purify import Purifier
 from .scf import SCF
 
 
@@ -143,7 +144,7 @@ class UHF(SCF):
         na, nb = self.mol.nelec
         self.nelec = (na, nb)
         small = n < self.sp2_min_nao or self.eig_method != "sp2"
-        warm = all(no == 0 or sp.vals["_sp2_plan"] is not None for sp, no in zip(self._spin_states(n), (na, nb)))
+        warm = all(no == 0 or sp.plan is not None for sp, no in zip(self._spin_states(n), (na, nb)))
         use_fast = self.fast_loop and (small or (self.fast_loop == "always" and warm))
         if use_fast:
             return self._kernel_fast(dm0)
@@ -153,42 +154,17 @@ class UHF(SCF):
     # trace history gives the bounds of a purification PLAN for that spin (sp2plan.bounds_from_traces, as in the closed-shell
     # cold path) and the following cycles run the ~21 planned passes instead of the 40-60 of the recursion; the result is checked
     # on the host like the recursion's (this loop synchronises per spin anyway) and a failed check drops the plan.
-    def _planned_spin_density(self, fo, no, state, gnorm):
-        plan = state.get("plan")
+    def _planned_spin_density(self, fo, no, pur):
         n = fo.shape[0]
-        if plan is None or not (self.sp2_planned and self.sp2_trace_plan and n <= self.sp2_fused_max and self.sp2_fused):
+        if pur.plan is None or not (self.sp2_planned and self.sp2_trace_plan and n <= self.sp2_fused_max):
             return None
-        keep = (self._sp2_plan, getattr(self, "_sp2_plan_len", 0))
-        try:
-            self._sp2_plan, self._sp2_plan_len = plan["coef"], plan["len"]
-            res, tr_dev = self._sp2_planned_async(fo, no, scale=2.0)
-            shape, self._sp2_hist_shape = self._sp2_hist_shape, None
-        finally:
-            self._sp2_plan, self._sp2_plan_len = keep
-        hist = tr_dev.cpu().numpy()
-        if shape is None or hist.size != shape[0] * 64:
-            state["plan"] = None
+        res, tr_dev, layout = pur.planned(fo, no, scale=2.0)
+        if not pur.accept(tr_dev.cpu().numpy(), layout, no):
+            pur.plan = None                 # the spectrum left the planned window: checked recursion, new plan from its traces
             return None
-        h = hist.reshape(shape[0], 32, 2)[:, :shape[1], :]
-        tx, tx2 = h[:, :, 0].sum(axis=1), h[:, :, 1].sum(axis=1)
-        ok = (np.abs(tx - tx2) < self.sp2_tol) & (np.abs(tx - no) < 1e-8)
-        if not ok[-1]:
-            state["plan"] = None            # the spectrum left the planned window: checked recursion, new plan from its traces
-            return None
-        plan["len"] = min(plan["coef"].shape[0] - 1, max(int(np.argmax(ok)) + 1, 4))
         self.path_counts = getattr(self, "path_counts", {})
         self.path_counts["planned_spin"] = self.path_counts.get("planned_spin", 0) + 1
-        return res.clone()                  # (a view of the ping-pong buffers the other spin is about to reuse)
-
-    def _plan_spin_from_traces(self, state, gnorm):
-        tb, self._trace_bounds = self._trace_bounds, None
-        if tb is None or not (self.sp2_planned and self.sp2_trace_plan) or gnorm > self.sp2_trace_plan_gnorm:
-            return
-        from . import sp2plan
-        b = sp2plan.bounds_from_traces(tb[0], tb[1], tb[2], tb[3], self.sp2_inner_margin)
-        coef = sp2plan.plan(*b) if b is not None else None
-        if coef is not None:
-            state["plan"] = dict(coef=coef, len=coef.shape[0] - 1)
+        return res.clone()                  # (a view of the spin's ping-pong buffers, which its next purification reuses)
 
     def _seed_plans(self, mo_e):
         """Purification plans of both spins from the orbital energies of a finished SCF (for the next kernel() of this object)."""
@@ -197,63 +173,42 @@ class UHF(SCF):
             return
         for s_, sp in enumerate(self._spin_states(n)):
             if 0 < self.nelec[s_] < n:
-                self._with_spin(sp, self._sp2_replan, mo_e[s_], self.nelec[s_])
+                sp.replan(mo_e[s_], self.nelec[s_])
 
     scf = kernel
 
-    class _Spin:
-        """Purification state of one spin channel (plan, trimmed length, work buffers): swapped into the SCF object around the
-        calls of the shared `_sp2_*` helpers."""
-        KEYS = ("_sp2_plan", "_sp2_plan_len", "_sp2p", "_sp2g", "_sp2_hist_shape")
-
-        def __init__(self):
-            self.vals = {k: None for k in self.KEYS}
-            self.vals["_sp2_plan_len"] = 0
-
     def _spin_states(self, n):
-        """The purification plans live on the object: a geometry optimisation (same `mf`, `kernel(dm0=...)` per step) reuses the
-        plans of the previous geometry and diagonalises nothing after its first SCF."""
+        """The purifiers of the fast loop's two spin channels live on the object: a geometry optimisation (same `mf`,
+        `kernel(dm0=...)` per step) reuses the plans of the previous geometry and diagonalises nothing after its first SCF."""
         key = (n, tuple(self.nelec))
         if getattr(self, "_spin_key", None) != key:
-            self._spin_key, self._spin_pair = key, [UHF._Spin(), UHF._Spin()]
+            self._spin_key, self._spin_pair = key, [Purifier(self), Purifier(self)]
         return self._spin_pair
 
-    def _with_spin(self, sp, fn, *a, **kw):
-        saved = {k: getattr(self, k, None) for k in sp.KEYS}
-        for k in sp.KEYS:
-            setattr(self, k, sp.vals[k])
-        try:
-            return fn(*a, **kw)
-        finally:
-            for k in sp.KEYS:
-                sp.vals[k] = getattr(self, k, None)
-                setattr(self, k, saved[k])
-
     def _projector(self, st, s_, fo, nocc_s, allow_plan=True):
-        """(X_s, traces or None, hist_shape, planned?) for one spin: planned purification when a plan exists, else `eigh`
+        """(X_s, traces or None, their purify.Layout) for one spin: planned purification when a plan exists, else `eigh`
         (which also yields the bounds for a plan).  X_s is the occupied projector (occupation 1) in the orthonormal basis."""
         n = fo.shape[0]
         sp = st["spin"][s_]
         if nocc_s == 0:
-            return torch.zeros_like(fo), None, None, False
-        can_plan = (self.eig_method == "sp2" and self.sp2_planned and n >= self.sp2_min_nao and self._sp2_plannable(n)
-                    and 0 < nocc_s < n and not self.level_shift)
+            return torch.zeros_like(fo), None, None
+        can_plan = (self.eig_method == "sp2" and self.sp2_planned and n >= self.sp2_min_nao and 0 < nocc_s < n
+                    and not self.level_shift)
         settled = st.get("gnorm") is not None and st["gnorm"] <= self.sp2_plan_gnorm
-        if can_plan and allow_plan and sp.vals["_sp2_plan"] is not None and not settled:
-            # plans exist but this SCF is still far from its solution (see SCF._step): checked purification, no redo cycles
-            d2 = self._density_sp2(fo, nocc_s, orth=True)
+        if can_plan and allow_plan and sp.plan is not None and not settled:
+            # plans exist but this SCF is still far from its solution (see SCF._route): checked purification, no redo cycles
+            # (pass count shared by both spins: the object's own purifier)
+            d2 = self._purifier.checked(fo, nocc_s)
             if d2 is not None:
-                return 0.5 * d2, None, None, False
-        if can_plan and allow_plan and sp.vals["_sp2_plan"] is not None and settled:
-            x, tr = self._with_spin(sp, self._sp2_planned_async, fo, nocc_s, 1.0)
-            shape, sp.vals["_sp2_hist_shape"] = sp.vals["_sp2_hist_shape"], None
-            return x, tr, shape, True
+                return 0.5 * d2, None, None
+        if can_plan and allow_plan and sp.plan is not None and settled:
+            return sp.planned(fo, nocc_s, 1.0)
         self.n_eigh = getattr(self, "n_eigh", 0) + 1
         e, c = torch.linalg.eigh(fo)
         co = c[:, :nocc_s]
         if can_plan:
-            self._with_spin(sp, self._sp2_replan, e, nocc_s)
-        return co @ co.T, None, None, False
+            sp.replan(e, nocc_s)
+        return co @ co.T, None, None
 
     def _ulaunch(self, st, dm, dmo, next_cycle, trs):
         """Device part of a cycle after the densities: Fock pair, F'_s = L^-1 F_s L^-T into the DIIS slot, error vectors
@@ -293,7 +248,7 @@ class UHF(SCF):
             ctx["event"] = self._pin_event
         return ctx
 
-    def _ufinish(self, st, ctx, shapes, planned, e_last):
+    def _ufinish(self, st, ctx, layouts, e_last):
         """Host part: wait for the scalars, validate the purifications, update the state.  False: a purification was not
         converged (nothing in `st` touched)."""
         if ctx["event"] is not None:
@@ -311,20 +266,8 @@ class UHF(SCF):
                 continue
             hist = vals[pos:pos + k]
             pos += k
-            nocc_s = st["nocc"][s_]
-            shape = shapes[s_]
-            if shape is not None and hist.size == shape[0] * 64:
-                h = hist.reshape(shape[0], 32, 2)[:, :shape[1], :]
-                tx, tx2 = h[:, :, 0].sum(axis=1), h[:, :, 1].sum(axis=1)
-                ok = (np.abs(tx - tx2) < self.sp2_tol) & (np.abs(tx - nocc_s) < 1e-8)
-                if not ok[-1]:
-                    return False
-                sp = st["spin"][s_]
-                sp.vals["_sp2_plan_len"] = min(sp.vals["_sp2_plan"].shape[0] - 1, max(int(np.argmax(ok)) + 1, 4))
-            else:
-                trx, trx2 = self._sp2_traces(hist)
-                if not (abs(trx - trx2) < self.sp2_tol and abs(trx - nocc_s) < 1e-8):
-                    return False
+            if not st["spin"][s_].accept(hist, layouts[s_], st["nocc"][s_]):
+                return False
         e_tot = e_el + st["enuc"]
         gnorm = float(np.sqrt(max(c2, 0.0) / 2.0)) / np.sqrt(st["nvo"])
         st.update(dm=ctx["dm"], dmo=ctx["dmo"], F=ctx["F"], fo=ctx["fo"], e_tot=e_tot, gnorm=gnorm,
@@ -339,23 +282,20 @@ class UHF(SCF):
         if st.get("gnorm") is None or st["gnorm"] > self.sp2_plan_gnorm:
             return None
         for s_ in range(2):
-            if st["nocc"][s_] > 0 and st["spin"][s_].vals["_sp2_plan"] is None:
+            if st["nocc"][s_] > 0 and st["spin"][s_].plan is None:
                 return None
         n = self._Linv.shape[0]
-        if not (self.eig_method == "sp2" and self.sp2_planned and n >= self.sp2_min_nao and self._sp2_plannable(n)):
+        if not (self.eig_method == "sp2" and self.sp2_planned and n >= self.sp2_min_nao):
             return None
         fo = st["diis"].extrapolate()
         return self._udensities(st, fo)
 
     def _udensities(self, st, fo, allow_plan=True):
         Li = self._Linv
-        xs, trs, shapes, planned = [], [], [], []
-        for s_ in range(2):
-            x, tr, shape, pl = self._projector(st, s_, fo[s_], st["nocc"][s_], allow_plan)
-            xs.append(x); trs.append(tr); shapes.append(shape); planned.append(pl)
+        xs, trs, layouts = zip(*(self._projector(st, s_, fo[s_], st["nocc"][s_], allow_plan) for s_ in range(2)))
         dmo = torch.stack(xs)
         dm = torch.stack([Li.T @ xs[0] @ Li, Li.T @ xs[1] @ Li])
-        return dict(fo=fo, dmo=dmo, dm=dm, trs=trs, shapes=shapes, planned=planned)
+        return dict(fo=fo, dmo=dmo, dm=dm, trs=trs, layouts=layouts)
 
     def _ustep(self, st):
         front = st.pop("front", None)
@@ -372,7 +312,7 @@ class UHF(SCF):
         e_prev = st["e_tot"]
         ctx = self._ulaunch(st, front["dm"], front["dmo"], st["cycle"] + 1, front["trs"])
         nxt = self._ufront(st)
-        ok = self._ufinish(st, ctx, front["shapes"], front["planned"], e_prev)
+        ok = self._ufinish(st, ctx, front["layouts"], e_prev)
         if not ok:
             # a planned purification had not converged (the spectrum left the planned bounds): roll the DIIS push back and
             # redo the cycle by diagonalisation, which also refreshes the plans
@@ -381,7 +321,7 @@ class UHF(SCF):
             st["diis"].count = saved_count
             redo = self._udensities(st, front["fo"], allow_plan=False)
             ctx = self._ulaunch(st, redo["dm"], redo["dmo"], st["cycle"] + 1, redo["trs"])
-            self._ufinish(st, ctx, redo["shapes"], redo["planned"], e_prev)
+            self._ufinish(st, ctx, redo["layouts"], e_prev)
         if nxt is not None:
             st["front"] = nxt
         st["cycle"] += 1
@@ -411,7 +351,7 @@ class UHF(SCF):
               "spin": self._spin_states(n), "nvo": max(na * (n - na) + nb * (n - nb), 1), "e_tot": None}
         dmo0 = torch.stack([L.T @ dm[0] @ L, L.T @ dm[1] @ L])
         ctx = self._ulaunch(st, dm, dmo0, 0, [None, None])
-        self._ufinish(st, ctx, [None, None], [False, False], None)
+        self._ufinish(st, ctx, [None, None], None)
         conv_tol = self.conv_tol
         conv_tol_grad = self.conv_tol_grad if self.conv_tol_grad is not None else np.sqrt(conv_tol)
         self._log(4, f"init E= {st['e_tot']:.15g}")
@@ -512,7 +452,9 @@ class UHF(SCF):
         # larger matrices: occupied projector of each spin by SP2 purification (same GEMM-only path as RHF, `scf.py`)
         # instead of a diagonalisation per cycle; orbitals are then only needed once, after convergence
         use_sp2 = self.eig_method == "sp2" and n >= self.sp2_min_nao
-        sp2_state = [dict(_sp2_iters=self._sp2_iters, _sp2_validated=False) for _ in range(2)]
+        # one purifier per spin for this kernel() only (plans from the traces of its checked runs), starting from the object's
+        # pass count
+        pur = [Purifier(self, self._purifier.iters) for _ in range(2)]
 
         def new_density(Fx):
             if not use_sp2:
@@ -526,14 +468,15 @@ class UHF(SCF):
                     xs.append(out[-1])
                     continue
                 fo = (Li @ Fx[s_] @ Li.T).contiguous()
-                self._sp2_iters, self._sp2_validated = sp2_state[s_]["_sp2_iters"], sp2_state[s_]["_sp2_validated"]
-                g_prev = gnorm if cycle > 0 else 1.0e9          # (no orbital gradient before the first cycle has finished)
-                dmo = self._planned_spin_density(fo, no, sp2_state[s_], g_prev)
+                p = pur[s_]
+                dmo = self._planned_spin_density(fo, no, p)
                 if dmo is None:
-                    self._trace_bounds = None
-                    dmo = self._density_sp2(fo, no, orth=True)
-                    self._plan_spin_from_traces(sp2_state[s_], g_prev)
-                sp2_state[s_].update(_sp2_iters=self._sp2_iters, _sp2_validated=self._sp2_validated)
+                    dmo = p.checked(fo, no)
+                    g_prev = gnorm if cycle > 0 else 1.0e9          # (no orbital gradient before the first cycle has finished)
+                    if (p.trace_bounds is not None and self.sp2_planned and self.sp2_trace_plan
+                            and g_prev <= self.sp2_trace_plan_gnorm):
+                        p.plan_from_traces()
+                    p.trace_bounds = None
                 if dmo is None:      # purification did not converge (vanishing gap): diagonalise this spin
                     e_, c_ = torch.linalg.eigh(fo)
                     co = Li.T @ c_[:, :no]
@@ -587,6 +530,8 @@ class UHF(SCF):
                 break
         self.cycles = cycle
         self.timing["loop_seconds"] = time.time() - t_loop
+        if use_sp2:
+            self._purifier.iters = pur[1 if nb else 0].iters   # the count of the spin purified last carries over to the object
         if self.converged and self.conv_check:
             mo_e, mo_c = orbitals(F)
             dm = density(mo_c)

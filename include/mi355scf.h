@@ -66,11 +66,9 @@ void mi_release_cache(void);
  *                 derivative blocks of at least this many rows (20), two quartets per wave up to 64 rows (1)
  *   "vmat_xcd"    xc_vmat: XCD-aware workgroup order (1, default: the tiles of one split share an XCD's L2; 0: natural order)
  *   "vmat_wgs"    xc_vmat: workgroups aimed at by the split over the grid points (0 = 1024, two full rounds; -1 = round-1 formula)
- *   "sp2_persist" planned purification as ONE resident launch with grid barriers (0 = one launch per pass, default and faster;
- *                 1 = release/acquire fences, 2 = write-through stores + L2-bypassing loads)
  *   "sp2_direct"  planned purification, one launch per pass, N <= 320: 1 = sp2_direct_kernel (MFMA operands loaded straight into
  *                 registers from the columns of the symmetric X, no LDS staging), 0 = sp2_plan_kernel (default of a new context;
- *                 the SCF driver sets 1).  sp2_persist takes precedence */
+ *                 the SCF driver sets 1) */
 int mi_set_option(mi_ctx *ctx, const char *key, double value);
 
 /* One-electron integrals into device buffers (any of them may be NULL): overlap S, kinetic T, nuclear

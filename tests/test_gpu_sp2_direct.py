@@ -171,7 +171,7 @@ def test_sp2_direct_every_pass_symmetric_and_equal_to_the_plan_kernel(n):
 
 
 @pytest.mark.parametrize("atom,basis", [("H2O", "cc-pVDZ"), ("BENZENE", "cc-pVDZ")])
-def test_scf_energy_same_with_either_pass_kernel(atom, basis):
+def test_planned_scf_energy_same_with_either_pass_kernel(atom, basis):
     """Planned, pipelined SCF (second kernel() of an object, HIP-graph head included) with sp2_direct_kernel and with
     sp2_plan_kernel: the same converged energy and density."""
     import gpu4pyscf
@@ -185,7 +185,7 @@ def test_scf_energy_same_with_either_pass_kernel(atom, basis):
         mf = gpu4pyscf.scf.RHF(mol).to_gpu()
         mf.sp2_direct, mf.conv_tol = direct, 1e-10
         mf.kernel()
-        assert mf._sp2_plan is not None
+        assert mf._purifier.plan is not None
         e = mf.kernel()                      # planned from its first cycle
         assert mf.converged
         assert mf.engine._sp2_direct == int(direct)

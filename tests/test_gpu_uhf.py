@@ -100,7 +100,7 @@ def test_uhf_sp2_path_matches_diagonalisation():
     print("UHF C6H6+ cc-pVTZ:", res)
 
 
-def test_uhf_fast_loop_with_planned_purification_equals_the_plain_loop():
+def test_uhf_fast_loop_with_per_spin_purifiers_equals_the_plain_loop():
     """The orthonormal-basis UHF/UKS loop (device-side pair DIIS, planned purification per spin, pipelined step) against the
     plain loop: benzene cation / cc-pVDZ with the purification forced on (sp2_min_nao = 0).  The first kernel() of an object is
     cold (plain loop, seeds the plans from its final orbitals), the second runs the fast loop with those plans."""
@@ -118,7 +118,7 @@ def test_uhf_fast_loop_with_planned_purification_equals_the_plain_loop():
     mf.sp2_min_nao, mf.conv_tol, mf.fast_loop = 0, 1e-10, "always"
     e_cold = mf.kernel()                               # plain loop + plans
     assert mf.converged and abs(e_cold - e_ref) < 1e-9
-    assert all(sp.vals["_sp2_plan"] is not None for sp in mf._spin_pair)
+    assert all(sp.plan is not None for sp in mf._spin_pair)
     dm = mf.make_rdm1()
     e_warm = mf.kernel(dm0=dm)                         # fast loop, planned purification of both spins from the first cycle
     assert mf.converged and abs(e_warm - e_ref) < 1e-9 and mf.cycles <= 4

@@ -350,7 +350,7 @@ def test_planned_purification_reaches_the_projector_in_about_twenty_quadratics()
 def test_gap_interval_from_sp2_traces_lies_inside_the_true_gap():
     """sp2plan.gap_from_traces: from the (tr X_i, tr X_i^2) sequence of a trace-correcting SP2 run alone, an energy interval that
     contains no orbital energy and brackets the Fermi level -- also with a degenerate HOMO / LUMO -- and a plan made from it
-    purifies the matrix (the cold-object path of SCF._plan_from_traces)."""
+    purifies the matrix (the cold-object path of purify.Purifier.plan_from_traces)."""
     from mi355scf import sp2plan
     rng = np.random.default_rng(7)
     for n, nocc, degenerate in ((60, 12, False), (80, 21, True), (40, 5, False)):
@@ -383,6 +383,43 @@ def test_gap_interval_from_sp2_traces_lies_inside_the_true_gap():
         p = q[:, :nocc] @ q[:, :nocc].T
         assert np.abs(y - p).max() < 1e-9
     assert sp2plan.gap_from_traces([3.0, 3.0], [1.0, 1.0], -1.0, 1.0) is None      # no step with a small enough tr(X - X^2)
+
+
+def test_purification_trace_history_check():
+    """purify.check_history on synthetic histories in the kernels' layout (64 slots per pass, 2 ceil(n/16) interleaved
+    tr X / tr X^2 partials used, the rest never written): the first passing pass, a failing last pass, a tail of Gershgorin
+    discs, and garbage in the unused slots, which must not be read."""
+    from mi355scf.purify import Layout, check_history
+    n, nocc, tol = 40, 7, 1e-11
+    nbd = (n + 15) // 16                                   # 3 diagonal tiles
+
+    def history(traces, fill):
+        h = np.full((len(traces), 32, 2), fill)            # unused slots: garbage
+        for k, (tx, tx2) in enumerate(traces):
+            h[k, :nbd, 0] = tx / nbd                       # partials that add up to the pass's traces
+            h[k, :nbd, 1] = tx2 / nbd
+            h[k, 0, 0] += tx - h[k, :nbd, 0].sum()         # (exactly, in index order)
+            h[k, 0, 1] += tx2 - h[k, :nbd, 1].sum()
+        return h.reshape(-1)
+
+    conv = (float(nocc), float(nocc))
+    moving = [(9.3, 6.1), (7.6, 6.9), (7.01, 6.98)]
+    for fill in (np.nan, 1e300, -3.0):
+        # first passing pass in the middle
+        first, tx, tx2, discs = check_history(history(moving + [conv] * 3, fill), Layout(6, nbd), nocc, tol)
+        assert first == 3 and discs is None
+        assert np.allclose(tx, [t[0] for t in moving] + [nocc] * 3, rtol=0, atol=1e-12)
+        # the last pass fails: rejected, even though an earlier one passed
+        assert check_history(history(moving + [conv, conv, (7.0, 6.9)], fill), Layout(6, nbd), nocc, tol)[0] is None
+        # converged, but to the wrong occupation
+        assert check_history(history([(8.0, 8.0)] * 2, fill), Layout(2, nbd), nocc, tol)[0] is None
+        # a tail of Gershgorin discs (lower ends, then upper ends) behind the history
+        lo, hi = np.linspace(-20.0, -1.0, n), np.linspace(0.5, 9.0, n)
+        h = np.concatenate([history(moving + [conv], fill), lo, hi])
+        first, tx, tx2, discs = check_history(h, Layout(4, nbd, 2 * n), nocc, tol)
+        assert first == 3 and np.array_equal(discs, np.concatenate([lo, hi]))
+    with pytest.raises(ValueError):
+        check_history(np.zeros(64 * 3 + 1), Layout(3, nbd), nocc, tol)
 
 
 def test_density_fitting_host_helpers():

@@ -25,8 +25,10 @@ for rep in range(2):
     torch.cuda.synchronize()
     t_all = time.perf_counter()
     for i in range(9):
+        before = dict(getattr(mf, "path_counts", {}))
         t0 = time.perf_counter(); had_front = "front" in st; mf._step(st)
-        print(f"rep {rep} cycle {i + 1}: {1e3 * (time.perf_counter() - t0):7.2f} ms  front={had_front} planned={mf._sp2_planned_pass} iters={mf._sp2_iters} "
+        path = [k for k, v in mf.path_counts.items() if v != before.get(k, 0)]
+        print(f"rep {rep} cycle {i + 1}: {1e3 * (time.perf_counter() - t0):7.2f} ms  front={had_front} path={path} iters={mf._purifier.iters} "
               f"redo={getattr(mf, 'n_redo', 0)} |g|={st['gnorm']:.2e} E={st['e_tot']:.10f}", flush=True)
     torch.cuda.synchronize()
-    print(f"rep {rep}: 9 cycles {1e3 * (time.perf_counter() - t_all):.2f} ms  plan_len={getattr(mf, '_sp2_plan_len', None)} paths={mf.path_counts}")
+    print(f"rep {rep}: 9 cycles {1e3 * (time.perf_counter() - t_all):.2f} ms  plan_len={mf._purifier.plan_len} paths={mf.path_counts}")

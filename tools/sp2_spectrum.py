@@ -15,7 +15,7 @@ mf.kernel()
 fo = (mf._Linv @ (mf._h1 + mf._vhf) @ mf._Linv.T)
 d = torch.diagonal(fo); rad = fo.abs().sum(dim=1) - d.abs()
 out = dict(basis=basis, nao=mol.nao, nocc=mol.nelectron // 2, mo_energy=mf.mo_energy.tolist(), gersh_min=float((d - rad).min()),
-           gersh_max=float((d + rad).max()), sp2_iters=mf._sp2_iters, cycles=mf.cycles)
+           gersh_max=float((d + rad).max()), sp2_iters=mf._purifier.iters, cycles=mf.cycles)
 json.dump(out, open(os.path.join(ROOT, "gpurun_out", f"sp2_spectrum_{basis}.json"), "w"))
 print(basis, mol.nao, "emin", mf.mo_energy[0], "homo", mf.mo_energy[out["nocc"] - 1], "lumo", mf.mo_energy[out["nocc"]], "emax", mf.mo_energy[-1],
-      "gersh", out["gersh_min"], out["gersh_max"], "sp2_iters", mf._sp2_iters)
+      "gersh", out["gersh_min"], out["gersh_max"], "sp2_iters", mf._purifier.iters)

@@ -20,13 +20,13 @@ e, c = torch.linalg.eigh(fo)
 P = c[:, :nocc] @ c[:, :nocc].T
 print("gap", float(e[nocc] - e[nocc - 1]), "homo", float(e[nocc - 1]), "lumo", float(e[nocc]), "range", float(e[0]), float(e[-1]))
 mf.eig_method = "sp2"
-mf._sp2_replan(e, nocc)
-print("plan steps", mf._sp2_plan.shape[0] - 1)
-X2, tr = mf._sp2_planned_async(fo, nocc)
+mf._purifier.replan(e, nocc)
+print("plan steps", mf._purifier.plan.shape[0] - 1)
+X2, tr, _layout = mf._purifier.planned(fo, nocc)
 X = 0.5 * X2
 d = X - P
 print("planned gemm: |X-P|_F", float(d.norm()), "max", float(d.abs().max()), "tr", tr.cpu().numpy(), "tr(F d)", float((fo * d).sum()), "asym", float((X - X.T).abs().max()))
-D2 = mf._density_sp2(fo, nocc, orth=True)
+D2 = mf._purifier.checked(fo, nocc)
 d = 0.5 * D2 - P
 print("checked sp2 : |X-P|_F", float(d.norm()), "max", float(d.abs().max()), "tr(F d)", float((fo * d).sum()))
 Li = mf._Linv
