@@ -402,6 +402,8 @@ struct mi_ctx {
     bool eri_ready = false;
     // tunables (mi_set_option)
     int opt_runmax = 0;      // tiles per J/K work item (0 = auto: ntiles/2048 clamped to [8,64])
+    double opt_omega = 0.0;  // > 0: the next mi_eri_prepare stores erf(omega r12)/r12 integrals (long-range store)
+    double eri_omega = 0.0;  // omega of the current store (0: full Coulomb)
     int opt_jk_waves = 0;    // 0: one wave per work item, longest first; >0: that many waves, equal-cost shares
     int opt_jk_nt = 1;       // nontemporal loads for the tile stream
     double opt_grad_dtol = 1e-13; // gradient: skip quartets with q_ab q_cd max|G| below this (0: Schwarz only)
@@ -742,6 +744,10 @@ extern "C" int mi_set_option(mi_ctx *c, const char *key, double value)
     if (!c || !key) return fail("mi_set_option: null argument");
     std::string k(key);
     if (k == "runmax") c->opt_runmax = (int)value;           // takes effect at the next mi_eri_prepare
+    else if (k == "omega") {                                  // takes effect at the next mi_eri_prepare
+        if (!(value >= 0.0) || !std::isfinite(value)) return fail("mi_set_option: omega must be finite and >= 0");
+        c->opt_omega = value;
+    }
     else if (k == "jk_waves") c->opt_jk_waves = (int)value; // takes effect at the next mi_eri_prepare
     else if (k == "jk_nt") c->opt_jk_nt = (int)value;
     else if (k == "jk_pipe") c->opt_jk_pipe = (int)value;
@@ -997,7 +1003,19 @@ struct EriArgs {
     int prim_lds;            // > 0: stage the primitive-pair records of the quartet in LDS (room for this many records per quartet)
     double qtol;             // > 0: skip tasks with q_bra q_ket < qtol (kets of a surviving cluster that fail the Schwarz test themselves)
     unsigned xcd;            // > 0: XCD-aware block map with chunks of this many blocks (xcd_block), grid rounded up to 8 * xcd
+    double omega;            // > 0: erf(omega r12)/r12 integrals (long-range store, rys_attenuate); 0: full Coulomb
 };
+
+// Long-range (erf-attenuated) Rys quadrature: with theta = omega^2 / (omega^2 + rho), rho = p q / (p + q), the integrals of
+// erf(omega r12)/r12 are those of 1/r12 with the Rys argument theta x, the roots u theta and the weights (prefactor) sqrt(theta)
+// -- the substitution of the PCM kernels (pcm_eval).  `f` < n is a root function, f >= n a weight function.  Called only
+// under a uniform `omega > 0` branch, so the full-Coulomb path keeps its instruction sequence.
+__device__ inline double rys_attenuate(const RysDev &R, int n, int f, double rho, double x, double omega)
+{
+    const double w2 = omega * omega, th = w2 / (w2 + rho);
+    const double v = rys_eval(R, n, f, x * th);
+    return f < n ? v * th : v * sqrt(th);
+}
 
 // Block index -> position in the task order such that `C` consecutive positions run on ONE XCD (blocks b and b + 8 share an
 // XCD under the observed round-robin placement; speed only, never correctness): the pieces of a tile line written by
@@ -1218,7 +1236,8 @@ __global__ __launch_bounds__(64) void eri_rys_kernel(EriArgs A)
                 double p = b[0], q = k[0];
                 double dx = b[1] - k[1], dy = b[2] - k[2], dz = b[3] - k[3];
                 double x = p * q / (p + q) * (dx * dx + dy * dy + dz * dz);
-                rw[pql * 2 * n + f] = rys_eval(A.rys, n, f, x);
+                if (A.omega > 0.0) rw[pql * 2 * n + f] = rys_attenuate(A.rys, n, f, p * q / (p + q), x, A.omega);
+                else rw[pql * 2 * n + f] = rys_eval(A.rys, n, f, x);
             }
             __syncthreads();
             // ---- phase A
@@ -1308,7 +1327,9 @@ __device__ __forceinline__ void rys_core(const EriArgs &A, const PairRec &ab, co
                 const double *b = prim_b + (size_t)ip * 8, *k = prim_k + (size_t)jp * 8;
                 const double p = b[0], q = k[0];
                 const double dx = b[1] - k[1], dy = b[2] - k[2], dz = b[3] - k[3];
-                rw[pql * 2 * n + f] = rys_eval(A.rys, n, f, p * q / (p + q) * (dx * dx + dy * dy + dz * dz));
+                const double rho = p * q / (p + q), x = rho * (dx * dx + dy * dy + dz * dz);
+                if (A.omega > 0.0) rw[pql * 2 * n + f] = rys_attenuate(A.rys, n, f, rho, x, A.omega);
+                else rw[pql * 2 * n + f] = rys_eval(A.rys, n, f, p * q / (p + q) * (dx * dx + dy * dy + dz * dz));
             }
             __syncthreads();
             if (lane < npq * n * 3) {                  // 2-D recurrence tables
@@ -1700,6 +1721,7 @@ struct TpqArgs {
     const double *q_bra, *q_ket; // per-task Schwarz rejection (qtol > 0), see EriArgs
     double qtol;
     unsigned xcd;            // XCD-aware block map (xcd_block)
+    double omega;            // > 0: erf(omega r12)/r12 integrals (see rys_attenuate)
 };
 
 // HRR + cart->sph of one shell pair applied to one index of a register array:
@@ -1819,8 +1841,15 @@ __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_kernel(TpqArgs A)
             const double PQ[3] = {Px - kk[1], Py - kk[2], Pz - kk[3]};
             const double QC[3] = {kk[4], kk[5], kk[6]};
             const double pq1 = 1.0 / (p + q);
-            const double x = p * q * pq1 * (PQ[0] * PQ[0] + PQ[1] * PQ[1] + PQ[2] * PQ[2]);
-            const double pref = Kab * kk[7] * 34.986836655249725 /* 2 pi^2.5 */ * pq1 * sqrt(p + q) / (p * q);
+            double x = p * q * pq1 * (PQ[0] * PQ[0] + PQ[1] * PQ[1] + PQ[2] * PQ[2]);
+            double pref = Kab * kk[7] * 34.986836655249725 /* 2 pi^2.5 */ * pq1 * sqrt(p + q) / (p * q);
+            double th = 1.0;   // long-range store: argument x theta, roots u theta (below), prefactor sqrt(theta) (rys_attenuate)
+            if (A.omega > 0.0) {
+                const double w2 = A.omega * A.omega;
+                th = w2 / (w2 + p * q * pq1);
+                x *= th;
+                pref *= sqrt(th);
+            }
             // Rys roots u_r and weights w_r: Chebyshev interpolation from the LDS copy, asymptotic form beyond the table
             double u[NR], w[NR];
             if (x < nint * RYS_H) {
@@ -1845,6 +1874,10 @@ __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_kernel(TpqArgs A)
                 const double rx = 1.0 / x, rsx = rsqrt(x);
 #pragma unroll
                 for (int f = 0; f < NR; f++) { u[f] = A.rys.herm_r[NR * RYS_NMAX + f] * rx; w[f] = A.rys.herm_w[NR * RYS_NMAX + f] * rsx; }
+            }
+            if (A.omega > 0.0) {
+#pragma unroll
+                for (int f = 0; f < NR; f++) u[f] *= th;
             }
 #pragma unroll
             for (int r = 0; r < NR; r++) {
@@ -2290,6 +2323,7 @@ extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void 
     std::vector<double> &prim = c->h_prim, &Mbuf = c->h_M;
     prim.clear(); Mbuf.clear();
     c->tol = tol; c->grad_ready = false; c->rank = rank; c->nranks = nranks;
+    c->eri_omega = c->opt_omega;   // Schwarz bounds below stay full-Coulomb (valid for erf(omega r)/r, see the header)
     for (int la = 0; la <= LMAX; la++)
         for (int lb = 0; lb <= la; lb++) {
             PairClass &P = c->pc[pc_index(la, lb)];
@@ -2710,7 +2744,7 @@ extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void 
             HIPCHK(hipMemcpyAsync(d_comp, comp.data(), sizeof(uint32_t) * comp.size(), hipMemcpyHostToDevice, st));
             HIPCHK(hipStreamSynchronize(st)); // host vectors go out of scope below
             E.bra = B.d_recs; E.ket = Kc.d_recs; E.prim = c->d_prim; E.prefix = d_prefix; E.nbra = (int)B.recs.size();
-            E.comp = d_comp; E.work = d_work; E.rys = c->rys; E.diag = 0;
+            E.comp = d_comp; E.work = d_work; E.rys = c->rys; E.diag = 0; E.omega = c->eri_omega;
             E.ni = 2 * B.la + 1; E.nj = 2 * B.lb + 1; E.nk = 2 * Kc.la + 1; E.nl = 2 * Kc.lb + 1;
             E.own_table = nranks > 1 ? c->d_tile_table : nullptr;
             E.h_shared_np = B.mean_np; E.h_vary_mean = Kc.mean_np; E.h_vary_max4 = Kc.max4_np;
@@ -2752,7 +2786,7 @@ extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void 
                 Q.c2s = c->d_c2s;
                 for (int q = 0; q <= LMAX + 1; q++) Q.c2s_off[q] = c->c2s_off[q];
                 Q.rys = c->rys; Q.X = X; Q.shell_xyz = c->d_shell_xyz; Q.check_owner = nranks > 1;
-                Q.q_bra = E.q_bra; Q.q_ket = E.q_ket; Q.qtol = E.qtol; Q.xcd = xcd_tpq;
+                Q.q_bra = E.q_bra; Q.q_ket = E.q_ket; Q.qtol = E.qtol; Q.xcd = xcd_tpq; Q.omega = E.omega;
                 auto ta = std::chrono::steady_clock::now();
                 if (dbg) hipStreamSynchronize(st);
                 const int used = launch_eri_tpq(B.la, B.lb, Kc.la, Kc.lb, Q, st);
@@ -2893,6 +2927,8 @@ struct DfPairs {
 extern "C" int mi_df_build(mi_ctx *c, mi_ctx *aux, double *d_int3c, double *d_int2c, void *stream)
 {
     if (!c || !aux) return fail("mi_df_build: null context");
+    if (c->opt_omega != 0.0 || c->eri_omega != 0.0 || aux->opt_omega != 0.0 || aux->eri_omega != 0.0)
+        return fail("mi_df_build: density fitting of long-range (omega != 0) integrals is not implemented");
     if (aux->nbas < 2) return fail("mi_df_build: the auxiliary context needs at least one function plus the unit shell");
     const ShellH &U = aux->shells.back();
     if (U.l != 0 || U.nprim != 1 || U.exps[0] != 0.0) return fail("mi_df_build: the last auxiliary shell must be the unit s function (exponent 0)");
@@ -4715,11 +4751,15 @@ template <int N> __device__ inline DN<N> dsqrt(DN<N> a) { double s = sqrt(a.v); 
 template <int N> __device__ inline DN<N> dpow(DN<N> a, double p) { double f = pow(a.v, p); return chain(a, f, p * f / a.v); }
 template <int N> __device__ inline DN<N> datan(DN<N> a) { return chain(a, atan(a.v), 1.0 / (1.0 + a.v * a.v)); }
 template <int N> __device__ inline DN<N> dasinh(DN<N> a) { return chain(a, asinh(a.v), rsqrt(1.0 + a.v * a.v)); }
+template <int N> __device__ inline DN<N> derf(DN<N> a) { return chain(a, erf(a.v), 1.1283791670955126 * exp(-a.v * a.v)); } // 2/sqrt(pi) e^-x^2
 typedef DN<2> D2;
 typedef DN<5> D5;
 
 enum { XC_SLATER = 1, XC_B88 = 2, XC_VWN_RPA = 3, XC_VWN5 = 4, XC_LYP = 5, XC_PBE_X = 6, XC_PBE_C = 7,
-       XC_TPSS_X = 8, XC_TPSS_C = 9, XC_M062X_X = 10, XC_M062X_C = 11 };   // 8..11: meta-GGA (need tau)
+       XC_TPSS_X = 8, XC_TPSS_C = 9, XC_M062X_X = 10, XC_M062X_C = 11,   // 8..11: meta-GGA (need tau)
+       XC_B88_SR = 12 };   // short-range B88 (ITYH), GGA; needs its omega as the term's parameter
+// functional ids a closed-shell or spin GGA evaluation accepts (mi_xc_eval*, mi_xc_eval_spin*)
+__host__ inline bool xc_gga_kind(int k) { return (k >= XC_SLATER && k <= XC_PBE_C) || k == XC_B88_SR; }
 
 // ---- closed-shell energy densities per volume e(rho, sigma); T is a dual-number type
 template <class T> __device__ inline T f_slater(T rho) { return T(-0.7385587663820224) * dpow(rho, 4.0 / 3.0); } // -(3/4)(3/pi)^(1/3)
@@ -4732,6 +4772,36 @@ template <class T> __device__ inline T f_b88(T rho, T sig)
     T x = dsqrt(sig * T(0.25) + T(1e-300)) / r43;
     T corr = T(-beta) * r43 * x * x / (T(1.0) + T(6.0 * beta) * x * dasinh(x));
     return f_slater(rho) + T(2.0) * corr;
+}
+
+// ITYH attenuation (Iikura, Tsuneda, Yanai, Hirao, JCP 115, 3540 (2001)) of one spin channel's exchange by erfc(omega r12):
+//   F(a) = 1 - 8/3 a [sqrt(pi) erf(1/(2a)) + (2a - 4a^3) exp(-1/(4a^2)) - 3a + 4a^3],  a = omega / (2 k_sigma).
+// The bracket cancels catastrophically in FP64 for large a (relative error 4e-10 at a = 5, 3 % at a = 100; low-density grid
+// points reach a ~ 100), so from a = 4 on the asymptotic series 1/(36a^2) - 1/(960a^4) + 1/(26880a^6) - 1/(829440a^8) is used
+// (relative error 2e-11 at a = 4, 3e-12 at 5, ~1e-14 from 10 on; the closed form is good to ~1e-10 below the switch).
+#define ITYH_SERIES_A 4.0
+template <class T> __device__ inline T ityh_factor(T a)
+{
+    if (a.v >= ITYH_SERIES_A) {
+        const T i2 = T(1.0) / (a * a);
+        return i2 * (T(1.0 / 36.0) - i2 * (T(1.0 / 960.0) - i2 * (T(1.0 / 26880.0) - i2 * T(1.0 / 829440.0))));
+    }
+    const T a2 = a * a, a3 = a2 * a;
+    return T(1.0) - T(8.0 / 3.0) * a * (T(1.7724538509055159) * derf(T(0.5) / a) + (T(2.0) * a - T(4.0) * a3) * dexp(T(-0.25) / a2)
+                                        - T(3.0) * a + T(4.0) * a3);
+}
+
+// Short-range B88 of CAM-B3LYP, closed shell: per spin channel e_s^SR = e_s^B88 F(a_s) with e_s^B88 = -1/2 rho_s^(4/3) K_s (Slater
+// included, as f_b88), k_s = sqrt(9 pi / K_s) rho_s^(1/3), a_s = omega / (2 k_s).  omega > 0 (checked by the entry points).
+template <class T> __device__ inline T f_b88_sr(T rho, T sig, double omega)
+{
+    const double beta = 0.0042;
+    T rs = rho * T(0.5);                 // one spin channel
+    T r13 = dpow(rs, 1.0 / 3.0), r43 = rs * r13;
+    T x = dsqrt(sig * T(0.25) + T(1e-300)) / r43;
+    T K = T(1.8610514726982001) /* 3/2 (6/pi)^(1/3) */ + T(2.0 * beta) * x * x / (T(1.0) + T(6.0 * beta) * x * dasinh(x));
+    T a = T(0.5 * omega) / (dsqrt(T(9.0 * M_PI) / K) * r13);
+    return -(r43 * K * ityh_factor(a));  // 2 e_s^SR
 }
 
 // VWN fit: correlation energy per electron as a function of x = sqrt(rs)
@@ -5028,7 +5098,7 @@ template <class T> __device__ inline T f_m062x_c_spin(T ra, T rb, T saa, T sbb, 
     return e;
 }
 
-struct XcSpec { int n; int kind[8]; double coef[8]; };
+struct XcSpec { int n; int kind[8]; double coef[8]; double param[8]; };   // param: omega of an XC_B88_SR term
 
 // exc[g] = e(rho,sigma) per volume; wv[0] = 0.5 w de/drho ; wv[1..3] = 2 w de/dsigma * grad rho
 __global__ __launch_bounds__(256) void xc_eval_kernel(XcSpec X, const double *rho, const double *w, int64_t ng, int gga,
@@ -5052,6 +5122,7 @@ __global__ __launch_bounds__(256) void xc_eval_kernel(XcSpec X, const double *rh
             case XC_LYP: f = f_lyp(R, S); break;
             case XC_PBE_X: f = f_pbe_x(R, S); break;
             case XC_PBE_C: f = f_pbe_c(R, S); break;
+            case XC_B88_SR: f = f_b88_sr(R, S, X.param[t]); break;
             default: f = D2(0.0);
             }
             acc = acc + D2(X.coef[t]) * f;
@@ -5096,6 +5167,11 @@ __global__ __launch_bounds__(256) void xc_eval_spin_kernel(XcSpec X, const doubl
             case XC_SLATER: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](D5 r, D5) { return f_slater(r); }); break;
             case XC_B88: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](D5 r, D5 s_) { return f_b88(r, s_); }); break;
             case XC_PBE_X: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](D5 r, D5 s_) { return f_pbe_x(r, s_); }); break;
+            case XC_B88_SR: {
+                const double om = X.param[t];
+                f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [om](D5 r, D5 s_) { return f_b88_sr(r, s_, om); });
+                break;
+            }
             case XC_VWN_RPA: f = f_vwn_rpa_spin(Ra, Rb); break;
             case XC_VWN5: f = f_vwn5_spin(Ra, Rb); break;
             case XC_LYP: f = f_lyp_spin(Ra, Rb, Saa, Sab, Sbb); break;
@@ -5118,14 +5194,28 @@ __global__ __launch_bounds__(256) void xc_eval_spin_kernel(XcSpec X, const doubl
         }
 }
 
-extern "C" int mi_xc_eval_spin(const int32_t *kinds, const double *coefs, int nterms, const double *d_rhoa, const double *d_rhob,
-                               const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wva, double *d_wvb, void *stream)
+// kinds / coefs / params -> XcSpec; `params` (may be NULL) carries each term's runtime parameter: the omega of XC_B88_SR
+static int fill_gga_spec(XcSpec &X, const int32_t *kinds, const double *coefs, const double *params, int nterms, const char *who)
 {
-    if (nterms < 0 || nterms > 8) return fail("mi_xc_eval_spin: at most 8 functional terms");
-    if (!d_rhoa || !d_rhob || !d_w || !d_wva || !d_wvb) return fail("mi_xc_eval_spin: null argument");
-    XcSpec X{};
+    if (nterms < 0 || nterms > 8) return fail("%s: at most 8 functional terms", who);
+    X = XcSpec{};
     X.n = nterms;
-    for (int i = 0; i < nterms; i++) { X.kind[i] = kinds[i]; X.coef[i] = coefs[i]; }
+    for (int i = 0; i < nterms; i++) {
+        if (!xc_gga_kind(kinds[i])) return fail("%s: unknown functional id %d", who, kinds[i]);
+        X.kind[i] = kinds[i]; X.coef[i] = coefs[i]; X.param[i] = params ? params[i] : 0.0;
+        if (kinds[i] == XC_B88_SR && !(X.param[i] > 0.0 && std::isfinite(X.param[i])))
+            return fail("%s: term %d (short-range B88) needs omega > 0 in params", who, i);
+    }
+    return 0;
+}
+
+extern "C" int mi_xc_eval_spin_p(const int32_t *kinds, const double *coefs, const double *params, int nterms, const double *d_rhoa,
+                                 const double *d_rhob, const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wva, double *d_wvb,
+                                 void *stream)
+{
+    if (!d_rhoa || !d_rhob || !d_w || !d_wva || !d_wvb) return fail("mi_xc_eval_spin: null argument");
+    XcSpec X;
+    if (fill_gga_spec(X, kinds, coefs, params, nterms, "mi_xc_eval_spin")) return -1;
     if (ng <= 0) return 0;
     hipLaunchKernelGGL(xc_eval_spin_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, d_rhoa, d_rhob, d_w,
                        ng, gga, d_exc, d_wva, d_wvb);
@@ -5133,21 +5223,29 @@ extern "C" int mi_xc_eval_spin(const int32_t *kinds, const double *coefs, int nt
     return 0;
 }
 
-extern "C" int mi_xc_eval(const int32_t *kinds, const double *coefs, int nterms, const double *d_rho, const double *d_w,
-                          int64_t ng, int gga, double *d_exc, double *d_wv, double *d_vrho, double *d_vsigma, void *stream)
+extern "C" int mi_xc_eval_spin(const int32_t *kinds, const double *coefs, int nterms, const double *d_rhoa, const double *d_rhob,
+                               const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wva, double *d_wvb, void *stream)
 {
-    if (nterms < 0 || nterms > 8) return fail("mi_xc_eval: at most 8 functional terms");
+    return mi_xc_eval_spin_p(kinds, coefs, nullptr, nterms, d_rhoa, d_rhob, d_w, ng, gga, d_exc, d_wva, d_wvb, stream);
+}
+
+extern "C" int mi_xc_eval_p(const int32_t *kinds, const double *coefs, const double *params, int nterms, const double *d_rho,
+                            const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wv, double *d_vrho, double *d_vsigma,
+                            void *stream)
+{
     if (!d_rho || (d_wv && !d_w)) return fail("mi_xc_eval: null argument");
-    XcSpec X{};
-    X.n = nterms;
-    for (int i = 0; i < nterms; i++) {
-        if (kinds[i] < XC_SLATER || kinds[i] > XC_PBE_C) return fail("mi_xc_eval: unknown functional id %d", kinds[i]);
-        X.kind[i] = kinds[i]; X.coef[i] = coefs[i];
-    }
+    XcSpec X;
+    if (fill_gga_spec(X, kinds, coefs, params, nterms, "mi_xc_eval")) return -1;
     hipLaunchKernelGGL(xc_eval_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, d_rho, d_w, ng, gga,
                        d_exc, d_wv, d_vrho, d_vsigma);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+extern "C" int mi_xc_eval(const int32_t *kinds, const double *coefs, int nterms, const double *d_rho, const double *d_w,
+                          int64_t ng, int gga, double *d_exc, double *d_wv, double *d_vrho, double *d_vsigma, void *stream)
+{
+    return mi_xc_eval_p(kinds, coefs, nullptr, nterms, d_rho, d_w, ng, gga, d_exc, d_wv, d_vrho, d_vsigma, stream);
 }
 
 // ---- meta-GGA evaluation.  Closed shell: rho[0..3] = density and gradient, tau = 1/2 sum_i |grad phi_i|^2 (all electrons);
@@ -5156,12 +5254,13 @@ extern "C" int mi_xc_eval(const int32_t *kinds, const double *coefs, int nterms,
 typedef DN<3> D3;
 typedef DN<7> D7;
 template <class T>
-__device__ inline T xc_term_spin(int kind, T Ra, T Rb, T Saa, T Sab, T Sbb, T Ta, T Tb)
+__device__ inline T xc_term_spin(int kind, double prm, T Ra, T Rb, T Saa, T Sab, T Sbb, T Ta, T Tb)
 {
     switch (kind) {
     case XC_SLATER: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T) { return f_slater(r); });
     case XC_B88: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T s_) { return f_b88(r, s_); });
     case XC_PBE_X: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T s_) { return f_pbe_x(r, s_); });
+    case XC_B88_SR: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [prm](T r, T s_) { return f_b88_sr(r, s_, prm); });
     case XC_VWN_RPA: return f_vwn_rpa_spin(Ra, Rb);
     case XC_VWN5: return f_vwn5_spin(Ra, Rb);
     case XC_LYP: return f_lyp_spin(Ra, Rb, Saa, Sab, Sbb);
@@ -5185,7 +5284,7 @@ __global__ __launch_bounds__(256) void xc_eval_mgga_kernel(XcSpec X, const doubl
         D3 R = D3::var(r, 0), S = D3::var(gx * gx + gy * gy + gz * gz, 1), Tt = D3::var(fmax(t, 0.0), 2);
         D3 Rh = R * D3(0.5), S4 = S * D3(0.25), Th = Tt * D3(0.5);
         D3 acc(0.0);
-        for (int q = 0; q < X.n; q++) acc = acc + D3(X.coef[q]) * xc_term_spin(X.kind[q], Rh, Rh, S4, S4, S4, Th, Th);
+        for (int q = 0; q < X.n; q++) acc = acc + D3(X.coef[q]) * xc_term_spin(X.kind[q], X.param[q], Rh, Rh, S4, S4, S4, Th, Th);
         e = acc.v; vr = acc.d[0]; vs = acc.d[1]; vt = acc.d[2];
     }
     if (exc) exc[g] = e;
@@ -5214,7 +5313,7 @@ __global__ __launch_bounds__(256) void xc_eval_mgga_spin_kernel(XcSpec X, const 
         D7 Sbb = D7::var(gb[0] * gb[0] + gb[1] * gb[1] + gb[2] * gb[2], 4);
         D7 Ta = D7::var(fmax(taua[g], 0.0), 5), Tb = D7::var(fmax(taub[g], 0.0), 6);
         D7 acc(0.0);
-        for (int q = 0; q < X.n; q++) acc = acc + D7(X.coef[q]) * xc_term_spin(X.kind[q], Ra, Rb, Saa, Sab, Sbb, Ta, Tb);
+        for (int q = 0; q < X.n; q++) acc = acc + D7(X.coef[q]) * xc_term_spin(X.kind[q], X.param[q], Ra, Rb, Saa, Sab, Sbb, Ta, Tb);
         e = acc.v;
         for (int k = 0; k < 7; k++) v[k] = acc.d[k];
     }
@@ -6541,6 +6640,7 @@ extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d
 {
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail("mi_grad_eri: bad rank/nranks");
     if (!c || !d_D || !d_grad) return fail("mi_grad_eri: null argument");
+    if (c->opt_omega != 0.0 || c->eri_omega != 0.0) return fail("mi_grad_eri: no derivative integrals for a long-range (omega != 0) context");
     if (!c->eri_ready) return fail("mi_grad_eri: call mi_eri_prepare first");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
@@ -6847,6 +6947,8 @@ extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d
 extern "C" int mi_df_grad(mi_ctx *c, mi_ctx *aux, const double *d_Z3, const double *d_Z2, double *d_grad, int rank, int nranks, void *stream)
 {
     if (!c || !aux || !d_grad) return fail("mi_df_grad: null argument");
+    if (c->opt_omega != 0.0 || c->eri_omega != 0.0 || aux->opt_omega != 0.0 || aux->eri_omega != 0.0)
+        return fail("mi_df_grad: no derivative integrals for a long-range (omega != 0) context");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail("mi_df_grad: bad rank/nranks");
     if (aux->nbas < 2) return fail("mi_df_grad: the auxiliary context needs at least one function plus the unit shell");
     if (aux->natm != c->natm) return fail("mi_df_grad: orbital and auxiliary contexts must share the atom list");

@@ -5,6 +5,10 @@ Reference call sites: `templates/calculate_energy.py:148-149,163-164,202-203` (`
 HYB_GGA_XC_B3LYP (VWN-RPA) as PySCF >= 2.3 does [MEM].  XC quadrature: HIP kernels for AO values,
 density, functional (forward-mode dual numbers) and weighted AOs; the two dense contractions per grid
 block are rocBLAS DGEMMs (FP64 MFMA) through torch.matmul.
+
+Range-separated hybrid CAM-B3LYP (Yanai, Tew, Handy 2004): exact exchange K_eff = hyb K + (alpha - hyb) K_LR with K_LR from a
+second, long-range ERI store (`omega` engine option: erf(omega r12)/r12 integrals), semilocal part 0.35 B88 + 0.46 B88_SR(omega)
++ 0.19 VWN5 + 0.81 LYP (VWN5 as libxc's HYB_GGA_XC_CAM_B3LYP [MEM]).  `rsh_coeff` mirrors PySCF's `rsh_and_hybrid_coeff`.
 """
 import os
 
@@ -15,13 +19,22 @@ from .grids import Grids, _grid_generation
 from .scf import RHF
 
 XC_IDS = {"slater": 1, "b88": 2, "vwn_rpa": 3, "vwn5": 4, "lyp": 5, "pbe_x": 6, "pbe_c": 7,
-          "tpss_x": 8, "tpss_c": 9, "m062x_x": 10, "m062x_c": 11}
+          "tpss_x": 8, "tpss_c": 9, "m062x_x": 10, "m062x_c": 11, "b88_sr": 12}
 MGGA_KINDS = ("tpss_x", "tpss_c", "m062x_x", "m062x_c")
+PARAM_KINDS = ("b88_sr",)   # terms whose kernel takes omega as a runtime parameter (mi_xc_eval_p)
+
+# Range-separated hybrids: key -> (omega, alpha, hyb) as PySCF's rsh_and_hybrid_coeff returns them: exact exchange
+# vk = hyb K + (alpha - hyb) K_LR.  CAM-B3LYP: alpha + beta = 0.65 at long range, alpha = 0.19 at short range, omega = 0.33.
+_RSH = {"CAMB3LYP": (0.33, 0.65, 0.19)}
+
+
+def _xc_key(name):
+    return str(name).upper().replace("-", "").replace("_", "").replace(" ", "")
 
 
 def parse_xc(name):
     """-> (hyb, [(coef, kind_id)], level): level 0 LDA, 1 GGA, 2 meta-GGA (truthy wherever AO gradients are needed)."""
-    key = str(name).upper().replace("-", "").replace("_", "").replace(" ", "")
+    key = _xc_key(name)
     table = {
         "HF": (1.0, []),
         "B3LYP": (0.2, [(0.08, "slater"), (0.72, "b88"), (0.19, "vwn_rpa"), (0.81, "lyp")]),
@@ -41,6 +54,8 @@ def parse_xc(name):
         "TPSS": (0.0, [(1.0, "tpss_x"), (1.0, "tpss_c")]),
         "TPSS,TPSS": (0.0, [(1.0, "tpss_x"), (1.0, "tpss_c")]),
         "M062X": (0.54, [(1.0, "m062x_x"), (1.0, "m062x_c")]),
+        # range-separated hybrid: `hyb` is the short-range fraction 0.19; the long-range exchange comes through rsh_coeff
+        "CAMB3LYP": (0.19, [(0.35, "b88"), (0.46, "b88_sr"), (0.19, "vwn5"), (0.81, "lyp")]),
     }
     if key not in table:
         raise NotImplementedError(f"xc functional '{name}' is not implemented on the MI355X engine "
@@ -48,6 +63,86 @@ def parse_xc(name):
     hyb, terms = table[key]
     gga = 2 if any(k in MGGA_KINDS for _c, k in terms) else int(any(k not in ("slater", "vwn_rpa", "vwn5") for _c, k in terms))
     return hyb, [(c, XC_IDS[k]) for c, k in terms], gga
+
+
+def rsh_coeff(name):
+    """(omega, alpha, hyb) of PySCF's rsh_and_hybrid_coeff [MEM]: exact exchange hyb K + (alpha - hyb) K_LR with K_LR built
+    from erf(omega r12)/r12.  (0, hyb, hyb) for every global hybrid and pure functional (HF: (0, 1, 1))."""
+    hyb = parse_xc(name)[0]
+    return _RSH.get(_xc_key(name), (0.0, hyb, hyb))
+
+
+def is_rsh(name):
+    return name is not None and rsh_coeff(name)[0] != 0.0
+
+
+def xc_params(name):
+    """Runtime parameter of each term of parse_xc(name)[1] (omega of a short-range B88 term, 0 otherwise), or None when no
+    term takes one -- the argument `params` of Engine.xc_eval / xc_eval_spin."""
+    terms = parse_xc(name)[1]
+    ids = {XC_IDS[k] for k in PARAM_KINDS}
+    if not any(k in ids for _c, k in terms):
+        return None
+    omega = rsh_coeff(name)[0]
+    return [omega if k in ids else 0.0 for _c, k in terms]
+
+
+def require_no_rsh(mf, what):
+    """NotImplementedError for paths that have no long-range exchange (K_LR) and would silently drop it."""
+    xc = getattr(mf, "xc", None)
+    if is_rsh(xc):
+        raise NotImplementedError(f"{what}: not implemented for the range-separated hybrid {xc} (no long-range exchange "
+                                  "integrals on this path)")
+
+
+def check_rsh_scf(mf):
+    """Configurations a range-separated-hybrid SCF refuses instead of running without K_LR."""
+    xc = mf.xc
+    if getattr(mf, "omega", None) is not None:
+        raise NotImplementedError(f"{xc}: mf.omega overrides are not implemented (the functional's own omega is used)")
+    if getattr(mf, "with_df", None) is not None:
+        raise NotImplementedError(f"{xc}: density fitting is not implemented for range-separated hybrids")
+    if getattr(mf, "with_solvent", None) is not None:
+        raise NotImplementedError(f"{xc}: PCM solvation is not implemented for range-separated hybrids")
+    if mf._nranks > 1:
+        raise NotImplementedError(f"{xc}: sharded runs are not implemented for range-separated hybrids")
+    if mf._stream_groups > 1:
+        raise NotImplementedError(f"{xc}: the ERI store does not fit (direct mode); not implemented for range-separated hybrids")
+
+
+def lr_engine(mf):
+    """The SCF object's long-range engine: a second context on the same molecule with the `omega` option, its store evaluated
+    once per geometry at the SCF's Schwarz threshold (lazily; dropped by reset()).  Holds K_LR's integrals beside the main store
+    (twice the HBM of a global hybrid)."""
+    from . import engine as _engine
+    omega = rsh_coeff(mf.xc)[0]
+    main = mf.engine
+    key = (id(mf.mol), omega, float(mf.direct_scf_tol), main.device)
+    e = mf.__dict__.get("_eng_lr")
+    if e is not None and mf.__dict__.get("_eng_lr_key") == key and e.mol is mf.mol:
+        return e
+    drop_lr_engine(mf)
+    e = _engine.Engine(mf.mol, device=main.device)
+    e.set_option("omega", omega)
+    try:
+        st = e.prepare_eri(mf.direct_scf_tol)
+    except _engine.EngineOutOfMemory as x:
+        e.close()
+        raise _engine.EngineError(f"{mf.xc}: the long-range ERI store ({x.need_bytes / 1e9:.1f} GB) does not fit in free HBM "
+                                  f"({x.free_bytes / 1e9:.1f} GB) beside the full store; direct mode is not implemented for "
+                                  "range-separated hybrids") from None
+    mf._eng_lr, mf._eng_lr_key = e, key
+    mf.timing["eri_lr_seconds"] = st["seconds_eri"]
+    mf._log(4, f"long-range ERI store (omega = {omega}): {st['n_tiles']} tiles, {st['stored_bytes'] / 1e6:.1f} MB in "
+               f"{st['seconds_eri']:.3f} s")
+    return e
+
+
+def drop_lr_engine(mf):
+    e = mf.__dict__.pop("_eng_lr", None)
+    mf.__dict__.pop("_eng_lr_key", None)
+    if e is not None:
+        e.close()
 
 
 class RKS(RHF):
@@ -71,6 +166,7 @@ class RKS(RHF):
         self.grids.level, self.grids.prune = old.level, old.prune   # user settings survive scanner / optimize() resets
         self._pruned = False
         self._ao_cache_key = self._ao_cache = None                  # AO values of the old geometry: drop (and free) them
+        drop_lr_engine(self)                                        # long-range store of the old geometry (CAM-B3LYP)
         return self
 
     def _setup(self):
@@ -95,6 +191,7 @@ class RKS(RHF):
         fraction of the functional."""
         eng = self.engine
         hyb, terms, gga = parse_xc(self.xc)
+        params = xc_params(self.xc)
         n = eng.nao
         coords, weights = self.grids.coords, self.grids.weights
         ng = coords.shape[0]
@@ -138,7 +235,7 @@ class RKS(RHF):
             if gga == 2:
                 e, wv = eng.xc_eval_mgga(terms, rho, tau, w)
             else:
-                e, wv = eng.xc_eval(terms, rho, w, gga)
+                e, wv = eng.xc_eval(terms, rho, w, gga, params=params)
             eng.xc_tail(w, (rho[0], e), tail)     # tail[0] += w.rho (N_elec), tail[1] += w.e (E_xc): one deterministic launch
             if os.environ.get("MI355_VMAT_MT") and not getattr(self, "_vmat_mt_set", False):
                 eng.set_option("vmat_fold_mt", float(os.environ["MI355_VMAT_MT"]))
@@ -273,6 +370,8 @@ class RKS(RHF):
         nn = n * n
         hyb = parse_xc(self.xc)[0]
         with_k = abs(hyb) > 1e-12
+        if is_rsh(self.xc):
+            return self._fock_energy_rsh(dm, part)
         if self._fused_fock_ok(dm):
             # single rank, resident tiles: no collective, so J and K need not exist -- the fused epilogue of the J/K pass adds
             # h, the unsymmetrised XC matrix and its transpose, and writes the energy partials (mi_build_fock)
@@ -307,6 +406,30 @@ class RKS(RHF):
         eng.fock_energy(self._h1, J, K, vxc, dm, 0.5 * hyb, F, part)
         return F, tail[0:2]      # [N_elec, E_xc]: the last entry is added to the energy, the first validates the quadrature
 
+    def _fock_energy_rsh(self, dm, part):
+        """Range-separated hybrid: F = h + J - 1/2 K_eff + V_xc, E2 = 1/2 tr(D J) - 1/4 tr(D K_eff) + E_xc with
+        K_eff = hyb K + (alpha - hyb) K_LR; K_LR from one K-only pass over the long-range store.  Unfused path (one rank,
+        resident stores only: check_rsh_scf)."""
+        check_rsh_scf(self)
+        eng = self.engine
+        n = eng.nao
+        nn = n * n
+        _omega, alpha, hyb = rsh_coeff(self.xc)
+        buf = torch.zeros(3 * nn + 2, dtype=torch.float64, device=eng.device)
+        J, K, V = buf[:nn].view(n, n), buf[nn:2 * nn].view(n, n), buf[2 * nn:3 * nn].view(n, n)
+        tail = buf[3 * nn:]
+        self._nr_rks_raw(dm, V, tail)
+        self._jk_into(dm, J, K)
+        _j, Klr = lr_engine(self).get_jk(dm, with_j=False)
+        K.mul_(hyb).add_(Klr, alpha=alpha - hyb)
+        self._nelec_grid = tail[0]
+        F = torch.empty_like(J)
+        eng.fock_energy(self._h1, J, K, V + V.T, dm, 0.5, F, part)
+        return F, tail[0:2]
+
+    def _fused_fock_ok(self, dm):
+        return not is_rsh(self.xc) and super()._fused_fock_ok(dm)
+
     def _xc_reduced(self, dm):
         nelec, exc, vxc, hyb = self.nr_rks(dm)
         if self._nranks > 1:
@@ -324,7 +447,14 @@ class RKS(RHF):
             parallel.all_reduce_fused([vxc, nelec, exc], self._pg)
             nelec, exc = nelec[0], exc[0]
         self._nelec_grid = nelec
-        if abs(hyb) > 1e-12:
+        if is_rsh(self.xc):
+            check_rsh_scf(self)
+            _omega, alpha, hyb = rsh_coeff(self.xc)
+            J, K = self._jk(dm)
+            K = hyb * K + (alpha - hyb) * lr_engine(self).get_jk(dm, with_j=False)[1]
+            v = J - 0.5 * K + vxc
+            e2 = 0.5 * torch.sum(dm * J) - 0.25 * torch.sum(dm * K) + exc
+        elif abs(hyb) > 1e-12:
             J, K = self._jk(dm)
             v = J - (0.5 * hyb) * K + vxc
             e2 = 0.5 * torch.sum(dm * J) - (0.25 * hyb) * torch.sum(dm * K) + exc

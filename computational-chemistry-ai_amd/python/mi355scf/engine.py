@@ -87,6 +87,8 @@ def lib():
         L.mi_xc_rho.argtypes = [vp, vp, vp, i64, ctypes.c_int, vp, vp]
         L.mi_xc_eval.argtypes = [ip, dp, ctypes.c_int, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp, vp]
         L.mi_xc_eval_spin.argtypes = [ip, dp, ctypes.c_int, vp, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp]
+        L.mi_xc_eval_p.argtypes = [ip, dp, dp, ctypes.c_int, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp, vp]
+        L.mi_xc_eval_spin_p.argtypes = [ip, dp, dp, ctypes.c_int, vp, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp]
         L.mi_xc_aow.argtypes = [vp, vp, vp, i64, ctypes.c_int, vp, vp]
         L.mi_xc_eval_mgga.argtypes = [ip, dp, ctypes.c_int, vp, vp, vp, i64, vp, vp, vp]
         L.mi_xc_eval_mgga_spin.argtypes = [ip, dp, ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
@@ -403,21 +405,29 @@ class Engine:
                                        tau.data_ptr() if tau is not None else None, self._stream()))
         return (rho, tau) if with_tau else rho
 
-    def xc_eval_spin(self, terms, rhoa, rhob, weights, gga=True):
-        """Spin-polarised functionals: (exc[ng], wva[(1|4)][ng], wvb[(1|4)][ng])."""
+    def xc_eval_spin(self, terms, rhoa, rhob, weights, gga=True, params=None):
+        """Spin-polarised functionals: (exc[ng], wva[(1|4)][ng], wvb[(1|4)][ng]).  `params`: one runtime parameter per term
+        (the omega of a short-range B88 term, `dft.xc_params`), None for functionals without one."""
         ng = rhoa.shape[-1]
         kinds = np.array([k for _c, k in terms], dtype=np.int32)
         coefs = np.array([c for c, _k in terms], dtype=np.float64)
         exc = self._new(ng)
         wva = self._new(4 if gga else 1, ng)
         wvb = self._new(4 if gga else 1, ng)
-        _check(lib().mi_xc_eval_spin(kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _dp(coefs), len(kinds),
-                                     rhoa.data_ptr(), rhob.data_ptr(), weights.data_ptr(), ng, int(gga), exc.data_ptr(),
-                                     wva.data_ptr(), wvb.data_ptr(), self._stream()))
+        kp = kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        if params is None:
+            _check(lib().mi_xc_eval_spin(kp, _dp(coefs), len(kinds), rhoa.data_ptr(), rhob.data_ptr(), weights.data_ptr(), ng,
+                                         int(gga), exc.data_ptr(), wva.data_ptr(), wvb.data_ptr(), self._stream()))
+        else:
+            prm = np.ascontiguousarray(params, dtype=np.float64)
+            assert prm.shape == (len(kinds),)
+            _check(lib().mi_xc_eval_spin_p(kp, _dp(coefs), _dp(prm), len(kinds), rhoa.data_ptr(), rhob.data_ptr(),
+                                           weights.data_ptr(), ng, int(gga), exc.data_ptr(), wva.data_ptr(), wvb.data_ptr(),
+                                           self._stream()))
         return exc, wva, wvb
 
-    def xc_eval(self, terms, rho, weights, gga=True, want_raw=False):
-        """terms: [(coef, kind_id)] -> (exc[ng], wv[(1|4)][ng]) (+ vrho, vsigma if want_raw)."""
+    def xc_eval(self, terms, rho, weights, gga=True, want_raw=False, params=None):
+        """terms: [(coef, kind_id)] -> (exc[ng], wv[(1|4)][ng]) (+ vrho, vsigma if want_raw).  `params` as in xc_eval_spin."""
         ng = rho.shape[-1]
         kinds = np.array([k for _c, k in terms], dtype=np.int32)
         coefs = np.array([c for c, _k in terms], dtype=np.float64)
@@ -425,9 +435,15 @@ class Engine:
         wv = self._new(4 if gga else 1, ng)
         vr = self._new(ng) if want_raw else None
         vs = self._new(ng) if want_raw else None
-        _check(lib().mi_xc_eval(kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _dp(coefs), len(kinds),
-                                rho.data_ptr(), weights.data_ptr(), ng, int(gga), exc.data_ptr(), wv.data_ptr(),
-                                vr.data_ptr() if want_raw else None, vs.data_ptr() if want_raw else None, self._stream()))
+        kp = kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        outs = (rho.data_ptr(), weights.data_ptr(), ng, int(gga), exc.data_ptr(), wv.data_ptr(),
+                vr.data_ptr() if want_raw else None, vs.data_ptr() if want_raw else None, self._stream())
+        if params is None:
+            _check(lib().mi_xc_eval(kp, _dp(coefs), len(kinds), *outs))
+        else:
+            prm = np.ascontiguousarray(params, dtype=np.float64)
+            assert prm.shape == (len(kinds),)
+            _check(lib().mi_xc_eval_p(kp, _dp(coefs), _dp(prm), len(kinds), *outs))
         return (exc, wv, vr, vs) if want_raw else (exc, wv)
 
     def xc_tau(self, ao, dm):

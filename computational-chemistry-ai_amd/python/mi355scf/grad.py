@@ -29,6 +29,8 @@ class Gradients:
     """Analytic RHF/RKS gradient on the MI355X engine."""
 
     def __init__(self, mf):
+        from .dft import require_no_rsh
+        require_no_rsh(mf, "nuclear gradients")
         self.base = mf
         self.mol = mf.mol
         self.de = None
@@ -240,6 +242,8 @@ class FDGradients:
     step = 2.0e-3  # Bohr
 
     def __init__(self, mf):
+        from .dft import require_no_rsh
+        require_no_rsh(mf, "nuclear gradients")
         self.base = mf
         self.mol = mf.mol
         self.de = None

@@ -21,6 +21,8 @@ class Hessian:
     step = 5.0e-3   # Bohr
 
     def __init__(self, mf):
+        from .dft import require_no_rsh
+        require_no_rsh(mf, "Hessian")
         self.base = mf
         self.mol = mf.mol
         self.verbose = mf.verbose

@@ -13,6 +13,8 @@ KM_PER_MOL = 974.8801   # (e^2/amu) -> km/mol  [= 42.2561 km/mol per (D/A)^2/amu
 
 class Infrared:
     def __init__(self, mf):
+        from .dft import require_no_rsh
+        require_no_rsh(mf, "infrared spectrum")
         self.base = mf
         self.mol = mf.mol
         self.verbose = mf.verbose

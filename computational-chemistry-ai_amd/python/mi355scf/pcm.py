@@ -452,6 +452,8 @@ def PCM(mf, **params):
         raise NotImplementedError("PCM with UHF / UKS is not implemented (closed-shell RHF / RKS only)")
     if getattr(mf, "_nranks", 1) > 1:
         raise NotImplementedError("PCM runs on one rank")
+    from .dft import require_no_rsh
+    require_no_rsh(mf, "PCM")
     base = mf.__class__
     cls = _CLASSES.get(base)
     if cls is None:

@@ -1059,6 +1059,8 @@ class SCF:
         set, or a {element: shells} dict.  Returns `self` (PySCF returns a DF-decorated copy; the templates' idiom
         `mf = mf.density_fit()` works with both)."""
         from . import df
+        from .dft import require_no_rsh
+        require_no_rsh(self, "density_fit()")
         self.with_df = with_df if with_df is not None else df.DF(self.mol, auxbasis)
         self._eng_df_ready = False
         return self

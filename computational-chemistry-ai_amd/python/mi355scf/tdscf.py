@@ -11,6 +11,9 @@ ground-state density along D_s, evaluated with the SCF's own quadrature kernels.
   (A+B) t = de t + [4 J[D_s] - 2 c_x K[D_s] + 4 dVxc[D_s]]_ov          (singlet; triplet: [-2 c_x K[D_s]]_ov)
   (A-B) t = de t - 2 c_x [K[D_a]]_ov
 
+Range-separated hybrids (CAM-B3LYP): every c_x K above is hyb K + (alpha - hyb) K_LR (dft.rsh_coeff), K_LR from the same batched
+K-only passes over the SCF object's long-range store (dft.lr_engine).
+
 Outputs follow PySCF: `e` ascending in Hartree, `xy[n] = (X, Y)` of shape [nocc, nvir] with X.X - Y.Y = 1/2, oscillator
 strengths f = 2/3 w |2 sum_ia (X+Y)_ia <i|r|a>|^2 (length gauge).
 """
@@ -179,7 +182,7 @@ class _TDBase:
     fd_step = 1e-4            # step of the central difference of the XC potential (dVxc)
 
     def __init__(self, mf):
-        from .dft import parse_xc
+        from .dft import parse_xc, rsh_coeff
         if not getattr(mf, "_spin_restricted", True):
             raise NotImplementedError("TDA/TDDFT: only closed-shell RHF/RKS references are supported (UHF/UKS are not)")
         if getattr(mf, "with_df", None) is not None:
@@ -187,13 +190,17 @@ class _TDBase:
         if getattr(mf, "_nranks", 1) > 1:
             raise NotImplementedError("TDA/TDDFT: sharded references are not supported")
         xc = getattr(mf, "xc", None)
+        self._omega, self._alpha = 0.0, 0.0
         if xc is None:
             self._hyb, self._dft = 1.0, False
         else:
-            hyb, _, level = parse_xc(xc)   # raises for range-separated functionals
+            hyb, _, level = parse_xc(xc)
             if level >= 2:
                 raise NotImplementedError(f"TDDFT: the meta-GGA kernel of {xc} is not supported")
             self._hyb, self._dft = float(hyb), True
+            omega, alpha, _h = rsh_coeff(xc)
+            if omega != 0.0:           # exact exchange hyb K + (alpha - hyb) K_LR
+                self._omega, self._alpha = float(omega), float(alpha)
         self._scf = mf
         self.verbose = mf.verbose
         self.stdout = getattr(mf, "stdout", None) or sys.stdout
@@ -217,6 +224,9 @@ class _TDBase:
             raise NotImplementedError("TDA/TDDFT: the ERI store does not fit (direct mode); not supported")
         if self._dft and not self.singlet:
             raise NotImplementedError("TDDFT triplets need the spin-resolved XC kernel, which is not implemented")
+        if self._omega != 0.0:
+            from .dft import check_rsh_scf
+            check_rsh_scf(mf)
         mf._setup_once()
         eng = mf.engine
         dev = eng.device
@@ -242,8 +252,18 @@ class _TDBase:
         return (self._Co.T @ M @ self._Cv).reshape(M.shape[0], -1)
 
     def _jk(self, dms, sym, with_j, with_k=True):
+        """J, K of the batch; for a range-separated hybrid K is already K_eff = hyb K + (alpha - hyb) K_LR (the long-range K
+        from the same batch over the long-range store)."""
         self.stats["n_jk_densities"] += dms.shape[0]
-        eng = self._scf.engine
+        J, K = self._jk_one(self._scf.engine, dms, sym, with_j, with_k)
+        if with_k and self._omega != 0.0:
+            from .dft import lr_engine
+            _j, Klr = self._jk_one(lr_engine(self._scf), dms, sym, False, True)
+            K = self._hyb * K + (self._alpha - self._hyb) * Klr
+        return J, K
+
+    @staticmethod
+    def _jk_one(eng, dms, sym, with_j, with_k):
         if all(s > 0 for s in sym) and len(sym) < JK_MULTI_MIN:
             return eng.get_jk(dms, with_j, with_k)     # few symmetric densities: the single-density kernel is faster
         return eng.get_jk_multi(dms, sym, with_j=with_j, with_k=with_k)
@@ -266,7 +286,11 @@ class _TDBase:
         return out
 
     def _need_k(self):
-        return abs(self._hyb) > 1e-12
+        return abs(self._hyb) > 1e-12 or self._alpha != 0.0
+
+    def _kx(self):
+        """Factor of K in the products: c_x of a global hybrid, 1 for a range-separated one (K is K_eff already, see _jk)."""
+        return 1.0 if self._omega != 0.0 else self._hyb
 
     # --- products --------------------------------------------------------------------------------
     def _tda_matvec(self, V):
@@ -274,7 +298,7 @@ class _TDBase:
         Dx = self._ao(V)
         Ds, Da = 0.5 * (Dx + Dx.transpose(1, 2)), 0.5 * (Dx - Dx.transpose(1, 2))
         m = V.shape[0]
-        cx = self._hyb
+        cx = self._kx()
         out = self._de[None, :] * V
         if self._need_k():
             J, K = self._jk(torch.cat([Ds, Da]), [1] * m + [-1] * m, with_j=self.singlet)
@@ -294,7 +318,7 @@ class _TDBase:
         Dx = self._ao(V)
         Ds, Da = 0.5 * (Dx + Dx.transpose(1, 2)), 0.5 * (Dx - Dx.transpose(1, 2))
         m = V.shape[0]
-        cx = self._hyb
+        cx = self._kx()
         apb = self._de[None, :] * V
         amb = self._de[None, :] * V
         if self._need_k():

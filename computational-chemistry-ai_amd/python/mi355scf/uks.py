@@ -9,7 +9,7 @@ The grid is not pruned by density (PySCF's `small_rho_cutoff` step is RKS-only h
 import numpy as np
 import torch
 
-from .dft import RKS, parse_xc
+from .dft import RKS, check_rsh_scf, drop_lr_engine, is_rsh, lr_engine, parse_xc, rsh_coeff, xc_params
 from .grids import Grids
 from .uhf import UHF
 
@@ -33,6 +33,7 @@ class UKS(UHF):
         self.grids = Grids(self.mol)
         self.grids.level, self.grids.prune = old.level, old.prune
         self._ao_cache_key = self._ao_cache = None
+        drop_lr_engine(self)
         return self
 
     def _setup(self):
@@ -62,6 +63,7 @@ class UKS(UHF):
         """Unsymmetrised V_xc,s into `vmat[2,N,N]`, [N_alpha, N_beta, E_xc] into `tail` (views of a zeroed caller buffer)."""
         eng = self.engine
         hyb, terms, gga = parse_xc(self.xc)
+        params = xc_params(self.xc)
         n = eng.nao
         coords, weights = self.grids.coords, self.grids.weights
         ng = coords.shape[0]
@@ -102,7 +104,7 @@ class UKS(UHF):
             if gga == 2:
                 e, wva, wvb = eng.xc_eval_mgga_spin(terms, rho[0], rho[1], tau[0], tau[1], w)
             else:
-                e, wva, wvb = eng.xc_eval_spin(terms, rho[0], rho[1], w, gga)
+                e, wva, wvb = eng.xc_eval_spin(terms, rho[0], rho[1], w, gga, params=params)
             eng.xc_tail(w, (rho[0][0], rho[1][0], e), tail)   # N_alpha, N_beta, E_xc of the block: one deterministic launch
             for s_, wv in ((0, wva), (1, wvb)):
                 eng.xc_vmat(ao[0], eng.xc_aow(ao, wv, gga), vmat[s_])
@@ -118,7 +120,11 @@ class UKS(UHF):
         n = eng.nao
         nn = n * n
         hyb = parse_xc(self.xc)[0]
-        with_k = abs(hyb) > 1e-12
+        rsh = is_rsh(self.xc)
+        if rsh:          # K_s -> K_eff,s = hyb K_s + (alpha - hyb) K_LR,s (one K-only pass over the long-range store)
+            check_rsh_scf(self)
+            _omega, alpha, hyb = rsh_coeff(self.xc)
+        with_k = abs(hyb) > 1e-12 or rsh
         nj = 2 if with_k else 1          # pure functionals: one J build for the total density
         nk = 2 if with_k else 0
         buf = torch.zeros((nj + nk + 2) * nn + 3, dtype=torch.float64, device=eng.device)
@@ -138,6 +144,9 @@ class UKS(UHF):
             from . import parallel
             parallel.all_reduce_sum(buf, self._pg)
             Jt = J[0] + J[1] if with_k else J[0]
+        if rsh:
+            K.mul_(hyb).add_(lr_engine(self).get_jk(dm.contiguous(), with_j=False)[1], alpha=alpha - hyb)
+            hyb = 1.0
         vxc = V + V.transpose(1, 2)
         self._nelec_grid = tail[:2]
         exc = tail[2]

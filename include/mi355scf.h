@@ -54,6 +54,13 @@ void mi_release_cache(void);
  *   "tri_tiles"   1 = block-diagonal tiles store triangular rows (default), 0 = full rows
  *   "xf_mfma_min" transform kernel: FP64-MFMA tiles for spherical blocks of at least this many elements
  *   "eri_tpq", "tpq_maxprim"  thread-per-quartet kernels for the low angular classes / their contraction-depth limit
+ *   "omega"       > 0: the store holds long-range integrals (ij|erf(omega r12)/r12|kl) instead of (ij|kl) (range-separated
+ *                 hybrids: CAM-B3LYP's K_LR).  Every evaluation path (Rys pair, fused, thread-per-quartet) uses theta = omega^2 /
+ *                 (omega^2 + rho), rho = pq/(p+q): Rys argument theta x, roots u theta, prefactor sqrt(theta).  Screening keeps
+ *                 the FULL-Coulomb Schwarz table (a valid bound: erf(omega r)/r and erfc(omega r)/r are both positive definite,
+ *                 so (ab|erf|ab) <= (ab|ab)); the LR store therefore has the tiles and the size of the full one.  mi_build_jk
+ *                 (K only: d_J = NULL), mi_build_jk_multi, mi_eri_unpack, mi_eri_read_quartet and mi_eri_get_stats work on it
+ *                 unchanged; mi_grad_eri*, mi_df_build and mi_df_grad refuse a context with omega != 0.  0 (default): full Coulomb.
  * Immediate:
  *   "jk_nt"       nontemporal loads for the tile stream (1 = when the tensor exceeds the Infinity Cache, 2 = always, 0 = never)
  *   "jk_cache_mb" MiB of tiles read with the default cache policy on such tensors (default 160)
@@ -277,7 +284,7 @@ int mi_xc_rho_lowrank(mi_ctx *ctx, const double *d_ao, const double *d_Zp, int l
                       double *d_tau, void *stream);
 
 /* Closed-shell XC energy density and potential on the grid.  kinds[]: 1 Slater, 2 B88, 3 VWN-RPA,
- * 4 VWN5, 5 LYP, 6 PBE-x, 7 PBE-c with weights coefs[].  Outputs (any may be NULL): d_exc[ng] energy
+ * 4 VWN5, 5 LYP, 6 PBE-x, 7 PBE-c, 12 short-range B88 (mi_xc_eval_p only) with weights coefs[].  Outputs (any may be NULL): d_exc[ng] energy
  * per volume; d_wv[(1|4)][ng] = {w*vrho/2, 2*w*vsigma*grad rho}; d_vrho, d_vsigma raw derivatives.
  * Replaces libxc (HYB_GGA_XC_B3LYP etc.) reached through mf.xc (templates/calculate_energy.py:149). */
 int mi_xc_eval(const int32_t *kinds, const double *coefs, int nterms, const double *d_rho,
@@ -287,6 +294,16 @@ int mi_xc_eval(const int32_t *kinds, const double *coefs, int nterms, const doub
  * of spin s; wv_s feed mi_xc_aow / mi_xc_vmat exactly like the closed-shell wv and give V_xc of spin s. */
 int mi_xc_eval_spin(const int32_t *kinds, const double *coefs, int nterms, const double *d_rhoa, const double *d_rhob,
                     const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wva, double *d_wvb, void *stream);
+/* The two above with one runtime parameter per term, params[nterms] (NULL: none; mi_xc_eval / mi_xc_eval_spin pass NULL).
+ * Kind 12 = short-range B88 of CAM-B3LYP, params[i] = omega > 0 (required): per spin channel e_s^B88 F(a_s), ITYH attenuation
+ * (Iikura, Tsuneda, Yanai, Hirao 2001) with a_s = omega / (2 k_s), k_s = sqrt(9 pi / K_s) rho_s^(1/3), e_s^B88 = -1/2
+ * rho_s^(4/3) K_s; F(a) in closed form below a = 4 and by its asymptotic series from there (the closed form cancels in FP64).
+ * The spin form applies it per channel by spin scaling.  Other kinds ignore their parameter. */
+int mi_xc_eval_p(const int32_t *kinds, const double *coefs, const double *params, int nterms, const double *d_rho,
+                 const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wv, double *d_vrho, double *d_vsigma, void *stream);
+int mi_xc_eval_spin_p(const int32_t *kinds, const double *coefs, const double *params, int nterms, const double *d_rhoa,
+                      const double *d_rhob, const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wva, double *d_wvb,
+                      void *stream);
 
 /* d_aow[nao][ng] = sum_c d_ao[c] * d_wv[c]; Vxc = ao0 @ aow^T + transpose is then one DGEMM.  ng == 0: no-op. */
 int mi_xc_aow(mi_ctx *ctx, const double *d_ao, const double *d_wv, int64_t ng, int gga, double *d_aow,
@@ -302,7 +319,8 @@ int mi_grad_1e(mi_ctx *ctx, const double *d_D, const double *d_W, double *d_grad
  * Schwarz-surviving quartets, derivative ERIs by the same Rys kernel on (l+1)/(l-1) auxiliary shells.
  * Replaces libcint int2e_ip1 + libcvhf nrs2/nrs4 J/K gradient contractions / gpu4pyscf rys gradient
  * kernels [MEM] (mf.nuc_grad_method().get_jk).  On a sharded context the quartet batches are dealt
- * round-robin to ranks: the result is a partial sum to be all-reduced by the caller. */
+ * round-robin to ranks: the result is a partial sum to be all-reduced by the caller.  Refused (error) on a context with
+ * "omega" != 0: there are no long-range derivative integrals. */
 int mi_grad_eri(mi_ctx *ctx, const double *d_D, double hyb, double *d_grad, void *stream);
 /* Open-shell form (UHF/UKS, templates/calculate_bde.py:224 optimises radicals): d_D = Da + Db, d_Dspin = Da - Db
  * (NULL: closed shell); the exchange part contracts sum_s Ds x Ds = (D x D + M x M) / 2. */
