@@ -4755,6 +4755,66 @@ template <int N> __device__ inline DN<N> derf(DN<N> a) { return chain(a, erf(a.v
 typedef DN<2> D2;
 typedef DN<5> D5;
 
+// ---- second-order forward mode: value, gradient and Hessian (upper triangle packed row by row: (0,0), (0,1), .., (1,1), ..)
+// in N variables, for the XC response kernels (mi_xc_fxc_prep).  The energy densities below instantiate with it unchanged.
+template <int N>
+struct HD {
+    static constexpr int NH = N * (N + 1) / 2;
+    double v, d[N], h[NH];
+    __device__ HD() {}
+    __device__ HD(double a) : v(a) {
+#pragma unroll
+        for (int i = 0; i < N; i++) d[i] = 0.0;
+#pragma unroll
+        for (int k = 0; k < NH; k++) h[k] = 0.0;
+    }
+    __device__ static HD var(double a, int which) { HD x(a); x.d[which] = 1.0; return x; }
+    __device__ double hess(int i, int j) const { return h[i * N - i * (i - 1) / 2 + (j - i)]; }   // i <= j
+};
+template <int N> __device__ inline HD<N> operator+(HD<N> a, HD<N> b) { HD<N> r; r.v = a.v + b.v;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.d[i] = a.d[i] + b.d[i];
+#pragma unroll
+    for (int k = 0; k < HD<N>::NH; k++) r.h[k] = a.h[k] + b.h[k]; return r; }
+template <int N> __device__ inline HD<N> operator-(HD<N> a, HD<N> b) { HD<N> r; r.v = a.v - b.v;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.d[i] = a.d[i] - b.d[i];
+#pragma unroll
+    for (int k = 0; k < HD<N>::NH; k++) r.h[k] = a.h[k] - b.h[k]; return r; }
+template <int N> __device__ inline HD<N> operator-(HD<N> a) { HD<N> r; r.v = -a.v;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.d[i] = -a.d[i];
+#pragma unroll
+    for (int k = 0; k < HD<N>::NH; k++) r.h[k] = -a.h[k]; return r; }
+template <int N> __device__ inline HD<N> operator*(HD<N> a, HD<N> b) { HD<N> r; r.v = a.v * b.v;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.d[i] = a.d[i] * b.v + a.v * b.d[i];
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int j = i; j < N; j++, k++) r.h[k] = a.h[k] * b.v + a.v * b.h[k] + a.d[i] * b.d[j] + a.d[j] * b.d[i];
+    return r; }
+// f(a) from f, f', f'' at a.v: d_i = f' a_i, h_ij = f' a_ij + f'' a_i a_j
+template <int N> __device__ inline HD<N> chain2(HD<N> a, double f, double f1, double f2) { HD<N> r; r.v = f;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.d[i] = f1 * a.d[i];
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < N; i++)
+#pragma unroll
+        for (int j = i; j < N; j++, k++) r.h[k] = f1 * a.h[k] + f2 * a.d[i] * a.d[j];
+    return r; }
+template <int N> __device__ inline HD<N> operator/(HD<N> a, HD<N> b) { double iv = 1.0 / b.v; return a * chain2(b, iv, -iv * iv, 2.0 * iv * iv * iv); }
+template <int N> __device__ inline HD<N> dexp(HD<N> a) { double e = exp(a.v); return chain2(a, e, e, e); }
+template <int N> __device__ inline HD<N> dlog(HD<N> a) { double iv = 1.0 / a.v; return chain2(a, log(a.v), iv, -iv * iv); }
+template <int N> __device__ inline HD<N> dsqrt(HD<N> a) { double s = sqrt(a.v); return chain2(a, s, 0.5 / s, -0.25 / (s * a.v)); }
+template <int N> __device__ inline HD<N> dpow(HD<N> a, double p) { double f = pow(a.v, p), iv = 1.0 / a.v;
+    return chain2(a, f, p * f * iv, p * (p - 1.0) * f * iv * iv); }
+template <int N> __device__ inline HD<N> datan(HD<N> a) { double q = 1.0 / (1.0 + a.v * a.v); return chain2(a, atan(a.v), q, -2.0 * a.v * q * q); }
+template <int N> __device__ inline HD<N> dasinh(HD<N> a) { double q = rsqrt(1.0 + a.v * a.v); return chain2(a, asinh(a.v), q, -a.v * q * q * q); }
+template <int N> __device__ inline HD<N> derf(HD<N> a) { double g = 1.1283791670955126 * exp(-a.v * a.v); return chain2(a, erf(a.v), g, -2.0 * a.v * g); }
+
 enum { XC_SLATER = 1, XC_B88 = 2, XC_VWN_RPA = 3, XC_VWN5 = 4, XC_LYP = 5, XC_PBE_X = 6, XC_PBE_C = 7,
        XC_TPSS_X = 8, XC_TPSS_C = 9, XC_M062X_X = 10, XC_M062X_C = 11,   // 8..11: meta-GGA (need tau)
        XC_B88_SR = 12 };   // short-range B88 (ITYH), GGA; needs its omega as the term's parameter
@@ -5100,6 +5160,54 @@ template <class T> __device__ inline T f_m062x_c_spin(T ra, T rb, T saa, T sbb, 
 
 struct XcSpec { int n; int kind[8]; double coef[8]; double param[8]; };   // param: omega of an XC_B88_SR term
 
+// sum_t coef_t e_t of the GGA terms of X: closed shell over (rho, sigma), spin-polarised over (rho_a, rho_b, sigma_aa, sigma_ab,
+// sigma_bb).  T is a first-order (DN) or second-order (HD) dual-number type.
+template <class T> __device__ inline T xc_closed_sum(const XcSpec &X, T R, T S)
+{
+    T acc(0.0);
+    for (int t = 0; t < X.n; t++) {
+        T f;
+        switch (X.kind[t]) {
+        case XC_SLATER: f = f_slater(R); break;
+        case XC_B88: f = f_b88(R, S); break;
+        case XC_VWN_RPA: f = f_vwn(R, 0.0310907, -0.409286, 13.0720, 42.7198); break;
+        case XC_VWN5: f = f_vwn(R, 0.0310907, -0.10498, 3.72744, 12.9352); break;
+        case XC_LYP: f = f_lyp(R, S); break;
+        case XC_PBE_X: f = f_pbe_x(R, S); break;
+        case XC_PBE_C: f = f_pbe_c(R, S); break;
+        case XC_B88_SR: f = f_b88_sr(R, S, X.param[t]); break;
+        default: f = T(0.0);
+        }
+        acc = acc + T(X.coef[t]) * f;
+    }
+    return acc;
+}
+
+template <class T> __device__ inline T xc_spin_sum(const XcSpec &X, T Ra, T Rb, T Saa, T Sab, T Sbb)
+{
+    T acc(0.0);
+    for (int t = 0; t < X.n; t++) {
+        T f(0.0);
+        switch (X.kind[t]) {
+        case XC_SLATER: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T) { return f_slater(r); }); break;
+        case XC_B88: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T s_) { return f_b88(r, s_); }); break;
+        case XC_PBE_X: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T s_) { return f_pbe_x(r, s_); }); break;
+        case XC_B88_SR: {
+            const double om = X.param[t];
+            f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [om](T r, T s_) { return f_b88_sr(r, s_, om); });
+            break;
+        }
+        case XC_VWN_RPA: f = f_vwn_rpa_spin(Ra, Rb); break;
+        case XC_VWN5: f = f_vwn5_spin(Ra, Rb); break;
+        case XC_LYP: f = f_lyp_spin(Ra, Rb, Saa, Sab, Sbb); break;
+        case XC_PBE_C: f = f_pbe_c_spin(Ra, Rb, Saa, Sab, Sbb); break;
+        default: break;
+        }
+        acc = acc + T(X.coef[t]) * f;
+    }
+    return acc;
+}
+
 // exc[g] = e(rho,sigma) per volume; wv[0] = 0.5 w de/drho ; wv[1..3] = 2 w de/dsigma * grad rho
 __global__ __launch_bounds__(256) void xc_eval_kernel(XcSpec X, const double *rho, const double *w, int64_t ng, int gga,
                                                       double *exc, double *wv, double *vrho_out, double *vsig_out)
@@ -5110,23 +5218,7 @@ __global__ __launch_bounds__(256) void xc_eval_kernel(XcSpec X, const double *rh
     double gx = gga ? rho[ng + g] : 0.0, gy = gga ? rho[2 * ng + g] : 0.0, gz = gga ? rho[3 * ng + g] : 0.0;
     double e = 0.0, vr = 0.0, vs = 0.0;
     if (r > 1e-10) {
-        D2 R = D2::var(r, 0), S = D2::var(gx * gx + gy * gy + gz * gz, 1);
-        D2 acc(0.0);
-        for (int t = 0; t < X.n; t++) {
-            D2 f;
-            switch (X.kind[t]) {
-            case XC_SLATER: f = f_slater(R); break;
-            case XC_B88: f = f_b88(R, S); break;
-            case XC_VWN_RPA: f = f_vwn(R, 0.0310907, -0.409286, 13.0720, 42.7198); break;
-            case XC_VWN5: f = f_vwn(R, 0.0310907, -0.10498, 3.72744, 12.9352); break;
-            case XC_LYP: f = f_lyp(R, S); break;
-            case XC_PBE_X: f = f_pbe_x(R, S); break;
-            case XC_PBE_C: f = f_pbe_c(R, S); break;
-            case XC_B88_SR: f = f_b88_sr(R, S, X.param[t]); break;
-            default: f = D2(0.0);
-            }
-            acc = acc + D2(X.coef[t]) * f;
-        }
+        D2 acc = xc_closed_sum(X, D2::var(r, 0), D2::var(gx * gx + gy * gy + gz * gz, 1));
         e = acc.v; vr = acc.d[0]; vs = acc.d[1];
     }
     if (exc) exc[g] = e;
@@ -5160,26 +5252,7 @@ __global__ __launch_bounds__(256) void xc_eval_spin_kernel(XcSpec X, const doubl
         D5 Saa = D5::var(ga[0] * ga[0] + ga[1] * ga[1] + ga[2] * ga[2], 2);
         D5 Sab = D5::var(ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2], 3);
         D5 Sbb = D5::var(gb[0] * gb[0] + gb[1] * gb[1] + gb[2] * gb[2], 4);
-        D5 acc(0.0);
-        for (int t = 0; t < X.n; t++) {
-            D5 f(0.0);
-            switch (X.kind[t]) {
-            case XC_SLATER: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](D5 r, D5) { return f_slater(r); }); break;
-            case XC_B88: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](D5 r, D5 s_) { return f_b88(r, s_); }); break;
-            case XC_PBE_X: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](D5 r, D5 s_) { return f_pbe_x(r, s_); }); break;
-            case XC_B88_SR: {
-                const double om = X.param[t];
-                f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [om](D5 r, D5 s_) { return f_b88_sr(r, s_, om); });
-                break;
-            }
-            case XC_VWN_RPA: f = f_vwn_rpa_spin(Ra, Rb); break;
-            case XC_VWN5: f = f_vwn5_spin(Ra, Rb); break;
-            case XC_LYP: f = f_lyp_spin(Ra, Rb, Saa, Sab, Sbb); break;
-            case XC_PBE_C: f = f_pbe_c_spin(Ra, Rb, Saa, Sab, Sbb); break;
-            default: break;
-            }
-            acc = acc + D5(X.coef[t]) * f;
-        }
+        D5 acc = xc_spin_sum(X, Ra, Rb, Saa, Sab, Sbb);
         e = acc.v;
         for (int k = 0; k < 5; k++) v[k] = acc.d[k];
     }
@@ -5246,6 +5319,110 @@ extern "C" int mi_xc_eval(const int32_t *kinds, const double *coefs, int nterms,
                           int64_t ng, int gga, double *d_exc, double *d_wv, double *d_vrho, double *d_vsigma, void *stream)
 {
     return mi_xc_eval_p(kinds, coefs, nullptr, nterms, d_rho, d_w, ng, gga, d_exc, d_wv, d_vrho, d_vsigma, stream);
+}
+
+// ---- XC response (closed-shell TDDFT).  A trial density rho1 (with grad rho1) enters the linearised potential through four
+// coefficients per point, coef = w {f_rr, f_rs, f_ss, v_s}:
+//   s1 = 2 grad rho0 . grad rho1,  wv1[0] = 1/2 (f_rr rho1 + f_rs s1),  wv1[1..3] = 2 ((f_rs rho1 + f_ss s1) grad rho0 + v_s grad rho1)
+// (w folded in), the layout of xc_eval_kernel's wv.  Singlet: the closed-shell functional's d2e/drho2, d2e/drho dsigma,
+// d2e/dsigma2 and de/dsigma.  Triplet (rho_a = rho_b = rho/2 moved by +-rho1/2): the same four numbers are the derivatives of
+// g(x, y, z) = e(rho/2 + x/2, rho/2 - x/2, sigma/4 + y/4 + z/4, sigma/4 - z/4, sigma/4 - y/4 + z/4) at 0 -- g_xx, g_xy, g_yy,
+// g_z -- i.e. (f_aa - f_ab)/2, (f_a,saa - f_a,sbb)/4, (f_saa,saa - f_saa,sbb)/8 and v_saa/2 - v_sab/4 of the spin-polarised
+// functional, which is evaluated over the three variables (x, y, z) only (10 doubles per value instead of the 21 of a full
+// Hessian in five).  Points at or below the density cut-off of xc_eval_kernel / xc_eval_spin_kernel (rho <= 1e-10) get zero.
+// sigma is floored at 1e-40: d2/dsigma2 of the sqrt(sigma) inside B88 is infinite at sigma = 0, where its products with
+// grad rho0 vanish anyway.
+template <bool TRIPLET>
+__global__ __launch_bounds__(256) void xc_fxc_prep_kernel(XcSpec X, const double *rho, const double *w, int64_t ng, int gga, double *coef)
+{
+    int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ng) return;
+    const double r = rho[g];
+    double s = 1e-40;
+    if (gga) {
+        const double gx = rho[ng + g], gy = rho[2 * ng + g], gz = rho[3 * ng + g];
+        s = fmax(gx * gx + gy * gy + gz * gz, 1e-40);
+    }
+    double c[4] = {0.0, 0.0, 0.0, 0.0};
+    if (r > 1e-10) {
+        if (!TRIPLET) {
+            typedef HD<2> H;
+            H acc = xc_closed_sum(X, H::var(r, 0), H::var(s, 1));
+            c[0] = acc.hess(0, 0); c[1] = acc.hess(0, 1); c[2] = acc.hess(1, 1); c[3] = acc.d[1];
+        } else {
+            typedef HD<3> H;
+            H Ra(0.5 * r), Rb(0.5 * r), Saa(0.25 * s), Sab(0.25 * s), Sbb(0.25 * s);
+            Ra.d[0] = 0.5; Rb.d[0] = -0.5;
+            Saa.d[1] = 0.25; Saa.d[2] = 0.25;
+            Sbb.d[1] = -0.25; Sbb.d[2] = 0.25;
+            Sab.d[2] = -0.25;
+            H acc = xc_spin_sum(X, Ra, Rb, Saa, Sab, Sbb);
+            c[0] = acc.hess(0, 0); c[1] = acc.hess(0, 1); c[2] = acc.hess(1, 1); c[3] = acc.d[2];
+        }
+    }
+    const double ww = w[g];
+    coef[g] = ww * c[0];
+    if (gga) {
+        coef[ng + g] = ww * c[1]; coef[2 * ng + g] = ww * c[2]; coef[3 * ng + g] = ww * c[3];
+    }
+}
+
+// m trial densities rho1[m][(1|4)][ng] -> wv1[m][(1|4)][ng]; rho0 and coef read once per point for all m
+__global__ __launch_bounds__(256) void xc_fxc_apply_kernel(const double *__restrict__ rho0, const double *__restrict__ coef,
+                                                           const double *__restrict__ rho1, int m, int64_t ng, int gga,
+                                                           double *__restrict__ wv1)
+{
+    int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ng) return;
+    const int nc = gga ? 4 : 1;
+    const double c0 = coef[g];
+    if (!gga) {
+        for (int j = 0; j < m; j++) wv1[(int64_t)j * ng + g] = 0.5 * c0 * rho1[(int64_t)j * ng + g];
+        return;
+    }
+    const double c1 = coef[ng + g], c2 = coef[2 * ng + g], c3 = coef[3 * ng + g];
+    const double g0x = rho0[ng + g], g0y = rho0[2 * ng + g], g0z = rho0[3 * ng + g];
+    for (int j = 0; j < m; j++) {
+        const double *r1 = rho1 + (int64_t)j * nc * ng;
+        double *o = wv1 + (int64_t)j * nc * ng;
+        const double r = r1[g], gx = r1[ng + g], gy = r1[2 * ng + g], gz = r1[3 * ng + g];
+        const double s1 = 2.0 * (g0x * gx + g0y * gy + g0z * gz);
+        const double t = 2.0 * (c1 * r + c2 * s1), u = 2.0 * c3;
+        o[g] = 0.5 * (c0 * r + c1 * s1);
+        o[ng + g] = t * g0x + u * gx;
+        o[2 * ng + g] = t * g0y + u * gy;
+        o[3 * ng + g] = t * g0z + u * gz;
+    }
+}
+
+extern "C" int mi_xc_fxc_prep(const int32_t *kinds, const double *coefs, const double *params, int nterms, const double *d_rho,
+                              const double *d_w, int64_t ng, int gga, int triplet, double *d_coef, void *stream)
+{
+    if (!d_rho || !d_w || !d_coef) return fail("mi_xc_fxc_prep: null argument");
+    if (ng < 0) return fail("mi_xc_fxc_prep: negative number of grid points");
+    XcSpec X;
+    if (fill_gga_spec(X, kinds, coefs, params, nterms, "mi_xc_fxc_prep")) return -1;
+    if (ng == 0) return 0;
+    if (triplet)
+        hipLaunchKernelGGL(xc_fxc_prep_kernel<true>, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, d_rho, d_w,
+                           ng, gga ? 1 : 0, d_coef);
+    else
+        hipLaunchKernelGGL(xc_fxc_prep_kernel<false>, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, d_rho, d_w,
+                           ng, gga ? 1 : 0, d_coef);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mi_xc_fxc_apply(const double *d_rho0, const double *d_coef, const double *d_rho1, int m, int64_t ng, int gga,
+                               double *d_wv1, void *stream)
+{
+    if (m < 0 || ng < 0) return fail("mi_xc_fxc_apply: negative size");
+    if (m == 0 || ng == 0) return 0;
+    if (!d_rho0 || !d_coef || !d_rho1 || !d_wv1) return fail("mi_xc_fxc_apply: null argument");
+    hipLaunchKernelGGL(xc_fxc_apply_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_rho0, d_coef, d_rho1,
+                       m, ng, gga ? 1 : 0, d_wv1);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // ---- meta-GGA evaluation.  Closed shell: rho[0..3] = density and gradient, tau = 1/2 sum_i |grad phi_i|^2 (all electrons);

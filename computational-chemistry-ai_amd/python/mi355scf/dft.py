@@ -196,13 +196,7 @@ class RKS(RHF):
         coords, weights = self.grids.coords, self.grids.weights
         ng = coords.shape[0]
         lo, hi = self._grid_range(ng)
-        # grid block: as large as a ~1.5 GB working set allows (fewer launches for small molecules), at least grid_block
-        B = max(self.grid_block, int(self._xc_block_bytes() / (48.0 * n)) // 1024 * 1024)
-        if hi - lo <= 1.5 * B:
-            B = max(hi - lo, 1)   # no small remainder block: its kernels would be pure launch latency (0.15 ms per build on benzene/cc-pVTZ)
-        else:                     # equal blocks instead of full ones plus a short tail
-            nblk = (hi - lo + B - 1) // B
-            B = ((hi - lo + nblk - 1) // nblk + 1023) // 1024 * 1024
+        B = self._xc_block_size(n, hi - lo)
         cache = self._ao_cache_for(n, hi - lo, 4 if gga else 1)
         Zt = self._occ_factor(dm)
         if Zt is not None:   # [nao, ldz] with the orbital index fastest, zero-padded to the kernel's chunk (24 GGA / 32 LDA)
@@ -249,6 +243,34 @@ class RKS(RHF):
                 for k in (1, 2, 3):
                     eng.xc_vmat(ao[k], wv[4] * ao[k], vmat)
         return hyb
+
+    def _xc_block_size(self, n, npts):
+        """Points per grid block of `npts` points of this rank (the blocks the AO cache holds)."""
+        # grid block: as large as a ~1.5 GB working set allows (fewer launches for small molecules), at least grid_block
+        B = max(self.grid_block, int(self._xc_block_bytes() / (48.0 * n)) // 1024 * 1024)
+        if npts <= 1.5 * B:
+            return max(npts, 1)   # no small remainder block: its kernels would be pure launch latency (0.15 ms per build on benzene/cc-pVTZ)
+        nblk = (npts + B - 1) // B   # equal blocks instead of full ones plus a short tail
+        return ((npts + nblk - 1) // nblk + 1023) // 1024 * 1024
+
+    def _ao_blocks(self, gga):
+        """(weights, ao) of each grid block of this rank: the blocks of `_nr_rks_raw`, AO values from the resident cache where
+        it holds them (XC response of tdscf)."""
+        eng = self.engine
+        n = eng.nao
+        coords, weights = self.grids.coords, self.grids.weights
+        lo, hi = self._grid_range(coords.shape[0])
+        B = self._xc_block_size(n, hi - lo)
+        cache = self._ao_cache_for(n, hi - lo, 4 if gga else 1)
+        for ib, p0 in enumerate(range(lo, hi, B)):
+            p1 = min(p0 + B, hi)
+            if cache is not None and ib < len(cache):
+                ao = cache[ib]
+            else:
+                ao = eng.eval_ao(coords[p0:p1], deriv=1 if gga else 0)
+                if cache is not None:
+                    cache.append(ao)
+            yield weights[p0:p1], ao
 
     # Working set of one grid block (AO values + weighted AOs).  The per-point kernels are one thread per grid point: a block of
     # 55 k points (1.5 GB at N = 573, the round-1 size) is 216 workgroups for 256 CUs -- one wave per SIMD for a latency-bound

@@ -90,6 +90,8 @@ def lib():
         L.mi_xc_eval_p.argtypes = [ip, dp, dp, ctypes.c_int, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp, vp]
         L.mi_xc_eval_spin_p.argtypes = [ip, dp, dp, ctypes.c_int, vp, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp]
         L.mi_xc_aow.argtypes = [vp, vp, vp, i64, ctypes.c_int, vp, vp]
+        L.mi_xc_fxc_prep.argtypes = [ip, dp, dp, ctypes.c_int, vp, vp, i64, ctypes.c_int, ctypes.c_int, vp, vp]
+        L.mi_xc_fxc_apply.argtypes = [vp, vp, vp, ctypes.c_int, i64, ctypes.c_int, vp, vp]
         L.mi_xc_eval_mgga.argtypes = [ip, dp, ctypes.c_int, vp, vp, vp, i64, vp, vp, vp]
         L.mi_xc_eval_mgga_spin.argtypes = [ip, dp, ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
         L.mi_xc_vmat.argtypes = [vp, vp, vp, i64, vp, vp]
@@ -380,9 +382,10 @@ class Engine:
         _check(lib().mi_eval_ao(self._h, coords.data_ptr(), ng, int(deriv), out.data_ptr(), self._stream()))
         return out
 
-    def xc_rho(self, ao, C, deriv=1):
+    def xc_rho(self, ao, C, deriv=1, out=None):
         ng = ao.shape[-1]
-        rho = self._new(4 if deriv else 1, ng)
+        rho = self._new(4 if deriv else 1, ng) if out is None else out
+        assert rho.is_contiguous() and rho.shape == (4 if deriv else 1, ng)
         _check(lib().mi_xc_rho(self._h, ao.data_ptr(), C.data_ptr(), ng, int(deriv), rho.data_ptr(), self._stream()))
         return rho
 
@@ -445,6 +448,32 @@ class Engine:
             assert prm.shape == (len(kinds),)
             _check(lib().mi_xc_eval_p(kp, _dp(coefs), _dp(prm), len(kinds), *outs))
         return (exc, wv, vr, vs) if want_raw else (exc, wv)
+
+    def xc_fxc_prep(self, terms, rho, weights, gga=True, triplet=False, params=None):
+        """XC response coefficients coef[(4|1)][ng] = w {f_rr, f_rs, f_ss, v_sigma} of the ground-state density rho (singlet:
+        closed-shell functional; triplet: spin-difference kernel of the spin-polarised one).  `params` as in xc_eval."""
+        ng = rho.shape[-1]
+        assert rho.is_contiguous() and weights.is_contiguous() and rho.shape[0] == (4 if gga else 1)
+        kinds = np.array([k for _c, k in terms], dtype=np.int32)
+        coefs = np.array([c for c, _k in terms], dtype=np.float64)
+        prm = None if params is None else np.ascontiguousarray(params, dtype=np.float64)
+        assert prm is None or prm.shape == (len(kinds),)
+        coef = self._new(4 if gga else 1, ng)
+        _check(lib().mi_xc_fxc_prep(kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _dp(coefs),
+                                    _dp(prm) if prm is not None else None, len(kinds), rho.data_ptr(), weights.data_ptr(), ng,
+                                    int(bool(gga)), int(bool(triplet)), coef.data_ptr(), self._stream()))
+        return coef
+
+    def xc_fxc_apply(self, rho0, coef, rho1, gga=True):
+        """wv1[m][(4|1)][ng] (the layout of xc_eval's wv) of m trial densities rho1[m][(4|1)][ng] from the coefficients of
+        xc_fxc_prep and the ground-state density rho0 whose gradient they were made at."""
+        m, nc, ng = rho1.shape
+        assert nc == (4 if gga else 1) and coef.shape == (nc, ng) and rho0.shape[-1] == ng and rho0.shape[0] >= nc
+        assert rho0.is_contiguous() and coef.is_contiguous() and rho1.is_contiguous()
+        wv1 = self._new(m, nc, ng)
+        _check(lib().mi_xc_fxc_apply(rho0.data_ptr(), coef.data_ptr(), rho1.data_ptr(), m, ng, int(bool(gga)), wv1.data_ptr(),
+                                     self._stream()))
+        return wv1
 
     def xc_tau(self, ao, dm):
         """tau[ng] = 1/2 sum_k sum_mu,nu D_mu,nu d_k phi_mu d_k phi_nu from AO gradients ao[1..3] (three D.ao_k GEMMs)."""

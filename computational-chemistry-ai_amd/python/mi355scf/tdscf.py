@@ -4,12 +4,16 @@
 
 Trial vectors x [nocc, nvir] enter the AO basis as D_x = C_o x C_v^T, split into D_s = (D_x + D_x^T)/2 and
 D_a = (D_x - D_x^T)/2.  All J/K of one Davidson iteration go through one `Engine.get_jk_multi` call (every resident ERI tile
-read once per launch of up to 8 densities by default, 16 at most); the XC response dVxc[D_s] is the central difference of the XC potential of the
-ground-state density along D_s, evaluated with the SCF's own quadrature kernels.
+read once per launch of up to 8 densities by default, 16 at most).  The XC response dV[D_s] is analytic: per grid point the
+second derivatives of the functional at the ground-state density (`Engine.xc_fxc_prep`, once per run), then per batch of trial
+vectors rho1 from one batched D_s.ao GEMM, the linearised potential (`Engine.xc_fxc_apply`) and the SCF's V_xc fold.
+`xc_response = "fd"` keeps the central difference of the XC potential as the independent check.
 
-  A x     = de x + [2 J[D_x] - c_x K[D_x] + 2 dVxc[D_s]]_ov            (singlet; triplet: [-c_x K[D_x]]_ov)
-  (A+B) t = de t + [4 J[D_s] - 2 c_x K[D_s] + 4 dVxc[D_s]]_ov          (singlet; triplet: [-2 c_x K[D_s]]_ov)
+  A x     = de x + [2 J[D_x] - c_x K[D_x] + 2 dV_S[D_s]]_ov            (triplet: [-c_x K[D_x] + 2 dV_T[D_s]]_ov)
+  (A+B) t = de t + [4 J[D_s] - 2 c_x K[D_s] + 4 dV_S[D_s]]_ov          (triplet: [-2 c_x K[D_s] + 4 dV_T[D_s]]_ov)
   (A-B) t = de t - 2 c_x [K[D_a]]_ov
+
+  dV_S[M] = d/dh V_a(D_a = D_b = (D0 + h M)/2) = d/dh V_xc,RKS(D0 + h M),  dV_T[M] = d/dh V_a(D_a = (D0 + h M)/2, D_b = (D0 - h M)/2)
 
 Range-separated hybrids (CAM-B3LYP): every c_x K above is hyb K + (alpha - hyb) K_LR (dft.rsh_coeff), K_LR from the same batched
 K-only passes over the SCF object's long-range store (dft.lr_engine).
@@ -179,7 +183,9 @@ class _TDBase:
     conv_tol = 1e-5
     max_cycle = 100
     max_space = None
-    fd_step = 1e-4            # step of the central difference of the XC potential (dVxc)
+    fd_step = 1e-4            # step of the central difference of the XC potential (xc_response = "fd")
+    xc_response = "analytic"  # "analytic": fxc kernels (Engine.xc_fxc_prep / xc_fxc_apply); "fd": central difference of V_xc
+    xc_rho_batch_bytes = 2e9  # bound on the D_s.ao0 products [m, nao, ng] formed by one batched GEMM
 
     def __init__(self, mf):
         from .dft import parse_xc, rsh_coeff
@@ -207,6 +213,7 @@ class _TDBase:
         self.e = self.xy = self.converged = None
         self.nstates = type(self).nstates
         self.stats = {}
+        self._fxc = None
 
     @property
     def mol(self):
@@ -222,8 +229,6 @@ class _TDBase:
             mf.kernel()
         if getattr(mf, "_stream_groups", 1) > 1:
             raise NotImplementedError("TDA/TDDFT: the ERI store does not fit (direct mode); not supported")
-        if self._dft and not self.singlet:
-            raise NotImplementedError("TDDFT triplets need the spin-resolved XC kernel, which is not implemented")
         if self._omega != 0.0:
             from .dft import check_rsh_scf
             check_rsh_scf(mf)
@@ -239,6 +244,7 @@ class _TDBase:
         self._de = (eps[None, self._nocc:] - eps[:self._nocc, None]).reshape(-1)
         if self._dft:
             self._D0 = torch.as_tensor(np.asarray(mf.make_rdm1()), dtype=torch.float64, device=dev)
+        self._fxc = None
         self.stats = {"n_jk_densities": 0, "n_matvec": 0}
 
     # --- AO-basis pieces -------------------------------------------------------------------------
@@ -268,22 +274,97 @@ class _TDBase:
             return eng.get_jk(dms, with_j, with_k)     # few symmetric densities: the single-density kernel is faster
         return eng.get_jk_multi(dms, sym, with_j=with_j, with_k=with_k)
 
-    def _dvxc(self, Ds):
-        """dVxc[M] = d/dh Vxc_RKS(D0 + h M) at h = 0 for each symmetric M (central difference, step fd_step / max|M|)."""
-        mf = self._scf
+    def _dvxc(self, Ds, triplet=False):
+        """XC response at h = 0 for each symmetric M of Ds [m, N, N]: dV_S[M] = d/dh Vxc_RKS(D0 + h M) (singlet), or
+        dV_T[M] = d/dh V_alpha(D_a = (D0 + h M)/2, D_b = (D0 - h M)/2) (triplet).  Analytic, or with xc_response = "fd" the
+        central difference (step fd_step / max|M|).  A functional without semilocal terms (xc = "HF") gives zero."""
+        from .dft import parse_xc
         t0 = time.perf_counter()
-        out = torch.empty_like(Ds)
-        for m in range(Ds.shape[0]):
-            M = Ds[m]
-            h = self.fd_step / max(float(M.abs().max()), 1e-300)
-            vp = mf.nr_rks(self._D0 + h * M)[2]
-            vm = mf.nr_rks(self._D0 - h * M)[2]
-            out[m] = (vp - vm) / (2.0 * h)
+        if not parse_xc(self._scf.xc)[1]:
+            out = torch.zeros_like(Ds)
+        elif self.xc_response == "analytic":
+            out = self._dvxc_analytic(Ds, triplet)
+        elif self.xc_response == "fd":
+            out = self._dvxc_fd(Ds, triplet)
+        else:
+            raise ValueError(f"xc_response must be 'analytic' or 'fd', not {self.xc_response!r}")
         if out.is_cuda:
             torch.cuda.synchronize(out.device)
         self.stats["xc_seconds"] = self.stats.get("xc_seconds", 0.0) + time.perf_counter() - t0
         self.stats["xc_vectors"] = self.stats.get("xc_vectors", 0) + Ds.shape[0]
         return out
+
+    def _dvxc_fd(self, Ds, triplet):
+        mf = self._scf
+        out = torch.empty_like(Ds)
+        for m in range(Ds.shape[0]):
+            M = Ds[m]
+            h = self.fd_step / max(float(M.abs().max()), 1e-300)
+            if triplet:
+                Dp, Dm = 0.5 * (self._D0 + h * M), 0.5 * (self._D0 - h * M)
+                vp, vm = self._vxc_alpha(Dp, Dm), self._vxc_alpha(Dm, Dp)
+            else:
+                vp = mf.nr_rks(self._D0 + h * M)[2]
+                vm = mf.nr_rks(self._D0 - h * M)[2]
+            out[m] = (vp - vm) / (2.0 * h)
+        return out
+
+    def _vxc_alpha(self, Da, Db):
+        """V_xc of spin alpha of the spin densities (Da, Db) on the SCF's grid (Engine.xc_eval_spin)."""
+        from .dft import parse_xc, xc_params
+        mf = self._scf
+        eng = mf.engine
+        _hyb, terms, gga = parse_xc(mf.xc)
+        params = xc_params(mf.xc)
+        deriv = 1 if gga else 0
+        vmat = torch.zeros_like(Da)
+        for w, ao in mf._ao_blocks(gga):
+            ra = eng.xc_rho(ao, Da @ ao[0], deriv)
+            rb = eng.xc_rho(ao, Db @ ao[0], deriv)
+            _e, wva, _wvb = eng.xc_eval_spin(terms, ra, rb, w, gga, params=params)
+            eng.xc_vmat(ao[0], eng.xc_aow(ao, wva, gga), vmat)
+        return vmat + vmat.T
+
+    def _fxc_blocks(self, triplet):
+        """[(rho0, coef)] per grid block: the ground-state density and its XC kernel coefficients for the channel, made once
+        per run (Engine.xc_fxc_prep)."""
+        if self._fxc is None or self._fxc[0] != bool(triplet):
+            from .dft import parse_xc, xc_params
+            mf = self._scf
+            eng = mf.engine
+            _hyb, terms, gga = parse_xc(mf.xc)
+            params = xc_params(mf.xc)
+            blocks = []
+            for w, ao in mf._ao_blocks(gga):
+                rho0 = eng.xc_rho(ao, self._D0 @ ao[0], 1 if gga else 0)
+                blocks.append((rho0, eng.xc_fxc_prep(terms, rho0, w, gga, triplet=triplet, params=params)))
+            self._fxc = (bool(triplet), blocks)
+        return self._fxc[1]
+
+    def _dvxc_analytic(self, Ds, triplet):
+        """Per grid block: C = Ds.ao0 for as many vectors as xc_rho_batch_bytes allows (one batched GEMM), rho1 of each, wv1
+        of the whole batch in one launch, then the V_xc fold (xc_aow + xc_vmat) of each vector."""
+        from .dft import parse_xc
+        mf = self._scf
+        eng = mf.engine
+        gga = parse_xc(mf.xc)[2]
+        deriv, nc = (1, 4) if gga else (0, 1)
+        m, n = Ds.shape[0], Ds.shape[1]
+        vmat = torch.zeros_like(Ds)
+        for (w, ao), (rho0, coef) in zip(mf._ao_blocks(gga), self._fxc_blocks(triplet)):
+            ng = ao.shape[-1]
+            mc = max(1, min(m, int(self.xc_rho_batch_bytes // (8.0 * n * ng))))
+            for j0 in range(0, m, mc):
+                j1 = min(j0 + mc, m)
+                C = torch.matmul(Ds[j0:j1], ao[0])
+                rho1 = torch.empty(j1 - j0, nc, ng, dtype=torch.float64, device=Ds.device)
+                for j in range(j1 - j0):
+                    eng.xc_rho(ao, C[j], deriv, out=rho1[j])
+                del C
+                wv1 = eng.xc_fxc_apply(rho0, coef, rho1, gga)
+                for j in range(j1 - j0):
+                    eng.xc_vmat(ao[0], eng.xc_aow(ao, wv1[j], gga), vmat[j0 + j])
+        return vmat + vmat.transpose(1, 2)
 
     def _need_k(self):
         return abs(self._hyb) > 1e-12 or self._alpha != 0.0
@@ -305,11 +386,13 @@ class _TDBase:
             F = -cx * (K[:m] + K[m:])
             if self.singlet:
                 F = F + 2.0 * J[:m]
-        else:
+        elif self.singlet:
             J, _ = self._jk(Ds, [1] * m, with_j=True, with_k=False)   # pure functional: no exchange
             F = 2.0 * J
+        else:
+            F = torch.zeros_like(Ds)                                  # triplet of a pure functional: neither J nor K
         if self._dft:
-            F = F + 2.0 * self._dvxc(Ds)
+            F = F + 2.0 * self._dvxc(Ds, triplet=not self.singlet)
         return out + self._ov(F)
 
     def _rpa_products(self, V):
@@ -327,11 +410,13 @@ class _TDBase:
             if self.singlet:
                 F = F + 4.0 * J[:m]
             amb = amb - 2.0 * cx * self._ov(K[m:])
-        else:
+        elif self.singlet:
             J, _ = self._jk(Ds, [1] * m, with_j=True, with_k=False)   # pure functional: no exchange
             F = 4.0 * J
+        else:
+            F = torch.zeros_like(Ds)
         if self._dft:
-            F = F + 4.0 * self._dvxc(Ds)
+            F = F + 4.0 * self._dvxc(Ds, triplet=not self.singlet)
         return apb + self._ov(F), amb
 
     # --- properties ------------------------------------------------------------------------------

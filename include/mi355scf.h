@@ -305,6 +305,23 @@ int mi_xc_eval_spin_p(const int32_t *kinds, const double *coefs, const double *p
                       const double *d_rhob, const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wva, double *d_wvb,
                       void *stream);
 
+/* XC response of closed-shell TDDFT, step 1: per point of the ground-state density d_rho[(1|4)][ng] (mi_xc_rho layout) the
+ * weighted kernel coefficients d_coef[(1|4)][ng] = w {f_rr, f_rs, f_ss, v_s} (LDA, gga = 0: w f_rr only) of one response
+ * channel, by second-order forward-mode dual numbers.  triplet = 0: second derivatives and v_sigma of the closed-shell
+ * functional.  triplet = 1: the spin-difference combination of the spin-polarised functional at rho_a = rho_b = rho/2,
+ * sigma_ss' = sigma/4: (f_aa - f_ab)/2, (f_a,saa - f_a,sbb)/4, (f_saa,saa - f_saa,sbb)/8, v_saa/2 - v_sab/4.  kinds / coefs /
+ * params as mi_xc_eval_p (LDA and GGA kinds 1-7, 12; meta-GGA kinds are an error); points with rho <= 1e-10 get zero, the
+ * cut-off of mi_xc_eval / mi_xc_eval_spin.  Replaces the fxc of libxc reached through pyscf.tdscf (numint.nr_rks_fxc /
+ * nr_rks_fxc_st [MEM]). */
+int mi_xc_fxc_prep(const int32_t *kinds, const double *coefs, const double *params, int nterms, const double *d_rho,
+                   const double *d_w, int64_t ng, int gga, int triplet, double *d_coef, void *stream);
+/* Step 2: m trial densities d_rho1[m][(1|4)][ng] (each from mi_xc_rho of a symmetric M) -> d_wv1[m][(1|4)][ng], the
+ * linearised mi_xc_eval wv: with s1 = 2 grad rho0 . grad rho1, wv1[0] = 1/2 (c_rr rho1 + c_rs s1), wv1[1..3] =
+ * 2 ((c_rs rho1 + c_ss s1) grad rho0 + c_s grad rho1), c = d_coef of step 1.  mi_xc_aow + mi_xc_vmat (or mi_xc_vmat_fold)
+ * of each wv1[j] then give dV_xc[M_j] = vmat + vmat^T.  m == 0 or ng == 0: no-op. */
+int mi_xc_fxc_apply(const double *d_rho0, const double *d_coef, const double *d_rho1, int m, int64_t ng, int gga, double *d_wv1,
+                    void *stream);
+
 /* d_aow[nao][ng] = sum_c d_ao[c] * d_wv[c]; Vxc = ao0 @ aow^T + transpose is then one DGEMM.  ng == 0: no-op. */
 int mi_xc_aow(mi_ctx *ctx, const double *d_ao, const double *d_wv, int64_t ng, int gga, double *d_aow,
               void *stream);

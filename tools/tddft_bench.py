@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Linear-response figures, one JSON line: J/K per density of the batched build (mi_build_jk_multi) against the looped
 single-density build for n_dm in --ndm (call time, synchronised, median of --reps), and the wall time of td.kernel() for
-B3LYP TDA / RPA with the number of densities that went through J/K.
+B3LYP TDA / RPA with the number of densities that went through J/K.  --xc-response analytic,fd runs every TD kind once per
+route, the routes alternated in one process for --reps rounds (XC seconds per trial vector and td.kernel() wall time).
 
-  python tools/tddft_bench.py --jk benzene:cc-pvtz --ndm 1,2,4,8,16,32 --td O=C1C=CC(=O)C=C1:6-31g*"""
+  python tools/tddft_bench.py --jk benzene:cc-pvtz --ndm 1,2,4,8,16,32 --td O=C1C=CC(=O)C=C1:6-31g*
+  python tools/tddft_bench.py --td benzene:cc-pvtz --xc-response analytic,fd --reps 3"""
 import argparse
 import json
 import os
@@ -66,7 +68,22 @@ def bench_jk(spec, ndms, reps):
     return out
 
 
-def bench_td(spec, nstates):
+def _run_td(mf, cls, nstates, route):
+    td = cls(mf)
+    td.nstates = nstates
+    if route is not None:
+        td.xc_response = route
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    e, _ = td.kernel()
+    torch.cuda.synchronize()
+    xs, xv = td.stats.get("xc_seconds", 0.0), td.stats.get("xc_vectors", 0)
+    return {"seconds": time.perf_counter() - t0, "converged": bool(np.all(td.converged)),
+            "jk_densities": td.stats["n_jk_densities"], "matvecs": td.stats["n_matvec"], "xc_seconds": xs, "xc_vectors": xv,
+            "xc_ms_per_vector": 1e3 * xs / max(xv, 1), "e_ev": (np.asarray(e) * 27.211386245988).round(4).tolist()}
+
+
+def bench_td(spec, nstates, routes=None, reps=1):
     from pyscf import dft, tdscf
     mol = _mol(spec)
     mf = dft.RKS(mol)
@@ -74,15 +91,20 @@ def bench_td(spec, nstates):
     mf.kernel()
     res = {"system": spec, "nao": mol.nao, "nstates": nstates}
     for kind, cls in (("tda", tdscf.TDA), ("rpa", tdscf.TDDFT)):
-        td = cls(mf)
-        td.nstates = nstates
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        e, _ = td.kernel()
-        torch.cuda.synchronize()
-        res[kind] = {"seconds": time.perf_counter() - t0, "converged": bool(np.all(td.converged)),
-                     "jk_densities": td.stats["n_jk_densities"], "matvecs": td.stats["n_matvec"],
-                     "xc_seconds": td.stats.get("xc_seconds", 0.0), "xc_vectors": td.stats.get("xc_vectors", 0), "e_ev": (np.asarray(e) * 27.211386245988).round(4).tolist()}
+        if not routes:
+            res[kind] = _run_td(mf, cls, nstates, None)
+            continue
+        runs = {r: [] for r in routes}
+        for _ in range(reps):            # A/B alternated inside one process
+            for r in routes:
+                runs[r].append(_run_td(mf, cls, nstates, r))
+        res[kind] = {}
+        for r, rr in runs.items():
+            out = dict(rr[-1])
+            for key in ("seconds", "xc_seconds", "xc_ms_per_vector"):
+                v = [x[key] for x in rr]
+                out[key], out[key + "_spread"] = float(np.median(v)), [float(min(v)), float(max(v))]
+            res[kind][r] = out
     return res
 
 
@@ -93,12 +115,14 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--td", default=None)
     ap.add_argument("--nstates", type=int, default=10)
+    ap.add_argument("--xc-response", default=None, help="comma-separated TD XC routes to alternate: analytic,fd")
     a = ap.parse_args()
     out = {}
     if a.jk:
         out["jk"] = bench_jk(a.jk, [int(x) for x in a.ndm.split(",")], a.reps)
     if a.td:
-        out["td"] = bench_td(a.td, a.nstates)
+        routes = a.xc_response.split(",") if a.xc_response else None
+        out["td"] = bench_td(a.td, a.nstates, routes, a.reps if routes else 1)
     print(json.dumps(out))
 
 
