@@ -145,12 +145,13 @@ def drop_lr_engine(mf):
         e.close()
 
 
-class RKS(RHF):
+class KSMixin:
+    """What RKS and UKS share, in front of RHF / UHF in their bases: the XC grid of the object, the blocks it is integrated in
+    with their resident AO values, and the low-rank factor of a projector density."""
     xc = "LDA,VWN"
     grid_block = 32768
     cache_ao = True
     direct_reserve_gb = 10.0  # direct mode: room kept for the quadrature (AO blocks, optional AO cache) beside the tile groups
-    small_rho_cutoff = 1e-7   # PySCF RKS default [MEM]
 
     def __init__(self, mol, xc=None):
         super().__init__(mol)
@@ -164,7 +165,6 @@ class RKS(RHF):
         old = self.grids
         self.grids = Grids(self.mol)
         self.grids.level, self.grids.prune = old.level, old.prune   # user settings survive scanner / optimize() resets
-        self._pruned = False
         self._ao_cache_key = self._ao_cache = None                  # AO values of the old geometry: drop (and free) them
         drop_lr_engine(self)                                        # long-range store of the old geometry (CAM-B3LYP)
         return self
@@ -176,74 +176,6 @@ class RKS(RHF):
             self.grids.build(engine=self.engine)
             self._log(4, f"XC grid: {self.grids.size} points (level {self.grids.level})")
 
-    def nr_rks(self, dm):
-        """(N_elec, E_xc, V_xc, hyb) on device for a closed-shell density (numint.nr_rks [MEM]): this rank's share of the
-        grid; sharded callers all-reduce."""
-        n = self.engine.nao
-        vmat = torch.zeros(n, n, dtype=torch.float64, device=self.engine.device)
-        tail = torch.zeros(2, dtype=torch.float64, device=self.engine.device)
-        hyb = self._nr_rks_raw(dm, vmat, tail)
-        return tail[0], tail[1], vmat + vmat.T, hyb
-
-    def _nr_rks_raw(self, dm, vmat, tail):
-        """Accumulate the UNsymmetrised XC matrix (V_xc = vmat + vmat^T) into `vmat` and [N_elec, E_xc] into `tail` -- views of
-        a caller-owned (zeroed) buffer, e.g. the fused all-reduce buffer of `_fock_energy`.  Returns the exact-exchange
-        fraction of the functional."""
-        eng = self.engine
-        hyb, terms, gga = parse_xc(self.xc)
-        params = xc_params(self.xc)
-        n = eng.nao
-        coords, weights = self.grids.coords, self.grids.weights
-        ng = coords.shape[0]
-        lo, hi = self._grid_range(ng)
-        B = self._xc_block_size(n, hi - lo)
-        cache = self._ao_cache_for(n, hi - lo, 4 if gga else 1)
-        Zt = self._occ_factor(dm)
-        if Zt is not None:   # [nao, ldz] with the orbital index fastest, zero-padded to the kernel's chunk (24 GGA / 32 LDA)
-            ch = 24 if gga else 32
-            ldz = (Zt.shape[0] + ch - 1) // ch * ch
-            Zp = getattr(self, "_zp_buf", None)      # persistent: the padding columns are zeroed once, not every cycle
-            if Zp is None or Zp.shape != (n, ldz) or Zp.device != Zt.device or self._zp_nocc != Zt.shape[0]:
-                Zp = self._zp_buf = torch.zeros(n, ldz, dtype=torch.float64, device=Zt.device)
-                self._zp_nocc = Zt.shape[0]
-            Zp[:, :Zt.shape[0]].copy_(Zt.T)
-        for ib, p0 in enumerate(range(lo, hi, B)):
-            p1 = min(p0 + B, hi)
-            c, w = coords[p0:p1], weights[p0:p1]
-            if cache is not None and ib < len(cache):
-                ao = cache[ib]                       # AO values stay resident in HBM across SCF cycles
-            else:
-                ao = eng.eval_ao(c, deriv=1 if gga else 0)
-                if cache is not None:
-                    cache.append(ao)
-            if Zt is not None:
-                # D = Z Z^T: densities from the occupied orbitals on the grid (nao / n_occ times fewer flops and bytes than D.ao)
-                if gga == 2:
-                    rho, tau = eng.xc_rho_lowrank(ao, Zp, deriv=1, with_tau=True)
-                else:
-                    rho, tau = eng.xc_rho_lowrank(ao, Zp, deriv=1 if gga else 0), None
-            else:
-                C = dm @ ao[0]
-                rho = eng.xc_rho(ao, C, deriv=1 if gga else 0)
-                tau = eng.xc_tau(ao, dm) if gga == 2 else None
-            if gga == 2:
-                e, wv = eng.xc_eval_mgga(terms, rho, tau, w)
-            else:
-                e, wv = eng.xc_eval(terms, rho, w, gga, params=params)
-            eng.xc_tail(w, (rho[0], e), tail)     # tail[0] += w.rho (N_elec), tail[1] += w.e (E_xc): one deterministic launch
-            if os.environ.get("MI355_VMAT_MT") and not getattr(self, "_vmat_mt_set", False):
-                eng.set_option("vmat_fold_mt", float(os.environ["MI355_VMAT_MT"]))
-                self._vmat_mt_set = True
-            if self.xc_vmat_fold or os.environ.get("MI355_XC_FOLD", "0") == "1":
-                eng.xc_vmat_fold(ao, wv, gga, vmat)    # vmat += ao0 . (sum_c wv_c ao_c)^T, weighted AOs formed inside the MFMA kernel
-            else:
-                aow = eng.xc_aow(ao, wv, gga)
-                eng.xc_vmat(ao[0], aow, vmat)      # vmat += ao0 . aow^T  (split-K FP64 MFMA kernel)
-            if gga == 2:                        # kinetic-energy-density term: sum_k ao_k . (w/4 vtau ao_k)^T
-                for k in (1, 2, 3):
-                    eng.xc_vmat(ao[k], wv[4] * ao[k], vmat)
-        return hyb
-
     def _xc_block_size(self, n, npts):
         """Points per grid block of `npts` points of this rank (the blocks the AO cache holds)."""
         # grid block: as large as a ~1.5 GB working set allows (fewer launches for small molecules), at least grid_block
@@ -254,8 +186,9 @@ class RKS(RHF):
         return ((npts + nblk - 1) // nblk + 1023) // 1024 * 1024
 
     def _ao_blocks(self, gga):
-        """(weights, ao) of each grid block of this rank: the blocks of `_nr_rks_raw`, AO values from the resident cache where
-        it holds them (XC response of tdscf)."""
+        """(weights, ao) of each grid block of this rank, in order: the one loop over the grid that the SCF quadrature
+        (`_nr_rks_raw`, `_nr_uks_raw`) and the XC response of tdscf share.  AO values come from the resident cache where it
+        holds them and are put there otherwise, so every caller has to walk the same `_xc_block_size` blocks."""
         eng = self.engine
         n = eng.nao
         coords, weights = self.grids.coords, self.grids.weights
@@ -265,7 +198,7 @@ class RKS(RHF):
         for ib, p0 in enumerate(range(lo, hi, B)):
             p1 = min(p0 + B, hi)
             if cache is not None and ib < len(cache):
-                ao = cache[ib]
+                ao = cache[ib]                       # AO values stay resident in HBM across SCF cycles
             else:
                 ao = eng.eval_ao(coords[p0:p1], deriv=1 if gga else 0)
                 if cache is not None:
@@ -279,24 +212,10 @@ class RKS(RHF):
     xc_block_gb = 4.0
 
     def _xc_block_bytes(self):
-        import os
         return float(os.environ.get("MI355_XC_BLOCK_GB", self.xc_block_gb)) * 1e9
 
-    xc_vmat_fold = False  # V_xc product with the weighted AOs formed on the fly (round 3 experiment: 0.88-1.8 ms against 0.75 ms for the xc_aow pass + xc_vmat)
     xc_lowrank = True   # inside the SCF loop: rho from occupied-orbital values (D = Z Z^T) instead of D.ao
     xc_lowrank_min_nao = 128   # below this the dozen small launches of the factorisation cost more than the D.ao GEMM (CH3/cc-pVTZ UKS: 2.9 -> 3.4 ms)
-
-    def _occ_factor(self, dm):
-        """Z^T [n_occ, nao] with D = Z Z^T when the SCF step declared `dm` a closed-shell projector density (`_xc_projector`:
-        D' = 2 X in the orthonormal basis, X idempotent of rank n_occ), else None.  No diagonalisation: W = X G for a fixed
-        Gaussian G [nao, n_occ] spans the occupied space, M = G^T X G = W^T W, Cholesky M = R R^T, Z' = W R^-T has orthonormal
-        columns (X = Z' Z'^T), Z = sqrt(2) L^-T Z'.  cond(M) is that of a square Gaussian matrix squared (~1e3-1e4), so the
-        factorisation is accurate to ~1e-12 (PySCF's numint takes the same shortcut from mo_coeff / mo_occ [MEM: eval_rho2])."""
-        proj = getattr(self, "_xc_projector", None)
-        if not self.xc_lowrank or proj is None or proj[0] is not dm:
-            return None
-        _dm, dmo, nocc = proj
-        return self._lowrank_factor(dmo, nocc, "rks")
 
     def _lowrank_factor(self, dmo, nocc, key):
         """Z^T [nocc, nao] with L^-T dmo L^-1 = Z Z^T for a positive semidefinite orthonormal-basis matrix `dmo` of rank nocc
@@ -353,6 +272,84 @@ class RKS(RHF):
     def _grid_range(self, ng):
         from . import parallel
         return parallel.split_range(ng, self._rank, self._nranks)
+
+
+class RKS(KSMixin, RHF):
+    small_rho_cutoff = 1e-7   # PySCF RKS default [MEM]
+
+    def reset(self, mol=None):
+        super().reset(mol)
+        self._pruned = False    # the new grid is pruned by the first density it sees
+        return self
+
+    def nr_rks(self, dm):
+        """(N_elec, E_xc, V_xc, hyb) on device for a closed-shell density (numint.nr_rks [MEM]): this rank's share of the
+        grid; sharded callers all-reduce."""
+        n = self.engine.nao
+        vmat = torch.zeros(n, n, dtype=torch.float64, device=self.engine.device)
+        tail = torch.zeros(2, dtype=torch.float64, device=self.engine.device)
+        hyb = self._nr_rks_raw(dm, vmat, tail)
+        return tail[0], tail[1], vmat + vmat.T, hyb
+
+    def _nr_rks_raw(self, dm, vmat, tail):
+        """Accumulate the UNsymmetrised XC matrix (V_xc = vmat + vmat^T) into `vmat` and [N_elec, E_xc] into `tail` -- views of
+        a caller-owned (zeroed) buffer, e.g. the fused all-reduce buffer of `_fock_energy`.  Returns the exact-exchange
+        fraction of the functional."""
+        eng = self.engine
+        hyb, terms, gga = parse_xc(self.xc)
+        params = xc_params(self.xc)
+        n = eng.nao
+        Zt = self._occ_factor(dm)
+        if Zt is not None:   # [nao, ldz] with the orbital index fastest, zero-padded to the kernel's chunk (24 GGA / 32 LDA)
+            ch = 24 if gga else 32
+            ldz = (Zt.shape[0] + ch - 1) // ch * ch
+            Zp = getattr(self, "_zp_buf", None)      # persistent: the padding columns are zeroed once, not every cycle
+            if Zp is None or Zp.shape != (n, ldz) or Zp.device != Zt.device or self._zp_nocc != Zt.shape[0]:
+                Zp = self._zp_buf = torch.zeros(n, ldz, dtype=torch.float64, device=Zt.device)
+                self._zp_nocc = Zt.shape[0]
+            Zp[:, :Zt.shape[0]].copy_(Zt.T)
+        for w, ao in self._ao_blocks(gga):
+            if Zt is not None:
+                # D = Z Z^T: densities from the occupied orbitals on the grid (nao / n_occ times fewer flops and bytes than D.ao)
+                if gga == 2:
+                    rho, tau = eng.xc_rho_lowrank(ao, Zp, deriv=1, with_tau=True)
+                else:
+                    rho, tau = eng.xc_rho_lowrank(ao, Zp, deriv=1 if gga else 0), None
+            else:
+                C = dm @ ao[0]
+                rho = eng.xc_rho(ao, C, deriv=1 if gga else 0)
+                tau = eng.xc_tau(ao, dm) if gga == 2 else None
+            if gga == 2:
+                e, wv = eng.xc_eval_mgga(terms, rho, tau, w)
+            else:
+                e, wv = eng.xc_eval(terms, rho, w, gga, params=params)
+            eng.xc_tail(w, (rho[0], e), tail)     # tail[0] += w.rho (N_elec), tail[1] += w.e (E_xc): one deterministic launch
+            if os.environ.get("MI355_VMAT_MT") and not getattr(self, "_vmat_mt_set", False):
+                eng.set_option("vmat_fold_mt", float(os.environ["MI355_VMAT_MT"]))
+                self._vmat_mt_set = True
+            if self.xc_vmat_fold or os.environ.get("MI355_XC_FOLD", "0") == "1":
+                eng.xc_vmat_fold(ao, wv, gga, vmat)    # vmat += ao0 . (sum_c wv_c ao_c)^T, weighted AOs formed inside the MFMA kernel
+            else:
+                aow = eng.xc_aow(ao, wv, gga)
+                eng.xc_vmat(ao[0], aow, vmat)      # vmat += ao0 . aow^T  (split-K FP64 MFMA kernel)
+            if gga == 2:                        # kinetic-energy-density term: sum_k ao_k . (w/4 vtau ao_k)^T
+                for k in (1, 2, 3):
+                    eng.xc_vmat(ao[k], wv[4] * ao[k], vmat)
+        return hyb
+
+    xc_vmat_fold = False  # V_xc product with the weighted AOs formed on the fly (round 3 experiment: 0.88-1.8 ms against 0.75 ms for the xc_aow pass + xc_vmat; DESIGN.md 8.8)
+
+    def _occ_factor(self, dm):
+        """Z^T [n_occ, nao] with D = Z Z^T when the SCF step declared `dm` a closed-shell projector density (`_xc_projector`:
+        D' = 2 X in the orthonormal basis, X idempotent of rank n_occ), else None.  No diagonalisation: W = X G for a fixed
+        Gaussian G [nao, n_occ] spans the occupied space, M = G^T X G = W^T W, Cholesky M = R R^T, Z' = W R^-T has orthonormal
+        columns (X = Z' Z'^T), Z = sqrt(2) L^-T Z'.  cond(M) is that of a square Gaussian matrix squared (~1e3-1e4), so the
+        factorisation is accurate to ~1e-12 (PySCF's numint takes the same shortcut from mo_coeff / mo_occ [MEM: eval_rho2])."""
+        proj = getattr(self, "_xc_projector", None)
+        if not self.xc_lowrank or proj is None or proj[0] is not dm:
+            return None
+        _dm, dmo, nocc = proj
+        return self._lowrank_factor(dmo, nocc, "rks")
 
     def _prune_small_rho_grids(self, dm):
         """Drop grid points whose |rho * w| is below small_rho_cutoff / n_grid for the first density the SCF sees
@@ -451,15 +448,6 @@ class RKS(RHF):
 
     def _fused_fock_ok(self, dm):
         return not is_rsh(self.xc) and super()._fused_fock_ok(dm)
-
-    def _xc_reduced(self, dm):
-        nelec, exc, vxc, hyb = self.nr_rks(dm)
-        if self._nranks > 1:
-            from . import parallel
-            nelec, exc = nelec.reshape(1), exc.reshape(1)
-            parallel.all_reduce_fused([vxc, nelec, exc], self._pg)
-            nelec, exc = nelec[0], exc[0]
-        return nelec, exc, vxc, hyb
 
     def _veff(self, dm):
         nelec, exc, vxc, hyb = self.nr_rks(dm)

@@ -25,6 +25,28 @@ def grad_nuc(mol):
     return g
 
 
+_D2 = {(0, 0): 4, (0, 1): 5, (0, 2): 6, (1, 1): 7, (1, 2): 8, (2, 2): 9}   # component of eval_ao(deriv=2) holding d_j d_k phi, j <= k
+
+
+def _add_xc_force(fmu, ao, dm, C, wv, gga):
+    """fmu[mu] += -2 D_mu,nu int [v_rho dphi_mu phi_nu + 2 v_sigma grad rho . grad(dphi_mu phi_nu)] (+ the tau term) over one
+    grid block, for one density `dm` (closed shell, or one spin) with C = dm.ao0 and the weighted derivatives `wv` of the
+    functional that belong to it."""
+    T1 = 2.0 * wv[0] * C
+    if gga:
+        Ck = [dm @ ao[1 + j] for j in range(3)]
+        for j in range(3):
+            T1 += wv[1 + j] * Ck[j]
+        for k in range(3):
+            t2 = sum(wv[1 + j] * ao[_D2[(min(j, k), max(j, k))]] for j in range(3))
+            fmu[:, k] += -2.0 * ((ao[1 + k] * T1).sum(dim=1) + (t2 * C).sum(dim=1))
+            if gga == 2:   # d tau / d A_x = - sum_k (d_x d_k phi_mu) (D d_k phi)_mu ; wv[4] = w/4 de/dtau
+                fmu[:, k] += -4.0 * sum((ao[_D2[(min(j, k), max(j, k))]] * (wv[4] * Ck[j])).sum(dim=1) for j in range(3))
+    else:
+        for k in range(3):
+            fmu[:, k] += -2.0 * (ao[1 + k] * T1).sum(dim=1)
+
+
 class Gradients:
     """Analytic RHF/RKS gradient on the MI355X engine."""
 
@@ -37,7 +59,7 @@ class Gradients:
         self.verbose = mf.verbose
 
     def grad_xc(self, dm):
-        """-2 sum_{mu on A} D_mu,nu int [v_rho dphi_mu phi_nu + 2 v_sigma grad rho . grad(dphi_mu phi_nu)]"""
+        """XC gradient of RKS: `_add_xc_force` of the closed-shell density over this rank's grid, summed per atom."""
         from .dft import parse_xc
         mf = self.base
         eng = mf.engine
@@ -47,7 +69,6 @@ class Gradients:
         lo, hi = mf._grid_range(coords.shape[0])
         fmu = torch.zeros(n, 3, dtype=torch.float64, device=eng.device)
         B = max(4096, mf.grid_block // 4)
-        pair = {(0, 0): 4, (0, 1): 5, (0, 2): 6, (1, 1): 7, (1, 2): 8, (2, 2): 9}
         for p0 in range(lo, hi, B):
             p1 = min(p0 + B, hi)
             c, w = coords[p0:p1], weights[p0:p1]
@@ -58,20 +79,7 @@ class Gradients:
                 _e, wv = eng.xc_eval_mgga(terms, rho, eng.xc_tau(ao, dm), w)
             else:
                 _e, wv = eng.xc_eval(terms, rho, w, gga)
-            if gga:
-                Ck = [dm @ ao[1 + j] for j in range(3)]
-                T1 = 2.0 * wv[0] * C
-                for j in range(3):
-                    T1 += wv[1 + j] * Ck[j]
-                for k in range(3):
-                    t2 = sum(wv[1 + j] * ao[pair[(min(j, k), max(j, k))]] for j in range(3))
-                    fmu[:, k] += -2.0 * ((ao[1 + k] * T1).sum(dim=1) + (t2 * C).sum(dim=1))
-                    if gga == 2:   # d tau / d A_x = - sum_k (d_x d_k phi_mu) (D d_k phi)_mu ; wv[4] = w/4 de/dtau
-                        fmu[:, k] += -4.0 * sum((ao[pair[(min(j, k), max(j, k))]] * (wv[4] * Ck[j])).sum(dim=1) for j in range(3))
-            else:
-                T1 = 2.0 * wv[0] * C
-                for k in range(3):
-                    fmu[:, k] += -2.0 * (ao[1 + k] * T1).sum(dim=1)
+            _add_xc_force(fmu, ao, dm, C, wv, gga)
         if mf._nranks > 1:
             from . import parallel
             parallel.all_reduce_sum(fmu, mf._pg)
@@ -194,7 +202,7 @@ class UGradients(Gradients):
     grad = kernel
 
     def grad_xc_spin(self, dm):
-        """XC gradient of UKS: the restricted expression per spin with (D_s, wv_s) from the spin-polarised functional."""
+        """XC gradient of UKS: `_add_xc_force` per spin with (D_s, wv_s) from the spin-polarised functional."""
         from .dft import parse_xc
         mf = self.base
         eng = mf.engine
@@ -204,7 +212,6 @@ class UGradients(Gradients):
         lo, hi = mf._grid_range(coords.shape[0])
         fmu = torch.zeros(n, 3, dtype=torch.float64, device=eng.device)
         B = max(4096, mf.grid_block // 4)
-        pair = {(0, 0): 4, (0, 1): 5, (0, 2): 6, (1, 1): 7, (1, 2): 8, (2, 2): 9}
         for p0 in range(lo, hi, B):
             p1 = min(p0 + B, hi)
             c, w = coords[p0:p1], weights[p0:p1]
@@ -216,20 +223,7 @@ class UGradients(Gradients):
             else:
                 _e, wva, wvb = eng.xc_eval_spin(terms, rho[0], rho[1], w, gga)
             for s_, wv in ((0, wva), (1, wvb)):
-                C = Cs[s_]
-                T1 = 2.0 * wv[0] * C
-                if gga:
-                    Ck = [dm[s_] @ ao[1 + j] for j in range(3)]
-                    for j in range(3):
-                        T1 += wv[1 + j] * Ck[j]
-                    for k in range(3):
-                        t2 = sum(wv[1 + j] * ao[pair[(min(j, k), max(j, k))]] for j in range(3))
-                        fmu[:, k] += -2.0 * ((ao[1 + k] * T1).sum(dim=1) + (t2 * C).sum(dim=1))
-                        if gga == 2:
-                            fmu[:, k] += -4.0 * sum((ao[pair[(min(j, k), max(j, k))]] * (wv[4] * Ck[j])).sum(dim=1) for j in range(3))
-                else:
-                    for k in range(3):
-                        fmu[:, k] += -2.0 * (ao[1 + k] * T1).sum(dim=1)
+                _add_xc_force(fmu, ao, dm[s_], Cs[s_], wv, gga)
         if mf._nranks > 1:
             from . import parallel
             parallel.all_reduce_sum(fmu, mf._pg)

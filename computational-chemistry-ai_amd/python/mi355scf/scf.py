@@ -53,10 +53,8 @@ class DeviceDIIS:
         shape = (space, n, n) if nmat == 1 else (space, nmat, n, n)    # nmat = 2: the spin-stacked pair of UHF / UKS
         self.F = torch.empty(*shape, dtype=torch.float64, device=eng.device)
         self.E = torch.empty(*shape, dtype=torch.float64, device=eng.device)
-        self.B = np.zeros((space, space))
-        self._e = torch.empty(n, n, dtype=torch.float64, device=eng.device)
 
-    # --- split form used by the SCF step: `push*` (error-vector Gram row + Pulay solve, all on the device, no sync) then
+    # --- the SCF step's two halves: `push_inplace` (error-vector Gram row + Pulay solve, all on the device, no sync) then
     # `extrapolate` (combination with the device-resident coefficients): no host round trip inside a cycle ---
     NS = 16   # partial sums per Gram-row entry (DIIS_NS of the kernel), added in index order by the solve kernel
 
@@ -70,58 +68,24 @@ class DeviceDIIS:
         self.eng.diis_solve(self.dots_dev, m, slot, self.space, self.B_dev, self.coef_dev)
         self._pending = (slot, m)
 
-    def push(self, f, e):
-        """Store (F_i, e_i); leaves the Pulay coefficients of the enlarged history in `self.coef_dev[:m]` on the device."""
-        slot = self.count % self.space
-        self.F[slot].copy_(f)
-        self.E[slot].copy_(e)
-        self.count += 1
-        m = min(self.count, self.space)
-        self._gram_and_solve(slot, m)
-        return m
-
     def next_slot(self):
         """History slot the next push will use: the SCF step lets its GEMMs write F' and e straight into it."""
         return self.count % self.space
 
     def push_inplace(self):
-        """`push` for data already written into `F[next_slot()]` / `E[next_slot()]` (no device copies)."""
+        """Take (F_i, e_i) already written into `F[next_slot()]` / `E[next_slot()]` (no device copies) into the history; leaves
+        the Pulay coefficients of the enlarged history in `self.coef_dev[:m]` on the device."""
         slot = self.count % self.space
         self.count += 1
         m = min(self.count, self.space)
         self._gram_and_solve(slot, m)
         return m
 
-    def extrapolate(self, dots=None):
-        """F = sum_i c_i F_i with the coefficients the last push solved for (`dots` is ignored: kept for callers of the
-        round-1 host-solve signature)."""
+    def extrapolate(self):
+        """F = sum_i c_i F_i with the coefficients the last push solved for."""
         _slot, m = self._pending
         out = torch.empty_like(self.F[0])
         self.eng.diis_combine_dev(self.F, self.coef_dev, m, out)
-        return out
-
-    def update(self, s, d, f):
-        sdf = s @ d @ f
-        self.eng.diis_errvec(sdf, self._e)
-        slot = self.count % self.space
-        self.F[slot].copy_(f)
-        self.E[slot].copy_(self._e)
-        self.count += 1
-        m = min(self.count, self.space)
-        dots = self.eng.diis_dots(self.E, self._e, m)
-        self.B[slot, :m] = dots
-        self.B[:m, slot] = dots
-        A = np.zeros((m + 1, m + 1))
-        A[0, 1:] = A[1:, 0] = 1.0
-        A[1:, 1:] = self.B[:m, :m]
-        rhs = np.zeros(m + 1)
-        rhs[0] = 1.0
-        try:
-            c = np.linalg.solve(A, rhs)
-        except np.linalg.LinAlgError:
-            c = np.linalg.lstsq(A, rhs, rcond=None)[0]
-        out = torch.empty_like(f)
-        self.eng.diis_combine(self.F, c[1:], out)
         return out
 
 
@@ -703,35 +667,42 @@ class SCF:
         else:
             parts = [part] + ([extra.reshape(-1)] if extra is not None else []) + ([sp2_tr] if sp2_tr is not None else [])
             packed = torch.cat(parts) if len(parts) > 1 else part
+        return dict(dm=dm, fock=fock, fo=fo, nb=nb, n_extra=0 if extra is None else extra.numel(), has_tr=sp2_tr is not None,
+                    layout=layout, lowrank=self._xc_projector is not None, scalars=self._scalars_launch(packed))
+
+    def _scalars_launch(self, packed):
+        """Start the read-back of a cycle's packed control scalars: (packed, event) for `_scalars_wait`; event None = the
+        vector is too long for the pinned buffer and the wait copies it blocking."""
         # Sharded runs: every rank holds the same all-reduced J/K(/Vxc) and the replicated algebra above is free of atomics
         # (fixed-order partial sums), so these scalars should be bit-identical on all ranks; until a multi-GPU run has confirmed
         # that for the library GEMMs in between, rank 0's copy is made authoritative (`sync_control`, one small broadcast).
         if self._sync_control_on():
             from . import parallel
             parallel.broadcast0(packed, self._pg)
-        ctx = dict(dm=dm, fock=fock, fo=fo, nb=nb, n_extra=0 if extra is None else extra.numel(), has_tr=sp2_tr is not None,
-                   layout=layout, lowrank=self._xc_projector is not None,
-                   packed=packed, event=None)
         k = packed.numel()
-        if k <= self._PIN_DOUBLES:
-            pin = getattr(self, "_pin", None)
-            if pin is None:
-                pin = self._pin = torch.empty(self._PIN_DOUBLES, dtype=torch.float64).pin_memory()
-                self._pin_event = torch.cuda.Event()
-            pin[:k].copy_(packed, non_blocking=True)
-            self._pin_event.record()
-            ctx["event"] = self._pin_event
-        return ctx
+        if k > self._PIN_DOUBLES:
+            return packed, None
+        pin = getattr(self, "_pin", None)
+        if pin is None:
+            pin = self._pin = torch.empty(self._PIN_DOUBLES, dtype=torch.float64).pin_memory()
+            self._pin_event = torch.cuda.Event()
+        pin[:k].copy_(packed, non_blocking=True)
+        self._pin_event.record()
+        return packed, self._pin_event
+
+    def _scalars_wait(self, scalars):
+        """The host array of `_scalars_launch`'s vector: the only host synchronisation of a cycle."""
+        packed, event = scalars
+        if event is None:
+            return packed.cpu().numpy()
+        event.synchronize()
+        return self._pin[:packed.numel()].numpy().copy()
 
     def _after_density_finish(self, st, ctx, e_last, nocc=0):
         """Host part: wait for the scalars of the cycle (the only host synchronisation of a cycle), validate the optimistic
         purification, update the state.  False: the purification had not converged -- nothing in `st` was touched."""
         nb = ctx["nb"]
-        if ctx["event"] is not None:
-            ctx["event"].synchronize()
-            vals = self._pin[:ctx["packed"].numel()].numpy().copy()
-        else:
-            vals = ctx["packed"].cpu().numpy()
+        vals = self._scalars_wait(ctx["scalars"])
         e_el = float(vals[:nb].sum())                  # numpy's pairwise sum: the same order on every rank
         c2 = float(vals[nb:2 * nb].sum())
         pos = 2 * nb

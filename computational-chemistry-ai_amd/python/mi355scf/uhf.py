@@ -13,7 +13,22 @@ import numpy as np
 import torch
 
 from .purify import Purifier
-from .scf import SCF
+from .scf import SCF, DeviceDIIS
+
+
+def pulay_coefficients(B, m):
+    """Coefficients c[:m] (sum 1) that minimise |sum_i c_i e_i| for the Gram matrix B[:m, :m] of the error vectors: the
+    bordered Pulay system, by least squares when it is singular."""
+    A = np.zeros((m + 1, m + 1))
+    A[0, 1:] = A[1:, 0] = 1.0
+    A[1:, 1:] = B[:m, :m]
+    rhs = np.zeros(m + 1)
+    rhs[0] = 1.0
+    try:
+        c = np.linalg.solve(A, rhs)
+    except np.linalg.LinAlgError:
+        c = np.linalg.lstsq(A, rhs, rcond=None)[0]
+    return c[1:]
 
 
 class PairDIIS:
@@ -45,16 +60,8 @@ class PairDIIS:
         dots = dots.cpu().numpy()
         self.B[slot, :m] = dots
         self.B[:m, slot] = dots
-        A = np.zeros((m + 1, m + 1))
-        A[0, 1:] = A[1:, 0] = 1.0
-        A[1:, 1:] = self.B[:m, :m]
-        rhs = np.zeros(m + 1)
-        rhs[0] = 1.0
-        try:
-            c = np.linalg.solve(A, rhs)
-        except np.linalg.LinAlgError:
-            c = np.linalg.lstsq(A, rhs, rcond=None)[0]
-        cw = torch.as_tensor(c[1:], dtype=f.dtype, device=f.device).reshape(m, 1, 1, 1)
+        c = pulay_coefficients(self.B, m)
+        cw = torch.as_tensor(c, dtype=f.dtype, device=f.device).reshape(m, 1, 1, 1)
         return (cw * self.F[:m]).sum(dim=0)
 
 
@@ -232,30 +239,13 @@ class UHF(SCF):
         if keep:
             diis.push_inplace()
         parts = [e_el.reshape(1), part] + [t for t in trs if t is not None]
-        packed = torch.cat(parts)
-        if self._sync_control_on():     # sharded: rank 0's control scalars are everybody's (see scf.SCF.sync_control)
-            from . import parallel
-            parallel.broadcast0(packed, self._pg)
-        ctx = dict(dm=dm, dmo=dmo, F=F, fo=fo, nb=nb, packed=packed, tr_sizes=[0 if t is None else t.numel() for t in trs], event=None)
-        k = packed.numel()
-        if k <= self._PIN_DOUBLES:
-            pin = getattr(self, "_pin", None)
-            if pin is None:
-                pin = self._pin = torch.empty(self._PIN_DOUBLES, dtype=torch.float64).pin_memory()
-                self._pin_event = torch.cuda.Event()
-            pin[:k].copy_(packed, non_blocking=True)
-            self._pin_event.record()
-            ctx["event"] = self._pin_event
-        return ctx
+        return dict(dm=dm, dmo=dmo, F=F, fo=fo, nb=nb, tr_sizes=[0 if t is None else t.numel() for t in trs],
+                    scalars=self._scalars_launch(torch.cat(parts)))
 
     def _ufinish(self, st, ctx, layouts, e_last):
         """Host part: wait for the scalars, validate the purifications, update the state.  False: a purification was not
         converged (nothing in `st` touched)."""
-        if ctx["event"] is not None:
-            ctx["event"].synchronize()
-            vals = self._pin[:ctx["packed"].numel()].numpy().copy()
-        else:
-            vals = ctx["packed"].cpu().numpy()
+        vals = self._scalars_wait(ctx["scalars"])
         nb = ctx["nb"]
         e_el = float(vals[0])
         c2 = float(vals[1:1 + 2 * nb].sum())
@@ -327,26 +317,62 @@ class UHF(SCF):
         st["cycle"] += 1
         return st
 
-    def _kernel_fast(self, dm0=None):
-        t_start = time.time()
-        mol = self.mol
-        self._setup_once()
-        eng = self.engine
-        L, Li = self._L, self._Linv
-        na, nb = mol.nelec
-        self.nelec = (na, nb)
-        n = eng.nao
+    def _udm0(self, dm0):
+        """Starting spin densities [2, N, N] on the device (`self.nelec` set): the guess when `dm0` is None, a spin-summed
+        density split by electron count, the same on every rank."""
+        na, nb = self.nelec
         if dm0 is None:
             dm0 = self.get_init_guess()
         dm0 = np.asarray(dm0)
         if dm0.ndim == 2:
             ne = max(na + nb, 1)
             dm0 = np.stack([dm0 * (na / ne), dm0 * (nb / ne)])
-        dm = torch.as_tensor(dm0, dtype=torch.float64, device=eng.device).contiguous()
+        dm = torch.as_tensor(dm0, dtype=torch.float64, device=self.engine.device).contiguous()
         if self._nranks > 1:   # one-off: identical starting density on every rank (see SCF._start)
             from . import parallel
             parallel.broadcast0(dm, self._pg)
-        from .scf import DeviceDIIS
+        return dm
+
+    def _uorbitals(self, F):
+        """(mo_energy[2, N], mo_coeff[2, N, N]) on the device: one `eigh` of the Cholesky-orthogonalised Fock matrix per spin."""
+        Li = self._Linv
+        es, cs = [], []
+        for s_ in range(2):
+            e_, c_ = torch.linalg.eigh(Li @ F[s_] @ Li.T)
+            es.append(e_); cs.append(Li.T @ c_)
+        return torch.stack(es), torch.stack(cs)
+
+    def _uresult(self, dm, F, e_tot, mo_e, mo_c, t_start):
+        """Results of a finished loop onto the object (host copies of the orbitals, aufbau occupations, plans for the next
+        kernel()); returns e_tot."""
+        na, nb = self.nelec
+        self._dm, self._fock = dm, F
+        self.e_tot = e_tot
+        self.mo_energy = mo_e.cpu().numpy()
+        self._seed_plans(mo_e)
+        self.mo_coeff = mo_c.cpu().numpy()
+        occ = np.zeros((2, self.engine.nao))
+        occ[0, :na] = 1.0
+        occ[1, :nb] = 1.0
+        self.mo_occ = occ
+        self.timing["total_seconds"] = time.time() - t_start
+        if self.converged:
+            ss, mult = self.spin_square()
+            self._log(3, f"converged SCF energy = {self.e_tot:.15g}  <S^2> = {ss:.8g}  2S+1 = {mult:.8g}")
+        else:
+            self._log(3, f"SCF not converged.\nSCF energy = {self.e_tot:.15g} after {self.max_cycle} cycles")
+        return self.e_tot
+
+    def _kernel_fast(self, dm0=None):
+        t_start = time.time()
+        mol = self.mol
+        self._setup_once()
+        eng = self.engine
+        L = self._L
+        na, nb = mol.nelec
+        self.nelec = (na, nb)
+        n = eng.nao
+        dm = self._udm0(dm0)
         st = {"nocc": (na, nb), "enuc": mol.energy_nuc(), "cycle": 0, "diis": DeviceDIIS(eng, self.diis_space, nmat=2),
               "spin": self._spin_states(n), "nvo": max(na * (n - na) + nb * (n - nb), 1), "e_tot": None}
         dmo0 = torch.stack([L.T @ dm[0] @ L, L.T @ dm[1] @ L])
@@ -366,16 +392,8 @@ class UHF(SCF):
         st.pop("front", None)
         self.cycles = st["cycle"]
         self.timing["loop_seconds"] = time.time() - t_loop
-
-        def orbitals(Fx):
-            es, cs = [], []
-            for s_ in range(2):
-                e_, c_ = torch.linalg.eigh(Li @ Fx[s_] @ Li.T)
-                es.append(e_); cs.append(Li.T @ c_)
-            return torch.stack(es), torch.stack(cs)
-
         F, dm, e_tot = st["F"], st["dm"], st["e_tot"]
-        mo_e, mo_c = orbitals(F)
+        mo_e, mo_c = self._uorbitals(F)
         if self.converged and self.conv_check:
             ca, cb = mo_c[0][:, :na], mo_c[1][:, :nb]
             dm = torch.stack([ca @ ca.T, cb @ cb.T])
@@ -383,22 +401,7 @@ class UHF(SCF):
             e_new = float(e_el) + st["enuc"]
             self._log(4, f"Extra cycle  E= {e_new:.15g}  delta_E= {e_new - e_tot:.3g}")
             e_tot = e_new
-        self._dm, self._fock = dm, F
-        self.e_tot = e_tot
-        self.mo_energy = mo_e.cpu().numpy()
-        self._seed_plans(mo_e)
-        self.mo_coeff = mo_c.cpu().numpy()
-        occ = np.zeros((2, n))
-        occ[0, :na] = 1.0
-        occ[1, :nb] = 1.0
-        self.mo_occ = occ
-        self.timing["total_seconds"] = time.time() - t_start
-        if self.converged:
-            ss, mult = self.spin_square()
-            self._log(3, f"converged SCF energy = {self.e_tot:.15g}  <S^2> = {ss:.8g}  2S+1 = {mult:.8g}")
-        else:
-            self._log(3, f"SCF not converged.\nSCF energy = {self.e_tot:.15g} after {self.max_cycle} cycles")
-        return self.e_tot
+        return self._uresult(dm, F, e_tot, mo_e, mo_c, t_start)
 
     def _kernel_plain(self, dm0=None, **kw):
         t_start = time.time()
@@ -409,16 +412,7 @@ class UHF(SCF):
         na, nb = mol.nelec
         self.nelec = (na, nb)
         n = eng.nao
-        if dm0 is None:
-            dm0 = self.get_init_guess()
-        dm0 = np.asarray(dm0)
-        if dm0.ndim == 2:
-            ne = max(na + nb, 1)
-            dm0 = np.stack([dm0 * (na / ne), dm0 * (nb / ne)])
-        dm = torch.as_tensor(dm0, dtype=torch.float64, device=eng.device).contiguous()
-        if self._nranks > 1:   # one-off: identical starting density on every rank (see SCF._start)
-            from . import parallel
-            parallel.broadcast0(dm, self._pg)
+        dm = self._udm0(dm0)
         enuc = mol.energy_nuc()
         conv_tol = self.conv_tol
         conv_tol_grad = self.conv_tol_grad if self.conv_tol_grad is not None else np.sqrt(conv_tol)
@@ -438,13 +432,6 @@ class UHF(SCF):
         t_loop = time.time()
         mo_e = mo_c = None
 
-        def orbitals(Fx):
-            es, cs = [], []
-            for s_ in range(2):
-                e_, c_ = torch.linalg.eigh(Li @ Fx[s_] @ Li.T)
-                es.append(e_); cs.append(Li.T @ c_)
-            return torch.stack(es), torch.stack(cs)
-
         def density(cs):
             ca, cb = cs[0][:, :na], cs[1][:, :nb]
             return torch.stack([ca @ ca.T, cb @ cb.T])
@@ -458,7 +445,7 @@ class UHF(SCF):
 
         def new_density(Fx):
             if not use_sp2:
-                e_, c_ = orbitals(Fx)
+                e_, c_ = self._uorbitals(Fx)
                 return density(c_), (e_, c_)
             out = []
             xs = []        # spin projectors X_s in the orthonormal basis (UKS: rho_s from a low-rank factor, `_xc_projector_pair`)
@@ -533,7 +520,7 @@ class UHF(SCF):
         if use_sp2:
             self._purifier.iters = pur[1 if nb else 0].iters   # the count of the spin purified last carries over to the object
         if self.converged and self.conv_check:
-            mo_e, mo_c = orbitals(F)
+            mo_e, mo_c = self._uorbitals(F)
             dm = density(mo_c)
             F, e_el = self._fock_pair(dm)
             e_el = e_el.reshape(1)
@@ -543,23 +530,8 @@ class UHF(SCF):
             self._log(4, f"Extra cycle  E= {e_new:.15g}  delta_E= {e_new - e_tot:.3g}")
             e_tot = e_new
         if mo_e is None or (use_sp2 and not (self.converged and self.conv_check)):
-            mo_e, mo_c = orbitals(F)
-        self._dm, self._fock = dm, F
-        self.e_tot = e_tot
-        self.mo_energy = mo_e.cpu().numpy()
-        self._seed_plans(mo_e)
-        self.mo_coeff = mo_c.cpu().numpy()
-        occ = np.zeros((2, n))
-        occ[0, :na] = 1.0
-        occ[1, :nb] = 1.0
-        self.mo_occ = occ
-        self.timing["total_seconds"] = time.time() - t_start
-        if self.converged:
-            ss, mult = self.spin_square()
-            self._log(3, f"converged SCF energy = {self.e_tot:.15g}  <S^2> = {ss:.8g}  2S+1 = {mult:.8g}")
-        else:
-            self._log(3, f"SCF not converged.\nSCF energy = {self.e_tot:.15g} after {self.max_cycle} cycles")
-        return self.e_tot
+            mo_e, mo_c = self._uorbitals(F)
+        return self._uresult(dm, F, e_tot, mo_e, mo_c, t_start)
 
     def dip_moment(self, mol=None, dm=None, unit="Debye", verbose=None, **kw):
         if dm is None:

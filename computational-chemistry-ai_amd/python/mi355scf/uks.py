@@ -9,46 +9,15 @@ The grid is not pruned by density (PySCF's `small_rho_cutoff` step is RKS-only h
 import numpy as np
 import torch
 
-from .dft import RKS, check_rsh_scf, drop_lr_engine, is_rsh, lr_engine, parse_xc, rsh_coeff, xc_params
-from .grids import Grids
+from .dft import KSMixin, check_rsh_scf, is_rsh, lr_engine, parse_xc, rsh_coeff, xc_params
 from .uhf import UHF
 
 
-class UKS(UHF):
-    xc = "LDA,VWN"
-    grid_block = RKS.grid_block
-    cache_ao = True
-    direct_reserve_gb = RKS.direct_reserve_gb
-
-    def __init__(self, mol, xc=None):
-        UHF.__init__(self, mol)
-        if xc is not None:
-            self.xc = xc
-        self.grids = Grids(mol)
-        self._nelec_grid = None
-
-    def reset(self, mol=None):
-        UHF.reset(self, mol)
-        old = self.grids
-        self.grids = Grids(self.mol)
-        self.grids.level, self.grids.prune = old.level, old.prune
-        self._ao_cache_key = self._ao_cache = None
-        drop_lr_engine(self)
-        return self
-
-    def _setup(self):
-        UHF._setup(self)
-        if self.grids.weights is None or self.grids.mol is not self.mol:
-            self.grids.mol = self.mol
-            self.grids.build(engine=self.engine)
-            self._log(4, f"XC grid: {self.grids.size} points (level {self.grids.level})")
-
-    _ao_cache_for = RKS._ao_cache_for
-    xc_block_gb = RKS.xc_block_gb
-    _xc_block_bytes = RKS._xc_block_bytes
-    _lowrank_factor = RKS._lowrank_factor
-    xc_lowrank, xc_lowrank_min_nao = True, RKS.xc_lowrank_min_nao
-    _grid_range = RKS._grid_range
+class UKS(KSMixin, UHF):
+    def _xc_block_size(self, n, npts):
+        """Full blocks of a 64 N bytes per point working set and a short tail, not the equal blocks of RKS (whose rule would
+        change the launch shapes of this loop)."""
+        return max(self.grid_block, int(self._xc_block_bytes() / (64.0 * n)) // 1024 * 1024)
 
     def nr_uks(self, dm):
         """((N_alpha, N_beta), E_xc, V_xc[2,N,N], hyb) on device for the spin densities dm[2,N,N] (numint.nr_uks [MEM]): this
@@ -65,11 +34,6 @@ class UKS(UHF):
         hyb, terms, gga = parse_xc(self.xc)
         params = xc_params(self.xc)
         n = eng.nao
-        coords, weights = self.grids.coords, self.grids.weights
-        ng = coords.shape[0]
-        lo, hi = self._grid_range(ng)
-        B = max(self.grid_block, int(self._xc_block_bytes() / (64.0 * n)) // 1024 * 1024)
-        cache = self._ao_cache_for(n, hi - lo, 4 if gga else 1)
         # spin densities declared projectors by the fast UHF/UKS loop (`_xc_projector_pair`): D_s = Z_s Z_s^T without orbitals
         Zps = [None, None]
         proj = getattr(self, "_xc_projector_pair", None)
@@ -81,18 +45,10 @@ class UKS(UHF):
                     Zp = torch.zeros(n, (Zt.shape[0] + ch - 1) // ch * ch, dtype=torch.float64, device=Zt.device)
                     Zp[:, :Zt.shape[0]] = Zt.T
                     Zps[s_] = Zp
-        for ib, p0 in enumerate(range(lo, hi, B)):
-            p1 = min(p0 + B, hi)
-            c, w = coords[p0:p1], weights[p0:p1]
-            if cache is not None and ib < len(cache):
-                ao = cache[ib]
-            else:
-                ao = eng.eval_ao(c, deriv=1 if gga else 0)
-                if cache is not None:
-                    cache.append(ao)
+        for w, ao in self._ao_blocks(gga):
             rho, tau = [None, None], [None, None]
             for s_ in range(2):
-                if Zps[s_] is not None:      # spin density from its low-rank factor (dft.RKS._lowrank_factor), one pass over ao
+                if Zps[s_] is not None:      # spin density from its low-rank factor (dft.KSMixin._lowrank_factor), one pass over ao
                     if gga == 2:
                         rho[s_], tau[s_] = eng.xc_rho_lowrank(ao, Zps[s_], deriv=1, with_tau=True)
                     else:

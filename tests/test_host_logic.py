@@ -439,3 +439,83 @@ def test_density_fitting_host_helpers():
     s = a @ a.T + 90.0 * torch.eye(90, dtype=torch.float64)
     lo = torch.linalg.cholesky(s)
     assert (tri_inv_lower(lo, base=16) @ lo - torch.eye(90, dtype=torch.float64)).abs().max() < 1e-12
+
+
+# (nao, grid points, ranks) -> the (p0, p1) blocks of every rank, computed at the commit before the loops were merged with the
+# arithmetic of `RKS._nr_rks_raw` (48 N bytes per point, one block up to 1.5 B, else equal blocks) and of `UKS._nr_uks_raw`
+# (64 N bytes per point, full blocks plus a tail), xc_block_gb = 4, grid_block = 32768
+_GRID_BLOCKS = {
+    "RKS": {
+        (264, 141000, 1): [[(0, 141000)]],                                                   # the single-block branch
+        (573, 400000, 1): [[(0, 134144), (134144, 268288), (268288, 400000)]],               # equal blocks and a remainder
+        (573, 400001, 2): [[(0, 200001)], [(200001, 400001)]],
+        (1200, 700003, 2): [[(0, 58368), (58368, 116736), (116736, 175104), (175104, 233472), (233472, 291840), (291840, 350002)],
+                            [(350002, 408370), (408370, 466738), (466738, 525106), (525106, 583474), (583474, 641842),
+                             (641842, 700003)]],
+    },
+    "UKS": {
+        (264, 141000, 1): [[(0, 141000)]],
+        (573, 400000, 1): [[(0, 108544), (108544, 217088), (217088, 325632), (325632, 400000)]],
+        (573, 400001, 2): [[(0, 108544), (108544, 200001)], [(200001, 308545), (308545, 400001)]],
+        (1200, 700003, 2): [[(0, 51200), (51200, 102400), (102400, 153600), (153600, 204800), (204800, 256000), (256000, 307200),
+                             (307200, 350002)],
+                            [(350002, 401202), (401202, 452402), (452402, 503602), (503602, 554802), (554802, 606002),
+                             (606002, 657202), (657202, 700003)]],
+    },
+}
+
+
+@pytest.mark.parametrize("rule", ["RKS", "UKS"])
+def test_grid_block_iterator_tiles_the_grid_and_serves_the_ao_cache(rule, monkeypatch):
+    """`KSMixin._ao_blocks` is the one loop over the grid behind the RKS, UKS and TDDFT quadratures: with either driver's
+    block-size rule its blocks tile this rank's points once and in order at the recorded boundaries, a second pass comes from
+    the resident AO cache, and a new grid generation (or a cache that does not fit) evaluates again."""
+    import types
+    import torch
+    from mi355scf import parallel
+    from mi355scf.dft import RKS
+    from mi355scf.uks import UKS
+    cls = {"RKS": RKS, "UKS": UKS}[rule]
+    monkeypatch.delenv("MI355_XC_BLOCK_GB", raising=False)
+    free = [64e9]
+    monkeypatch.setattr(torch.cuda, "mem_get_info", lambda device=None: (free[0], 288e9))
+
+    class StubEngine:
+        mol, device = None, "stub"
+
+        def __init__(self, nao):
+            self.nao, self.calls = nao, []
+
+        def eval_ao(self, coords, deriv=0):           # the "AO values" of a block name its first and last point
+            self.calls.append(deriv)
+            return torch.stack([coords[0, 0], coords[-1, 0] + 1])
+
+    for (nao, npts, ranks), expected in _GRID_BLOCKS[rule].items():
+        points = torch.arange(npts)
+        for rank in range(ranks):
+            mf = object.__new__(cls)
+            mf.mol, mf._eng, mf._rank, mf._nranks = None, StubEngine(nao), rank, ranks
+            mf.grids = types.SimpleNamespace(coords=points.reshape(-1, 1), weights=points, generation=7)
+
+            def one_pass(gga):
+                out = list(mf._ao_blocks(gga))
+                assert all(tuple(ao.tolist()) == (int(w[0]), int(w[-1]) + 1) for w, ao in out)    # weights and AOs of one block
+                return [tuple(ao.tolist()) for _w, ao in out], [ao for _w, ao in out]
+
+            blocks, aos = one_pass(1)
+            lo, hi = parallel.split_range(npts, rank, ranks)
+            assert blocks[0][0] == lo and blocks[-1][1] == hi
+            assert all(a[1] == b[0] for a, b in zip(blocks, blocks[1:])) and all(p0 < p1 for p0, p1 in blocks)
+            assert blocks == expected[rank]
+            assert mf._eng.calls == [1] * len(blocks)
+            blocks2, aos2 = one_pass(1)                    # served from the cache: the same tensors, nothing evaluated
+            assert blocks2 == blocks and all(a is b for a, b in zip(aos, aos2)) and len(mf._eng.calls) == len(blocks)
+            mf.grids.generation = 8                        # new point set: the cache is emptied and filled again
+            blocks3, aos3 = one_pass(1)
+            assert blocks3 == blocks and not any(a is b for a, b in zip(aos, aos3)) and len(mf._eng.calls) == 2 * len(blocks)
+            assert len(mf._ao_cache) == len(blocks)
+            free[0] = 4.0 * 8.0 * 1 * nao * (hi - lo)      # LDA values would need exactly a quarter of this: not kept
+            for _ in range(2):
+                assert one_pass(0)[0] == blocks and mf._ao_cache is None
+            assert mf._eng.calls[2 * len(blocks):] == [0] * (2 * len(blocks))
+            free[0] = 64e9
