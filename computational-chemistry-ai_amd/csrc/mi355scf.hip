@@ -3972,6 +3972,222 @@ extern "C" int mi_build_jk_multi(mi_ctx *c, const double *d_D, int n_dm, const i
     return 0;
 }
 
+// =================================================================================================
+// Occupied-index quarter transformation of the resident tiles (mi_eri_qtrans; first quarter of the AO -> MO transformation of
+// MP2): Y[o][p][q][r] = sum_s C[s][o] (s p|q r) for a batch of n <= QT_BATCH columns of C, one pass over the store per batch.
+//
+// A stored value x = w (ij|kl) (w: the tile weight of put_tile) adds
+//   C_i x to A[j][k][l],   C_j x to A[i][k][l],   C_k x to A[l][i][j],   C_l x to A[k][i][j]
+// -- the four images of the quartet that keep (k,l) resp. (i,j) in stored order.  The other four are these with the trailing
+// pair swapped, so Y = A + A^T(q <-> r) (finalize kernel; exactly symmetric, a + b == b + a).  The set of eight is invariant under
+// i <-> j, k <-> l and (ij) <-> (kl), which is why the halved block diagonals (weight 1/2 per block coincidence, or only i >= j /
+// k >= l stored in the triangular layout) give the full sum -- the argument of the batched J/K kernel above.
+//
+// Work distribution and tile image as in jk_multi_kernel: a workgroup (four waves here) digests one work item, every tile is
+// expanded to the full 8x8x8x8 block in LDS (not-stored and ragged lanes zero).  Each of the four contractions has 512 outputs
+// per tile and orbital, two per thread; a thread reads its 8 summands from LDS once and uses them for all NB orbitals (the
+// coefficients are wave-uniform scalar loads), so LDS traffic per FP64 FMA falls as 1/NB.  A[.][J][K L] is shared by the tiles
+// of a run (they differ in I only) and stays in registers until the run ends; the other three are added per tile with FP64
+// global atomics into the padded accumulator A[n][ld][ld][ld] (tile AO order).
+// =================================================================================================
+constexpr int QT_BATCH = 8;                    // orbitals per pass
+constexpr int QT_THREADS = 256;
+
+struct QtArgs {
+    const double *tiles;
+    const int64_t *tile_off;
+    const int *tile_I;
+    const RunRec *runs;
+    const int *wave_seg;
+    const double *C;           // [ld][QT_BATCH] coefficient rows in tile order, zero-padded
+    double *A;                 // [n][ld][ld][ld]
+    size_t p3;                 // ld^3
+    int ld, nao, n_cached, tri;
+    int n;                     // orbitals of this launch (<= NB of the instantiation; slots beyond it are never written)
+};
+
+template <bool NT>
+__device__ __forceinline__ void qt_load_tile(const QtArgs &A, double *__restrict__ Tl, const int64_t toff, const int bi, const int bk,
+                                             const bool dij, const bool dkl)
+{
+    const d2_t *__restrict__ T = reinterpret_cast<const d2_t *>(A.tiles + toff);
+    constexpr int NS = 2048 / QT_THREADS;
+    d2_t v[NS];
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        const int c2 = threadIdx.x + QT_THREADS * s;
+        const int j = c2 >> 8, m = (c2 >> 6) & 3, i = (c2 >> 3) & 7, k = c2 & 7;
+        const int ch = (i < bi && k < bk) ? tile_chunk(dij, dkl, bi, bk, i, j, k, m) : -1;
+        d2_t x = {0.0, 0.0};
+        if (ch >= 0) x = NT ? __builtin_nontemporal_load(T + ch) : T[ch];
+        v[s] = x;
+    }
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        const int c2 = threadIdx.x + QT_THREADS * s;
+        const int j = c2 >> 8, m = (c2 >> 6) & 3, i = (c2 >> 3) & 7, k = c2 & 7;
+        const int a = JKM_SI * i + JKM_SJ * j + JKM_SK * k + 2 * m;
+        Tl[a] = v[s].x;
+        Tl[a + 1] = v[s].y;
+    }
+}
+
+// acc[o] += sum_c Tl[base + sc * c] * Crow[c][o]  (Crow: 8 coefficient rows of QT_BATCH doubles, wave-uniform)
+template <int NB>
+__device__ __forceinline__ void qt_contract(const double *__restrict__ Tl, const int base, const int sc,
+                                            const MI_CONST_AS double *Crow, double (&acc)[NB])
+{
+    double x[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) x[c] = Tl[base + sc * c];
+#pragma unroll
+    for (int c = 0; c < 8; c++)
+#pragma unroll
+        for (int o = 0; o < NB; o++) acc[o] = fma(x[c], Crow[c * QT_BATCH + o], acc[o]);
+}
+
+template <bool NT, int NB>
+__device__ __forceinline__ void qt_segment(const QtArgs &A, double *__restrict__ Tl, const int seg)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int a = lane >> 3, b = lane & 7;
+    const MI_CONST_AS RunRec *rr = as_const(A.runs) + seg;
+    const RunRec R{rr->J, rr->K, rr->L, rr->first, rr->count};
+    const int J0 = R.J * BLK, K0 = R.K * BLK, L0 = R.L * BLK;
+    const size_t ld = A.ld;
+    const int bk = min(BLK, A.nao - K0);
+    const bool dkl = A.tri && R.K == R.L;
+    const MI_CONST_AS double *Cc = as_const(A.C);
+    const MI_CONST_AS int *tile_I = as_const(A.tile_I);
+    const MI_CONST_AS int64_t *tile_off = as_const(A.tile_off);
+    double run[2][NB];
+#pragma unroll
+    for (int s = 0; s < 2; s++)
+#pragma unroll
+        for (int o = 0; o < NB; o++) run[s][o] = 0.0;
+    for (int t = 0; t < R.count; t++) {
+        const int I = tile_I[R.first + t];
+        const int64_t toff = tile_off[R.first + t];
+        const int I0 = I * BLK;
+        const int bi = min(BLK, A.nao - I0);
+        __syncthreads();   // the previous tile's image is no longer read
+        qt_load_tile<NT>(A, Tl, toff, bi, bk, A.tri && I == R.J, dkl);
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            const int u = wave + 4 * s;      // the output index that is uniform over the wave
+            double acc[NB];
+            // A[J0+u][K0+a][L0+b] += sum_i C_i T[i,u,a,b]   (run-wide)
+            qt_contract<NB>(Tl, JKM_SJ * u + JKM_SK * a + b, JKM_SI, Cc + (size_t)I0 * QT_BATCH, run[s]);
+            // A[I0+u][K0+a][L0+b] += sum_j C_j T[u,j,a,b]
+#pragma unroll
+            for (int o = 0; o < NB; o++) acc[o] = 0.0;
+            qt_contract<NB>(Tl, JKM_SI * u + JKM_SK * a + b, JKM_SJ, Cc + (size_t)J0 * QT_BATCH, acc);
+#pragma unroll
+            for (int o = 0; o < NB; o++)
+                if (o < A.n && acc[o] != 0.0) atomicAdd(&A.A[o * A.p3 + ((size_t)(I0 + u) * ld + K0 + a) * ld + L0 + b], acc[o]);
+            // A[L0+u][I0+a][J0+b] += sum_k C_k T[a,b,k,u]
+#pragma unroll
+            for (int o = 0; o < NB; o++) acc[o] = 0.0;
+            qt_contract<NB>(Tl, JKM_SI * a + JKM_SJ * b + u, JKM_SK, Cc + (size_t)K0 * QT_BATCH, acc);
+#pragma unroll
+            for (int o = 0; o < NB; o++)
+                if (o < A.n && acc[o] != 0.0) atomicAdd(&A.A[o * A.p3 + ((size_t)(L0 + u) * ld + I0 + a) * ld + J0 + b], acc[o]);
+            // A[K0+u][I0+a][J0+b] += sum_l C_l T[a,b,u,l]
+#pragma unroll
+            for (int o = 0; o < NB; o++) acc[o] = 0.0;
+            qt_contract<NB>(Tl, JKM_SI * a + JKM_SJ * b + JKM_SK * u, 1, Cc + (size_t)L0 * QT_BATCH, acc);
+#pragma unroll
+            for (int o = 0; o < NB; o++)
+                if (o < A.n && acc[o] != 0.0) atomicAdd(&A.A[o * A.p3 + ((size_t)(K0 + u) * ld + I0 + a) * ld + J0 + b], acc[o]);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < 2; s++)
+#pragma unroll
+        for (int o = 0; o < NB; o++)
+            if (o < A.n && run[s][o] != 0.0) atomicAdd(&A.A[o * A.p3 + ((size_t)(J0 + wave + 4 * s) * ld + K0 + a) * ld + L0 + b], run[s][o]);
+}
+
+template <bool NT, int NB>
+__global__ __launch_bounds__(QT_THREADS) void eri_qtrans_kernel(QtArgs A)
+{
+    __shared__ double Tl[JKM_LDS];
+    const MI_CONST_AS int *wave_seg = as_const(A.wave_seg);
+    const int seg_end = wave_seg[blockIdx.x + 1];
+    for (int seg = wave_seg[blockIdx.x]; seg < seg_end; seg++) {
+        if (NT && seg < A.n_cached) qt_segment<false, NB>(A, Tl, seg);
+        else qt_segment<NT, NB>(A, Tl, seg);
+    }
+}
+
+// Cp[r][o] = C[iperm[r]][o0 + o] for r < nao, o < n; zero elsewhere (tile AO order, QT_BATCH columns)
+__global__ void qt_pad_coeff_kernel(const double *C, int ldc, int n, int nao, int ld, double *Cp, const int *__restrict__ iperm)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= ld * QT_BATCH) return;
+    const int r = idx / QT_BATCH, o = idx - r * QT_BATCH;
+    Cp[idx] = (r < nao && o < n) ? C[(size_t)iperm[r] * ldc + o] : 0.0;
+}
+
+// Y[o][p][q][r] = A[o][p'][q'][r'] + A[o][p'][r'][q'] in the caller's AO order (x' = perm[x]), padding dropped
+__global__ void qt_finalize_kernel(const double *A, double *Y, int nao, int ld, size_t p3, const int *__restrict__ perm)
+{
+    const size_t n2 = (size_t)nao * nao;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // (p, q, r) of orbital blockIdx.y
+    if (idx >= n2 * nao) return;
+    const int p = perm[idx / n2], q = perm[(idx / nao) % nao], r = perm[idx % nao];
+    const double *Ao = A + blockIdx.y * p3 + (size_t)p * ld * ld;
+    Y[blockIdx.y * n2 * nao + idx] = Ao[(size_t)q * ld + r] + Ao[(size_t)r * ld + q];
+}
+
+extern "C" int mi_eri_qtrans_batch(void) { return QT_BATCH; }
+
+extern "C" int mi_eri_qtrans(mi_ctx *c, const double *d_C, int nb, int ldc, double *d_Y, void *stream)
+{
+    if (!c || !d_C || !d_Y || nb < 0 || ldc < nb) return fail("mi_eri_qtrans: bad argument");
+    if (!c->eri_ready) return fail("mi_eri_qtrans: call mi_eri_prepare first");
+    if (c->nranks != 1) return fail("mi_eri_qtrans: needs the whole (unsharded) tile store");
+    if (nb == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ld = c->ldp, p3 = ld * ld * ld, n3 = (size_t)c->nao * c->nao * c->nao;
+    const int nmax = std::min(nb, QT_BATCH);
+    double *d_A = nullptr, *d_Cp = nullptr;
+    if (dev_malloc(&d_A, sizeof(double) * p3 * nmax) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("mi_eri_qtrans: no device memory for the %.2f GB accumulator", 8e-9 * p3 * nmax);
+    }
+    if (dev_malloc(&d_Cp, sizeof(double) * ld * QT_BATCH) != hipSuccess) { (void)hipGetLastError(); dev_free(d_A); return fail("mi_eri_qtrans: no device memory"); }
+    const bool nt = c->opt_jk_nt != 0 && (c->opt_jk_nt > 1 || c->tile_doubles * 8 > ((int64_t)256 << 20));
+    int rc = 0;
+    for (int m0 = 0; m0 < nb && !rc; m0 += QT_BATCH) {
+        const int n = std::min(QT_BATCH, nb - m0);
+        hipLaunchKernelGGL(qt_pad_coeff_kernel, dim3((unsigned)((ld * QT_BATCH + 255) / 256)), dim3(256), 0, st, d_C + m0, ldc, n, c->nao,
+                           (int)ld, d_Cp, c->d_iperm);
+        if (hipMemsetAsync(d_A, 0, sizeof(double) * p3 * n, st) != hipSuccess) { rc = fail("mi_eri_qtrans: memset failed"); break; }
+        if (c->n_tiles > 0) {
+            QtArgs A{c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg, d_Cp, d_A, p3, (int)ld, c->nao, c->n_jk_cached, c->tri, n};
+            dim3 g(c->n_jk_waves), b(QT_THREADS);
+#define QT_LAUNCH(P) do { if (nt) hipLaunchKernelGGL((eri_qtrans_kernel<true, P>), g, b, 0, st, A); \
+                          else hipLaunchKernelGGL((eri_qtrans_kernel<false, P>), g, b, 0, st, A); } while (0)
+            if (n <= 1) QT_LAUNCH(1);
+            else if (n <= 2) QT_LAUNCH(2);
+            else if (n <= 4) QT_LAUNCH(4);
+            else QT_LAUNCH(8);
+#undef QT_LAUNCH
+        }
+        hipLaunchKernelGGL(qt_finalize_kernel, dim3((unsigned)((n3 + 255) / 256), (unsigned)n), dim3(256), 0, st, d_A, d_Y + (size_t)m0 * n3,
+                           c->nao, (int)ld, p3, c->d_perm);
+        if (hipGetLastError() != hipSuccess) rc = fail("mi_eri_qtrans: kernel launch failed");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail("mi_eri_qtrans: %s", hipGetErrorString(hipGetLastError()));
+    dev_free(d_A);
+    dev_free(d_Cp);
+    return rc;
+}
+
 extern "C" int mi_time_jk_variant(mi_ctx *c, const double *d_D, int with_j, int with_k, int reps, double *ms, void *stream)
 {
     if (!c || !d_D || !ms || reps < 1 || (!with_j && !with_k)) return fail("mi_time_jk_variant: bad argument");

@@ -69,6 +69,7 @@ def lib():
         L.mi_build_jk.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
         L.mi_build_jk_multi.argtypes = [vp, vp, ctypes.c_int, ip, vp, vp, vp]
         L.mi_eri_unpack.argtypes = [vp, vp, vp]
+        L.mi_eri_qtrans.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
         L.mi_time_jk_kernel.argtypes = [vp, vp, ctypes.c_int, dp, vp]
         L.mi_time_jk_variant.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, vp]
         L.mi_diis_errvec.argtypes = [vp, vp, vp, vp]
@@ -358,6 +359,33 @@ class Engine:
         out = self._new(n, n, n, n)
         with torch.cuda.device(self.device):
             _check(lib().mi_eri_unpack(self._h, out.data_ptr(), self._stream()))
+        return out
+
+    @staticmethod
+    def qtrans_batch():
+        """Columns `eri_qtrans` transforms per pass over the store (more run as several passes)."""
+        return int(lib().mi_eri_qtrans_batch())
+
+    def eri_qtrans(self, C_batch, out=None):
+        """Y[o, p, q, r] = sum_s C_batch[s, o] (s p|q r) from the resident tiles (mi_eri_qtrans): device tensor [nb, N, N, N],
+        symmetric in (q, r).  `out`: contiguous [nb, N, N, N] device tensor to write into.  Unsharded resident store only."""
+        if not self.eri_ready:
+            self.prepare_eri()
+        C = torch.as_tensor(C_batch, dtype=torch.float64, device=self.device)
+        if C.dim() == 1:
+            C = C[:, None]
+        C = C.contiguous()
+        n = self.nao
+        if C.dim() != 2 or C.shape[0] != n:
+            raise ValueError(f"eri_qtrans: C_batch must be [{n}, nb]")
+        nb = C.shape[1]
+        if out is None:
+            out = self._new(nb, n, n, n)
+        elif tuple(out.shape) != (nb, n, n, n) or not out.is_contiguous() or out.dtype != torch.float64 or out.device != self.device:
+            raise ValueError(f"eri_qtrans: out must be a contiguous float64 [{nb}, {n}, {n}, {n}] tensor on the engine's device")
+        if nb:
+            with torch.cuda.device(self.device):
+                _check(lib().mi_eri_qtrans(self._h, C.data_ptr(), nb, nb, out.data_ptr(), self._stream()))
         return out
 
     def time_jk_kernel(self, dm, reps=20, with_j=True, with_k=True):

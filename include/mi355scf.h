@@ -166,6 +166,18 @@ int mi_build_jk_multi(mi_ctx *ctx, const double *d_D, int n_dm, const int *sym, 
  * small molecules: `mp.MP2(mf).kernel()` in templates/calculate_interaction.py:116-120.  Unsharded contexts only. */
 int mi_eri_unpack(mi_ctx *ctx, double *d_out, void *stream);
 
+/* First quarter of the AO -> MO transformation straight from the resident tiles (post-SCF methods at any size the store
+ * fits: `mp.MP2(mf).kernel()`, templates/calculate_energy.py:117-141, calculate_interaction.py:116-120):
+ *   Y[o][p][q][r] = sum_s C[s][o] (s p|q r),  o < nb,
+ * d_C: [nao][ldc] device (column o of row s at d_C[s * ldc + o], ldc >= nb), d_Y: [nb][nao][nao][nao] device, caller's AO order,
+ * exactly symmetric in (q, r); screened-out tiles contribute zero.  One streaming pass over the store per
+ * mi_eri_qtrans_batch() (= 8) columns, larger requests run as several passes.  Allocates a padded accumulator of
+ * min(nb, batch) * (8 ceil(nao / 8) + 8)^3 doubles for the duration of the call and synchronises `stream` before returning.
+ * Unsharded contexts only (error otherwise, and before mi_eri_prepare); a long-range ("omega") store is transformed as it is.
+ * Stands in for the first step of pyscf.ao2mo's half transformation (AO2MOnr_e1_drv) [MEM]. */
+int mi_eri_qtrans(mi_ctx *ctx, const double *d_C, int nb, int ldc, double *d_Y, void *stream);
+int mi_eri_qtrans_batch(void);
+
 /* Time `reps` back-to-back launches of the J/K digestion kernel alone with HIP events on `stream`
  * and return the average milliseconds per launch (bench.py's roofline leg). */
 int mi_time_jk_kernel(mi_ctx *ctx, const double *d_D, int reps, double *ms_per_launch, void *stream);
