@@ -666,6 +666,48 @@ struct Scratch {   // RAII handle of one slot (or of a private allocation)
     }
 };
 
+template <class T>
+static int upload(T **dst, const std::vector<T> &v)
+{
+    if (*dst) { dev_free(*dst); *dst = nullptr; }
+    size_t n = std::max<size_t>(v.size(), 1);
+    HIPCHK(dev_malloc_impl((void **)dst, sizeof(T) * n));
+    if (!v.empty()) HIPCHK(hipMemcpy(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// Owning handle of a function-local device buffer (a block of the pool): given back when the call ends, whichever way.
+// Buffers owned by a context (mi_ctx::d_*) are not DevBufs; they live until free_eri / mi_ctx_destroy.  dev_free synchronises
+// the device, so a DevBuf that a loop reuses is declared outside the loop and grown with reserve().
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;   // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { reset(); }
+    void reset() { if (p) dev_free(p); p = nullptr; cap = 0; }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+    hipError_t alloc(size_t n)   // contents undefined
+    {
+        reset();
+        const hipError_t e = dev_malloc(&p, sizeof(T) * n);
+        if (e == hipSuccess) cap = n; else p = nullptr;
+        return e;
+    }
+    // room for n elements, contents undefined; a buffer that has to grow doubles (task prefixes of class pair after class pair)
+    hipError_t reserve(size_t n) { return n > cap ? alloc(2 * n) : hipSuccess; }
+    int upload(const std::vector<T> &v)
+    {
+        cap = 0;
+        if (::upload(&p, v)) return -1;
+        cap = std::max<size_t>(v.size(), 1);
+        return 0;
+    }
+};
+
 extern "C" void mi_release_cache(void)
 {
     {
@@ -2106,16 +2148,6 @@ static int64_t class_prefix(const PairClass &B, const PairClass &Kc, bool same, 
     return ntask;
 }
 
-template <class T>
-static int upload(T **dst, const std::vector<T> &v)
-{
-    if (*dst) { dev_free(*dst); *dst = nullptr; }
-    size_t n = std::max<size_t>(v.size(), 1);
-    HIPCHK(dev_malloc_impl((void **)dst, sizeof(T) * n));
-    if (!v.empty()) HIPCHK(hipMemcpy(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
-    return 0;
-}
-
 // Classes that run four quartets per wave (measured per class on ibuprofen/def2-TZVP: with more roots or components
 // the 16-lane groups need more primitive batches / passes than they win by overlapping four latency chains).
 static bool eri_small_class(const EriArgs &E) { return E.nroots <= 2 && E.ncomp <= 18; }
@@ -2295,34 +2327,146 @@ extern "C" int mi_plan_shards(int nao, const double *qblk, double tol, int nrank
     return 0;
 }
 
-static int grad_records_host(mi_ctx *c);
-
-extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void *stream)
+static std::vector<std::vector<double>> c2s_tables()
 {
-    if (c && check_orbital_lmax(c, "mi_eri_prepare")) return -1;
-    if (!c) return fail("mi_eri_prepare: null context");
-    if (nranks < 1 || rank < 0 || rank >= nranks) return fail("mi_eri_prepare: bad rank/nranks");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    auto t_start = std::chrono::steady_clock::now();
-    auto t_phase = t_start;
-    auto lap = [&](const char *what) {
-        if (!getenv("MI355_DEBUG")) return;
-        hipStreamSynchronize(st);
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[mi355] eri_prepare %-28s %.3f s\n", what, std::chrono::duration<double>(now - t_phase).count());
-        t_phase = now;
-    };
-    free_eri(c);
-    if (set_tile_order(c, c->opt_ao_order ? 1 : 0)) return -1;
-    const int nbas = c->nbas;
     std::vector<std::vector<double>> c2s(LMAX + 1);
     for (int l = 0; l <= LMAX; l++) c2s_generic(l, c2s[l]);
+    return c2s;
+}
 
-    // ---- 1. shell pairs, primitive-pair records, transformation matrices
+// ---- Primitive-pair records of a shell pair (I, J): 8 doubles {p, Px, Py, Pz, PAx, PAy, PAz, K} per primitive pair, the
+// primitives of I outermost.  Primitive pairs with mu r^2 > 80 are dropped.  Every driver (mi_eri_prepare, mi_df_build, the
+// variant records of the two gradients) counts and writes through these two functions: the record order defines
+// PairRec::prim_off, so the count and the writer must agree to the bit.
+static int count_prim_pairs(const ShellH &I, const ShellH &J)
+{
+    double r2 = 0.0;
+    for (int d = 0; d < 3; d++) r2 += (I.r[d] - J.r[d]) * (I.r[d] - J.r[d]);
+    int np = 0;
+    for (int ip = 0; ip < I.nprim; ip++)
+        for (int jp = 0; jp < J.nprim; jp++)
+            if (I.exps[ip] * J.exps[jp] / (I.exps[ip] + J.exps[jp]) * r2 <= 80.0) np++;
+    return np;
+}
+// Writes the records to `dst` (room for I.nprim * J.nprim of them) and returns their number.  times_2a: the coefficient of
+// I's primitive carries 2 alpha (the l+1 variant of a differentiated shell, see the gradient section).
+static int write_prim_pairs(const ShellH &I, const ShellH &J, bool times_2a, double *dst)
+{
+    double AB[3] = {I.r[0] - J.r[0], I.r[1] - J.r[1], I.r[2] - J.r[2]};
+    double r2 = AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2];
+    int np = 0;
+    for (int ip = 0; ip < I.nprim; ip++)
+        for (int jp = 0; jp < J.nprim; jp++) {
+            double a = I.exps[ip], b = J.exps[jp], p = a + b, mu = a * b / p;
+            if (mu * r2 > 80.0) continue; // exp(-80) = 1.8e-35: below double resolution of any sum
+            double K = I.coef[ip] * J.coef[jp] * std::exp(-mu * r2) * (times_2a ? 2.0 * a : 1.0);
+            double Pc[3];
+            for (int d = 0; d < 3; d++) Pc[d] = (a * I.r[d] + b * J.r[d]) / p;
+            double rec[8] = {p, Pc[0], Pc[1], Pc[2], Pc[0] - I.r[0], Pc[1] - I.r[1], Pc[2] - I.r[2], K};
+            memcpy(dst, rec, sizeof rec);
+            dst += 8;
+            np++;
+        }
+    return np;
+}
+static int append_prim_pairs(const ShellH &I, const ShellH &J, std::vector<double> &prim)
+{
+    const size_t at = prim.size();
+    prim.resize(at + (size_t)8 * I.nprim * J.nprim);
+    const int np = write_prim_pairs(I, J, false, prim.data() + at);
+    prim.resize(at + (size_t)8 * np);
+    return np;
+}
+// The auxiliary "pair" (P, unit s function) of density fitting: p = alpha, centre P = A, P - A = 0, K = c_P * c_unit
+static void write_aux_prims(const ShellH &S, const ShellH &U, double *dst)
+{
+    for (int ip = 0; ip < S.nprim; ip++) {
+        double rec[8] = {S.exps[ip], S.r[0], S.r[1], S.r[2], 0.0, 0.0, 0.0, S.coef[ip] * U.coef[0]};
+        memcpy(dst + (size_t)8 * ip, rec, sizeof rec);
+    }
+}
+// M [nsab][ne] (build_M) followed by its transpose [ne][nsab]: the MFMA transform reads both operands with the lane index on
+// the contiguous dimension
+static void build_M_and_transpose(int la, int lb, const double AB[3], const std::vector<double> &ca, const std::vector<double> &cb, double *M)
+{
+    build_M(la, lb, AB, ca, cb, M);
+    const int nsab = (2 * la + 1) * (2 * lb + 1), ne = ne_of(la, lb);
+    double *Mt = M + (size_t)nsab * ne;
+    for (int r = 0; r < nsab; r++)
+        for (int e = 0; e < ne; e++) Mt[(size_t)e * nsab + r] = M[(size_t)r * ne + e];
+}
+
+// ---- Set-up of one pass over a (bra class, ket class) pair, shared by the four integral drivers
+// dense task list: every bra meets all `nket` kets (density fitting)
+static int64_t dense_prefix(int nbra, int nket, std::vector<int64_t> &prefix)
+{
+    prefix.resize((size_t)nbra + 1);
+    for (int b = 0; b <= nbra; b++) prefix[b] = (int64_t)b * nket;
+    const int64_t ntask = prefix.back();
+    append_coarse_index(prefix);
+    return ntask;
+}
+// the copy is asynchronous: `prefix` must live until the stream is synchronised (upload_comp_table below does)
+static int prefix_to_device(const std::vector<int64_t> &prefix, DevBuf<int64_t> &d_prefix, hipStream_t st)
+{
+    HIPCHK(d_prefix.reserve(prefix.size()));
+    HIPCHK(hipMemcpyAsync(d_prefix, prefix.data(), sizeof(int64_t) * prefix.size(), hipMemcpyHostToDevice, st));
+    return 0;
+}
+static const size_t COMP_CAP = 16384;   // entries of a device component table ((g+1 f|f f) needs 7400)
+static int upload_comp_table(int la, int lb, int lc, int ld, uint32_t *d_comp, hipStream_t st)
+{
+    std::vector<uint32_t> comp;
+    build_comp_table(la, lb, lc, ld, comp);
+    if (comp.size() > COMP_CAP) return fail("component table too large");
+    HIPCHK(hipMemcpyAsync(d_comp, comp.data(), sizeof(uint32_t) * comp.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st)); // host vectors go out of scope
+    return 0;
+}
+// the fields of EriArgs every Rys launch sets: class dimensions, the two pair lists, task prefix, component table, output
+static EriArgs eri_class_args(const mi_ctx *c, int la, int lb, int lc, int ld, const PairRec *bra, const PairRec *ket, const double *prim,
+                              const int64_t *prefix, int nbra, const uint32_t *comp, double *work)
+{
+    EriArgs E{};
+    setup_eri_dims(E, la, lb, lc, ld);
+    E.bra = bra; E.ket = ket; E.prim = prim; E.prefix = prefix; E.nbra = nbra;
+    E.comp = comp; E.work = work; E.rys = c->rys; E.diag = 0;
+    return E;
+}
+
+static int grad_records_host(mi_ctx *c);
+
+// =================================================================================================
+// mi_eri_prepare: a sequence of phases (the functions below, in call order).  What outlives the call lives in mi_ctx; what
+// only the phases hand to one another travels in PrepareState.
+// =================================================================================================
+struct PrepareState {
+    mi_ctx *c;
+    hipStream_t st;
+    double tol;
+    int rank, nranks;
+    size_t work_doubles = 0;            // capacity of the [e0|f0] hand-over buffer
+    Scratch scr_work, scr_tasks;        // (returned to the per-device cache when the call ends, whichever way)
+    DevBuf<uint32_t> d_comp;
+    DevBuf<int64_t> d_prefix;
+    double qmax = 0.0;                  // largest Schwarz factor
+    std::vector<double> Qblk;           // block-pair Schwarz bounds [nbp]
+    double *early_zero_ptr = nullptr;   // parked store whose zero-fill was queued early, and its size
+    int64_t early_zero_doubles = 0;
+    std::vector<int32_t> table;         // tile directory [nbp(nbp+1)/2] -> local tile index or -1
+    int64_t off = 0;                    // doubles of the store
+    int64_t nuniq = 0, nquart = 0;      // statistics: unique integrals stored, quartets evaluated
+};
+
+// ---- 1. shell pairs, primitive-pair records, transformation matrices
+static int prepare_pairs(PrepareState &S)
+{
+    mi_ctx *c = S.c;
+    const int nbas = c->nbas;
+    const std::vector<std::vector<double>> c2s = c2s_tables();
     std::vector<double> &prim = c->h_prim, &Mbuf = c->h_M;
     prim.clear(); Mbuf.clear();
-    c->tol = tol; c->grad_ready = false; c->rank = rank; c->nranks = nranks;
+    c->tol = S.tol; c->grad_ready = false; c->rank = S.rank; c->nranks = S.nranks;
     c->eri_omega = c->opt_omega;   // Schwarz bounds below stay full-Coulomb (valid for erf(omega r)/r, see the header)
     for (int la = 0; la <= LMAX; la++)
         for (int lb = 0; lb <= la; lb++) {
@@ -2335,25 +2479,11 @@ extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void 
             if (c->shells[si].l < c->shells[sj].l) std::swap(si, sj);
             const ShellH &I = c->shells[si], &J = c->shells[sj];
             PairClass &P = c->pc[pc_index(I.l, J.l)];
-            double AB[3] = {I.r[0] - J.r[0], I.r[1] - J.r[1], I.r[2] - J.r[2]};
-            double r2 = AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2];
             PairRec R;
             R.sh_i = si; R.sh_j = sj; R.ao_i = I.ao; R.ao_j = J.ao; R.pad = 0;
             R.prim_off = (int)(prim.size() / 8);
-            int np = 0;
-            for (int ip = 0; ip < I.nprim; ip++)
-                for (int jp = 0; jp < J.nprim; jp++) {
-                    double a = I.exps[ip], b = J.exps[jp], p = a + b, mu = a * b / p;
-                    if (mu * r2 > 80.0) continue; // exp(-80) = 1.8e-35: below double resolution of any sum
-                    double K = I.coef[ip] * J.coef[jp] * std::exp(-mu * r2);
-                    double Pc[3];
-                    for (int d = 0; d < 3; d++) Pc[d] = (a * I.r[d] + b * J.r[d]) / p;
-                    double rec[8] = {p, Pc[0], Pc[1], Pc[2], Pc[0] - I.r[0], Pc[1] - I.r[1], Pc[2] - I.r[2], K};
-                    prim.insert(prim.end(), rec, rec + 8);
-                    np++;
-                }
-            if (np == 0) continue;
-            R.nprim = np;
+            R.nprim = append_prim_pairs(I, J, prim);
+            if (R.nprim == 0) continue;
             R.m_off = (int)Mbuf.size();
             Mbuf.resize(Mbuf.size() + (size_t)2 * P.nsab * P.ne); // M [nsab][ne] followed by its transpose [ne][nsab]
             P.recs.push_back(R);
@@ -2366,88 +2496,78 @@ extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void 
         for (size_t q = 0; q < all.size(); q++) {
             const ShellH &I = c->shells[all[q]->sh_i], &J = c->shells[all[q]->sh_j];
             double AB[3] = {I.r[0] - J.r[0], I.r[1] - J.r[1], I.r[2] - J.r[2]};
-            double *M = Mbuf.data() + all[q]->m_off;
-            build_M(I.l, J.l, AB, c2s[I.l], c2s[J.l], M);
-            // transposed copy: the MFMA transform reads both operands with the lane index on the contiguous dimension
-            const int nsab = (2 * I.l + 1) * (2 * J.l + 1), ne = ne_of(I.l, J.l);
-            double *Mt = M + (size_t)nsab * ne;
-            for (int r = 0; r < nsab; r++)
-                for (int e = 0; e < ne; e++) Mt[(size_t)e * nsab + r] = M[(size_t)r * ne + e];
+            build_M_and_transpose(I.l, J.l, AB, c2s[I.l], c2s[J.l], Mbuf.data() + all[q]->m_off);
         }
     }
     if (Mbuf.size() > (size_t)INT32_MAX) return fail("transformation-matrix buffer exceeds 2^31 doubles");
     if (upload(&c->d_prim, prim)) return -1;
     if (upload(&c->d_M, Mbuf)) return -1;
+    return 0;
+}
 
-    lap("pairs + M matrices");
+// ---- 2. Schwarz bounds per pair (GPU)
+static int prepare_schwarz(PrepareState &S)
+{
+    mi_ctx *c = S.c;
+    hipStream_t st = S.st;
     // workspace for cartesian intermediates
     // [e0|f0] blocks travel from the Rys launch to the transform launch through this buffer: small enough that a batch written by
     // one launch is still in the 256 MiB Infinity Cache when the next reads it (`work_mb`)
     // sized to what the molecule can need (atoms of the initial guess: a few MiB), at most `work_mb`
-    size_t WORK_DOUBLES = (size_t)8 << 17;
-    {
-        const size_t cap = (size_t)std::max(8, c->opt_work_mb) << 17;
-        for (int bc = 0; bc < NPC; bc++)
-            for (int kc = 0; kc <= bc; kc++) {
-                const PairClass &B = c->pc[bc], &Kc = c->pc[kc];
-                const double need = (double)B.recs.size() * (double)Kc.recs.size() * (double)B.ne * (double)Kc.ne;
-                WORK_DOUBLES = (size_t)std::min<double>((double)cap, std::max<double>((double)WORK_DOUBLES, need));
-            }
-    }
-    Scratch scr_work, scr_tasks;   // (returned to the per-device cache when this call ends, whichever way)
-    if (scr_work.ensure(c->device, SCR_EVAL_WORK, sizeof(double) * WORK_DOUBLES)) return -1;
-    double *d_work = (double *)scr_work.p;
-    uint32_t *d_comp = nullptr;
-    HIPCHK(dev_malloc(&d_comp, sizeof(uint32_t) * 8192));
-
-    // ---- 2. Schwarz bounds per pair (GPU)
-    double qmax = 0.0;
+    S.work_doubles = (size_t)8 << 17;
+    const size_t cap = (size_t)std::max(8, c->opt_work_mb) << 17;
+    for (int bc = 0; bc < NPC; bc++)
+        for (int kc = 0; kc <= bc; kc++) {
+            const PairClass &B = c->pc[bc], &Kc = c->pc[kc];
+            const double need = (double)B.recs.size() * (double)Kc.recs.size() * (double)B.ne * (double)Kc.ne;
+            S.work_doubles = (size_t)std::min<double>((double)cap, std::max<double>((double)S.work_doubles, need));
+        }
+    if (S.scr_work.ensure(c->device, SCR_EVAL_WORK, sizeof(double) * S.work_doubles)) return -1;
+    HIPCHK(S.d_comp.alloc(COMP_CAP));
+    double *d_work = (double *)S.scr_work.p;
     for (int ci = 0; ci < NPC; ci++) {
         PairClass &P = c->pc[ci];
         if (P.recs.empty()) continue;
         if (upload(&P.d_recs, P.recs)) return -1;
         P.q.assign(P.recs.size(), 0.0);
         HIPCHK(dev_malloc(&P.d_q, sizeof(double) * P.recs.size()));
-        EriArgs E{};
-        setup_eri_dims(E, P.la, P.lb, P.la, P.lb);
-        std::vector<uint32_t> comp;
-        build_comp_table(P.la, P.lb, P.la, P.lb, comp);
-        HIPCHK(hipMemcpyAsync(d_comp, comp.data(), sizeof(uint32_t) * comp.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        E.bra = E.ket = P.d_recs; E.prim = c->d_prim; E.prefix = nullptr; E.nbra = (int)P.recs.size();
-        E.comp = d_comp; E.work = d_work; E.rys = c->rys; E.diag = 1;
-        size_t per = WORK_DOUBLES / E.ncomp;
+        if (upload_comp_table(P.la, P.lb, P.la, P.lb, S.d_comp, st)) return -1;
+        EriArgs E = eri_class_args(c, P.la, P.lb, P.la, P.lb, P.d_recs, P.d_recs, c->d_prim, nullptr, (int)P.recs.size(), S.d_comp, d_work);
+        E.diag = 1;
+        size_t per = S.work_doubles / E.ncomp;
         for (size_t b0 = 0; b0 < P.recs.size(); b0 += per) {
             int nb = (int)std::min(per, P.recs.size() - b0);
             E.t0 = (int64_t)b0; E.ntask = nb;
             if (launch_eri(c, E, nb, st)) return -1;
-            SchwarzArgs S{P.d_recs + b0, c->d_M, d_work, P.ne, P.nsab, E.ncomp, P.d_q + b0};
-            hipLaunchKernelGGL(schwarz_diag_kernel, dim3(nb), dim3(64), sizeof(double) * P.ne * P.ne, st, S);
+            SchwarzArgs A{P.d_recs + b0, c->d_M, d_work, P.ne, P.nsab, E.ncomp, P.d_q + b0};
+            hipLaunchKernelGGL(schwarz_diag_kernel, dim3(nb), dim3(64), sizeof(double) * P.ne * P.ne, st, A);
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipMemcpyAsync(P.q.data(), P.d_q, sizeof(double) * P.q.size(), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
     for (int ci = 0; ci < NPC; ci++)
-        for (double v : c->pc[ci].q) qmax = std::max(qmax, v);
+        for (double v : c->pc[ci].q) S.qmax = std::max(S.qmax, v);
+    return 0;
+}
 
-    lap("schwarz");
-    // The store of the previous geometry is parked and will most likely be taken again below: its zero-fill (100 GB, 15 ms for
-    // ibuprofen) is queued NOW, so that it runs while the host sorts the pairs and plans tiles, runs and segments (~25 ms)
-    // instead of after them.  (If the parked store turns out not to fit it is freed by arena_take and the fresh one is filled.)
-    double *early_zero_ptr = nullptr;
-    int64_t early_zero_doubles = 0;
-    {
-        TileArena &pk = g_arena[c->device & 15];
-        if (pk.ptr && pk.doubles > 0 && !getenv("MI355_DEBUG")) {   // (the debug laps synchronise: keep their attribution)
-            early_zero_ptr = pk.ptr; early_zero_doubles = pk.doubles;
-            HIPCHK(hipMemsetAsync(pk.ptr, 0, sizeof(double) * (size_t)pk.doubles, st));
-        }
+// The store of the previous geometry is parked and will most likely be taken again below: its zero-fill (100 GB, 15 ms for
+// ibuprofen) is queued NOW, so that it runs while the host sorts the pairs and plans tiles, runs and segments (~25 ms)
+// instead of after them.  (If the parked store turns out not to fit it is freed by arena_take and the fresh one is filled.)
+// ---- 3. sort pairs by q (descending), drop negligible ones; block-pair Schwarz bounds
+static int prepare_sort_pairs(PrepareState &S)
+{
+    mi_ctx *c = S.c;
+    TileArena &pk = g_arena[c->device & 15];
+    if (pk.ptr && pk.doubles > 0 && !getenv("MI355_DEBUG")) {   // (the debug laps synchronise: keep their attribution)
+        S.early_zero_ptr = pk.ptr; S.early_zero_doubles = pk.doubles;
+        HIPCHK(hipMemsetAsync(pk.ptr, 0, sizeof(double) * (size_t)pk.doubles, S.st));
     }
-    // ---- 3. sort pairs by q (descending), drop negligible ones; block-pair Schwarz bounds
+    const double tol = S.tol, qmax = S.qmax;
     const int nblk = c->nblk;
     const int nbp = nblk * (nblk + 1) / 2;
-    std::vector<double> Qblk(nbp, 0.0);
+    std::vector<double> &Qblk = S.Qblk;
+    Qblk.assign(nbp, 0.0);
     for (int ci = 0; ci < NPC; ci++) {
         PairClass &P = c->pc[ci];
         std::vector<int> ord(P.recs.size());
@@ -2519,125 +2639,141 @@ extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void 
             P.max4_np = np_ ? s4 / ((np_ + 3) / 4) : 1.0;
         }
     }
+    return 0;
+}
 
-    lap("sort pairs");
-    // ---- 4. tiles and runs.  Run = tiles sharing (J,K,L), ordered by I.  Runs are the sharding unit: plan_runs deals them
-    // to ranks longest-processing-time first by streamed bytes (every rank computes the same plan).
-    std::vector<int> bpI(nbp), bpJ(nbp);
-    for (int I = 0, n = 0; I < nblk; I++)
-        for (int J = 0; J <= I; J++, n++) { bpI[n] = I; bpJ[n] = J; }
+// ---- 4. tiles and runs.  Run = tiles sharing (J,K,L), ordered by I.  Runs are the sharding unit: plan_runs deals them
+// to ranks longest-processing-time first by streamed bytes (every rank computes the same plan).
+static int prepare_enumerate_tiles(PrepareState &S)
+{
+    mi_ctx *c = S.c;
+    const double tol = S.tol;
+    const int rank = S.rank, nranks = S.nranks;
+    const int nblk = c->nblk;
+    const int nbp = nblk * (nblk + 1) / 2;
+    const std::vector<double> &Qblk = S.Qblk;
     auto bsize = [&](int B) { return std::min(BLK, c->nao - B * BLK); };
     c->tiles.clear(); c->tile_off.clear(); c->runs.clear();
-    std::vector<int32_t> table((size_t)nbp * (nbp + 1) / 2, -1);
-    int64_t off = 0, nuniq = 0;
-    {
-        std::vector<RunPlan> plan;
-        c->tri = c->opt_tri_tiles != 0;
-        plan_runs(c->nao, Qblk, qmax, tol, nranks, c->tri != 0, plan);
-        std::vector<uint8_t> present(nranks > 1 ? table.size() : 0, 0); // sharded store: slots that live on SOME rank
-        // first tile and first double of every run of this rank from the plan's counts / bytes, then the runs are filled by the
-        // host threads (disjoint slices of the tile list, disjoint directory slots)
-        const size_t nplan = plan.size();
-        std::vector<int64_t> first_tile(nplan + 1, 0), first_off(nplan + 1, 0);
-        std::vector<int> run_slot(nplan, -1);
-        int nown = 0;
-        for (size_t q = 0; q < nplan; q++) {
-            const bool mine = plan[q].owner == rank;
-            first_tile[q + 1] = first_tile[q] + (mine ? plan[q].count : 0);
-            first_off[q + 1] = first_off[q] + (mine ? plan[q].bytes / 8 : 0);
-            if (mine) run_slot[q] = nown++;
-        }
-        if (first_tile[nplan] >= INT32_MAX) return fail("too many tiles");
-        c->tiles.resize((size_t)first_tile[nplan]);
-        c->tile_off.resize((size_t)first_tile[nplan]);
-        c->runs.resize((size_t)nown);
-        int bad = 0;
+    std::vector<int32_t> &table = S.table;
+    table.assign((size_t)nbp * (nbp + 1) / 2, -1);
+    int64_t nuniq = 0;
+    std::vector<RunPlan> plan;
+    c->tri = c->opt_tri_tiles != 0;
+    plan_runs(c->nao, Qblk, S.qmax, tol, nranks, c->tri != 0, plan);
+    std::vector<uint8_t> present(nranks > 1 ? table.size() : 0, 0); // sharded store: slots that live on SOME rank
+    // first tile and first double of every run of this rank from the plan's counts / bytes, then the runs are filled by the
+    // host threads (disjoint slices of the tile list, disjoint directory slots)
+    const size_t nplan = plan.size();
+    std::vector<int64_t> first_tile(nplan + 1, 0), first_off(nplan + 1, 0);
+    std::vector<int> run_slot(nplan, -1);
+    int nown = 0;
+    for (size_t q = 0; q < nplan; q++) {
+        const bool mine = plan[q].owner == rank;
+        first_tile[q + 1] = first_tile[q] + (mine ? plan[q].count : 0);
+        first_off[q + 1] = first_off[q] + (mine ? plan[q].bytes / 8 : 0);
+        if (mine) run_slot[q] = nown++;
+    }
+    if (first_tile[nplan] >= INT32_MAX) return fail("too many tiles");
+    c->tiles.resize((size_t)first_tile[nplan]);
+    c->tile_off.resize((size_t)first_tile[nplan]);
+    c->runs.resize((size_t)nown);
+    int bad = 0;
 #pragma omp parallel for schedule(dynamic, 256) num_threads(host_threads()) reduction(+ : nuniq) reduction(| : bad)
-        for (size_t q = 0; q < nplan; q++) {
-            const RunPlan &rp = plan[q];
-            const int J = rp.J, K = rp.K, L = rp.L, kl = K * (K + 1) / 2 + L;
-            if (rp.owner != rank) {
-                for (int I = J; I < nblk; I++) {
-                    int ij = I * (I + 1) / 2 + J;
-                    if (ij >= kl && Qblk[ij] * Qblk[kl] >= tol) present[(size_t)ij * (ij + 1) / 2 + kl] = 1;
-                }
-                continue;
-            }
-            int tid = (int)first_tile[q];
-            int64_t o = first_off[q];
-            RunRec cur{J, K, L, tid, 0};
+    for (size_t q = 0; q < nplan; q++) {
+        const RunPlan &rp = plan[q];
+        const int J = rp.J, K = rp.K, L = rp.L, kl = K * (K + 1) / 2 + L;
+        if (rp.owner != rank) {
             for (int I = J; I < nblk; I++) {
                 int ij = I * (I + 1) / 2 + J;
-                if (ij < kl) continue;
-                if (Qblk[ij] * Qblk[kl] < tol) continue;
-                table[(size_t)ij * (ij + 1) / 2 + kl] = (int32_t)tid;
-                c->tiles[tid] = {I, J, K, L};
-                c->tile_off[tid] = o;
-                int bi = bsize(I), bj = bsize(J), bk = bsize(K), bl = bsize(L);
-                o += tile_doubles_padded(c->tri && I == J, c->tri && K == L, bi, bk); // j is always padded to 8 rows (J==last implies I==last: rare)
-                int64_t nij = (I > J) ? (int64_t)bi * bj : (int64_t)bi * (bi + 1) / 2;
-                int64_t nkl = (K > L) ? (int64_t)bk * bl : (int64_t)bk * (bk + 1) / 2;
-                nuniq += (ij > kl) ? nij * nkl : nij * (nij + 1) / 2;
-                cur.count++; tid++;
+                if (ij >= kl && Qblk[ij] * Qblk[kl] >= tol) present[(size_t)ij * (ij + 1) / 2 + kl] = 1;
             }
-            if (cur.count != rp.count || o != first_off[q + 1]) bad |= 1;
-            c->runs[run_slot[q]] = cur;
+            continue;
         }
-        if (bad) return fail("internal: run plan / tile enumeration mismatch");
-        off = first_off[nplan];
-        if (c->d_tile_present) { dev_free(c->d_tile_present); c->d_tile_present = nullptr; }
-        if (nranks > 1 && upload(&c->d_tile_present, present)) return -1;
+        int tid = (int)first_tile[q];
+        int64_t o = first_off[q];
+        RunRec cur{J, K, L, tid, 0};
+        for (int I = J; I < nblk; I++) {
+            int ij = I * (I + 1) / 2 + J;
+            if (ij < kl) continue;
+            if (Qblk[ij] * Qblk[kl] < tol) continue;
+            table[(size_t)ij * (ij + 1) / 2 + kl] = (int32_t)tid;
+            c->tiles[tid] = {I, J, K, L};
+            c->tile_off[tid] = o;
+            int bi = bsize(I), bj = bsize(J), bk = bsize(K), bl = bsize(L);
+            o += tile_doubles_padded(c->tri && I == J, c->tri && K == L, bi, bk); // j is always padded to 8 rows (J==last implies I==last: rare)
+            int64_t nij = (I > J) ? (int64_t)bi * bj : (int64_t)bi * (bi + 1) / 2;
+            int64_t nkl = (K > L) ? (int64_t)bk * bl : (int64_t)bk * (bk + 1) / 2;
+            nuniq += (ij > kl) ? nij * nkl : nij * (nij + 1) / 2;
+            cur.count++; tid++;
+        }
+        if (cur.count != rp.count || o != first_off[q + 1]) bad |= 1;
+        c->runs[run_slot[q]] = cur;
     }
+    if (bad) return fail("internal: run plan / tile enumeration mismatch");
+    S.off = first_off[nplan];
+    S.nuniq = nuniq;
+    if (c->d_tile_present) { dev_free(c->d_tile_present); c->d_tile_present = nullptr; }
+    if (nranks > 1 && upload(&c->d_tile_present, present)) return -1;
     c->n_tiles = (int64_t)c->tiles.size();
-    c->tile_doubles = off;
+    c->tile_doubles = S.off;
     if (c->n_tiles >= INT32_MAX) return fail("too many tiles");
-    lap("  plan + tile enumeration");
-    if (upload(&c->d_tile_table, table)) return -1;
+    return 0;
+}
+
+static int prepare_upload_directory(PrepareState &S)
+{
+    mi_ctx *c = S.c;
+    if (upload(&c->d_tile_table, S.table)) return -1;
     if (upload(&c->d_tile_off, c->tile_off)) return -1;
-    {
-        std::vector<int> tI(c->tiles.size());
-        for (size_t i = 0; i < tI.size(); i++) tI[i] = c->tiles[i].I;
-        if (upload(&c->d_tile_I, tI)) return -1;
-        if (upload(&c->d_runs, c->runs)) return -1;
-        lap("  directory uploads");
-        // J/K work items ("segments"): runs cut into chunks; either one wave per item (longest first, the
-        // hardware dispatcher balances) or a fixed number of waves with equal-cost contiguous shares.
-        auto tile_cost = [&](int tid) {
-            int64_t nd = (tid + 1 < (int)c->tile_off.size() ? c->tile_off[tid + 1] : off) - c->tile_off[tid];
-            return (double)nd * 8.0 + 8192.0; // streamed bytes + fixed per-tile overhead
-        };
-        const int chunk = c->opt_runmax > 0 ? c->opt_runmax : (int)std::min<int64_t>(64, std::max<int64_t>(8, c->n_tiles / 2048));
-        std::vector<RunRec> segs;
-        std::vector<int> wave_seg;
-        int nw, w = 0;
-        if (c->opt_jk_waves <= 0) {
-            for (const RunRec &r : c->runs)
-                for (int t0 = 0; t0 < r.count; t0 += chunk) segs.push_back(RunRec{r.J, r.K, r.L, r.first + t0, std::min(chunk, r.count - t0)});
-            std::vector<double> cost(segs.size(), 0.0);
+    std::vector<int> tI(c->tiles.size());
+    for (size_t i = 0; i < tI.size(); i++) tI[i] = c->tiles[i].I;
+    if (upload(&c->d_tile_I, tI)) return -1;
+    if (upload(&c->d_runs, c->runs)) return -1;
+    return 0;
+}
+
+// J/K work items ("segments"): runs cut into chunks; either one wave per item (longest first, the
+// hardware dispatcher balances) or a fixed number of waves with equal-cost contiguous shares.
+static int prepare_jk_segments(PrepareState &S)
+{
+    mi_ctx *c = S.c;
+    const int64_t off = S.off;
+    auto tile_cost = [&](int tid) {
+        int64_t nd = (tid + 1 < (int)c->tile_off.size() ? c->tile_off[tid + 1] : off) - c->tile_off[tid];
+        return (double)nd * 8.0 + 8192.0; // streamed bytes + fixed per-tile overhead
+    };
+    const int chunk = c->opt_runmax > 0 ? c->opt_runmax : (int)std::min<int64_t>(64, std::max<int64_t>(8, c->n_tiles / 2048));
+    std::vector<RunRec> segs;
+    std::vector<int> wave_seg;
+    int nw, w = 0;
+    if (c->opt_jk_waves <= 0) {
+        for (const RunRec &r : c->runs)
+            for (int t0 = 0; t0 < r.count; t0 += chunk) segs.push_back(RunRec{r.J, r.K, r.L, r.first + t0, std::min(chunk, r.count - t0)});
+        std::vector<double> cost(segs.size(), 0.0);
+#pragma omp parallel for schedule(static) num_threads(host_threads())
+        for (size_t q = 0; q < segs.size(); q++)
+            for (int t = 0; t < segs[q].count; t++) cost[q] += tile_cost(segs[q].first + t);
+        std::vector<int> ord(segs.size());
+        std::iota(ord.begin(), ord.end(), 0);
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return cost[a] > cost[b]; });
+        std::vector<RunRec> sorted(segs.size());
+        for (size_t q = 0; q < segs.size(); q++) sorted[q] = segs[ord[q]];
+        segs.swap(sorted);
+        c->n_jk_cached = 0;
+        if (off * 8 > ((int64_t)256 << 20) && c->opt_jk_cache_mb > 0) {
+            double acc_b = 0.0;
+            const double lim = (double)c->opt_jk_cache_mb * 1048576.0;
+            std::vector<double> sc(segs.size(), 0.0);
 #pragma omp parallel for schedule(static) num_threads(host_threads())
             for (size_t q = 0; q < segs.size(); q++)
-                for (int t = 0; t < segs[q].count; t++) cost[q] += tile_cost(segs[q].first + t);
-            std::vector<int> ord(segs.size());
-            std::iota(ord.begin(), ord.end(), 0);
-            std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-            std::vector<RunRec> sorted(segs.size());
-            for (size_t q = 0; q < segs.size(); q++) sorted[q] = segs[ord[q]];
-            segs.swap(sorted);
-            c->n_jk_cached = 0;
-            if (off * 8 > ((int64_t)256 << 20) && c->opt_jk_cache_mb > 0) {
-                double acc_b = 0.0;
-                const double lim = (double)c->opt_jk_cache_mb * 1048576.0;
-                std::vector<double> sc(segs.size(), 0.0);
-#pragma omp parallel for schedule(static) num_threads(host_threads())
-                for (size_t q = 0; q < segs.size(); q++)
-                    for (int t = 0; t < segs[q].count; t++) sc[q] += tile_cost(segs[q].first + t) - 8192.0;
-                while (c->n_jk_cached < (int)segs.size() && acc_b + sc[c->n_jk_cached] <= lim) acc_b += sc[c->n_jk_cached++];
-            }
-            nw = (int)segs.size();
-            wave_seg.resize(nw + 1);
-            std::iota(wave_seg.begin(), wave_seg.end(), 0);
-            w = nw - 1;
-        } else {
+                for (int t = 0; t < segs[q].count; t++) sc[q] += tile_cost(segs[q].first + t) - 8192.0;
+            while (c->n_jk_cached < (int)segs.size() && acc_b + sc[c->n_jk_cached] <= lim) acc_b += sc[c->n_jk_cached++];
+        }
+        nw = (int)segs.size();
+        wave_seg.resize(nw + 1);
+        std::iota(wave_seg.begin(), wave_seg.end(), 0);
+        w = nw - 1;
+    } else {
         nw = (int)std::min<int64_t>(c->opt_jk_waves, std::max<int64_t>(c->n_tiles, 1));
         wave_seg.assign(nw + 1, 0);
         double total_cost = 0.0;
@@ -2660,23 +2796,30 @@ extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void 
             }
             if (cur.count) segs.push_back(cur);
         }
-        }
-        for (int x = w + 1; x <= nw; x++) wave_seg[x] = (int)segs.size();
-        c->n_jk_waves = nw;
-        if (getenv("MI355_DEBUG")) {
-            int mx = 0, mn = 1 << 30, maxseg = 0;
-            for (int x = 0; x < nw; x++) {
-                int nt = 0;
-                for (int sgi = wave_seg[x]; sgi < wave_seg[x + 1]; sgi++) nt += segs[sgi].count;
-                mx = std::max(mx, nt); mn = std::min(mn, nt); maxseg = std::max(maxseg, wave_seg[x + 1] - wave_seg[x]);
-            }
-            fprintf(stderr, "[mi355] tiles=%ld runs=%zu segs=%zu waves=%d tiles/wave min=%d max=%d maxsegs/wave=%d\n",
-                    (long)c->n_tiles, c->runs.size(), segs.size(), nw, mn, mx, maxseg);
-        }
-        if (upload(&c->d_segs, segs)) return -1;
-        if (upload(&c->d_wave_seg, wave_seg)) return -1;
     }
-    lap("  J/K segments");
+    for (int x = w + 1; x <= nw; x++) wave_seg[x] = (int)segs.size();
+    c->n_jk_waves = nw;
+    if (getenv("MI355_DEBUG")) {
+        int mx = 0, mn = 1 << 30, maxseg = 0;
+        for (int x = 0; x < nw; x++) {
+            int nt = 0;
+            for (int sgi = wave_seg[x]; sgi < wave_seg[x + 1]; sgi++) nt += segs[sgi].count;
+            mx = std::max(mx, nt); mn = std::min(mn, nt); maxseg = std::max(maxseg, wave_seg[x + 1] - wave_seg[x]);
+        }
+        fprintf(stderr, "[mi355] tiles=%ld runs=%zu segs=%zu waves=%d tiles/wave min=%d max=%d maxsegs/wave=%d\n",
+                (long)c->n_tiles, c->runs.size(), segs.size(), nw, mn, mx, maxseg);
+    }
+    if (upload(&c->d_segs, segs)) return -1;
+    if (upload(&c->d_wave_seg, wave_seg)) return -1;
+    return 0;
+}
+
+// The store itself: a host-side decision first (MI_ERR_NOMEM before anything is allocated; sizes: mi_eri_get_memory), then the
+// parked store of the previous geometry or a fresh allocation, zero-filled unless prepare_sort_pairs queued that already
+static int prepare_allocate_store(PrepareState &S)
+{
+    mi_ctx *c = S.c;
+    const int64_t off = S.off;
     size_t freeb = 0, totb = 0;
     HIPCHK(hipMemGetInfo(&freeb, &totb));
     freeb += (size_t)g_arena[c->device & 15].doubles * 8; // a parked store is reusable (or freed) by arena_take
@@ -2684,7 +2827,6 @@ extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void 
     c->mem_need_bytes = (int64_t)off * 8;
     c->mem_free_bytes = (int64_t)freeb;
     if ((size_t)off * 8 + ((size_t)1 << 30) > freeb) {
-        dev_free(d_comp);
         fail("resident ERI store needs %.1f GB but only %.1f GB of HBM is free; shard over more GPUs",
              off * 8e-9, freeb * 1e-9);
         return MI_ERR_NOMEM; // sizes: mi_eri_get_memory
@@ -2702,176 +2844,260 @@ extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void 
         }
     }
     if (arena_take(c->device, c->tile_alloc, &c->d_tiles)) return -1;
-    if (!(c->d_tiles == early_zero_ptr && off <= early_zero_doubles))
-        HIPCHK(hipMemsetAsync(c->d_tiles, 0, sizeof(double) * std::max<int64_t>(off, 1), st));
+    if (!(c->d_tiles == S.early_zero_ptr && off <= S.early_zero_doubles))
+        HIPCHK(hipMemsetAsync(c->d_tiles, 0, sizeof(double) * std::max<int64_t>(off, 1), S.st));
+    return 0;
+}
 
-    lap("tiles/runs/segments + alloc");
-    // ---- 5. evaluate every Schwarz-surviving canonical shell quartet, class by class
-    int64_t nquart = 0;
-    int64_t *d_prefix = nullptr;
-    size_t prefix_cap = 0;
-    TaskIdx *d_tasks = nullptr;
-    size_t tasks_cap = 0;
-    for (int bc = 0; bc < NPC; bc++)
-        for (int kc = 0; kc <= bc; kc++) {
-            PairClass &B = c->pc[bc], &Kc = c->pc[kc];
-            if (B.recs.empty() || Kc.recs.empty()) continue;
-            std::vector<int64_t> prefix;
-            const int64_t ntask = class_prefix(B, Kc, bc == kc, tol, prefix);
-            if (ntask == 0) continue;
-            nquart += ntask;
-            if (prefix.size() > prefix_cap) {
-                if (d_prefix) dev_free(d_prefix);
-                prefix_cap = prefix.size() * 2;
-                HIPCHK(dev_malloc(&d_prefix, sizeof(int64_t) * prefix_cap));
-            }
-            HIPCHK(hipMemcpyAsync(d_prefix, prefix.data(), sizeof(int64_t) * prefix.size(), hipMemcpyHostToDevice, st));
-            EriArgs E{};
-            setup_eri_dims(E, B.la, B.lb, Kc.la, Kc.lb);
-            const bool tpq_class = c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= 32768 &&
-                                   tpq_has_class(B.la, B.lb, Kc.la, Kc.lb);
-            if (c->opt_task_table && !tpq_class && ntask >= 65536) {   // the wave-per-quartet pair walks the task list twice
-                if ((size_t)ntask > tasks_cap) {
-                    if (scr_tasks.ensure(c->device, SCR_EVAL_TASKS, sizeof(TaskIdx) * (size_t)ntask)) return -1;
-                    d_tasks = (TaskIdx *)scr_tasks.p;
-                    tasks_cap = scr_tasks.bytes / sizeof(TaskIdx);
-                }
-                hipLaunchKernelGGL(fill_tasks_kernel, dim3((unsigned)((ntask + 255) / 256)), dim3(256), 0, st, d_prefix, (int)B.recs.size(), ntask, d_tasks);
-                E.tasks = d_tasks;
-            }
-            std::vector<uint32_t> comp;
-            build_comp_table(B.la, B.lb, Kc.la, Kc.lb, comp);
-            HIPCHK(hipMemcpyAsync(d_comp, comp.data(), sizeof(uint32_t) * comp.size(), hipMemcpyHostToDevice, st));
-            HIPCHK(hipStreamSynchronize(st)); // host vectors go out of scope below
-            E.bra = B.d_recs; E.ket = Kc.d_recs; E.prim = c->d_prim; E.prefix = d_prefix; E.nbra = (int)B.recs.size();
-            E.comp = d_comp; E.work = d_work; E.rys = c->rys; E.diag = 0; E.omega = c->eri_omega;
-            E.ni = 2 * B.la + 1; E.nj = 2 * B.lb + 1; E.nk = 2 * Kc.la + 1; E.nl = 2 * Kc.lb + 1;
-            E.own_table = nranks > 1 ? c->d_tile_table : nullptr;
-            E.h_shared_np = B.mean_np; E.h_vary_mean = Kc.mean_np; E.h_vary_max4 = Kc.max4_np;
-            E.q_bra = B.d_q; E.q_ket = Kc.d_q; E.qtol = c->opt_ket_cluster ? tol : 0.0;
-            E.prim_lds = (c->opt_prim_lds && B.max_np + Kc.max_np <= 160) ? B.max_np + Kc.max_np : 0;
-            const unsigned xcd_wave = c->opt_xcd_map ? 32u : 0u, xcd_tpq = c->opt_xcd_map ? 8u : 0u;
-            E.xcd = xcd_wave;
-            XfArgs X{};
-            X.bra = B.d_recs; X.ket = Kc.d_recs; X.Mbuf = c->d_M; X.prefix = d_prefix; X.nbra = E.nbra;
-            X.ne = B.ne; X.nf = Kc.ne; X.nsab = B.nsab; X.nscd = Kc.nsab; X.nsb = 2 * B.lb + 1; X.nsd = 2 * Kc.lb + 1;
-            X.work = d_work; X.ncomp = E.ncomp; X.tile_table = c->d_tile_table; X.tile_off = c->d_tile_off;
-            X.tiles = c->d_tiles; X.nao = c->nao; X.tri = c->tri;
-            X.check_owner = nranks > 1; X.ni = E.ni; X.nj = E.nj; X.nk = E.nk; X.nl = E.nl;
-            X.q_bra = E.q_bra; X.q_ket = E.q_ket; X.qtol = E.qtol; X.xcd = xcd_wave; X.tasks = E.tasks;
-            int64_t per = std::min<int64_t>((int64_t)(WORK_DOUBLES / E.ncomp), (int64_t)1 << 24);
-            size_t shm2 = sizeof(double) * ((size_t)X.ne * X.nf + (size_t)X.nsab * X.nf);
-            {
-                const size_t with_m = shm2 + sizeof(double) * ((size_t)2 * X.nsab * X.ne + (size_t)2 * X.nscd * X.nf);
-                X.m_lds = (c->opt_xf_mlds && with_m <= (size_t)c->opt_xf_mlds * 1024) ? 1 : 0;
-                if (X.m_lds) shm2 = with_m;
-            }
-            // matrix-core path only for the large classes: below, the lean per-lane kernel (56 VGPRs, 8 waves per SIMD) hides the
-            // per-quartet latency chain better than MFMA tiles at 3-4 waves per SIMD (measured per class on ibuprofen/def2-TZVP)
-            const bool xf_mfma = (mfma_worthwhile(X.nsab, X.nf, X.ne) || mfma_worthwhile(X.nsab, X.nscd, X.nf)) &&
-                                 X.nsab * X.nscd >= c->opt_xf_mfma_min;
-            const bool xf_small = !xf_mfma && X.nsab * X.nscd <= c->opt_xf_qpw_max && shm2 * 4 <= 64 * 1024; // four quartets per wave
-            if (shm2 > 64 * 1024)
-                HIPCHK(hipFuncSetAttribute(xf_mfma ? (const void *)eri_transform_scatter<true, 64> : (const void *)eri_transform_scatter<false, 64>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm2));
-            const bool dbg = getenv("MI355_DEBUG") != nullptr && getenv("MI355_DEBUG")[0] == '2';
-            double t_rys = 0.0, t_xf = 0.0;
-            // low angular classes: one thread per quartet, fused Rys + HRR + cart->sph + scatter (eri_tpq_kernel)
-            // ... when the contraction is shallow enough: a thread walks ALL primitive quartets of its shell quartet, so deeply
-            // contracted shells (cc-pVXZ s shells: hundreds of primitive quartets) serialise and the wave-per-quartet path, which
-            // spreads them over lanes, wins (measured: benzene/cc-pVTZ 54 vs 63 ms, ibuprofen/def2-TZVP 0.40 vs 0.29 s)
-            if (c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= 32768) {
-                TpqArgs Q{};
-                Q.bra = B.d_recs; Q.ket = Kc.d_recs; Q.prim = c->d_prim; Q.prefix = d_prefix; Q.nbra = E.nbra; Q.t0 = 0; Q.ntask = ntask;
-                Q.c2s = c->d_c2s;
-                for (int q = 0; q <= LMAX + 1; q++) Q.c2s_off[q] = c->c2s_off[q];
-                Q.rys = c->rys; Q.X = X; Q.shell_xyz = c->d_shell_xyz; Q.check_owner = nranks > 1;
-                Q.q_bra = E.q_bra; Q.q_ket = E.q_ket; Q.qtol = E.qtol; Q.xcd = xcd_tpq; Q.omega = E.omega;
-                auto ta = std::chrono::steady_clock::now();
-                if (dbg) hipStreamSynchronize(st);
-                const int used = launch_eri_tpq(B.la, B.lb, Kc.la, Kc.lb, Q, st);
-                if (used < 0) return -1;
-                if (used) {
-                    if (dbg) {
-                        hipStreamSynchronize(st);
-                        t_rys = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
-                        fprintf(stderr, "[mi355] eri class (%d%d|%d%d): %ld quartets, thread-per-quartet fused kernel %.4f s (%.2f ns/q)\n", B.la, B.lb,
-                                Kc.la, Kc.lb, (long)ntask, t_rys, t_rys / ntask * 1e9);
-                    }
-                    continue;
-                }
-            }
-            if (c->opt_eri_fused && !E.diag) {
-                // one fused launch per (at most 2^30) tasks: no hand-over buffer, so no batching by its size
-                FusedArgs F;
-                F.R = E; F.X = X;
-                F.R.PB = std::max(1, std::min(E.PB, B.max_np * Kc.max_np));   // uncontracted d / f shells: one primitive quartet per batch
-                F.R.prim_lds = 0; F.R.own_table = nullptr; F.R.qtol = 0.0; F.R.dmax = nullptr;   // (the transform half screens: check_owner, qtol)
-                F.X.m_lds = 0;
-                const size_t scratch = (size_t)F.R.PB * E.nroots * 3 * E.tsz + (size_t)F.R.PB * 2 * E.nroots;
-                const size_t shmf = sizeof(double) * ((size_t)X.ne * X.nf + std::max((size_t)X.nsab * X.nf, scratch));
-                if (shmf <= 160 * 1024) {
-                    const int perlane = (E.ncomp + 63) / 64;
-                    auto ta = std::chrono::steady_clock::now();
-                    if (dbg) hipStreamSynchronize(st);
-                    for (int64_t t0 = 0; t0 < ntask; t0 += (int64_t)1 << 30) {
-                        const int64_t nb = std::min<int64_t>((int64_t)1 << 30, ntask - t0);
-                        F.X.t0 = t0; F.X.ntask = nb; F.X.xcd = nb >= 2048 ? xcd_wave : 0u;
-                        const dim3 grid(eri_grid(nb, F.X.xcd));
+// ---- 5. evaluate every Schwarz-surviving canonical shell quartet, class by class.  One (bra class, ket class) pair is set
+// up once (ClassPairEval) and offered to three routes in turn; each returns 1 (handled), 0 (not its class) or -1 (error).
+struct ClassPairEval {
+    const PairClass *B, *Kc;
+    int64_t ntask;
+    EriArgs E;
+    XfArgs X;
+    size_t shm2;              // LDS of the transform kernel per quartet
+    bool xf_mfma, xf_small;   // transform kernel: MFMA tiles / four quartets per wave
+    unsigned xcd_wave, xcd_tpq;
+    bool dbg;                 // MI355_DEBUG=2: per-class timing
+};
+static int eval_route_tpq(PrepareState &S, const ClassPairEval &P);
+static int eval_route_fused(PrepareState &S, const ClassPairEval &P);
+static int eval_route_two_launch(PrepareState &S, ClassPairEval &P);
+
+static int prepare_evaluate_class_pair(PrepareState &S, PairClass &B, PairClass &Kc, bool same)
+{
+    mi_ctx *c = S.c;
+    hipStream_t st = S.st;
+    const double tol = S.tol;
+    const int nranks = S.nranks;
+    double *d_work = (double *)S.scr_work.p;
+    std::vector<int64_t> prefix;
+    const int64_t ntask = class_prefix(B, Kc, same, tol, prefix);
+    if (ntask == 0) return 0;
+    S.nquart += ntask;
+    if (prefix_to_device(prefix, S.d_prefix, st)) return -1;
+    const int64_t *d_prefix = S.d_prefix;
+    ClassPairEval P{};
+    P.B = &B; P.Kc = &Kc; P.ntask = ntask;
+    const bool tpq_class = c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= 32768 &&
+                           tpq_has_class(B.la, B.lb, Kc.la, Kc.lb);
+    const TaskIdx *d_tasks = nullptr;
+    if (c->opt_task_table && !tpq_class && ntask >= 65536) {   // the wave-per-quartet pair walks the task list twice
+        if (S.scr_tasks.ensure(c->device, SCR_EVAL_TASKS, sizeof(TaskIdx) * (size_t)ntask)) return -1;
+        hipLaunchKernelGGL(fill_tasks_kernel, dim3((unsigned)((ntask + 255) / 256)), dim3(256), 0, st, d_prefix, (int)B.recs.size(), ntask,
+                           (TaskIdx *)S.scr_tasks.p);
+        d_tasks = (const TaskIdx *)S.scr_tasks.p;
+    }
+    if (upload_comp_table(B.la, B.lb, Kc.la, Kc.lb, S.d_comp, st)) return -1;
+    EriArgs &E = P.E;
+    E = eri_class_args(c, B.la, B.lb, Kc.la, Kc.lb, B.d_recs, Kc.d_recs, c->d_prim, d_prefix, (int)B.recs.size(), S.d_comp, d_work);
+    E.tasks = d_tasks;
+    E.omega = c->eri_omega;
+    E.ni = 2 * B.la + 1; E.nj = 2 * B.lb + 1; E.nk = 2 * Kc.la + 1; E.nl = 2 * Kc.lb + 1;
+    E.own_table = nranks > 1 ? c->d_tile_table : nullptr;
+    E.h_shared_np = B.mean_np; E.h_vary_mean = Kc.mean_np; E.h_vary_max4 = Kc.max4_np;
+    E.q_bra = B.d_q; E.q_ket = Kc.d_q; E.qtol = c->opt_ket_cluster ? tol : 0.0;
+    E.prim_lds = (c->opt_prim_lds && B.max_np + Kc.max_np <= 160) ? B.max_np + Kc.max_np : 0;
+    P.xcd_wave = c->opt_xcd_map ? 32u : 0u; P.xcd_tpq = c->opt_xcd_map ? 8u : 0u;
+    E.xcd = P.xcd_wave;
+    XfArgs &X = P.X;
+    X.bra = B.d_recs; X.ket = Kc.d_recs; X.Mbuf = c->d_M; X.prefix = d_prefix; X.nbra = E.nbra;
+    X.ne = B.ne; X.nf = Kc.ne; X.nsab = B.nsab; X.nscd = Kc.nsab; X.nsb = 2 * B.lb + 1; X.nsd = 2 * Kc.lb + 1;
+    X.work = d_work; X.ncomp = E.ncomp; X.tile_table = c->d_tile_table; X.tile_off = c->d_tile_off;
+    X.tiles = c->d_tiles; X.nao = c->nao; X.tri = c->tri;
+    X.check_owner = nranks > 1; X.ni = E.ni; X.nj = E.nj; X.nk = E.nk; X.nl = E.nl;
+    X.q_bra = E.q_bra; X.q_ket = E.q_ket; X.qtol = E.qtol; X.xcd = P.xcd_wave; X.tasks = E.tasks;
+    P.shm2 = sizeof(double) * ((size_t)X.ne * X.nf + (size_t)X.nsab * X.nf);
+    {
+        const size_t with_m = P.shm2 + sizeof(double) * ((size_t)2 * X.nsab * X.ne + (size_t)2 * X.nscd * X.nf);
+        X.m_lds = (c->opt_xf_mlds && with_m <= (size_t)c->opt_xf_mlds * 1024) ? 1 : 0;
+        if (X.m_lds) P.shm2 = with_m;
+    }
+    // matrix-core path only for the large classes: below, the lean per-lane kernel (56 VGPRs, 8 waves per SIMD) hides the
+    // per-quartet latency chain better than MFMA tiles at 3-4 waves per SIMD (measured per class on ibuprofen/def2-TZVP)
+    P.xf_mfma = (mfma_worthwhile(X.nsab, X.nf, X.ne) || mfma_worthwhile(X.nsab, X.nscd, X.nf)) && X.nsab * X.nscd >= c->opt_xf_mfma_min;
+    P.xf_small = !P.xf_mfma && X.nsab * X.nscd <= c->opt_xf_qpw_max && P.shm2 * 4 <= 64 * 1024; // four quartets per wave
+    if (P.shm2 > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute(P.xf_mfma ? (const void *)eri_transform_scatter<true, 64> : (const void *)eri_transform_scatter<false, 64>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.shm2));
+    P.dbg = getenv("MI355_DEBUG") != nullptr && getenv("MI355_DEBUG")[0] == '2';
+    int used = eval_route_tpq(S, P);
+    if (!used) used = eval_route_fused(S, P);
+    if (!used) used = eval_route_two_launch(S, P);
+    return used < 0 ? -1 : 0;
+}
+
+// low angular classes: one thread per quartet, fused Rys + HRR + cart->sph + scatter (eri_tpq_kernel)
+// ... when the contraction is shallow enough: a thread walks ALL primitive quartets of its shell quartet, so deeply
+// contracted shells (cc-pVXZ s shells: hundreds of primitive quartets) serialise and the wave-per-quartet path, which
+// spreads them over lanes, wins (measured: benzene/cc-pVTZ 54 vs 63 ms, ibuprofen/def2-TZVP 0.40 vs 0.29 s)
+static int eval_route_tpq(PrepareState &S, const ClassPairEval &P)
+{
+    mi_ctx *c = S.c;
+    hipStream_t st = S.st;
+    const PairClass &B = *P.B, &Kc = *P.Kc;
+    const EriArgs &E = P.E;
+    const int64_t ntask = P.ntask;
+    if (!(c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= 32768)) return 0;
+    TpqArgs Q{};
+    Q.bra = B.d_recs; Q.ket = Kc.d_recs; Q.prim = c->d_prim; Q.prefix = E.prefix; Q.nbra = E.nbra; Q.t0 = 0; Q.ntask = ntask;
+    Q.c2s = c->d_c2s;
+    for (int q = 0; q <= LMAX + 1; q++) Q.c2s_off[q] = c->c2s_off[q];
+    Q.rys = c->rys; Q.X = P.X; Q.shell_xyz = c->d_shell_xyz; Q.check_owner = S.nranks > 1;
+    Q.q_bra = E.q_bra; Q.q_ket = E.q_ket; Q.qtol = E.qtol; Q.xcd = P.xcd_tpq; Q.omega = E.omega;
+    auto ta = std::chrono::steady_clock::now();
+    if (P.dbg) hipStreamSynchronize(st);
+    const int used = launch_eri_tpq(B.la, B.lb, Kc.la, Kc.lb, Q, st);
+    if (used > 0 && P.dbg) {
+        hipStreamSynchronize(st);
+        const double t_rys = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
+        fprintf(stderr, "[mi355] eri class (%d%d|%d%d): %ld quartets, thread-per-quartet fused kernel %.4f s (%.2f ns/q)\n", B.la, B.lb,
+                Kc.la, Kc.lb, (long)ntask, t_rys, t_rys / ntask * 1e9);
+    }
+    return used;
+}
+
+// (option eri_fused) one fused launch per (at most 2^30) tasks: no hand-over buffer, so no batching by its size
+static int eval_route_fused(PrepareState &S, const ClassPairEval &P)
+{
+    mi_ctx *c = S.c;
+    hipStream_t st = S.st;
+    const PairClass &B = *P.B, &Kc = *P.Kc;
+    const EriArgs &E = P.E;
+    const XfArgs &X = P.X;
+    const int64_t ntask = P.ntask;
+    if (!(c->opt_eri_fused && !E.diag)) return 0;
+    FusedArgs F;
+    F.R = E; F.X = X;
+    F.R.PB = std::max(1, std::min(E.PB, B.max_np * Kc.max_np));   // uncontracted d / f shells: one primitive quartet per batch
+    F.R.prim_lds = 0; F.R.own_table = nullptr; F.R.qtol = 0.0; F.R.dmax = nullptr;   // (the transform half screens: check_owner, qtol)
+    F.X.m_lds = 0;
+    const size_t scratch = (size_t)F.R.PB * E.nroots * 3 * E.tsz + (size_t)F.R.PB * 2 * E.nroots;
+    const size_t shmf = sizeof(double) * ((size_t)X.ne * X.nf + std::max((size_t)X.nsab * X.nf, scratch));
+    if (shmf > 160 * 1024) return 0;
+    const int perlane = (E.ncomp + 63) / 64;
+    auto ta = std::chrono::steady_clock::now();
+    if (P.dbg) hipStreamSynchronize(st);
+    for (int64_t t0 = 0; t0 < ntask; t0 += (int64_t)1 << 30) {
+        const int64_t nb = std::min<int64_t>((int64_t)1 << 30, ntask - t0);
+        F.X.t0 = t0; F.X.ntask = nb; F.X.xcd = nb >= 2048 ? P.xcd_wave : 0u;
+        const dim3 grid(eri_grid(nb, F.X.xcd));
 #define FUSED_LAUNCH(MF, MC)                                                                                                               \
     do {                                                                                                                                   \
         if (shmf > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)eri_fused_kernel<MF, MC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmf)); \
         hipLaunchKernelGGL((eri_fused_kernel<MF, MC>), grid, dim3(64), shmf, st, F);                                                        \
     } while (0)
-                        if (xf_mfma) {
-                            if (perlane <= 4) FUSED_LAUNCH(true, 4); else if (perlane <= 16) FUSED_LAUNCH(true, 16); else FUSED_LAUNCH(true, 32);
-                        } else {
-                            if (perlane <= 1) FUSED_LAUNCH(false, 1); else if (perlane <= 4) FUSED_LAUNCH(false, 4);
-                            else if (perlane <= 16) FUSED_LAUNCH(false, 16); else FUSED_LAUNCH(false, 32);
-                        }
-#undef FUSED_LAUNCH
-                        HIPCHK(hipGetLastError());
-                    }
-                    if (dbg) {
-                        hipStreamSynchronize(st);
-                        t_rys = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
-                        fprintf(stderr, "[mi355] eri class (%d%d|%d%d): %ld quartets, fused rys+transform+scatter %.4f s (%.2f ns/q)\n", B.la, B.lb,
-                                Kc.la, Kc.lb, (long)ntask, t_rys, t_rys / ntask * 1e9);
-                    }
-                    continue;
-                }
-            }
-            for (int64_t t0 = 0; t0 < ntask; t0 += per) {
-                int nb = (int)std::min<int64_t>(per, ntask - t0);
-                E.t0 = t0; E.ntask = nb; X.t0 = t0;
-                auto ta = std::chrono::steady_clock::now();
-                if (dbg) hipStreamSynchronize(st);
-                if (launch_eri(c, E, nb, st)) return -1;
-                if (dbg) { hipStreamSynchronize(st); t_rys += std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count(); ta = std::chrono::steady_clock::now(); }
-                X.ntask = nb;
-                X.xcd = nb >= 2048 ? xcd_wave : 0u;
-                E.xcd = xcd_wave;   // (launch_eri switches the map off for small launches)
-                if (xf_mfma) hipLaunchKernelGGL((eri_transform_scatter<true, 64>), dim3(eri_grid(nb, X.xcd)), dim3(64), shm2, st, X);
-                else if (xf_small) hipLaunchKernelGGL((eri_transform_scatter<false, 16>), dim3(eri_grid((nb + 3) / 4, X.xcd)), dim3(64), shm2 * 4, st, X);
-                else hipLaunchKernelGGL((eri_transform_scatter<false, 64>), dim3(eri_grid(nb, X.xcd)), dim3(64), shm2, st, X);
-                HIPCHK(hipGetLastError());
-                if (dbg) { hipStreamSynchronize(st); t_xf += std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count(); }
-            }
-            if (dbg)
-                fprintf(stderr, "[mi355] eri class (%d%d|%d%d): %ld quartets, rys %.4f s (%.2f ns/q), transform+scatter %.4f s (%.2f ns/q)\n", B.la, B.lb,
-                        Kc.la, Kc.lb, (long)ntask, t_rys, t_rys / ntask * 1e9, t_xf, t_xf / ntask * 1e9);
+        if (P.xf_mfma) {
+            if (perlane <= 4) FUSED_LAUNCH(true, 4); else if (perlane <= 16) FUSED_LAUNCH(true, 16); else FUSED_LAUNCH(true, 32);
+        } else {
+            if (perlane <= 1) FUSED_LAUNCH(false, 1); else if (perlane <= 4) FUSED_LAUNCH(false, 4);
+            else if (perlane <= 16) FUSED_LAUNCH(false, 16); else FUSED_LAUNCH(false, 32);
         }
-    HIPCHK(hipStreamSynchronize(st));
+#undef FUSED_LAUNCH
+        HIPCHK(hipGetLastError());
+    }
+    if (P.dbg) {
+        hipStreamSynchronize(st);
+        const double t_rys = std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
+        fprintf(stderr, "[mi355] eri class (%d%d|%d%d): %ld quartets, fused rys+transform+scatter %.4f s (%.2f ns/q)\n", B.la, B.lb,
+                Kc.la, Kc.lb, (long)ntask, t_rys, t_rys / ntask * 1e9);
+    }
+    return 1;
+}
+
+// everything else: Rys launch -> hand-over buffer -> transform + scatter launch, in batches of what the buffer holds
+static int eval_route_two_launch(PrepareState &S, ClassPairEval &P)
+{
+    mi_ctx *c = S.c;
+    hipStream_t st = S.st;
+    const PairClass &B = *P.B, &Kc = *P.Kc;
+    EriArgs &E = P.E;
+    XfArgs &X = P.X;
+    const int64_t ntask = P.ntask;
+    const size_t shm2 = P.shm2;
+    const bool dbg = P.dbg;
+    double t_rys = 0.0, t_xf = 0.0;
+    const int64_t per = std::min<int64_t>((int64_t)(S.work_doubles / E.ncomp), (int64_t)1 << 24);
+    for (int64_t t0 = 0; t0 < ntask; t0 += per) {
+        int nb = (int)std::min<int64_t>(per, ntask - t0);
+        E.t0 = t0; E.ntask = nb; X.t0 = t0;
+        auto ta = std::chrono::steady_clock::now();
+        if (dbg) hipStreamSynchronize(st);
+        if (launch_eri(c, E, nb, st)) return -1;
+        if (dbg) { hipStreamSynchronize(st); t_rys += std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count(); ta = std::chrono::steady_clock::now(); }
+        X.ntask = nb;
+        X.xcd = nb >= 2048 ? P.xcd_wave : 0u;
+        E.xcd = P.xcd_wave;   // (launch_eri switches the map off for small launches)
+        if (P.xf_mfma) hipLaunchKernelGGL((eri_transform_scatter<true, 64>), dim3(eri_grid(nb, X.xcd)), dim3(64), shm2, st, X);
+        else if (P.xf_small) hipLaunchKernelGGL((eri_transform_scatter<false, 16>), dim3(eri_grid((nb + 3) / 4, X.xcd)), dim3(64), shm2 * 4, st, X);
+        else hipLaunchKernelGGL((eri_transform_scatter<false, 64>), dim3(eri_grid(nb, X.xcd)), dim3(64), shm2, st, X);
+        HIPCHK(hipGetLastError());
+        if (dbg) { hipStreamSynchronize(st); t_xf += std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count(); }
+    }
+    if (dbg)
+        fprintf(stderr, "[mi355] eri class (%d%d|%d%d): %ld quartets, rys %.4f s (%.2f ns/q), transform+scatter %.4f s (%.2f ns/q)\n", B.la, B.lb,
+                Kc.la, Kc.lb, (long)ntask, t_rys, t_rys / ntask * 1e9, t_xf, t_xf / ntask * 1e9);
+    return 1;
+}
+
+static int prepare_evaluate(PrepareState &S)
+{
+    mi_ctx *c = S.c;
+    for (int bc = 0; bc < NPC; bc++)
+        for (int kc = 0; kc <= bc; kc++) {
+            PairClass &B = c->pc[bc], &Kc = c->pc[kc];
+            if (B.recs.empty() || Kc.recs.empty()) continue;
+            if (prepare_evaluate_class_pair(S, B, Kc, bc == kc)) return -1;
+        }
+    HIPCHK(hipStreamSynchronize(S.st));
+    return 0;
+}
+
+extern "C" int mi_eri_prepare(mi_ctx *c, double tol, int rank, int nranks, void *stream)
+{
+    if (c && check_orbital_lmax(c, "mi_eri_prepare")) return -1;
+    if (!c) return fail("mi_eri_prepare: null context");
+    if (nranks < 1 || rank < 0 || rank >= nranks) return fail("mi_eri_prepare: bad rank/nranks");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    auto t_start = std::chrono::steady_clock::now();
+    auto t_phase = t_start;
+    auto lap = [&](const char *what) {
+        if (!getenv("MI355_DEBUG")) return;
+        hipStreamSynchronize(st);
+        auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[mi355] eri_prepare %-28s %.3f s\n", what, std::chrono::duration<double>(now - t_phase).count());
+        t_phase = now;
+    };
+    free_eri(c);
+    if (set_tile_order(c, c->opt_ao_order ? 1 : 0)) return -1;
+    PrepareState S;
+    S.c = c; S.tol = tol; S.rank = rank; S.nranks = nranks; S.st = st;
+    if (prepare_pairs(S)) return -1;
+    lap("pairs + M matrices");
+    if (prepare_schwarz(S)) return -1;
+    lap("schwarz");
+    if (prepare_sort_pairs(S)) return -1;
+    lap("sort pairs");
+    if (prepare_enumerate_tiles(S)) return -1;
+    lap("  plan + tile enumeration");
+    if (prepare_upload_directory(S)) return -1;
+    lap("  directory uploads");
+    if (prepare_jk_segments(S)) return -1;
+    lap("  J/K segments");
+    if (int rc = prepare_allocate_store(S)) return rc;   // -1, or MI_ERR_NOMEM: the caller shards or goes direct
+    lap("tiles/runs/segments + alloc");
+    if (prepare_evaluate(S)) return -1;
     lap("quartet evaluation");
-    if (d_prefix) dev_free(d_prefix);
-    dev_free(d_comp);
-    scr_work.release(); scr_tasks.release();
+    S.d_prefix.reset(); S.d_comp.reset();
+    S.scr_work.release(); S.scr_tasks.release();
     lap("free scratch");
     c->stats.n_tiles = c->n_tiles;
     c->stats.n_runs = (int64_t)c->runs.size();
-    c->stats.stored_bytes = off * 8;
-    c->stats.n_unique_eri = nuniq;
-    c->stats.n_quartets = nquart;
+    c->stats.stored_bytes = S.off * 8;
+    c->stats.n_unique_eri = S.nuniq;
+    c->stats.n_quartets = S.nquart;
     c->stats.seconds_eri = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     c->eri_ready = true;
     if (c->opt_grad_prefetch) {
@@ -2935,8 +3161,7 @@ extern "C" int mi_df_build(mi_ctx *c, mi_ctx *aux, double *d_int3c, double *d_in
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const int naux = aux->nao - 1, unit_ao = aux->nao - 1, nP = aux->nbas - 1;
-    std::vector<std::vector<double>> c2s(LMAX + 1);
-    for (int l = 0; l <= LMAX; l++) c2s_generic(l, c2s[l]);
+    const std::vector<std::vector<double>> c2s = c2s_tables();
     DfPairs D;
     // orbital pairs (as in mi_eri_prepare step 1, no Schwarz sorting: every pair is fitted)
     for (int A = 0; A < c->nbas; A++)
@@ -2945,81 +3170,47 @@ extern "C" int mi_df_build(mi_ctx *c, mi_ctx *aux, double *d_int3c, double *d_in
             if (c->shells[si].l < c->shells[sj].l) std::swap(si, sj);
             const ShellH &I = c->shells[si], &J = c->shells[sj];
             double AB[3] = {I.r[0] - J.r[0], I.r[1] - J.r[1], I.r[2] - J.r[2]};
-            double r2 = AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2];
             PairRec R{si, sj, I.ao_nat, J.ao_nat, (int)(D.prim.size() / 8), 0, 0, 0};   // dense output in the caller's AO order
-            for (int ip = 0; ip < I.nprim; ip++)
-                for (int jp = 0; jp < J.nprim; jp++) {
-                    double a = I.exps[ip], b = J.exps[jp], p = a + b, mu = a * b / p;
-                    if (mu * r2 > 80.0) continue;
-                    double K = I.coef[ip] * J.coef[jp] * std::exp(-mu * r2), Pc[3];
-                    for (int d = 0; d < 3; d++) Pc[d] = (a * I.r[d] + b * J.r[d]) / p;
-                    double rec[8] = {p, Pc[0], Pc[1], Pc[2], Pc[0] - I.r[0], Pc[1] - I.r[1], Pc[2] - I.r[2], K};
-                    D.prim.insert(D.prim.end(), rec, rec + 8);
-                    R.nprim++;
-                }
+            R.nprim = append_prim_pairs(I, J, D.prim);
             if (R.nprim == 0) continue;
-            const int nsab = (2 * I.l + 1) * (2 * J.l + 1), ne = ne_of(I.l, J.l);
             R.m_off = (int)D.Mbuf.size();
-            D.Mbuf.resize(D.Mbuf.size() + (size_t)2 * nsab * ne);
-            build_M(I.l, J.l, AB, c2s[I.l], c2s[J.l], D.Mbuf.data() + R.m_off);
-            double *M = D.Mbuf.data() + R.m_off, *Mt = M + (size_t)nsab * ne;
-            for (int r = 0; r < nsab; r++)
-                for (int e = 0; e < ne; e++) Mt[(size_t)e * nsab + r] = M[(size_t)r * ne + e];
+            D.Mbuf.resize(D.Mbuf.size() + (size_t)2 * (2 * I.l + 1) * (2 * J.l + 1) * ne_of(I.l, J.l));
+            build_M_and_transpose(I.l, J.l, AB, c2s[I.l], c2s[J.l], D.Mbuf.data() + R.m_off);
             D.recs[pc_index(I.l, J.l)].push_back(R);
         }
-    // auxiliary "pairs" (P, unit): p = alpha, centre P = A, P - A = 0, K = c_P * c_unit
+    // auxiliary "pairs" (P, unit)
     for (int Pn = 0; Pn < nP; Pn++) {
         const ShellH &S = aux->shells[Pn];
         PairRec R{Pn, aux->nbas - 1, S.ao_nat, unit_ao, (int)(D.prim.size() / 8), S.nprim, 0, 0};
-        for (int ip = 0; ip < S.nprim; ip++) {
-            double rec[8] = {S.exps[ip], S.r[0], S.r[1], S.r[2], 0.0, 0.0, 0.0, S.coef[ip] * U.coef[0]};
-            D.prim.insert(D.prim.end(), rec, rec + 8);
-        }
-        const int ns = 2 * S.l + 1, ne = ncart(S.l);
+        D.prim.resize(D.prim.size() + (size_t)8 * S.nprim);
+        write_aux_prims(S, U, D.prim.data() + (size_t)8 * R.prim_off);
         double AB[3] = {0.0, 0.0, 0.0};
         R.m_off = (int)D.Mbuf.size();
-        D.Mbuf.resize(D.Mbuf.size() + (size_t)2 * ns * ne);
-        build_M(S.l, 0, AB, c2s[S.l], c2s[0], D.Mbuf.data() + R.m_off);
-        double *M = D.Mbuf.data() + R.m_off, *Mt = M + (size_t)ns * ne;
-        for (int r = 0; r < ns; r++)
-            for (int e = 0; e < ne; e++) Mt[(size_t)e * ns + r] = M[(size_t)r * ne + e];
+        D.Mbuf.resize(D.Mbuf.size() + (size_t)2 * (2 * S.l + 1) * ncart(S.l));
+        build_M_and_transpose(S.l, 0, AB, c2s[S.l], c2s[0], D.Mbuf.data() + R.m_off);
         // c2s of the unit function: build_M multiplied by c2s[0] = 1/sqrt(4 pi); its coefficient sqrt(4 pi) restores 1
         D.aux[S.l].push_back(R);
     }
     if (D.Mbuf.size() > (size_t)INT32_MAX) return fail("mi_df_build: transformation-matrix buffer exceeds 2^31 doubles");
-    double *d_prim = nullptr, *d_M = nullptr, *d_work = nullptr;
-    uint32_t *d_comp = nullptr;
-    int64_t *d_prefix = nullptr;
-    PairRec *d_rec_o[NPC] = {nullptr}, *d_rec_a[LMAX + 1] = {nullptr};
-    if (upload(&d_prim, D.prim) || upload(&d_M, D.Mbuf)) return -1;
-    for (int q = 0; q < NPC; q++) if (!D.recs[q].empty() && upload(&d_rec_o[q], D.recs[q])) return -1;
-    for (int l = 0; l <= LMAX; l++) if (!D.aux[l].empty() && upload(&d_rec_a[l], D.aux[l])) return -1;
+    DevBuf<double> d_prim, d_M, d_work;
+    DevBuf<uint32_t> d_comp;
+    DevBuf<int64_t> d_prefix;
+    DevBuf<PairRec> d_rec_o[NPC], d_rec_a[LMAX + 1];
+    if (d_prim.upload(D.prim) || d_M.upload(D.Mbuf)) return -1;
+    for (int q = 0; q < NPC; q++) if (!D.recs[q].empty() && d_rec_o[q].upload(D.recs[q])) return -1;
+    for (int l = 0; l <= LMAX; l++) if (!D.aux[l].empty() && d_rec_a[l].upload(D.aux[l])) return -1;
     const size_t WORK_DOUBLES = (size_t)32 << 20;
-    HIPCHK(dev_malloc(&d_work, sizeof(double) * WORK_DOUBLES));
-    HIPCHK(dev_malloc(&d_comp, sizeof(uint32_t) * 8192));
-    size_t prefix_cap = 0;
+    HIPCHK(d_work.alloc(WORK_DOUBLES));
+    HIPCHK(d_comp.alloc(COMP_CAP));
     // one pass per (bra class, auxiliary l): bra = orbital pairs (3-index) or auxiliary pairs (2-index)
     auto run = [&](const PairRec *d_bra, int nbra, int la, int lb, int lk, int mode, double *out, int ld_nao) -> int {
         const int nket = (int)D.aux[lk].size();
         if (nbra == 0 || nket == 0) return 0;
-        std::vector<int64_t> prefix(nbra + 1);
-        for (int b = 0; b <= nbra; b++) prefix[b] = (int64_t)b * nket;
-        const int64_t ntask = prefix.back();
-        append_coarse_index(prefix);
-        if (prefix.size() > prefix_cap) {
-            if (d_prefix) dev_free(d_prefix);
-            prefix_cap = prefix.size() * 2;
-            HIPCHK(dev_malloc(&d_prefix, sizeof(int64_t) * prefix_cap));
-        }
-        HIPCHK(hipMemcpyAsync(d_prefix, prefix.data(), sizeof(int64_t) * prefix.size(), hipMemcpyHostToDevice, st));
-        EriArgs E{};
-        setup_eri_dims(E, la, lb, lk, 0);
-        std::vector<uint32_t> comp;
-        build_comp_table(la, lb, lk, 0, comp);
-        HIPCHK(hipMemcpyAsync(d_comp, comp.data(), sizeof(uint32_t) * comp.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        E.bra = d_bra; E.ket = d_rec_a[lk]; E.prim = d_prim; E.prefix = d_prefix; E.nbra = nbra;
-        E.comp = d_comp; E.work = d_work; E.rys = c->rys; E.diag = 0;
+        std::vector<int64_t> prefix;
+        const int64_t ntask = dense_prefix(nbra, nket, prefix);
+        if (prefix_to_device(prefix, d_prefix, st)) return -1;
+        if (upload_comp_table(la, lb, lk, 0, d_comp, st)) return -1;
+        EriArgs E = eri_class_args(c, la, lb, lk, 0, d_bra, d_rec_a[lk], d_prim, d_prefix, nbra, d_comp, d_work);
         E.ni = 2 * la + 1; E.nj = 2 * lb + 1; E.nk = 2 * lk + 1; E.nl = 1;
         XfArgs X{};
         X.bra = d_bra; X.ket = d_rec_a[lk]; X.Mbuf = d_M; X.prefix = d_prefix; X.nbra = nbra;
@@ -3050,10 +3241,6 @@ extern "C" int mi_df_build(mi_ctx *c, mi_ctx *aux, double *d_int3c, double *d_in
     if (d_int2c)
         for (int lp = 0; lp <= LMAX && !rc; lp++)
             for (int lk = 0; lk <= LMAX && !rc; lk++) rc = run(d_rec_a[lp], (int)D.aux[lp].size(), lp, 0, lk, 2, d_int2c, naux);
-    for (int q = 0; q < NPC; q++) if (d_rec_o[q]) dev_free(d_rec_o[q]);
-    for (int l = 0; l <= LMAX; l++) if (d_rec_a[l]) dev_free(d_rec_a[l]);
-    dev_free(d_prim); dev_free(d_M); dev_free(d_work); dev_free(d_comp);
-    if (d_prefix) dev_free(d_prefix);
     return rc;
 }
 
@@ -3555,12 +3742,11 @@ extern "C" int mi_eri_unpack(mi_ctx *c, double *d_out, void *stream)
     const size_t n = c->nao;
     HIPCHK(hipMemsetAsync(d_out, 0, sizeof(double) * n * n * n * n, st));   // screened-out tiles stay zero
     if (c->n_tiles == 0) return 0;
-    TileInfo *d_info = nullptr;
-    if (upload(&d_info, c->tiles)) return -1;
-    hipLaunchKernelGGL(eri_unpack_kernel, dim3((unsigned)c->n_tiles), dim3(256), 0, st, c->d_tiles, c->d_tile_off, d_info, c->nao, c->tri, d_out, c->d_iperm);
+    DevBuf<TileInfo> d_info;
+    if (d_info.upload(c->tiles)) return -1;
+    hipLaunchKernelGGL(eri_unpack_kernel, dim3((unsigned)c->n_tiles), dim3(256), 0, st, c->d_tiles, c->d_tile_off, d_info.get(), c->nao, c->tri, d_out, c->d_iperm);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
-    dev_free(d_info);
     return 0;
 }
 
@@ -3600,13 +3786,12 @@ extern "C" int mi_eri_read_quartet(mi_ctx *c, int ish, int jsh, int ksh, int lsh
     int ao[4], n[4];
     for (int q = 0; q < 4; q++) { ao[q] = c->shells[sh[q]].ao; n[q] = 2 * c->shells[sh[q]].l + 1; }
     const int tot = n[0] * n[1] * n[2] * n[3];
-    double *d_out = nullptr;
-    HIPCHK(dev_malloc(&d_out, sizeof(double) * tot));
+    DevBuf<double> d_out;
+    HIPCHK(d_out.alloc(tot));
     hipLaunchKernelGGL(eri_read_quartet_kernel, dim3((tot + 255) / 256), dim3(256), 0, nullptr, c->d_tiles, c->d_tile_off, c->d_tile_table,
-                       c->nao, ao[0], n[0], ao[1], n[1], ao[2], n[2], ao[3], n[3], c->d_tile_present, c->tri, d_out);
+                       c->nao, ao[0], n[0], ao[1], n[1], ao[2], n[2], ao[3], n[3], c->d_tile_present, c->tri, d_out.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, d_out, sizeof(double) * tot, hipMemcpyDeviceToHost));
-    dev_free(d_out);
     return 0;
 }
 
@@ -3641,14 +3826,17 @@ __global__ void finalize_jk_kernel(const double *Jacc, const double *Kacc, doubl
     if (K) K[idx] = Kacc[(size_t)r * ld + c] + Kacc[(size_t)c * ld + r];
 }
 
+// tile stream of the J/K, batched J/K and quarter-transformation kernels (option jk_nt): nontemporal loads only when the tensor
+// cannot stay in the 256 MiB Infinity Cache between SCF cycles
+static bool jk_stream_nt(const mi_ctx *c) { return c->opt_jk_nt != 0 && (c->opt_jk_nt > 1 || c->tile_doubles * 8 > ((int64_t)256 << 20)); }
+
 static int launch_jk(mi_ctx *c, bool wj, bool wk, hipStream_t st)
 {
     JkArgs A{c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg, c->n_jk_waves, c->d_Dpad, c->d_Jacc, c->d_Kacc, c->ldp, c->nao,
              c->n_jk_cached, c->tri, (size_t)c->ldp * c->ldp, 0, c->opt_jk_dpp};
     if (c->n_tiles == 0) return 0;
     dim3 g(A.nruns), b(64);
-    // nontemporal loads only when the tensor cannot stay in the 256 MiB Infinity Cache between SCF cycles
-    const bool nt = c->opt_jk_nt != 0 && (c->opt_jk_nt > 1 || c->tile_doubles * 8 > ((int64_t)256 << 20));
+    const bool nt = jk_stream_nt(c);
     // the half-tile pipeline only exists for full-row tiles: with triangular rows (the default) the plain kernel is the faster
     // one on cache-resident tensors too (benzene/cc-pVDZ J+K 39.8 us vs 41.5 us for full rows + pipeline, 48 us for both)
     const bool pipe = !c->tri && (c->opt_jk_pipe > 0 || (c->opt_jk_pipe < 0 && c->tile_doubles * 8 <= ((int64_t)256 << 20)));
@@ -3684,7 +3872,7 @@ extern "C" int mi_build_jk(mi_ctx *c, const double *d_D, int n_dm, double *d_J, 
         dim3 g(A.nruns), b(128);
         // same cache policy as the single-density kernel: nontemporal stream + default-policy prefix for tensors beyond the
         // Infinity Cache (an all-default-policy stream of 4.9 GB made the launch time erratic: 1.65 ... 2.75 ms)
-        const bool nt = c->opt_jk_nt != 0 && (c->opt_jk_nt > 1 || c->tile_doubles * 8 > ((int64_t)256 << 20));
+        const bool nt = jk_stream_nt(c);
         if (d_J && d_K) { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<true, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<true, true, false>), g, b, 0, st, A); }
         else if (d_J) { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<true, false, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<true, false, false>), g, b, 0, st, A); }
         else { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<false, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<false, true, false>), g, b, 0, st, A); }
@@ -3765,16 +3953,18 @@ __device__ __forceinline__ void jkm_contract(const double *__restrict__ Tl, cons
     }
 }
 
-template <bool NT, int NPW>
-__device__ __forceinline__ void jkm_load_tile(const JkmArgs &A, double *__restrict__ Tl, const int64_t toff, const int bi, const int bk,
-                                              const bool dij, const bool dkl)
+// full 8x8x8x8 image of one stored tile in LDS (not-stored and ragged lanes zero), by a workgroup of NTHREADS threads
+template <bool NT, int NTHREADS>
+__device__ __forceinline__ void load_tile_image(const double *tiles, double *__restrict__ Tl, const int64_t toff, const int bi, const int bk,
+                                                const bool dij, const bool dkl)
 {
-    const d2_t *__restrict__ T = reinterpret_cast<const d2_t *>(A.tiles + toff);
-    // 2048 chunks {T[i,j,k,2m], T[i,j,k,2m+1]} in the store's order (row (j, m), then lanes (i, k)): 16 per thread
-    d2_t v[16];
+    const d2_t *__restrict__ T = reinterpret_cast<const d2_t *>(tiles + toff);
+    // 2048 chunks {T[i,j,k,2m], T[i,j,k,2m+1]} in the store's order (row (j, m), then lanes (i, k)): 16 per thread of 128
+    constexpr int NS = 2048 / NTHREADS;
+    d2_t v[NS];
 #pragma unroll
-    for (int s = 0; s < 16; s++) {
-        const int c2 = threadIdx.x + 128 * s;
+    for (int s = 0; s < NS; s++) {
+        const int c2 = threadIdx.x + NTHREADS * s;
         const int j = c2 >> 8, m = (c2 >> 6) & 3, i = (c2 >> 3) & 7, k = c2 & 7;
         const int ch = (i < bi && k < bk) ? tile_chunk(dij, dkl, bi, bk, i, j, k, m) : -1;
         d2_t x = {0.0, 0.0};
@@ -3782,8 +3972,8 @@ __device__ __forceinline__ void jkm_load_tile(const JkmArgs &A, double *__restri
         v[s] = x;
     }
 #pragma unroll
-    for (int s = 0; s < 16; s++) {
-        const int c2 = threadIdx.x + 128 * s;
+    for (int s = 0; s < NS; s++) {
+        const int c2 = threadIdx.x + NTHREADS * s;
         const int j = c2 >> 8, m = (c2 >> 6) & 3, i = (c2 >> 3) & 7, k = c2 & 7;
         const int a = JKM_SI * i + JKM_SJ * j + JKM_SK * k + 2 * m;
         Tl[a] = v[s].x;
@@ -3827,7 +4017,7 @@ __device__ __forceinline__ void jkm_segment(const JkmArgs &A, double *__restrict
         const int I0 = I * BLK;
         const int bi = min(BLK, A.nao - I0);
         __syncthreads();   // the previous tile's image is no longer read
-        jkm_load_tile<NT, NPW>(A, Tl, toff, bi, bk, A.tri && I == R.J, dkl);
+        load_tile_image<NT, 128>(A.tiles, Tl, toff, bi, bk, A.tri && I == R.J, dkl);
         __syncthreads();
         const MI_CONST_AS double *Dq[NPW];
         double acc[NPW];
@@ -3938,7 +4128,7 @@ extern "C" int mi_build_jk_multi(mi_ctx *c, const double *d_D, int n_dm, const i
         HIPCHK(dev_malloc(&c->d_mKacc, sizeof(double) * JKM_BATCH * pp));
     }
     const int batch = std::max(1, std::min(JKM_BATCH, c->opt_jk_multi_batch));
-    const bool nt = c->opt_jk_nt != 0 && (c->opt_jk_nt > 1 || c->tile_doubles * 8 > ((int64_t)256 << 20));
+    const bool nt = jk_stream_nt(c);
     for (int m0 = 0; m0 < n_dm; m0 += batch) {
         const int n = std::min(batch, n_dm - m0);
         JkmSigns sg{};
@@ -4006,32 +4196,6 @@ struct QtArgs {
     int n;                     // orbitals of this launch (<= NB of the instantiation; slots beyond it are never written)
 };
 
-template <bool NT>
-__device__ __forceinline__ void qt_load_tile(const QtArgs &A, double *__restrict__ Tl, const int64_t toff, const int bi, const int bk,
-                                             const bool dij, const bool dkl)
-{
-    const d2_t *__restrict__ T = reinterpret_cast<const d2_t *>(A.tiles + toff);
-    constexpr int NS = 2048 / QT_THREADS;
-    d2_t v[NS];
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const int c2 = threadIdx.x + QT_THREADS * s;
-        const int j = c2 >> 8, m = (c2 >> 6) & 3, i = (c2 >> 3) & 7, k = c2 & 7;
-        const int ch = (i < bi && k < bk) ? tile_chunk(dij, dkl, bi, bk, i, j, k, m) : -1;
-        d2_t x = {0.0, 0.0};
-        if (ch >= 0) x = NT ? __builtin_nontemporal_load(T + ch) : T[ch];
-        v[s] = x;
-    }
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        const int c2 = threadIdx.x + QT_THREADS * s;
-        const int j = c2 >> 8, m = (c2 >> 6) & 3, i = (c2 >> 3) & 7, k = c2 & 7;
-        const int a = JKM_SI * i + JKM_SJ * j + JKM_SK * k + 2 * m;
-        Tl[a] = v[s].x;
-        Tl[a + 1] = v[s].y;
-    }
-}
-
 // acc[o] += sum_c Tl[base + sc * c] * Crow[c][o]  (Crow: 8 coefficient rows of QT_BATCH doubles, wave-uniform)
 template <int NB>
 __device__ __forceinline__ void qt_contract(const double *__restrict__ Tl, const int base, const int sc,
@@ -4072,7 +4236,7 @@ __device__ __forceinline__ void qt_segment(const QtArgs &A, double *__restrict__
         const int I0 = I * BLK;
         const int bi = min(BLK, A.nao - I0);
         __syncthreads();   // the previous tile's image is no longer read
-        qt_load_tile<NT>(A, Tl, toff, bi, bk, A.tri && I == R.J, dkl);
+        load_tile_image<NT, QT_THREADS>(A.tiles, Tl, toff, bi, bk, A.tri && I == R.J, dkl);
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < 2; s++) {
@@ -4154,18 +4318,18 @@ extern "C" int mi_eri_qtrans(mi_ctx *c, const double *d_C, int nb, int ldc, doub
     hipStream_t st = (hipStream_t)stream;
     const size_t ld = c->ldp, p3 = ld * ld * ld, n3 = (size_t)c->nao * c->nao * c->nao;
     const int nmax = std::min(nb, QT_BATCH);
-    double *d_A = nullptr, *d_Cp = nullptr;
-    if (dev_malloc(&d_A, sizeof(double) * p3 * nmax) != hipSuccess) {
+    DevBuf<double> d_A, d_Cp;
+    if (d_A.alloc(p3 * nmax) != hipSuccess) {
         (void)hipGetLastError();
         return fail("mi_eri_qtrans: no device memory for the %.2f GB accumulator", 8e-9 * p3 * nmax);
     }
-    if (dev_malloc(&d_Cp, sizeof(double) * ld * QT_BATCH) != hipSuccess) { (void)hipGetLastError(); dev_free(d_A); return fail("mi_eri_qtrans: no device memory"); }
-    const bool nt = c->opt_jk_nt != 0 && (c->opt_jk_nt > 1 || c->tile_doubles * 8 > ((int64_t)256 << 20));
+    if (d_Cp.alloc(ld * QT_BATCH) != hipSuccess) { (void)hipGetLastError(); return fail("mi_eri_qtrans: no device memory"); }
+    const bool nt = jk_stream_nt(c);
     int rc = 0;
     for (int m0 = 0; m0 < nb && !rc; m0 += QT_BATCH) {
         const int n = std::min(QT_BATCH, nb - m0);
         hipLaunchKernelGGL(qt_pad_coeff_kernel, dim3((unsigned)((ld * QT_BATCH + 255) / 256)), dim3(256), 0, st, d_C + m0, ldc, n, c->nao,
-                           (int)ld, d_Cp, c->d_iperm);
+                           (int)ld, d_Cp.get(), c->d_iperm);
         if (hipMemsetAsync(d_A, 0, sizeof(double) * p3 * n, st) != hipSuccess) { rc = fail("mi_eri_qtrans: memset failed"); break; }
         if (c->n_tiles > 0) {
             QtArgs A{c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg, d_Cp, d_A, p3, (int)ld, c->nao, c->n_jk_cached, c->tri, n};
@@ -4178,13 +4342,11 @@ extern "C" int mi_eri_qtrans(mi_ctx *c, const double *d_C, int nb, int ldc, doub
             else QT_LAUNCH(8);
 #undef QT_LAUNCH
         }
-        hipLaunchKernelGGL(qt_finalize_kernel, dim3((unsigned)((n3 + 255) / 256), (unsigned)n), dim3(256), 0, st, d_A, d_Y + (size_t)m0 * n3,
+        hipLaunchKernelGGL(qt_finalize_kernel, dim3((unsigned)((n3 + 255) / 256), (unsigned)n), dim3(256), 0, st, d_A.get(), d_Y + (size_t)m0 * n3,
                            c->nao, (int)ld, p3, c->d_perm);
         if (hipGetLastError() != hipSuccess) rc = fail("mi_eri_qtrans: kernel launch failed");
     }
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail("mi_eri_qtrans: %s", hipGetErrorString(hipGetLastError()));
-    dev_free(d_A);
-    dev_free(d_Cp);
     return rc;
 }
 
@@ -4499,15 +4661,14 @@ extern "C" int mi_grid_becke(mi_ctx *c, const double *d_coords, const int32_t *d
     std::vector<double> xyz(c->natm * 3);
     for (int i = 0; i < c->natm; i++)
         for (int d = 0; d < 3; d++) xyz[3 * i + d] = c->env[c->atm[i * ATM_SLOTS + 1] + d];
-    double *d_xyz = nullptr;
-    HIPCHK(dev_malloc(&d_xyz, sizeof(double) * xyz.size()));
+    DevBuf<double> d_xyz;
+    HIPCHK(d_xyz.alloc(xyz.size()));
     HIPCHK(hipMemcpy(d_xyz, xyz.data(), sizeof(double) * xyz.size(), hipMemcpyHostToDevice));
     BeckeArgs A{d_coords, d_atom_of, d_vol, d_xyz, d_adjust, c->natm, ng, d_weights};
     hipLaunchKernelGGL(becke_weights_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), sizeof(double) * 3 * c->natm,
                        (hipStream_t)stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    dev_free(d_xyz);
     return 0;
 }
 
@@ -6096,72 +6257,64 @@ static void build_M_deriv(int l1, int l2, int sign, const double AB[3], const st
         }
 }
 
+// Variant records of differentiated shell pairs, for the four-centre and the density-fitted gradient alike.  Pass 1 (add_pair,
+// serial and cheap) fixes the offsets of every (l+1) / (l-1) record behind what the two host buffers already hold; pass 2
+// (fill, OpenMP) writes their primitive records and HRR x derivative x c2s matrices.
+struct VariantRecords {
+    struct Job { const ShellH *I, *J; size_t prim_off, m_off; int sign; };
+    std::vector<Job> jobs;
+    size_t prim_end, m_end;   // running ends of the primitive-record buffer (records) and of the matrix buffer (doubles)
+    VariantRecords(size_t prim_records, size_t m_doubles) : prim_end(prim_records), m_end(m_doubles) {}
+    // the two variants of the pair (I differentiated, J): out[0] = l+1, out[1] = l-1 (sh_i = -1 where I is an s shell)
+    void add_pair(const ShellH &I, const ShellH &J, int s1, int s2, int ao1, int ao2, PairRec out[2])
+    {
+        const int np = count_prim_pairs(I, J);
+        for (int sg = 0; sg < 2; sg++) {
+            const int sign = sg == 0 ? +1 : -1;
+            out[sg] = PairRec{-1, -1, 0, 0, 0, 0, 0, 0};
+            if (I.l + sign < 0) continue;
+            out[sg] = PairRec{s1, s2, ao1, ao2, (int)prim_end, np, (int)m_end, 0};
+            jobs.push_back({&I, &J, prim_end, m_end, sign});
+            prim_end += np;
+            m_end += (size_t)3 * (2 * I.l + 1) * (2 * J.l + 1) * ne_of(I.l + sign, J.l);
+        }
+    }
+    void fill(std::vector<double> &prim, std::vector<double> &Mbuf) const
+    {
+        const std::vector<std::vector<double>> c2s = c2s_tables();
+#pragma omp parallel for schedule(dynamic, 64) num_threads(host_threads())
+        for (size_t q = 0; q < jobs.size(); q++) {
+            const Job &jb = jobs[q];
+            const ShellH &I = *jb.I, &J = *jb.J;
+            double AB[3] = {I.r[0] - J.r[0], I.r[1] - J.r[1], I.r[2] - J.r[2]};
+            write_prim_pairs(I, J, jb.sign > 0, prim.data() + jb.prim_off * 8);
+            build_M_deriv(I.l, J.l, jb.sign, AB, c2s[I.l], c2s[J.l], Mbuf.data() + jb.m_off);
+        }
+    }
+};
+
 // host half: sizes, primitive records and derivative matrices of every variant pair (no HIP call: may run on the helper thread)
 static int grad_records_host(mi_ctx *c)
 {
-    std::vector<std::vector<double>> c2s(LMAX + 1);
-    for (int l = 0; l <= LMAX; l++) c2s_generic(l, c2s[l]);
     std::vector<double> &prim = c->h_prim, &Mbuf = c->h_M;
-    // pass 1 (serial, cheap): sizes and offsets of every variant record
-    struct Job { int ci, r, o, sg; };
-    std::vector<Job> jobs;
-    size_t prim_end = prim.size() / 8, m_end = Mbuf.size();
+    VariantRecords V(prim.size() / 8, Mbuf.size());
     for (int ci = 0; ci < NPC; ci++) {
         PairClass &P = c->pc[ci];
         for (int o = 0; o < 2; o++)
-            for (int sg = 0; sg < 2; sg++) P.g_recs[o][sg].assign(P.recs.size(), PairRec{-1, -1, 0, 0, 0, 0, 0, 0});
+            for (int sg = 0; sg < 2; sg++) P.g_recs[o][sg].resize(P.recs.size());
         for (size_t r = 0; r < P.recs.size(); r++)
             for (int o = 0; o < 2; o++) {
                 int s1 = o == 0 ? P.recs[r].sh_i : P.recs[r].sh_j, s2 = o == 0 ? P.recs[r].sh_j : P.recs[r].sh_i;
                 const ShellH &I = c->shells[s1], &J = c->shells[s2];
-                double r2 = 0.0;
-                for (int d = 0; d < 3; d++) r2 += (I.r[d] - J.r[d]) * (I.r[d] - J.r[d]);
-                int np = 0;
-                for (int ip = 0; ip < I.nprim; ip++)
-                    for (int jp = 0; jp < J.nprim; jp++)
-                        if (I.exps[ip] * J.exps[jp] / (I.exps[ip] + J.exps[jp]) * r2 <= 80.0) np++;
-                for (int sg = 0; sg < 2; sg++) {
-                    int sign = sg == 0 ? +1 : -1;
-                    if (I.l + sign < 0) continue;
-                    PairRec R;
-                    R.sh_i = s1; R.sh_j = s2; R.ao_i = I.ao; R.ao_j = J.ao; R.pad = 0;
-                    R.prim_off = (int)prim_end; R.nprim = np;
-                    prim_end += np;
-                    size_t msz = (size_t)3 * (2 * I.l + 1) * (2 * J.l + 1) * ne_of(I.l + sign, J.l);
-                    if (m_end + msz > (size_t)INT32_MAX) return fail("gradient transformation matrices exceed 2^31 doubles");
-                    R.m_off = (int)m_end;
-                    m_end += msz;
-                    P.g_recs[o][sg][r] = R;
-                    jobs.push_back({ci, (int)r, o, sg});
-                }
+                PairRec R[2];
+                V.add_pair(I, J, s1, s2, I.ao, J.ao, R);
+                if (V.m_end > (size_t)INT32_MAX) return fail("gradient transformation matrices exceed 2^31 doubles");
+                for (int sg = 0; sg < 2; sg++) P.g_recs[o][sg][r] = R[sg];
             }
     }
-    prim.resize(prim_end * 8);
-    Mbuf.resize(m_end);
-    // pass 2 (OpenMP): fill primitive records and HRR*derivative*c2s matrices
-#pragma omp parallel for schedule(dynamic, 64) num_threads(host_threads())
-    for (size_t q = 0; q < jobs.size(); q++) {
-        const Job jb = jobs[q];
-        PairClass &P = c->pc[jb.ci];
-        const PairRec &R = P.g_recs[jb.o][jb.sg][jb.r];
-        const ShellH &I = c->shells[R.sh_i], &J = c->shells[R.sh_j];
-        const int sign = jb.sg == 0 ? +1 : -1;
-        double AB[3] = {I.r[0] - J.r[0], I.r[1] - J.r[1], I.r[2] - J.r[2]};
-        double r2 = AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2];
-        double *dst = prim.data() + (size_t)R.prim_off * 8;
-        for (int ip = 0; ip < I.nprim; ip++)
-            for (int jp = 0; jp < J.nprim; jp++) {
-                double a = I.exps[ip], b = J.exps[jp], p = a + b, mu = a * b / p;
-                if (mu * r2 > 80.0) continue;
-                double K = I.coef[ip] * J.coef[jp] * std::exp(-mu * r2) * (sign > 0 ? 2.0 * a : 1.0);
-                double Pc[3];
-                for (int d = 0; d < 3; d++) Pc[d] = (a * I.r[d] + b * J.r[d]) / p;
-                double rec[8] = {p, Pc[0], Pc[1], Pc[2], Pc[0] - I.r[0], Pc[1] - I.r[1], Pc[2] - I.r[2], K};
-                memcpy(dst, rec, sizeof rec);
-                dst += 8;
-            }
-        build_M_deriv(I.l, J.l, sign, AB, c2s[I.l], c2s[J.l], Mbuf.data() + R.m_off);
-    }
+    prim.resize(V.prim_end * 8);
+    Mbuf.resize(V.m_end);
+    V.fill(prim, Mbuf);
     c->grad_host_ready = true;
     return 0;
 }
@@ -7012,17 +7165,296 @@ __global__ void grad_reduce_copies_kernel(const double *copies, int natm3, doubl
     grad[idx] += s;
 }
 
-extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, double *d_grad, int rank, int nranks,
-                                   void *stream);
-
-extern "C" int mi_grad_eri(mi_ctx *c, const double *d_D, double hyb, double *d_grad, void *stream)
+// eri_grad_contract for one batch of `nb` quartets whose [e0|f0] blocks are in X.work_p / X.work_m, shared by the four-centre
+// and the density-fitted (df) gradient: four quartets per wave for the small classes (four-centre only), else one wave per
+// quartet, on the matrix cores where one of the three products is large enough.
+static int launch_grad_contract(bool df, const GradXfArgs &X, bool has_m, int nb, size_t shm, hipStream_t st)
 {
-    return c ? mi_grad_eri_sharded(c, d_D, nullptr, hyb, d_grad, c->rank, c->nranks, stream) : fail("mi_grad_eri: null argument");
+    const int big = std::max({X.ns1 * X.ns2 * X.nscd, X.ns1 * X.ns2 * X.nf, X.ns1 * X.ns2 * X.ne_p});
+    const bool mfma = mfma_worthwhile(X.ns1 * X.ns2, X.nf, X.nscd) || mfma_worthwhile(X.ns1 * X.ns2, X.ne_p, X.nf) ||
+                      (has_m && mfma_worthwhile(X.ns1 * X.ns2, X.ne_m, X.nf));
+#define GRAD_CONTRACT(...)                                                                                                                 \
+    do {                                                                                                                                   \
+        if (shm > 64 * 1024)                                                                                                               \
+            HIPCHK(hipFuncSetAttribute((const void *)eri_grad_contract<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
+        hipLaunchKernelGGL((eri_grad_contract<__VA_ARGS__>), dim3(nb), dim3(64), shm, st, X);                                             \
+    } while (0)
+    if (!df && big <= 48 && shm * 4 <= 64 * 1024) { // small classes: four quartets per wave (16 lanes each)
+        hipLaunchKernelGGL((eri_grad_contract<16, false>), dim3((nb + 3) / 4), dim3(64), shm * 4, st, X);
+    } else if (!df) {
+        // (two or four waves sharing one quartet's LDS blocks -- eri_grad_contract<128|256, true> -- were measured at
+        // -2 % / +8 %, the six density sub-blocks of G staged in LDS first at +2 %: the kernel is parked 70 % of its
+        // wave cycles, but neither on a shortage of lanes nor on the G gather)
+        if (mfma) GRAD_CONTRACT(64, true); else GRAD_CONTRACT(64, false);
+    } else {
+        if (mfma) GRAD_CONTRACT(64, true, true); else GRAD_CONTRACT(64, false, true);
+    }
+#undef GRAD_CONTRACT
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
-extern "C" int mi_grad_eri_spin(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, double *d_grad, void *stream)
+// ---- mi_grad_eri_sharded: the per-call buffers (GradState), one (bra class, ket class) pair (GradClassPair), one of its role
+// permutations (GradPerm), and the three routes a permutation is offered to in turn -- thread per quartet, row kernel,
+// Rys -> hand-over -> contraction pipeline; each returns 1 (handled), 0 (not its class) or -1 (error).
+struct GradState {
+    mi_ctx *c;
+    hipStream_t st;
+    double hyb;
+    int rank, nranks;
+    int natm3;
+    size_t work_doubles = 0;                 // per hand-over buffer (plus / minus)
+    DevBuf<double> d_Mpad;                   // spin density Da - Db, padded like D (open shell only)
+    DevBuf<int> d_shell_atom, d_sh_ao, d_sh_n;
+    DevBuf<double> d_dmax;                   // max |D| per shell pair (null: no density-weighted screening)
+    DevBuf<double> d_gcopies;
+    Scratch scr_wp, scr_wm, scr_gtasks, scr_live;
+    DevBuf<uint32_t> d_comp_p, d_comp_m;
+    DevBuf<int64_t> d_prefix;
+    DevBuf<int> d_live_counts;
+    DevBuf<int64_t> d_live_off;
+    int64_t batch_counter = 0;               // pipeline batches are dealt round-robin to the ranks
+};
+struct GradClassPair {
+    PairClass *B, *Kc;
+    bool same;
+    int64_t ntask;
+    bool live_ok;                // the class pair may build the list of live quartets (grad_ensure_live)
+    int64_t nlive = -1;          // its length once built
+    const TaskIdx *tasks_dev = nullptr;   // (bra, ket) table of all tasks, where one was written
+};
+struct GradPerm {
+    int perm, orient;
+    bool swap;
+    PairClass *Dc, *Oc;          // class of the differentiated pair / of the other pair (plain ket)
+    int l1, l2, lc, ld;
+    bool has_m;                  // an (l1 - 1) variant exists
+    // what the wave-per-quartet launches (row kernel, pipeline) walk: the live list when there is one
+    int64_t ntask_w;
+    const TaskIdx *tasks_w;
+    const double *dmax_w;        // null: the live list is already screened
+    EriArgs Ep, Em;
+};
+
+// wave-per-quartet launches of a class pair walk the list of LIVE quartets (density-weighted screening done once, see
+// live_fill_kernel); built on first need -- classes wholly on the thread-per-quartet path never ask for it
+static int grad_ensure_live(GradState &G, GradClassPair &CP)
 {
-    return c ? mi_grad_eri_sharded(c, d_D, d_Dspin, hyb, d_grad, c->rank, c->nranks, stream) : fail("mi_grad_eri: null argument");
+    mi_ctx *c = G.c;
+    hipStream_t st = G.st;
+    const PairClass &B = *CP.B, &Kc = *CP.Kc;
+    const int64_t ntask = CP.ntask;
+    // (lists beyond 2^28 quartets -- 2 GB -- are not built: those launches screen per wave as before)
+    if (CP.nlive >= 0 || !CP.live_ok) return 0;
+    const int nblk = (int)((ntask + 255) / 256);
+    if ((size_t)nblk + 1 > G.d_live_counts.cap) {
+        const size_t live_cap = (size_t)nblk + 1 + (size_t)nblk / 4;
+        HIPCHK(G.d_live_counts.alloc(live_cap));
+        HIPCHK(G.d_live_off.alloc(live_cap));
+    }
+    if (G.scr_live.ensure(c->device, SCR_GRAD_LIVE, sizeof(TaskIdx) * (size_t)ntask)) return -1;
+    TaskIdx *d_live_tasks = (TaskIdx *)G.scr_live.p;
+    LiveArgs L{B.d_recs, Kc.d_recs, G.d_prefix, (int)B.recs.size(), ntask, B.d_q, Kc.d_q, G.d_dmax, c->nbas, G.hyb, c->opt_grad_dtol};
+    hipLaunchKernelGGL(live_count_kernel, dim3(nblk), dim3(256), 0, st, L, G.d_live_counts.get());
+    hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, st, G.d_live_counts.get(), nblk, G.d_live_off.get());
+    hipLaunchKernelGGL(live_fill_kernel, dim3(nblk), dim3(256), 0, st, L, G.d_live_off.get(), d_live_tasks);
+    HIPCHK(hipGetLastError());
+    int64_t n = 0;
+    HIPCHK(hipMemcpyAsync(&n, G.d_live_off + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    CP.nlive = n;
+    if (getenv("MI355_DEBUG"))
+        fprintf(stderr, "[mi355] grad class pair (%d%d|%d%d): %ld of %ld quartets live\n", B.la, B.lb, Kc.la, Kc.lb, (long)CP.nlive, (long)ntask);
+    return 0;
+}
+
+// low classes, shallow contraction: thread per (quartet, permutation)
+static int grad_route_tpq(GradState &G, GradClassPair &CP, const GradPerm &M)
+{
+    mi_ctx *c = G.c;
+    hipStream_t st = G.st;
+    const PairClass &B = *CP.B, &Kc = *CP.Kc, &Dc = *M.Dc, &Oc = *M.Oc;
+    const int64_t ntask = CP.ntask;
+    if (!(c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= 32768)) return 0;
+    TpqGradArgs Q{};
+    Q.dplus = Dc.d_g_recs[M.orient][0]; Q.dminus = M.l1 >= 1 ? Dc.d_g_recs[M.orient][1] : nullptr; Q.ket = Oc.d_recs;
+    Q.prim = c->d_prim; Q.prefix = G.d_prefix; Q.nbra = (int)B.recs.size();
+    // this rank's contiguous share of the task list (the compacted live list when the class has a kernel)
+    const bool has_tpq = tpq_grad_has_class(M.l1, M.l2, M.lc, M.ld);
+    if (has_tpq && grad_ensure_live(G, CP)) return -1;
+    const bool live_q = has_tpq && CP.nlive >= 0;
+    const int64_t nt_q = live_q ? CP.nlive : ntask;
+    const int64_t lo_t = nt_q * G.rank / G.nranks, hi_t = nt_q * (G.rank + 1) / G.nranks;
+    Q.t0 = lo_t; Q.ntask = hi_t - lo_t;
+    Q.tasks = live_q ? (const TaskIdx *)G.scr_live.p : nullptr;
+    Q.swap = M.swap ? 1 : 0; Q.same_class = CP.same;
+    Q.c2s = c->d_c2s;
+    for (int q = 0; q <= LMAX + 1; q++) Q.c2s_off[q] = c->c2s_off[q];
+    Q.rys = c->rys; Q.shell_xyz = c->d_shell_xyz; Q.D = c->d_Dpad; Q.Dm = G.d_Mpad; Q.ld = c->ldp; Q.hyb = G.hyb;
+    Q.shell_atom = G.d_shell_atom; Q.grad = G.d_gcopies; Q.natm3 = G.natm3; Q.inv_from_second = M.swap ? 0 : 1;
+    Q.q_bra = Dc.d_q; Q.q_ket = Oc.d_q; Q.dmax = live_q ? nullptr : G.d_dmax.get(); Q.nbas_d = c->nbas; Q.dtol = c->opt_grad_dtol;
+    const bool dbg1 = getenv("MI355_DEBUG") != nullptr;
+    auto tq0 = std::chrono::steady_clock::now();
+    if (dbg1) hipStreamSynchronize(st);
+    const int used = launch_eri_tpq_grad(M.l1, M.l2, M.lc, M.ld, Q, st);
+    if (used > 0 && dbg1) {
+        hipStreamSynchronize(st);
+        fprintf(stderr, "[mi355] grad class (%d%d|%d%d) perm %d: %ld quartets, %.3f s (thread per quartet)\n", M.l1, M.l2, M.lc, M.ld, M.perm,
+                (long)ntask, std::chrono::duration<double>(std::chrono::steady_clock::now() - tq0).count());
+    }
+    return used;
+}
+
+// row kernel: no hand-over, one launch (see eri_grad_rows_kernel)
+static int grad_route_rows(GradState &G, const GradClassPair &CP, const GradPerm &M)
+{
+    mi_ctx *c = G.c;
+    hipStream_t st = G.st;
+    const PairClass &B = *CP.B, &Dc = *M.Dc, &Oc = *M.Oc;
+    const int l1 = M.l1, l2 = M.l2, lc = M.lc, ldd = M.ld;
+    if (!c->opt_grad_rows) return 0;
+    const int ne_p = ne_of(l1 + 1, l2), ne_m = M.has_m ? ne_of(l1 - 1, l2) : 0, ne_all = ne_p + ne_m;
+    GradRowsArgs R{};
+    if (!(ne_all >= c->opt_grad_rows_min && launch_grad_rows(lc, ldd, ne_all, R, 0, st, true) == 1)) return 0;
+    R.dplus = Dc.d_g_recs[M.orient][0]; R.dminus = M.has_m ? Dc.d_g_recs[M.orient][1] : nullptr; R.ket = Oc.d_recs;
+    R.prim = c->d_prim; R.Mbuf = c->d_M; R.tasks = M.tasks_w; R.prefix = G.d_prefix; R.nbra = (int)B.recs.size();
+    const int64_t lo_t = M.ntask_w * G.rank / G.nranks, hi_t = M.ntask_w * (G.rank + 1) / G.nranks;
+    R.t0 = lo_t; R.ntask = hi_t - lo_t;
+    R.swap = M.swap ? 1 : 0; R.same_class = CP.same;
+    const RowsGeom gm = rows_geometry(ne_all);
+    R.nmax = M.Ep.nmax; R.nroots = M.Ep.nroots; R.tsz = M.Ep.tsz; R.PB = std::max(1, gm.gsz / (3 * M.Ep.nroots));
+    R.ne_p = ne_p; R.ne_m = ne_m; R.nsab = (2 * l1 + 1) * (2 * l2 + 1); R.ns2 = 2 * l2 + 1;
+    R.comp_p = G.d_comp_p; R.comp_m = G.d_comp_m; R.rys = c->rys;
+    R.D = c->d_Dpad; R.Dm = G.d_Mpad; R.ld = c->ldp; R.hyb = G.hyb; R.shell_atom = G.d_shell_atom; R.grad = G.d_gcopies; R.natm3 = G.natm3;
+    R.inv_from_second = M.swap ? 0 : 1;
+    R.q_bra = Dc.d_q; R.q_ket = Oc.d_q; R.dmax = M.dmax_w; R.nbas_d = c->nbas; R.dtol = c->opt_grad_dtol;
+    const int nscd_ = Oc.nsab, nf_ = Oc.ne;
+    const size_t shm_q = sizeof(double) * ((size_t)R.PB * R.nroots * 3 * R.tsz + (size_t)R.PB * 2 * R.nroots + (size_t)R.PB +
+                                           (size_t)nscd_ * nf_ + (size_t)R.nsab * nscd_);
+    if (!(R.ntask < ((int64_t)1 << 31))) return 0;
+    const bool dbgr = getenv("MI355_DEBUG") != nullptr;
+    auto tr0 = std::chrono::steady_clock::now();
+    if (dbgr) hipStreamSynchronize(st);
+    const int used = R.ntask > 0 ? launch_grad_rows(lc, ldd, ne_all, R, shm_q, st) : 1;
+    if (used > 0 && dbgr) {
+        hipStreamSynchronize(st);
+        fprintf(stderr, "[mi355] grad class (%d%d|%d%d) perm %d: %ld quartets, %.4f s (row kernel, %d rows x %d lanes)\n", l1, l2, lc,
+                ldd, M.perm, (long)M.ntask_w, std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count(), gm.rows, gm.gsz);
+    }
+    return used;
+}
+
+// everything else: two Rys launches (l+1, l-1) -> hand-over buffers -> eri_grad_contract, batch by batch
+static int grad_route_pipeline(GradState &G, const GradClassPair &CP, GradPerm &M)
+{
+    mi_ctx *c = G.c;
+    hipStream_t st = G.st;
+    const PairClass &B = *CP.B, &Kc = *CP.Kc, &Dc = *M.Dc, &Oc = *M.Oc;
+    const int l1 = M.l1, l2 = M.l2, lc = M.lc, ldd = M.ld, rank = G.rank, nranks = G.nranks;
+    const bool has_m = M.has_m;
+    const double hyb = G.hyb;
+    EriArgs &Ep = M.Ep, &Em = M.Em;
+    Ep.tasks = Em.tasks = M.tasks_w;
+    Ep.prim_lds = Em.prim_lds = (c->opt_prim_lds && B.max_np + Kc.max_np <= 160) ? B.max_np + Kc.max_np : 0;
+    Ep.h_shared_np = B.mean_np; Ep.h_vary_mean = Kc.mean_np; Ep.h_vary_max4 = Kc.max4_np;
+    Em.h_shared_np = B.mean_np; Em.h_vary_mean = Kc.mean_np; Em.h_vary_max4 = Kc.max4_np;
+    Ep.q_bra = Dc.d_q; Ep.q_ket = Oc.d_q; Ep.dmax = M.dmax_w; Ep.nbas_d = c->nbas; Ep.dtol = c->opt_grad_dtol; Ep.hyb = hyb;
+    if (has_m) { Em.q_bra = Ep.q_bra; Em.q_ket = Ep.q_ket; Em.dmax = M.dmax_w; Em.nbas_d = c->nbas; Em.dtol = Ep.dtol; Em.hyb = hyb; }
+    GradXfArgs X{};
+    X.q_bra = Ep.q_bra; X.q_ket = Ep.q_ket; X.dmax = M.dmax_w; X.nbas_d = c->nbas; X.dtol = Ep.dtol;
+    X.dplus = Dc.d_g_recs[M.orient][0]; X.dminus = has_m ? Dc.d_g_recs[M.orient][1] : nullptr; X.ket = Oc.d_recs;
+    X.Mbuf = c->d_M; X.prefix = G.d_prefix; X.nbra = Ep.nbra; X.swap = Ep.swap; X.same_class = CP.same;
+    X.ne_p = ne_of(l1 + 1, l2); X.ne_m = has_m ? ne_of(l1 - 1, l2) : 0; X.nf = Oc.ne;
+    X.ns1 = 2 * l1 + 1; X.ns2 = 2 * l2 + 1; X.nscd = Oc.nsab; X.nsd = 2 * Oc.lb + 1;
+    X.work_p = (double *)G.scr_wp.p; X.work_m = (double *)G.scr_wm.p; X.ncomp_p = Ep.ncomp; X.ncomp_m = has_m ? Em.ncomp : 0;
+    X.D = c->d_Dpad; X.Dm = G.d_Mpad; X.ld = c->ldp; X.hyb = hyb; X.shell_atom = G.d_shell_atom; X.grad = G.d_gcopies; X.natm3 = G.natm3;
+    X.inv_from_second = M.swap ? 0 : 1;
+    X.tasks = M.tasks_w;
+    size_t shm = sizeof(double) * ((size_t)X.ne_p * X.nf + (size_t)X.ne_m * X.nf + (size_t)X.ns1 * X.ns2 * (X.nf + X.nscd));
+    if (shm > 160 * 1024) return fail("gradient contraction needs %zu bytes of LDS", shm);
+    const bool dbg = getenv("MI355_DEBUG") != nullptr;
+    auto tc0 = std::chrono::steady_clock::now();
+    if (dbg) hipStreamSynchronize(st);
+    int64_t per = std::min<int64_t>((int64_t)(G.work_doubles / Ep.ncomp), (int64_t)1 << 23);
+    if (nranks > 1) per = std::min<int64_t>(per, std::max<int64_t>(1024, M.ntask_w / (8 * nranks)));
+    for (int64_t t0 = 0; t0 < M.ntask_w; t0 += per) {
+        if ((int)((G.batch_counter++) % nranks) != rank) continue; // batches dealt round-robin to ranks
+        int nb = (int)std::min<int64_t>(per, M.ntask_w - t0);
+        Ep.t0 = t0; Ep.ntask = nb;
+        if (launch_eri(c, Ep, nb, st)) return -1;
+        if (has_m) { Em.t0 = t0; Em.ntask = nb; if (launch_eri(c, Em, nb, st)) return -1; }
+        X.t0 = t0; X.nbatch = nb;
+        if (launch_grad_contract(false, X, has_m, nb, shm, st)) return -1;
+    }
+    if (dbg) {
+        hipStreamSynchronize(st);
+        fprintf(stderr, "[mi355] grad class (%d%d|%d%d) perm %d: %ld quartets, %.3f s\n", l1, l2, lc, ldd, M.perm, (long)CP.ntask,
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - tc0).count());
+    }
+    return 1;
+}
+
+// one role permutation of a class pair: derivative on the first shell of (ji|kl), (kl|ij) or (lk|ij)
+static int grad_permutation(GradState &G, GradClassPair &CP, int perm)
+{
+    mi_ctx *c = G.c;
+    hipStream_t st = G.st;
+    PairClass &B = *CP.B, &Kc = *CP.Kc;
+    GradPerm M{};
+    M.perm = perm;
+    M.swap = perm >= 2;
+    M.orient = perm & 1;
+    M.Dc = M.swap ? &Kc : &B;
+    M.Oc = M.swap ? &B : &Kc;
+    const PairClass &Dc = *M.Dc, &Oc = *M.Oc;
+    M.l1 = M.orient == 0 ? Dc.la : Dc.lb; M.l2 = M.orient == 0 ? Dc.lb : Dc.la;
+    M.lc = Oc.la; M.ld = Oc.lb;
+    M.has_m = M.l1 >= 1;
+    int used = grad_route_tpq(G, CP, M);
+    if (used) return used < 0 ? -1 : 0;
+    if (grad_ensure_live(G, CP)) return -1;
+    const bool use_live = CP.nlive >= 0;
+    if (use_live && CP.nlive == 0) return 0;
+    M.ntask_w = use_live ? CP.nlive : CP.ntask;            // tasks the wave-per-quartet launches walk
+    M.tasks_w = use_live ? (const TaskIdx *)G.scr_live.p : CP.tasks_dev;
+    M.dmax_w = use_live ? nullptr : G.d_dmax.get();          // the live list is already screened
+    if (upload_comp_table(M.l1 + 1, M.l2, M.lc, M.ld, G.d_comp_p, st)) return -1;
+    if (M.has_m && upload_comp_table(M.l1 - 1, M.l2, M.lc, M.ld, G.d_comp_m, st)) return -1;
+    M.Ep = eri_class_args(c, M.l1 + 1, M.l2, M.lc, M.ld, Dc.d_g_recs[M.orient][0], Oc.d_recs, c->d_prim, G.d_prefix, (int)B.recs.size(),
+                          G.d_comp_p, (double *)G.scr_wp.p);
+    M.Ep.swap = M.swap ? 1 : 0;
+    if (M.has_m) {
+        M.Em = eri_class_args(c, M.l1 - 1, M.l2, M.lc, M.ld, Dc.d_g_recs[M.orient][1], Oc.d_recs, c->d_prim, G.d_prefix, M.Ep.nbra,
+                              G.d_comp_m, (double *)G.scr_wm.p);
+        M.Em.swap = M.Ep.swap;
+    }
+    used = grad_route_rows(G, CP, M);
+    if (!used) used = grad_route_pipeline(G, CP, M);
+    return used < 0 ? -1 : 0;
+}
+
+static int grad_class_pair(GradState &G, PairClass &B, PairClass &Kc, bool same)
+{
+    mi_ctx *c = G.c;
+    hipStream_t st = G.st;
+    std::vector<int64_t> prefix;
+    GradClassPair CP{};
+    CP.B = &B; CP.Kc = &Kc; CP.same = same; CP.nlive = -1;
+    const int64_t ntask = CP.ntask = class_prefix(B, Kc, same, c->tol, prefix);
+    if (ntask == 0) return 0;
+    if (prefix_to_device(prefix, G.d_prefix, st)) return -1;
+    CP.live_ok = G.d_dmax && c->opt_grad_live && ntask >= 4096 && ntask <= ((int64_t)1 << 28);   // see grad_ensure_live
+    if (c->opt_task_table && ntask >= 65536 && ntask <= ((int64_t)1 << 28) && !CP.live_ok) {   // up to 3 permutations x 3 launches walk this task list
+        if (G.scr_gtasks.ensure(c->device, SCR_GRAD_TASKS, sizeof(TaskIdx) * (size_t)ntask)) return -1;
+        hipLaunchKernelGGL(fill_tasks_kernel, dim3((unsigned)((ntask + 255) / 256)), dim3(256), 0, st, G.d_prefix.get(), (int)B.recs.size(), ntask,
+                           (TaskIdx *)G.scr_gtasks.p);
+        CP.tasks_dev = (const TaskIdx *)G.scr_gtasks.p;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    // perm 0 (derivative on P.sh_i, the costliest: highest l) is skipped: sum of the four forces = 0
+    for (int perm = 1; perm < 4; perm++)
+        if (grad_permutation(G, CP, perm)) return -1;
+    return 0;
 }
 
 // (rank, nranks): which share of the derivative-quartet batches this call evaluates.  It is an ARGUMENT, not the split of
@@ -7040,34 +7472,31 @@ extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d
     auto tg0 = std::chrono::steady_clock::now();
     if (prepare_grad_records(c)) return -1;
     auto tg1 = std::chrono::steady_clock::now();
+    GradState G;
+    G.c = c; G.st = st; G.hyb = hyb; G.rank = rank; G.nranks = nranks; G.natm3 = c->natm * 3;
     size_t pp = (size_t)c->ldp * c->ldp;
     hipLaunchKernelGGL(pad_density_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_D, c->d_Dpad, c->nao, c->ldp, c->d_iperm);
-    double *d_Mpad = nullptr; // spin density Da - Db, padded like D (open shell only)
     if (d_Dspin) {
-        HIPCHK(dev_malloc(&d_Mpad, sizeof(double) * pp));
-        hipLaunchKernelGGL(pad_density_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_Dspin, d_Mpad, c->nao, c->ldp, c->d_iperm);
+        HIPCHK(G.d_Mpad.alloc(pp));
+        hipLaunchKernelGGL(pad_density_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_Dspin, G.d_Mpad.get(), c->nao, c->ldp, c->d_iperm);
     }
     std::vector<int> shell_atom(c->nbas);
     for (int i = 0; i < c->nbas; i++) shell_atom[i] = c->shells[i].atom;
-    int *d_shell_atom = nullptr;
-    if (upload(&d_shell_atom, shell_atom)) return -1;
+    if (G.d_shell_atom.upload(shell_atom)) return -1;
     // density-weighted screening: q_ab q_cd max|G| < grad_dtol skips the quartet (0 disables)
-    double *d_dmax = nullptr;
-    int *d_sh_ao = nullptr, *d_sh_n = nullptr;
     if (c->opt_grad_dtol > 0.0) {
         std::vector<int> sh_ao(c->nbas), sh_n(c->nbas);
         for (int i = 0; i < c->nbas; i++) { sh_ao[i] = c->shells[i].ao; sh_n[i] = 2 * c->shells[i].l + 1; }
-        if (upload(&d_sh_ao, sh_ao) || upload(&d_sh_n, sh_n)) return -1;
-        HIPCHK(dev_malloc(&d_dmax, sizeof(double) * (size_t)c->nbas * c->nbas));
-        hipLaunchKernelGGL(shell_dmax_kernel, dim3((c->nbas * c->nbas + 255) / 256), dim3(256), 0, st, c->d_Dpad, d_Mpad, c->ldp, d_sh_ao, d_sh_n,
-                           c->nbas, d_dmax);
+        if (G.d_sh_ao.upload(sh_ao) || G.d_sh_n.upload(sh_n)) return -1;
+        HIPCHK(G.d_dmax.alloc((size_t)c->nbas * c->nbas));
+        hipLaunchKernelGGL(shell_dmax_kernel, dim3((c->nbas * c->nbas + 255) / 256), dim3(256), 0, st, c->d_Dpad, G.d_Mpad.get(), c->ldp,
+                           G.d_sh_ao.get(), G.d_sh_n.get(), c->nbas, G.d_dmax.get());
         HIPCHK(hipGetLastError());
     }
-    const int natm3 = c->natm * 3;
-    double *d_gcopies = nullptr;
-    HIPCHK(dev_malloc(&d_gcopies, sizeof(double) * (size_t)GRAD_COPIES * natm3));
-    HIPCHK(hipMemsetAsync(d_gcopies, 0, sizeof(double) * (size_t)GRAD_COPIES * natm3, st));
-    size_t WORK_DOUBLES = (size_t)8 << 17; // per buffer (plus / minus): what the molecule can need, at most `grad_work_mb`
+    const int natm3 = G.natm3;
+    HIPCHK(G.d_gcopies.alloc((size_t)GRAD_COPIES * natm3));
+    HIPCHK(hipMemsetAsync(G.d_gcopies, 0, sizeof(double) * (size_t)GRAD_COPIES * natm3, st));
+    G.work_doubles = (size_t)8 << 17; // per buffer (plus / minus): what the molecule can need, at most `grad_work_mb`
     {
         const size_t cap = (size_t)std::max(8, c->opt_grad_work_mb) << 17;
         for (int bc = 0; bc < NPC; bc++)
@@ -7075,253 +7504,35 @@ extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d
                 const PairClass &B = c->pc[bc], &Kc = c->pc[kc];
                 const int ne_up = std::max(ne_of(B.la + 1, B.lb), ne_of(Kc.la + 1, Kc.lb));
                 const double need = (double)B.recs.size() * (double)Kc.recs.size() * (double)ne_up * (double)std::max(B.ne, Kc.ne);
-                WORK_DOUBLES = (size_t)std::min<double>((double)cap, std::max<double>((double)WORK_DOUBLES, need));
+                G.work_doubles = (size_t)std::min<double>((double)cap, std::max<double>((double)G.work_doubles, need));
             }
     }
-    Scratch scr_wp, scr_wm, scr_gtasks, scr_live;
-    if (scr_wp.ensure(c->device, SCR_GRAD_WP, sizeof(double) * WORK_DOUBLES) || scr_wm.ensure(c->device, SCR_GRAD_WM, sizeof(double) * WORK_DOUBLES)) return -1;
-    double *d_wp = (double *)scr_wp.p, *d_wm = (double *)scr_wm.p;
-    uint32_t *d_comp_p = nullptr, *d_comp_m = nullptr;
-    HIPCHK(dev_malloc(&d_comp_p, sizeof(uint32_t) * 16384));
-    HIPCHK(dev_malloc(&d_comp_m, sizeof(uint32_t) * 16384));
-    int64_t *d_prefix = nullptr;
-    size_t prefix_cap = 0;
-    TaskIdx *d_tasks = nullptr, *d_live_tasks = nullptr;
-    size_t tasks_cap = 0, live_tasks_cap = 0, live_cap = 0;
-    int *d_live_counts = nullptr;
-    int64_t *d_live_off = nullptr;
-    const double tol = c->tol;
-    int64_t batch_counter = 0;
+    if (G.scr_wp.ensure(c->device, SCR_GRAD_WP, sizeof(double) * G.work_doubles) || G.scr_wm.ensure(c->device, SCR_GRAD_WM, sizeof(double) * G.work_doubles)) return -1;
+    HIPCHK(G.d_comp_p.alloc(COMP_CAP));
+    HIPCHK(G.d_comp_m.alloc(COMP_CAP));
     for (int bc = 0; bc < NPC; bc++)
         for (int kc = 0; kc <= bc; kc++) {
             PairClass &B = c->pc[bc], &Kc = c->pc[kc];
             if (B.recs.empty() || Kc.recs.empty()) continue;
-            std::vector<int64_t> prefix;
-            const int64_t ntask = class_prefix(B, Kc, bc == kc, tol, prefix);
-            if (ntask == 0) continue;
-            if (prefix.size() > prefix_cap) {
-                if (d_prefix) dev_free(d_prefix);
-                prefix_cap = prefix.size() * 2;
-                HIPCHK(dev_malloc(&d_prefix, sizeof(int64_t) * prefix_cap));
-            }
-            HIPCHK(hipMemcpyAsync(d_prefix, prefix.data(), sizeof(int64_t) * prefix.size(), hipMemcpyHostToDevice, st));
-            const TaskIdx *tasks_dev = nullptr;
-            const bool live_ok = d_dmax && c->opt_grad_live && ntask >= 4096 && ntask <= ((int64_t)1 << 28);   // see ensure_live below
-            if (c->opt_task_table && ntask >= 65536 && ntask <= ((int64_t)1 << 28) && !live_ok) {   // up to 3 permutations x 3 launches walk this task list
-                if ((size_t)ntask > tasks_cap) {
-                    if (scr_gtasks.ensure(c->device, SCR_GRAD_TASKS, sizeof(TaskIdx) * (size_t)ntask)) return -1;
-                    d_tasks = (TaskIdx *)scr_gtasks.p;
-                    tasks_cap = scr_gtasks.bytes / sizeof(TaskIdx);
-                }
-                hipLaunchKernelGGL(fill_tasks_kernel, dim3((unsigned)((ntask + 255) / 256)), dim3(256), 0, st, d_prefix, (int)B.recs.size(), ntask, d_tasks);
-                tasks_dev = d_tasks;
-            }
-            HIPCHK(hipStreamSynchronize(st));
-            // wave-per-quartet launches of this class walk the list of LIVE quartets (density-weighted screening done once, see
-            // live_fill_kernel); built on first need -- classes wholly on the thread-per-quartet path never ask for it
-            int64_t nlive = -1;
-            auto ensure_live = [&]() -> int {
-                // (lists beyond 2^28 quartets -- 2 GB -- are not built: those launches screen per wave as before)
-                if (nlive >= 0 || !live_ok) return 0;
-                const int nblk = (int)((ntask + 255) / 256);
-                if ((size_t)nblk + 1 > live_cap) {
-                    if (d_live_counts) dev_free(d_live_counts);
-                    if (d_live_off) dev_free(d_live_off);
-                    live_cap = (size_t)nblk + 1 + (size_t)nblk / 4;
-                    HIPCHK(dev_malloc(&d_live_counts, sizeof(int) * live_cap));
-                    HIPCHK(dev_malloc(&d_live_off, sizeof(int64_t) * live_cap));
-                }
-                if ((size_t)ntask > live_tasks_cap) {
-                    if (scr_live.ensure(c->device, SCR_GRAD_LIVE, sizeof(TaskIdx) * (size_t)ntask)) return -1;
-                    d_live_tasks = (TaskIdx *)scr_live.p;
-                    live_tasks_cap = scr_live.bytes / sizeof(TaskIdx);
-                }
-                LiveArgs L{B.d_recs, Kc.d_recs, d_prefix, (int)B.recs.size(), ntask, B.d_q, Kc.d_q, d_dmax, c->nbas, hyb, c->opt_grad_dtol};
-                hipLaunchKernelGGL(live_count_kernel, dim3(nblk), dim3(256), 0, st, L, d_live_counts);
-                hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, st, d_live_counts, nblk, d_live_off);
-                hipLaunchKernelGGL(live_fill_kernel, dim3(nblk), dim3(256), 0, st, L, d_live_off, d_live_tasks);
-                HIPCHK(hipGetLastError());
-                int64_t n = 0;
-                HIPCHK(hipMemcpyAsync(&n, d_live_off + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                nlive = n;
-                if (getenv("MI355_DEBUG"))
-                    fprintf(stderr, "[mi355] grad class pair (%d%d|%d%d): %ld of %ld quartets live\n", B.la, B.lb, Kc.la, Kc.lb, (long)nlive, (long)ntask);
-                return 0;
-            };
-            // perm 0 (derivative on P.sh_i, the costliest: highest l) is skipped: sum of the four forces = 0
-            for (int perm = 1; perm < 4; perm++) {
-                const bool swap = perm >= 2;
-                const int orient = perm & 1;
-                PairClass &Dc = swap ? Kc : B;   // class of the differentiated pair
-                PairClass &Oc = swap ? B : Kc;   // class of the other pair (plain ket)
-                const int l1 = orient == 0 ? Dc.la : Dc.lb, l2 = orient == 0 ? Dc.lb : Dc.la;
-                const int lc = Oc.la, ldd = Oc.lb;
-                if (c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= 32768) {   // low classes, shallow contraction: thread per (quartet, permutation)
-                    TpqGradArgs Q{};
-                    Q.dplus = Dc.d_g_recs[orient][0]; Q.dminus = l1 >= 1 ? Dc.d_g_recs[orient][1] : nullptr; Q.ket = Oc.d_recs;
-                    Q.prim = c->d_prim; Q.prefix = d_prefix; Q.nbra = (int)B.recs.size();
-                    // this rank's contiguous share of the task list (the compacted live list when the class has a kernel)
-                    const bool has_tpq = tpq_grad_has_class(l1, l2, lc, ldd);
-                    if (has_tpq && ensure_live()) return -1;
-                    const bool live_q = has_tpq && nlive >= 0;
-                    const int64_t nt_q = live_q ? nlive : ntask;
-                    const int64_t lo_t = nt_q * rank / nranks, hi_t = nt_q * (rank + 1) / nranks;
-                    Q.t0 = lo_t; Q.ntask = hi_t - lo_t;
-                    Q.tasks = live_q ? d_live_tasks : nullptr;
-                    Q.swap = swap ? 1 : 0; Q.same_class = (bc == kc);
-                    Q.c2s = c->d_c2s;
-                    for (int q = 0; q <= LMAX + 1; q++) Q.c2s_off[q] = c->c2s_off[q];
-                    Q.rys = c->rys; Q.shell_xyz = c->d_shell_xyz; Q.D = c->d_Dpad; Q.Dm = d_Mpad; Q.ld = c->ldp; Q.hyb = hyb;
-                    Q.shell_atom = d_shell_atom; Q.grad = d_gcopies; Q.natm3 = natm3; Q.inv_from_second = swap ? 0 : 1;
-                    Q.q_bra = Dc.d_q; Q.q_ket = Oc.d_q; Q.dmax = live_q ? nullptr : d_dmax; Q.nbas_d = c->nbas; Q.dtol = c->opt_grad_dtol;
-                    const bool dbg1 = getenv("MI355_DEBUG") != nullptr;
-                    auto tq0 = std::chrono::steady_clock::now();
-                    if (dbg1) hipStreamSynchronize(st);
-                    const int used = launch_eri_tpq_grad(l1, l2, lc, ldd, Q, st);
-                    if (used < 0) return -1;
-                    if (used) {
-                        if (dbg1) {
-                            hipStreamSynchronize(st);
-                            fprintf(stderr, "[mi355] grad class (%d%d|%d%d) perm %d: %ld quartets, %.3f s (thread per quartet)\n", l1, l2, lc, ldd, perm,
-                                    (long)ntask, std::chrono::duration<double>(std::chrono::steady_clock::now() - tq0).count());
-                        }
-                        continue;
-                    }
-                }
-                if (ensure_live()) return -1;
-                const bool use_live = nlive >= 0;
-                if (use_live && nlive == 0) continue;
-                const int64_t ntask_w = use_live ? nlive : ntask;            // tasks the wave-per-quartet launches walk
-                const TaskIdx *tasks_w = use_live ? d_live_tasks : tasks_dev;
-                const double *dmax_w = use_live ? nullptr : d_dmax;          // the live list is already screened
-                EriArgs Ep{}, Em{};
-                setup_eri_dims(Ep, l1 + 1, l2, lc, ldd);
-                const bool has_m = l1 >= 1;
-                if (has_m) setup_eri_dims(Em, l1 - 1, l2, lc, ldd);
-                std::vector<uint32_t> comp;
-                build_comp_table(l1 + 1, l2, lc, ldd, comp);
-                if (comp.size() > 16384) return fail("component table too large");
-                HIPCHK(hipMemcpyAsync(d_comp_p, comp.data(), sizeof(uint32_t) * comp.size(), hipMemcpyHostToDevice, st));
-                HIPCHK(hipStreamSynchronize(st));
-                if (has_m) {
-                    build_comp_table(l1 - 1, l2, lc, ldd, comp);
-                    HIPCHK(hipMemcpyAsync(d_comp_m, comp.data(), sizeof(uint32_t) * comp.size(), hipMemcpyHostToDevice, st));
-                    HIPCHK(hipStreamSynchronize(st));
-                }
-                Ep.bra = Dc.d_g_recs[orient][0]; Ep.ket = Oc.d_recs; Ep.prim = c->d_prim; Ep.prefix = d_prefix; Ep.nbra = (int)B.recs.size();
-                Ep.comp = d_comp_p; Ep.work = d_wp; Ep.rys = c->rys; Ep.diag = 0; Ep.swap = swap ? 1 : 0;
-                if (has_m) {
-                    Em.bra = Dc.d_g_recs[orient][1]; Em.ket = Oc.d_recs; Em.prim = c->d_prim; Em.prefix = d_prefix; Em.nbra = Ep.nbra;
-                    Em.comp = d_comp_m; Em.work = d_wm; Em.rys = c->rys; Em.diag = 0; Em.swap = Ep.swap;
-                }
-                if (c->opt_grad_rows) {   // row kernel: no hand-over, one launch (see eri_grad_rows_kernel)
-                    const int ne_p = ne_of(l1 + 1, l2), ne_m = has_m ? ne_of(l1 - 1, l2) : 0, ne_all = ne_p + ne_m;
-                    GradRowsArgs R{};
-                    if (ne_all >= c->opt_grad_rows_min && launch_grad_rows(lc, ldd, ne_all, R, 0, st, true) == 1) {
-                        R.dplus = Dc.d_g_recs[orient][0]; R.dminus = has_m ? Dc.d_g_recs[orient][1] : nullptr; R.ket = Oc.d_recs;
-                        R.prim = c->d_prim; R.Mbuf = c->d_M; R.tasks = tasks_w; R.prefix = d_prefix; R.nbra = (int)B.recs.size();
-                        const int64_t lo_t = ntask_w * rank / nranks, hi_t = ntask_w * (rank + 1) / nranks;
-                        R.t0 = lo_t; R.ntask = hi_t - lo_t;
-                        R.swap = swap ? 1 : 0; R.same_class = (bc == kc);
-                        const RowsGeom gm = rows_geometry(ne_all);
-                        R.nmax = Ep.nmax; R.nroots = Ep.nroots; R.tsz = Ep.tsz; R.PB = std::max(1, gm.gsz / (3 * Ep.nroots));
-                        R.ne_p = ne_p; R.ne_m = ne_m; R.nsab = (2 * l1 + 1) * (2 * l2 + 1); R.ns2 = 2 * l2 + 1;
-                        R.comp_p = d_comp_p; R.comp_m = d_comp_m; R.rys = c->rys;
-                        R.D = c->d_Dpad; R.Dm = d_Mpad; R.ld = c->ldp; R.hyb = hyb; R.shell_atom = d_shell_atom; R.grad = d_gcopies; R.natm3 = natm3;
-                        R.inv_from_second = swap ? 0 : 1;
-                        R.q_bra = Dc.d_q; R.q_ket = Oc.d_q; R.dmax = dmax_w; R.nbas_d = c->nbas; R.dtol = c->opt_grad_dtol;
-                        const int nscd_ = Oc.nsab, nf_ = Oc.ne;
-                        const size_t shm_q = sizeof(double) * ((size_t)R.PB * R.nroots * 3 * R.tsz + (size_t)R.PB * 2 * R.nroots + (size_t)R.PB +
-                                                               (size_t)nscd_ * nf_ + (size_t)R.nsab * nscd_);
-                        if (R.ntask < ((int64_t)1 << 31)) {
-                            const bool dbgr = getenv("MI355_DEBUG") != nullptr;
-                            auto tr0 = std::chrono::steady_clock::now();
-                            if (dbgr) hipStreamSynchronize(st);
-                            const int used = R.ntask > 0 ? launch_grad_rows(lc, ldd, ne_all, R, shm_q, st) : 1;
-                            if (used < 0) return -1;
-                            if (used) {
-                                if (dbgr) {
-                                    hipStreamSynchronize(st);
-                                    fprintf(stderr, "[mi355] grad class (%d%d|%d%d) perm %d: %ld quartets, %.4f s (row kernel, %d rows x %d lanes)\n", l1, l2, lc,
-                                            ldd, perm, (long)ntask_w, std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count(), gm.rows, gm.gsz);
-                                }
-                                continue;
-                            }
-                        }
-                    }
-                }
-                Ep.tasks = Em.tasks = tasks_w;
-                Ep.prim_lds = Em.prim_lds = (c->opt_prim_lds && B.max_np + Kc.max_np <= 160) ? B.max_np + Kc.max_np : 0;
-                Ep.h_shared_np = B.mean_np; Ep.h_vary_mean = Kc.mean_np; Ep.h_vary_max4 = Kc.max4_np;
-                Em.h_shared_np = B.mean_np; Em.h_vary_mean = Kc.mean_np; Em.h_vary_max4 = Kc.max4_np;
-                Ep.q_bra = Dc.d_q; Ep.q_ket = Oc.d_q; Ep.dmax = dmax_w; Ep.nbas_d = c->nbas; Ep.dtol = c->opt_grad_dtol; Ep.hyb = hyb;
-                if (has_m) { Em.q_bra = Ep.q_bra; Em.q_ket = Ep.q_ket; Em.dmax = dmax_w; Em.nbas_d = c->nbas; Em.dtol = Ep.dtol; Em.hyb = hyb; }
-                GradXfArgs X{};
-                X.q_bra = Ep.q_bra; X.q_ket = Ep.q_ket; X.dmax = dmax_w; X.nbas_d = c->nbas; X.dtol = Ep.dtol;
-                X.dplus = Dc.d_g_recs[orient][0]; X.dminus = has_m ? Dc.d_g_recs[orient][1] : nullptr; X.ket = Oc.d_recs;
-                X.Mbuf = c->d_M; X.prefix = d_prefix; X.nbra = Ep.nbra; X.swap = Ep.swap; X.same_class = (bc == kc);
-                X.ne_p = ne_of(l1 + 1, l2); X.ne_m = has_m ? ne_of(l1 - 1, l2) : 0; X.nf = Oc.ne;
-                X.ns1 = 2 * l1 + 1; X.ns2 = 2 * l2 + 1; X.nscd = Oc.nsab; X.nsd = 2 * Oc.lb + 1;
-                X.work_p = d_wp; X.work_m = d_wm; X.ncomp_p = Ep.ncomp; X.ncomp_m = has_m ? Em.ncomp : 0;
-                X.D = c->d_Dpad; X.Dm = d_Mpad; X.ld = c->ldp; X.hyb = hyb; X.shell_atom = d_shell_atom; X.grad = d_gcopies; X.natm3 = natm3;
-                X.inv_from_second = swap ? 0 : 1;
-                X.tasks = tasks_w;
-                size_t shm = sizeof(double) * ((size_t)X.ne_p * X.nf + (size_t)X.ne_m * X.nf + (size_t)X.ns1 * X.ns2 * (X.nf + X.nscd));
-                if (shm > 160 * 1024) return fail("gradient contraction needs %zu bytes of LDS", shm);
-                const bool dbg = getenv("MI355_DEBUG") != nullptr;
-                auto tc0 = std::chrono::steady_clock::now();
-                if (dbg) hipStreamSynchronize(st);
-                int64_t per = std::min<int64_t>((int64_t)(WORK_DOUBLES / Ep.ncomp), (int64_t)1 << 23);
-                if (nranks > 1) per = std::min<int64_t>(per, std::max<int64_t>(1024, ntask_w / (8 * nranks)));
-                for (int64_t t0 = 0; t0 < ntask_w; t0 += per) {
-                    if ((int)((batch_counter++) % nranks) != rank) continue; // batches dealt round-robin to ranks
-                    int nb = (int)std::min<int64_t>(per, ntask_w - t0);
-                    Ep.t0 = t0; Ep.ntask = nb;
-                    if (launch_eri(c, Ep, nb, st)) return -1;
-                    if (has_m) { Em.t0 = t0; Em.ntask = nb; if (launch_eri(c, Em, nb, st)) return -1; }
-                    X.t0 = t0; X.nbatch = nb;
-                    const int big = std::max({X.ns1 * X.ns2 * X.nscd, X.ns1 * X.ns2 * X.nf, X.ns1 * X.ns2 * X.ne_p});
-                    if (big <= 48 && shm * 4 <= 64 * 1024) { // small classes: four quartets per wave (16 lanes each)
-                        hipLaunchKernelGGL((eri_grad_contract<16, false>), dim3((nb + 3) / 4), dim3(64), shm * 4, st, X);
-                    } else if (mfma_worthwhile(X.ns1 * X.ns2, X.nf, X.nscd) || mfma_worthwhile(X.ns1 * X.ns2, X.ne_p, X.nf) ||
-                               (has_m && mfma_worthwhile(X.ns1 * X.ns2, X.ne_m, X.nf))) {
-                        // (two or four waves sharing one quartet's LDS blocks -- eri_grad_contract<128|256, true> -- were measured at
-                        // -2 % / +8 %, the six density sub-blocks of G staged in LDS first at +2 %: the kernel is parked 70 % of its
-                        // wave cycles, but neither on a shortage of lanes nor on the G gather)
-                        if (shm > 64 * 1024)
-                            HIPCHK(hipFuncSetAttribute((const void *)eri_grad_contract<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-                        hipLaunchKernelGGL((eri_grad_contract<64, true>), dim3(nb), dim3(64), shm, st, X);
-                    } else {
-                        if (shm > 64 * 1024)
-                            HIPCHK(hipFuncSetAttribute((const void *)eri_grad_contract<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-                        hipLaunchKernelGGL((eri_grad_contract<64, false>), dim3(nb), dim3(64), shm, st, X);
-                    }
-                    HIPCHK(hipGetLastError());
-                }
-                if (dbg) {
-                    hipStreamSynchronize(st);
-                    fprintf(stderr, "[mi355] grad class (%d%d|%d%d) perm %d: %ld quartets, %.3f s\n", l1, l2, lc, ldd, perm, (long)ntask,
-                            std::chrono::duration<double>(std::chrono::steady_clock::now() - tc0).count());
-                }
-            }
+            if (grad_class_pair(G, B, Kc, bc == kc)) return -1;
         }
-    hipLaunchKernelGGL(grad_reduce_copies_kernel, dim3((natm3 + 63) / 64), dim3(64), 0, st, d_gcopies, natm3, d_grad);
+    hipLaunchKernelGGL(grad_reduce_copies_kernel, dim3((natm3 + 63) / 64), dim3(64), 0, st, G.d_gcopies.get(), natm3, d_grad);
     HIPCHK(hipStreamSynchronize(st));
-    dev_free(d_gcopies);
     if (getenv("MI355_DEBUG"))
         fprintf(stderr, "[mi355] grad_eri: variant records %.3f s, derivative quartets %.3f s\n",
                 std::chrono::duration<double>(tg1 - tg0).count(),
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - tg1).count());
-    if (d_prefix) dev_free(d_prefix);
-    if (d_live_counts) dev_free(d_live_counts);
-    if (d_live_off) dev_free(d_live_off);
-    dev_free(d_comp_p); dev_free(d_comp_m); dev_free(d_shell_atom);   // (the Scratch handles go back to the per-device cache)
-    if (d_dmax) dev_free(d_dmax);
-    if (d_Mpad) dev_free(d_Mpad);
-    if (d_sh_ao) dev_free(d_sh_ao);
-    if (d_sh_n) dev_free(d_sh_n);
-    return 0;
+    return 0;   // (the buffers of G go back to the pool, its Scratch handles to the per-device cache)
+}
+
+extern "C" int mi_grad_eri(mi_ctx *c, const double *d_D, double hyb, double *d_grad, void *stream)
+{
+    return c ? mi_grad_eri_sharded(c, d_D, nullptr, hyb, d_grad, c->rank, c->nranks, stream) : fail("mi_grad_eri: null argument");
+}
+
+extern "C" int mi_grad_eri_spin(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, double *d_grad, void *stream)
+{
+    return c ? mi_grad_eri_sharded(c, d_D, d_Dspin, hyb, d_grad, c->rank, c->nranks, stream) : fail("mi_grad_eri: null argument");
 }
 
 // =================================================================================================
@@ -7350,130 +7561,75 @@ extern "C" int mi_df_grad(mi_ctx *c, mi_ctx *aux, const double *d_Z3, const doub
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     const int naux = aux->nao - 1, unit_ao = aux->nao - 1, nP = aux->nbas - 1, nao = c->nao;
-    std::vector<std::vector<double>> c2s(LMAX + 1);
-    for (int l = 0; l <= LMAX; l++) c2s_generic(l, c2s[l]);
     std::vector<double> prim, Mbuf;
     // variant records: orbital pairs [class][orientation][l+1 | l-1] (parallel arrays), auxiliary pairs [l][l+1 | l-1]; plain auxiliary kets [l]
     std::vector<PairRec> orb[NPC][2][2], axv[LMAX + 1][2], axk[LMAX + 1];
-    // pass 1 (serial): offsets of every variant record; pass 2 (OpenMP): primitive records and HRR x derivative x c2s matrices
-    struct Job { const ShellH *I, *J; PairRec *R; int sign; };
-    std::vector<Job> jobs;
-    size_t prim_end = 0, m_end = 0;
-    auto add_variant = [&](const ShellH &I, const ShellH &J, int s1, int s2, int ao1, int ao2, int sign, PairRec &R) {
-        double r2 = 0.0;
-        for (int d = 0; d < 3; d++) r2 += (I.r[d] - J.r[d]) * (I.r[d] - J.r[d]);
-        int np = 0;
-        for (int ip = 0; ip < I.nprim; ip++)
-            for (int jp = 0; jp < J.nprim; jp++)
-                if (I.exps[ip] * J.exps[jp] / (I.exps[ip] + J.exps[jp]) * r2 <= 80.0) np++;
-        R = PairRec{s1, s2, ao1, ao2, (int)prim_end, np, (int)m_end, 0};
-        prim_end += np;
-        m_end += (size_t)3 * (2 * I.l + 1) * (2 * J.l + 1) * ne_of(I.l + sign, J.l);
-    };
-    auto fill_variant = [&](const Job &jb) {
-        const ShellH &I = *jb.I, &J = *jb.J;
-        double AB[3] = {I.r[0] - J.r[0], I.r[1] - J.r[1], I.r[2] - J.r[2]};
-        double r2 = AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2];
-        double *dst = prim.data() + (size_t)jb.R->prim_off * 8;
-        for (int ip = 0; ip < I.nprim; ip++)
-            for (int jp = 0; jp < J.nprim; jp++) {
-                double a = I.exps[ip], b = J.exps[jp], p = a + b, mu = a * b / p;
-                if (mu * r2 > 80.0) continue;
-                double K = I.coef[ip] * J.coef[jp] * std::exp(-mu * r2) * (jb.sign > 0 ? 2.0 * a : 1.0), Pc[3];
-                for (int d = 0; d < 3; d++) Pc[d] = (a * I.r[d] + b * J.r[d]) / p;
-                double rec[8] = {p, Pc[0], Pc[1], Pc[2], Pc[0] - I.r[0], Pc[1] - I.r[1], Pc[2] - I.r[2], K};
-                memcpy(dst, rec, sizeof rec);
-                dst += 8;
-            }
-        build_M_deriv(I.l, J.l, jb.sign, AB, c2s[I.l], c2s[J.l], Mbuf.data() + jb.R->m_off);
-    };
+    VariantRecords V(0, 0);
     if (d_Z3)
         for (int A = 0; A < c->nbas; A++)
             for (int B = 0; B <= A; B++) {
                 int si = A, sj = B;
                 if (c->shells[si].l < c->shells[sj].l) std::swap(si, sj);
                 const ShellH &I = c->shells[si], &J = c->shells[sj];
-                double r2 = 0.0;
-                for (int d = 0; d < 3; d++) r2 += (I.r[d] - J.r[d]) * (I.r[d] - J.r[d]);
-                bool any = false;
-                for (int ip = 0; ip < I.nprim && !any; ip++)
-                    for (int jp = 0; jp < J.nprim; jp++)
-                        if (I.exps[ip] * J.exps[jp] / (I.exps[ip] + J.exps[jp]) * r2 <= 80.0) { any = true; break; }
-                if (!any) continue;
+                if (count_prim_pairs(I, J) == 0) continue;
                 const int q = pc_index(I.l, J.l);
                 for (int o = 0; o < 2; o++) {
                     const ShellH &F = o == 0 ? I : J, &S = o == 0 ? J : I;
-                    const int s1 = o == 0 ? si : sj, s2 = o == 0 ? sj : si;
-                    for (int sg = 0; sg < 2; sg++) {
-                        PairRec R{-1, -1, 0, 0, 0, 0, 0, 0};
-                        if (F.l + (sg == 0 ? 1 : -1) >= 0) add_variant(F, S, s1, s2, F.ao_nat, S.ao_nat, sg == 0 ? +1 : -1, R);
-                        orb[q][o][sg].push_back(R);
-                    }
+                    PairRec R[2];
+                    V.add_pair(F, S, o == 0 ? si : sj, o == 0 ? sj : si, F.ao_nat, S.ao_nat, R);
+                    for (int sg = 0; sg < 2; sg++) orb[q][o][sg].push_back(R[sg]);
                 }
             }
     for (int Pn = 0; Pn < nP; Pn++) {
         const ShellH &S = aux->shells[Pn];
-        for (int sg = 0; sg < 2; sg++) {
-            PairRec R{-1, -1, 0, 0, 0, 0, 0, 0};
-            if (S.l + (sg == 0 ? 1 : -1) >= 0) add_variant(S, U, Pn, aux->nbas - 1, S.ao_nat, unit_ao, sg == 0 ? +1 : -1, R);
-            axv[S.l][sg].push_back(R);
-        }
-        PairRec R{Pn, aux->nbas - 1, S.ao_nat, unit_ao, (int)prim_end, S.nprim, (int)m_end, 0};     // plain ket record (filled below)
-        prim_end += S.nprim;
-        m_end += (size_t)(2 * S.l + 1) * ncart(S.l);
+        PairRec Rv[2];
+        V.add_pair(S, U, Pn, aux->nbas - 1, S.ao_nat, unit_ao, Rv);
+        for (int sg = 0; sg < 2; sg++) axv[S.l][sg].push_back(Rv[sg]);
+        PairRec R{Pn, aux->nbas - 1, S.ao_nat, unit_ao, (int)V.prim_end, S.nprim, (int)V.m_end, 0};     // plain ket record (filled below)
+        V.prim_end += S.nprim;
+        V.m_end += (size_t)(2 * S.l + 1) * ncart(S.l);
         axk[S.l].push_back(R);
     }
-    if (m_end > (size_t)INT32_MAX || prim_end > (size_t)INT32_MAX) return fail("mi_df_grad: record buffers exceed 2^31 entries");
-    prim.resize(prim_end * 8);
-    Mbuf.resize(m_end);
-    for (int q = 0; q < NPC; q++)
-        for (int o = 0; o < 2; o++)
-            for (int sg = 0; sg < 2; sg++)
-                for (PairRec &R : orb[q][o][sg])
-                    if (R.sh_i >= 0) jobs.push_back({&c->shells[R.sh_i], &c->shells[R.sh_j], &R, sg == 0 ? +1 : -1});
-    for (int l = 0; l <= LMAX; l++)
-        for (int sg = 0; sg < 2; sg++)
-            for (PairRec &R : axv[l][sg])
-                if (R.sh_i >= 0) jobs.push_back({&aux->shells[R.sh_i], &U, &R, sg == 0 ? +1 : -1});
-#pragma omp parallel for schedule(dynamic, 64) num_threads(host_threads())
-    for (size_t q = 0; q < jobs.size(); q++) fill_variant(jobs[q]);
-    for (int l = 0; l <= LMAX; l++)
-        for (PairRec &R : axk[l]) {
-            const ShellH &S = aux->shells[R.sh_i];
-            for (int ip = 0; ip < S.nprim; ip++) {
-                double rec[8] = {S.exps[ip], S.r[0], S.r[1], S.r[2], 0.0, 0.0, 0.0, S.coef[ip] * U.coef[0]};
-                memcpy(prim.data() + ((size_t)R.prim_off + ip) * 8, rec, sizeof rec);
+    if (V.m_end > (size_t)INT32_MAX || V.prim_end > (size_t)INT32_MAX) return fail("mi_df_grad: record buffers exceed 2^31 entries");
+    prim.resize(V.prim_end * 8);
+    Mbuf.resize(V.m_end);
+    V.fill(prim, Mbuf);
+    {
+        const std::vector<std::vector<double>> c2s = c2s_tables();
+        for (int l = 0; l <= LMAX; l++)
+            for (PairRec &R : axk[l]) {
+                const ShellH &S = aux->shells[R.sh_i];
+                write_aux_prims(S, U, prim.data() + (size_t)R.prim_off * 8);
+                double AB[3] = {0.0, 0.0, 0.0};
+                build_M(S.l, 0, AB, c2s[S.l], c2s[0], Mbuf.data() + R.m_off);
             }
-            double AB[3] = {0.0, 0.0, 0.0};
-            build_M(S.l, 0, AB, c2s[S.l], c2s[0], Mbuf.data() + R.m_off);
-        }
+    }
     std::vector<int> atom_o(c->nbas), atom_a(aux->nbas);
     for (int i = 0; i < c->nbas; i++) atom_o[i] = c->shells[i].atom;
     for (int i = 0; i < aux->nbas; i++) atom_a[i] = aux->shells[i].atom;
-    double *d_prim = nullptr, *d_M = nullptr, *d_wp = nullptr, *d_wm = nullptr, *d_gcopies = nullptr;
-    uint32_t *d_comp_p = nullptr, *d_comp_m = nullptr;
-    int64_t *d_prefix = nullptr;
-    int *d_atom_o = nullptr, *d_atom_a = nullptr;
-    PairRec *d_orb[NPC][2][2] = {}, *d_axv[LMAX + 1][2] = {}, *d_axk[LMAX + 1] = {};
-    if (upload(&d_prim, prim) || upload(&d_M, Mbuf) || upload(&d_atom_o, atom_o) || upload(&d_atom_a, atom_a)) return -1;
+    DevBuf<double> d_prim, d_M, d_wp, d_wm, d_gcopies;
+    DevBuf<uint32_t> d_comp_p, d_comp_m;
+    DevBuf<int64_t> d_prefix;
+    DevBuf<int> d_atom_o, d_atom_a;
+    DevBuf<PairRec> d_orb[NPC][2][2], d_axv[LMAX + 1][2], d_axk[LMAX + 1];
+    if (d_prim.upload(prim) || d_M.upload(Mbuf) || d_atom_o.upload(atom_o) || d_atom_a.upload(atom_a)) return -1;
     for (int q = 0; q < NPC; q++)
         for (int o = 0; o < 2; o++)
             for (int sg = 0; sg < 2; sg++)
-                if (!orb[q][o][sg].empty() && upload(&d_orb[q][o][sg], orb[q][o][sg])) return -1;
+                if (!orb[q][o][sg].empty() && d_orb[q][o][sg].upload(orb[q][o][sg])) return -1;
     for (int l = 0; l <= LMAX; l++) {
         for (int sg = 0; sg < 2; sg++)
-            if (!axv[l][sg].empty() && upload(&d_axv[l][sg], axv[l][sg])) return -1;
-        if (!axk[l].empty() && upload(&d_axk[l], axk[l])) return -1;
+            if (!axv[l][sg].empty() && d_axv[l][sg].upload(axv[l][sg])) return -1;
+        if (!axk[l].empty() && d_axk[l].upload(axk[l])) return -1;
     }
     const size_t WORK_DOUBLES = (size_t)32 << 20;
-    HIPCHK(dev_malloc(&d_wp, sizeof(double) * WORK_DOUBLES));
-    HIPCHK(dev_malloc(&d_wm, sizeof(double) * WORK_DOUBLES));
-    HIPCHK(dev_malloc(&d_comp_p, sizeof(uint32_t) * 16384));
-    HIPCHK(dev_malloc(&d_comp_m, sizeof(uint32_t) * 16384));
+    HIPCHK(d_wp.alloc(WORK_DOUBLES));
+    HIPCHK(d_wm.alloc(WORK_DOUBLES));
+    HIPCHK(d_comp_p.alloc(COMP_CAP));
+    HIPCHK(d_comp_m.alloc(COMP_CAP));
     const int natm3 = c->natm * 3;
-    HIPCHK(dev_malloc(&d_gcopies, sizeof(double) * (size_t)GRAD_COPIES * natm3));
+    HIPCHK(d_gcopies.alloc((size_t)GRAD_COPIES * natm3));
     HIPCHK(hipMemsetAsync(d_gcopies, 0, sizeof(double) * (size_t)GRAD_COPIES * natm3, st));
-    size_t prefix_cap = 0;
     int64_t batch_counter = 0;
     const bool dbg = getenv("MI355_DEBUG") != nullptr;
     // one pass: differentiated pairs `dp`/`dm` (l1 first, l2 second) against the auxiliary kets of angular momentum lk
@@ -7482,34 +7638,14 @@ extern "C" int mi_df_grad(mi_ctx *c, mi_ctx *aux, const double *d_Z3, const doub
         const int nket = (int)axk[lk].size();
         if (nbra == 0 || nket == 0) return 0;
         const auto tr0 = std::chrono::steady_clock::now();
-        std::vector<int64_t> prefix(nbra + 1);
-        for (int b = 0; b <= nbra; b++) prefix[b] = (int64_t)b * nket;
-        const int64_t ntask = prefix.back();
-        append_coarse_index(prefix);
-        if (prefix.size() > prefix_cap) {
-            if (d_prefix) dev_free(d_prefix);
-            prefix_cap = prefix.size() * 2;
-            HIPCHK(dev_malloc(&d_prefix, sizeof(int64_t) * prefix_cap));
-        }
-        HIPCHK(hipMemcpyAsync(d_prefix, prefix.data(), sizeof(int64_t) * prefix.size(), hipMemcpyHostToDevice, st));
+        std::vector<int64_t> prefix;
+        const int64_t ntask = dense_prefix(nbra, nket, prefix);
+        if (prefix_to_device(prefix, d_prefix, st)) return -1;
         const bool has_m = l1 >= 1;
-        EriArgs Ep{}, Em{};
-        setup_eri_dims(Ep, l1 + 1, l2, lk, 0);
-        if (has_m) setup_eri_dims(Em, l1 - 1, l2, lk, 0);
-        std::vector<uint32_t> comp;
-        build_comp_table(l1 + 1, l2, lk, 0, comp);
-        if (comp.size() > 16384) return fail("component table too large");
-        HIPCHK(hipMemcpyAsync(d_comp_p, comp.data(), sizeof(uint32_t) * comp.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (has_m) {
-            build_comp_table(l1 - 1, l2, lk, 0, comp);
-            HIPCHK(hipMemcpyAsync(d_comp_m, comp.data(), sizeof(uint32_t) * comp.size(), hipMemcpyHostToDevice, st));
-            HIPCHK(hipStreamSynchronize(st));
-        }
-        Ep.bra = dp; Ep.ket = d_axk[lk]; Ep.prim = d_prim; Ep.prefix = d_prefix; Ep.nbra = nbra; Ep.comp = d_comp_p; Ep.work = d_wp;
-        Ep.rys = c->rys; Ep.diag = 0;
-        if (has_m) { Em.bra = dm; Em.ket = d_axk[lk]; Em.prim = d_prim; Em.prefix = d_prefix; Em.nbra = nbra; Em.comp = d_comp_m; Em.work = d_wm;
-                     Em.rys = c->rys; Em.diag = 0; }
+        if (upload_comp_table(l1 + 1, l2, lk, 0, d_comp_p, st)) return -1;
+        if (has_m && upload_comp_table(l1 - 1, l2, lk, 0, d_comp_m, st)) return -1;
+        EriArgs Ep = eri_class_args(c, l1 + 1, l2, lk, 0, dp, d_axk[lk], d_prim, d_prefix, nbra, d_comp_p, d_wp), Em{};
+        if (has_m) Em = eri_class_args(c, l1 - 1, l2, lk, 0, dm, d_axk[lk], d_prim, d_prefix, nbra, d_comp_m, d_wm);
         GradXfArgs X{};
         X.dplus = dp; X.dminus = has_m ? dm : nullptr; X.ket = d_axk[lk]; X.Mbuf = d_M; X.prefix = d_prefix; X.nbra = nbra;
         X.ne_p = ne_of(l1 + 1, l2); X.ne_m = has_m ? ne_of(l1 - 1, l2) : 0; X.nf = ncart(lk);
@@ -7521,8 +7657,6 @@ extern "C" int mi_df_grad(mi_ctx *c, mi_ctx *aux, const double *d_Z3, const doub
         if (shm > 160 * 1024) return fail("gradient contraction needs %zu bytes of LDS", shm);
         int64_t per = std::min<int64_t>((int64_t)(WORK_DOUBLES / Ep.ncomp), (int64_t)1 << 22);
         if (nranks > 1) per = std::min<int64_t>(per, std::max<int64_t>(1024, ntask / (8 * nranks)));
-        const bool mf = mfma_worthwhile(X.ns1 * X.ns2, X.nf, X.nscd) || mfma_worthwhile(X.ns1 * X.ns2, X.ne_p, X.nf) ||
-                        (has_m && mfma_worthwhile(X.ns1 * X.ns2, X.ne_m, X.nf));
         for (int64_t t0 = 0; t0 < ntask; t0 += per) {
             if ((int)((batch_counter++) % nranks) != rank) continue;
             const int nb = (int)std::min<int64_t>(per, ntask - t0);
@@ -7530,16 +7664,7 @@ extern "C" int mi_df_grad(mi_ctx *c, mi_ctx *aux, const double *d_Z3, const doub
             if (launch_eri(c, Ep, nb, st)) return -1;
             if (has_m) { Em.t0 = t0; Em.ntask = nb; if (launch_eri(c, Em, nb, st)) return -1; }
             X.t0 = t0; X.nbatch = nb;
-            if (mf) {
-                if (shm > 64 * 1024)
-                    HIPCHK(hipFuncSetAttribute((const void *)eri_grad_contract<64, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-                hipLaunchKernelGGL((eri_grad_contract<64, true, true>), dim3(nb), dim3(64), shm, st, X);
-            } else {
-                if (shm > 64 * 1024)
-                    HIPCHK(hipFuncSetAttribute((const void *)eri_grad_contract<64, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-                hipLaunchKernelGGL((eri_grad_contract<64, false, true>), dim3(nb), dim3(64), shm, st, X);
-            }
-            HIPCHK(hipGetLastError());
+            if (launch_grad_contract(true, X, has_m, nb, shm, st)) return -1;
         }
         HIPCHK(hipStreamSynchronize(st));
         if (dbg)
@@ -7562,19 +7687,9 @@ extern "C" int mi_df_grad(mi_ctx *c, mi_ctx *aux, const double *d_Z3, const doub
             for (int lk = 0; lk <= LMAX && !rc; lk++)
                 rc = run(d_axv[lp][0], d_axv[lp][1], (int)axv[lp][0].size(), lp, 0, lk, d_Z2, (int64_t)naux, 0, d_atom_a, 1.0);
     if (!rc) {
-        hipLaunchKernelGGL(grad_reduce_copies_kernel, dim3((natm3 + 63) / 64), dim3(64), 0, st, d_gcopies, natm3, d_grad);
+        hipLaunchKernelGGL(grad_reduce_copies_kernel, dim3((natm3 + 63) / 64), dim3(64), 0, st, d_gcopies.get(), natm3, d_grad);
         HIPCHK(hipStreamSynchronize(st));
     }
-    for (int q = 0; q < NPC; q++)
-        for (int o = 0; o < 2; o++)
-            for (int sg = 0; sg < 2; sg++) if (d_orb[q][o][sg]) dev_free(d_orb[q][o][sg]);
-    for (int l = 0; l <= LMAX; l++) {
-        for (int sg = 0; sg < 2; sg++) if (d_axv[l][sg]) dev_free(d_axv[l][sg]);
-        if (d_axk[l]) dev_free(d_axk[l]);
-    }
-    dev_free(d_prim); dev_free(d_M); dev_free(d_wp); dev_free(d_wm); dev_free(d_comp_p); dev_free(d_comp_m); dev_free(d_gcopies);
-    dev_free(d_atom_o); dev_free(d_atom_a);
-    if (d_prefix) dev_free(d_prefix);
     return rc;
 }
 
@@ -8732,8 +8847,8 @@ static int pcm_dispatch(mi_ctx *c, bool grad, PcmArgs &A, int npts, hipStream_t 
     pcm_pair_list(c, grad ? 1 : 0, pairs, cs);
     const int n = cs[16];
     if ((int64_t)n * A.nblk >= (int64_t)1 << 31) return fail("mi_pcm: %d shell pairs x %d point blocks exceed one launch", n, A.nblk);
-    int *d_pairs = nullptr;
-    HIPCHK(dev_malloc(&d_pairs, sizeof(int) * std::max<size_t>(pairs.size(), 2)));
+    DevBuf<int> d_pairs;
+    HIPCHK(d_pairs.alloc(std::max<size_t>(pairs.size(), 2)));
     HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(int) * pairs.size(), hipMemcpyHostToDevice, st));
     A.atm = c->d_atm; A.bas = c->d_bas; A.env = c->d_env; A.shell_ao = c->d_shell_ao; A.c2s = c->d_c2s;
     for (int i = 0; i <= LMAX + 1; i++) A.c2s_off[i] = c->c2s_off[i];
@@ -8746,7 +8861,6 @@ static int pcm_dispatch(mi_ctx *c, bool grad, PcmArgs &A, int npts, hipStream_t 
     hipError_t e = hipGetLastError();
     // the pair list is read by the launches above: the pool's dev_free synchronises the device before parking the block
     HIPCHK(hipStreamSynchronize(st));
-    dev_free(d_pairs);
     if (e != hipSuccess) return fail("mi_pcm: launch failed: %s", hipGetErrorString(e));
     return 0;
 }
