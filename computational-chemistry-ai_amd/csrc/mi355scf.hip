@@ -388,6 +388,7 @@ struct mi_ctx {
     RunRec *d_segs = nullptr;            // runs cut at wave boundaries
     int *d_wave_seg = nullptr;           // [nwaves+1] segment range of each wave
     int n_jk_waves = 0;
+    int n_jk_segs = 0;                   // J/K work items (entries of d_segs)
     int n_jk_cached = 0;                 // leading J/K work items kept in the Infinity Cache (default-policy loads)
     double *d_tiles = nullptr;
     int64_t tile_doubles = 0, tile_alloc = 0;
@@ -2746,6 +2747,7 @@ static int prepare_jk_segments(PrepareState &S)
     std::vector<RunRec> segs;
     std::vector<int> wave_seg;
     int nw, w = 0;
+    c->n_jk_cached = 0;   // (the cached prefix exists for the longest-first order only)
     if (c->opt_jk_waves <= 0) {
         for (const RunRec &r : c->runs)
             for (int t0 = 0; t0 < r.count; t0 += chunk) segs.push_back(RunRec{r.J, r.K, r.L, r.first + t0, std::min(chunk, r.count - t0)});
@@ -2759,7 +2761,6 @@ static int prepare_jk_segments(PrepareState &S)
         std::vector<RunRec> sorted(segs.size());
         for (size_t q = 0; q < segs.size(); q++) sorted[q] = segs[ord[q]];
         segs.swap(sorted);
-        c->n_jk_cached = 0;
         if (off * 8 > ((int64_t)256 << 20) && c->opt_jk_cache_mb > 0) {
             double acc_b = 0.0;
             const double lim = (double)c->opt_jk_cache_mb * 1048576.0;
@@ -2799,6 +2800,7 @@ static int prepare_jk_segments(PrepareState &S)
     }
     for (int x = w + 1; x <= nw; x++) wave_seg[x] = (int)segs.size();
     c->n_jk_waves = nw;
+    c->n_jk_segs = (int)segs.size();
     if (getenv("MI355_DEBUG")) {
         int mx = 0, mn = 1 << 30, maxseg = 0;
         for (int x = 0; x < nw; x++) {
@@ -3830,25 +3832,74 @@ __global__ void finalize_jk_kernel(const double *Jacc, const double *Kacc, doubl
 // cannot stay in the 256 MiB Infinity Cache between SCF cycles
 static bool jk_stream_nt(const mi_ctx *c) { return c->opt_jk_nt != 0 && (c->opt_jk_nt > 1 || c->tile_doubles * 8 > ((int64_t)256 << 20)); }
 
-static int launch_jk(mi_ctx *c, bool wj, bool wk, hipStream_t st)
+// Which J/K digestion kernel a build runs, and how: every decision of launch_jk / mi_build_jk lives here, and mi_jk_describe
+// reports the same record, so what a caller is told and what is launched cannot drift.
+enum JkFamily { JK_PLAIN = 0, JK_KJLT, JK_PIPE, JK_PAIR };
+struct JkPlan {
+    JkFamily family;
+    bool nt;     // nontemporal tile stream (work items below n_jk_cached keep the default policy where the kernel has that split)
+    bool dpp;    // per-tile reduce-scatters through DPP moves (the pipeline kernel only has the ds_bpermute form)
+};
+static JkPlan jk_plan(const mi_ctx *c, bool wj, bool wk, int n_dm)
 {
-    JkArgs A{c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg, c->n_jk_waves, c->d_Dpad, c->d_Jacc, c->d_Kacc, c->ldp, c->nao,
-             c->n_jk_cached, c->tri, (size_t)c->ldp * c->ldp, 0, c->opt_jk_dpp};
-    if (c->n_tiles == 0) return 0;
-    dim3 g(A.nruns), b(64);
-    const bool nt = jk_stream_nt(c);
+    const int64_t bytes = c->tile_doubles * 8;
+    JkPlan P{JK_PLAIN, jk_stream_nt(c), c->opt_jk_dpp != 0};
+    // one pass for the pair when it pays: measured -9 % on the 103 GB ibuprofen tensor (UHF cycle 38 -> 34.5 ms), -3 % ... +60 %
+    // (erratic) on the 4.9 GB benzene/cc-pVTZ tensor -- so by default only for stores beyond 16 GB (jk_pair = 1: always, 0: never)
+    if (n_dm == 2 && (c->opt_jk_pair > 0 || (c->opt_jk_pair < 0 && bytes > ((int64_t)16 << 30)))) { P.family = JK_PAIR; return P; }
     // the half-tile pipeline only exists for full-row tiles: with triangular rows (the default) the plain kernel is the faster
     // one on cache-resident tensors too (benzene/cc-pVDZ J+K 39.8 us vs 41.5 us for full rows + pipeline, 48 us for both)
-    const bool pipe = !c->tri && (c->opt_jk_pipe > 0 || (c->opt_jk_pipe < 0 && c->tile_doubles * 8 <= ((int64_t)256 << 20)));
-    if (pipe && wk) {
+    const bool pipe = !c->tri && (c->opt_jk_pipe > 0 || (c->opt_jk_pipe < 0 && bytes <= ((int64_t)256 << 20)));
+    if (pipe && wk) { P.family = JK_PIPE; P.dpp = false; if (!wj) P.nt = true; }   // (its K-only form is built with the nontemporal stream only)
+    else if (wj && wk && c->opt_jk_kjlt) P.family = JK_KJLT;
+    return P;
+}
+
+static int launch_jk_plan(mi_ctx *c, const JkPlan &P, bool wj, bool wk, hipStream_t st)
+{
+    const bool pair = P.family == JK_PAIR;
+    JkArgs A{c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg, c->n_jk_waves, c->d_Dpad, c->d_Jacc, c->d_Kacc, c->ldp, c->nao,
+             c->n_jk_cached, c->tri, (size_t)c->ldp * c->ldp, pair ? 1 : 0, P.dpp ? 1 : 0};
+    if (c->n_tiles == 0) return 0;
+    dim3 g(A.nruns), b(pair ? 128 : 64);
+    const bool nt = P.nt;
+    switch (P.family) {
+    case JK_PAIR:
+        // same cache policy as the single-density kernel: nontemporal stream + default-policy prefix for tensors beyond the
+        // Infinity Cache (an all-default-policy stream of 4.9 GB made the launch time erratic: 1.65 ... 2.75 ms)
+        if (wj && wk) { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<true, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<true, true, false>), g, b, 0, st, A); }
+        else if (wj) { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<true, false, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<true, false, false>), g, b, 0, st, A); }
+        else { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<false, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<false, true, false>), g, b, 0, st, A); }
+        break;
+    case JK_PIPE:
         if (wj) { if (nt) hipLaunchKernelGGL((jk_tiles_pipe_kernel<true, true, false>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pipe_kernel<true, false, false>), g, b, 0, st, A); }
         else hipLaunchKernelGGL((jk_tiles_pipe_kernel<false, true, false>), g, b, 0, st, A);
+        break;
+    case JK_KJLT:
+        if (nt) hipLaunchKernelGGL((jk_tiles_kjlt_kernel<true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kjlt_kernel<false>), g, b, 0, st, A);
+        break;
+    case JK_PLAIN:
+        if (wj && wk) { if (nt) hipLaunchKernelGGL((jk_tiles_kernel<true, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kernel<true, true, false>), g, b, 0, st, A); }
+        else if (wj) { if (nt) hipLaunchKernelGGL((jk_tiles_kernel<true, false, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kernel<true, false, false>), g, b, 0, st, A); }
+        else { if (nt) hipLaunchKernelGGL((jk_tiles_kernel<false, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kernel<false, true, false>), g, b, 0, st, A); }
+        break;
     }
-    else if (wj && wk && c->opt_jk_kjlt) { if (nt) hipLaunchKernelGGL((jk_tiles_kjlt_kernel<true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kjlt_kernel<false>), g, b, 0, st, A); }
-    else if (wj && wk) { if (nt) hipLaunchKernelGGL((jk_tiles_kernel<true, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kernel<true, true, false>), g, b, 0, st, A); }
-    else if (wj) { if (nt) hipLaunchKernelGGL((jk_tiles_kernel<true, false, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kernel<true, false, false>), g, b, 0, st, A); }
-    else { if (nt) hipLaunchKernelGGL((jk_tiles_kernel<false, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kernel<false, true, false>), g, b, 0, st, A); }
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int launch_jk(mi_ctx *c, bool wj, bool wk, hipStream_t st) { return launch_jk_plan(c, jk_plan(c, wj, wk, 1), wj, wk, st); }
+
+extern "C" int mi_jk_describe(const mi_ctx *c, int with_j, int with_k, int n_dm, char *buf, size_t len)
+{
+    if (!c || !buf || len == 0) return fail("mi_jk_describe: null argument");
+    if (!c->eri_ready) return fail("mi_jk_describe: call mi_eri_prepare first");
+    if ((!with_j && !with_k) || n_dm < 1) return fail("mi_jk_describe: bad argument");
+    static const char *const names[] = {"plain", "kjlt", "pipe", "pair"};
+    const JkPlan P = jk_plan(c, with_j != 0, with_k != 0, n_dm);
+    const int n = snprintf(buf, len, "family=%s nt=%d dpp=%d tri=%d waves=%d segments=%d n_jk_cached=%d", names[P.family], P.nt ? 1 : 0,
+                           P.dpp ? 1 : 0, c->tri, c->n_jk_waves, c->n_jk_segs, c->n_jk_cached);
+    if (n < 0 || (size_t)n >= len) return fail("mi_jk_describe: buffer of %zu bytes is too small", len);
     return 0;
 }
 
@@ -3860,23 +3911,12 @@ extern "C" int mi_build_jk(mi_ctx *c, const double *d_D, int n_dm, double *d_J, 
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     size_t nn = (size_t)c->nao * c->nao, pp = (size_t)c->ldp * c->ldp;
-    // one pass for the pair when it pays: measured -9 % on the 103 GB ibuprofen tensor (UHF cycle 38 -> 34.5 ms), -3 % ... +60 %
-    // (erratic) on the 4.9 GB benzene/cc-pVTZ tensor -- so by default only for stores beyond 16 GB (jk_pair = 1: always, 0: never)
-    const bool use_pair = c->opt_jk_pair > 0 || (c->opt_jk_pair < 0 && c->tile_doubles * 8 > ((int64_t)16 << 30));
-    if (n_dm == 2 && use_pair && c->n_tiles > 0) {
+    const JkPlan P = jk_plan(c, d_J != nullptr, d_K != nullptr, n_dm);
+    if (P.family == JK_PAIR && c->n_tiles > 0) {
         for (int m = 0; m < 2; m++)
             hipLaunchKernelGGL(pad_density_clear_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_D + m * nn, c->d_Dpad + m * pp,
                                d_J ? c->d_Jacc + m * pp : nullptr, d_K ? c->d_Kacc + m * pp : nullptr, c->nao, c->ldp, c->d_iperm);
-        JkArgs A{c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg, c->n_jk_waves, c->d_Dpad, c->d_Jacc, c->d_Kacc, c->ldp, c->nao,
-                 c->n_jk_cached, c->tri, pp, 1, c->opt_jk_dpp};
-        dim3 g(A.nruns), b(128);
-        // same cache policy as the single-density kernel: nontemporal stream + default-policy prefix for tensors beyond the
-        // Infinity Cache (an all-default-policy stream of 4.9 GB made the launch time erratic: 1.65 ... 2.75 ms)
-        const bool nt = jk_stream_nt(c);
-        if (d_J && d_K) { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<true, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<true, true, false>), g, b, 0, st, A); }
-        else if (d_J) { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<true, false, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<true, false, false>), g, b, 0, st, A); }
-        else { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<false, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<false, true, false>), g, b, 0, st, A); }
-        HIPCHK(hipGetLastError());
+        if (launch_jk_plan(c, P, d_J != nullptr, d_K != nullptr, st)) return -1;
         for (int m = 0; m < 2; m++)
             hipLaunchKernelGGL(finalize_jk_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, c->d_Jacc + m * pp, c->d_Kacc + m * pp,
                                d_J ? d_J + m * nn : nullptr, d_K ? d_K + m * nn : nullptr, c->nao, c->ldp, c->d_perm);

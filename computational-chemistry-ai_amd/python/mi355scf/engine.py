@@ -67,6 +67,7 @@ def lib():
         L.mi_eri_prepare.argtypes = [vp, ctypes.c_double, ctypes.c_int, ctypes.c_int, vp]
         L.mi_eri_get_stats.argtypes = [vp, ctypes.POINTER(_Stats)]
         L.mi_build_jk.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
+        L.mi_jk_describe.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
         L.mi_build_jk_multi.argtypes = [vp, vp, ctypes.c_int, ip, vp, vp, vp]
         L.mi_eri_unpack.argtypes = [vp, vp, vp]
         L.mi_eri_qtrans.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
@@ -303,6 +304,14 @@ class Engine:
             J = J[0] if with_j else None
             K = K[0] if with_k else None
         return J, K
+
+    def jk_describe(self, with_j=True, with_k=True, n_dm=1):
+        """What `get_jk` would run on the current store and options (mi_jk_describe; nothing is launched): dict with `family`
+        ("plain", "kjlt", "pipe", "pair") and the integers `nt`, `dpp`, `tri`, `waves`, `segments`, `n_jk_cached`."""
+        buf = ctypes.create_string_buffer(256)
+        _check(lib().mi_jk_describe(self._h, int(with_j), int(with_k), int(n_dm), buf, len(buf)))
+        d = dict(f.split("=", 1) for f in buf.value.decode().split())
+        return {k: (v if k == "family" else int(v)) for k, v in d.items()}
 
     def get_jk_multi(self, dms, sym, with_j=True, with_k=True):
         """J, K of a stack [n, N, N] of densities that are each symmetric (sym[m] = +1) or antisymmetric (-1), every resident

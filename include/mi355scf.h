@@ -52,6 +52,9 @@ void mi_release_cache(void);
  *   "runmax"      tiles per J/K work item (0 = auto)
  *   "jk_waves"    0 = one wave per work item, longest first; N > 0 = N waves with equal-cost contiguous shares
  *   "tri_tiles"   1 = block-diagonal tiles store triangular rows (default), 0 = full rows
+ *   "jk_cache_mb" MiB of tiles (the leading, longest work items; jk_waves = 0 only) read with the default cache policy when the
+ *                 tensor exceeds the Infinity Cache and the stream is nontemporal (default 160, 0 = none)
+ *   "ao_order", "ket_cluster"  tile AO order (1 = angular-momentum major, 0 = caller's) / ket order inside Schwarz clusters
  *   "xf_mfma_min" transform kernel: FP64-MFMA tiles for spherical blocks of at least this many elements
  *   "eri_tpq", "tpq_maxprim"  thread-per-quartet kernels for the low angular classes / their contraction-depth limit
  *   "omega"       > 0: the store holds long-range integrals (ij|erf(omega r12)/r12|kl) instead of (ij|kl) (range-separated
@@ -63,7 +66,6 @@ void mi_release_cache(void);
  *                 unchanged; mi_grad_eri*, mi_df_build and mi_df_grad refuse a context with omega != 0.  0 (default): full Coulomb.
  * Immediate:
  *   "jk_nt"       nontemporal loads for the tile stream (1 = when the tensor exceeds the Infinity Cache, 2 = always, 0 = never)
- *   "jk_cache_mb" MiB of tiles read with the default cache policy on such tensors (default 160)
  *   "jk_pipe"     half-tile software pipeline for full-row tiles (-1 auto)
  *   "jk_pair"     n_dm = 2: one pass with two waves per work item (-1 = for stores > 16 GB, 0 = one pass per density, 1 = always)
  *   "grad_dtol"   derivative quartets with q_ab q_cd max|G| below this are skipped (default 1e-13, 0 = Schwarz only)
@@ -154,6 +156,14 @@ int mi_eri_get_stats(const mi_ctx *ctx, mi_eri_stats *out);
  * Replaces: libcvhf CVHFnr_direct_drv with CVHFnrs8_ji_s2kl / CVHFnrs8_li_s2kj [MEM] / gpu4pyscf
  * RYS_build_jk [MEM], reached from get_jk / get_veff inside mf.kernel(). */
 int mi_build_jk(mi_ctx *ctx, const double *d_D, int n_dm, double *d_J, double *d_K, void *stream);
+
+/* Read-only description of what mi_build_jk(ctx, d_D, n_dm, with_j ? d_J : NULL, with_k ? d_K : NULL) would run on the current
+ * store and options (n_dm > 2 runs as n_dm builds of one density): a NUL-terminated line of space-separated key=value fields
+ *   family=plain|kjlt|pipe|pair  nt=0|1  dpp=0|1  tri=0|1  waves=<launched waves or wave pairs>  segments=<J/K work items>
+ *   n_jk_cached=<leading work items read with the default cache policy under nt=1>
+ * taken from the very function the launch consults.  Launches nothing and touches no GPU state; error before mi_eri_prepare or
+ * when `len` is too small (128 bytes suffice).  Project-defined (tests, tuning); no reference counterpart. */
+int mi_jk_describe(const mi_ctx *ctx, int with_j, int with_k, int n_dm, char *buf, size_t len);
 
 /* J and K of n_dm densities that are each symmetric or antisymmetric, with every resident tile read once per batch
  * (linear response: many trial densities against one store).  sym: host array [n_dm], sym[m] = +1 (symmetric: J and K) or
