@@ -22,6 +22,7 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <mutex>
 #include <map>
 #include <unordered_map>
@@ -3265,12 +3266,73 @@ extern "C" int mi_eri_get_stats(const mi_ctx *c, mi_eri_stats *out)
 // =================================================================================================
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
-struct JkArgs {
+// The resident tile store as its streaming kernels see it (J/K, batched J/K, quarter transformation): the first member of
+// their argument structs.  Workgroup b digests the work items wave_seg[b] .. wave_seg[b+1]-1; a work item is a segment of a
+// run (tiles sharing J, K, L, ordered by I >= J) with the directory entries first .. first+count-1.
+struct TileDir {
     const double *tiles;
     const int64_t *tile_off;
     const int *tile_I;
     const RunRec *runs;      // segments (runs cut at wave boundaries)
     const int *wave_seg;     // [nwaves+1]
+};
+static TileDir tile_dir(const mi_ctx *c) { return {c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg}; }
+
+// body(seg, std::bool_constant<nontemporal>) over the work items of blockIdx.x.  PREFIX: the first `n_cached` work items (the
+// longest segments) are read with the default cache policy, everything else with nontemporal loads: on a tensor larger than
+// the 256 MiB Infinity Cache the nontemporal stream does not evict them, so that share of the tiles is served on-die in every
+// SCF cycle after the first instead of from HBM.
+template <bool NT, bool PREFIX, class F>
+__device__ __forceinline__ void for_work_items(const TileDir &S, const int n_cached, F &&body)
+{
+    const MI_CONST_AS int *wave_seg = as_const(S.wave_seg);
+    const int seg_end = wave_seg[blockIdx.x + 1];
+    for (int seg = wave_seg[blockIdx.x]; seg < seg_end; seg++) {
+        if (NT && PREFIX && seg < n_cached) body(seg, std::false_type{});
+        else body(seg, std::bool_constant<NT>{});
+    }
+}
+
+// Run header of work item `seg`.  tri: triangular rows in block-diagonal tiles (tile geometry above).
+struct RunHead {
+    int J, first, count;
+    int J0, K0, L0;
+    int bk;                  // tiles are padded to 8 j-rows
+    bool dkl;                // K == L block diagonal: holds for the whole run or not at all
+};
+__device__ __forceinline__ RunHead run_head(const TileDir &S, const int seg, const int nao, const bool tri)
+{
+    const MI_CONST_AS RunRec *rr = as_const(S.runs) + seg;
+    const RunRec R{rr->J, rr->K, rr->L, rr->first, rr->count};
+    return {R.J, R.first, R.count, R.J * BLK, R.K * BLK, R.L * BLK, min(BLK, nao - R.K * BLK), tri && R.K == R.L};
+}
+
+// One tile of a run: directory entry -> geometry
+struct TileEntry { int I; int64_t off; };
+struct TileHead {
+    int I0, bi;
+    bool dij;                // I == J block diagonal: only the first tile of a run can lie on it
+    int64_t toff;
+};
+__device__ __forceinline__ TileEntry tile_entry(const TileDir &S, const int tid)
+{
+    return {as_const(S.tile_I)[tid], as_const(S.tile_off)[tid]};
+}
+__device__ __forceinline__ TileHead tile_head(const RunHead &R, const TileEntry e, const int nao, const bool tri)
+{
+    return {e.I * BLK, min(BLK, nao - e.I * BLK), tri && e.I == R.J, e.off};
+}
+// tile t of the run, whose entry was fetched into `next` one tile ago; the directory entry of tile t+1 is fetched while tile t
+// is being digested
+__device__ __forceinline__ TileHead tile_step(const TileDir &S, const RunHead &R, const int t, TileEntry &next, const int nao, const bool tri)
+{
+    const TileHead T = tile_head(R, next, nao, tri);
+    if (t + 1 < R.count) next = tile_entry(S, R.first + t + 1);
+    return T;
+}
+
+struct JkArgs {
+    TileDir dir;
     int nruns;               // number of waves
     const double *D; // padded [ldp][ldp]
     double *Jacc, *Kacc;
@@ -3362,16 +3424,15 @@ __device__ __forceinline__ d2_t jk_load_chunk(const d2_t *__restrict__ tile, int
 // one reduce-scatter over the i-lanes, one more 512-byte atomic) instead of living in 64 run-wide accumulators per lane: 128
 // registers less, which is what keeps the K-carrying kernel at one wave per SIMD.
 template <bool WITH_J, bool WITH_K, bool NT, bool DIJ, bool DKL, bool KJLT = false>
-__device__ __forceinline__ void jk_digest_tile(const JkArgs &A, const int lane, const int i, const int k, const int I0, const int J0,
-                                               const int K0, const int L0, const int ld, const int bk, const int64_t toff,
+__device__ __forceinline__ void jk_digest_tile(const JkArgs &A, const int lane, const int i, const int k, const RunHead &R, const TileHead &H,
                                                const double (&dKL)[8], const double (&dJK)[8], double (&kjl)[8][8], double (&jkl)[8],
                                                double (&kjk)[8])
 {
     const double *__restrict__ D = A.D;
     const MI_CONST_AS double *Du = as_const(A.D);
-    const int bi = min(BLK, A.nao - I0);
+    const int I0 = H.I0, J0 = R.J0, K0 = R.K0, L0 = R.L0, ld = A.ld, bi = H.bi, bk = R.bk;
     const bool active = (i < bi) && (k < bk);
-    const d2_t *__restrict__ T = reinterpret_cast<const d2_t *>(A.tiles + toff);
+    const d2_t *__restrict__ T = reinterpret_cast<const d2_t *>(A.dir.tiles + H.toff);
     double dIJ[8], dIL[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) dIJ[j] = D[(size_t)(I0 + i) * ld + J0 + j];
@@ -3426,82 +3487,35 @@ __device__ __forceinline__ void jk_digest_tile(const JkArgs &A, const int lane, 
     }
 }
 
-template <bool WITH_J, bool WITH_K, bool NT, bool PAIR = false, bool KJLT = false>
-__device__ __forceinline__ void jk_segment(const JkArgs &A, const int seg)
+// Run-wide state of one work item: the run-invariant density rows and the zeroed J_KL / K_JK / K_JL accumulators
+__device__ __forceinline__ void jk_run_begin(const double *__restrict__ D, const RunHead &R, const int ld, const int k, double (&dKL)[8],
+                                             double (&dJK)[8], double (&kjl)[8][8], double (&jkl)[8], double (&kjk)[8])
 {
-    const int lane = threadIdx.x & 63;
-    const int i = lane >> 3, k = lane & 7;
-    const MI_CONST_AS int *tile_I = as_const(A.tile_I);
-    const MI_CONST_AS int64_t *tile_off = as_const(A.tile_off);
-  {
-    const MI_CONST_AS RunRec *rr = as_const(A.runs) + seg;
-    const RunRec R{rr->J, rr->K, rr->L, rr->first, rr->count};
-    const int J0 = R.J * BLK, K0 = R.K * BLK, L0 = R.L * BLK;
-    const int ld = A.ld;
-    const int bk = min(BLK, A.nao - K0); // tiles are padded to 8 j-rows
-    const double *__restrict__ D = A.D;
-
-    // run-invariant density rows
-    double dKL[8], dJK[8];
 #pragma unroll
-    for (int l = 0; l < 8; l++) dKL[l] = D[(size_t)(K0 + k) * ld + L0 + l];
+    for (int l = 0; l < 8; l++) dKL[l] = D[(size_t)(R.K0 + k) * ld + R.L0 + l];
 #pragma unroll
-    for (int j = 0; j < 8; j++) dJK[j] = D[(size_t)(J0 + j) * ld + K0 + k];
-    double kjl[8][8], jkl[8], kjk[8];
+    for (int j = 0; j < 8; j++) dJK[j] = D[(size_t)(R.J0 + j) * ld + R.K0 + k];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         jkl[j] = 0.0; kjk[j] = 0.0;
 #pragma unroll
         for (int l = 0; l < 8; l++) kjl[j][l] = 0.0;
     }
+}
 
-    // the directory entry of tile t+1 is fetched while tile t is being digested
-    int I_next = tile_I[R.first];
-    int64_t off_next = tile_off[R.first];
-    int t = 0;
-    // only the first tile of a run can lie on the I == J diagonal (tiles of a run are ordered by I >= J); K == L holds for
-    // the whole run or not at all
-    if (A.tri && R.K == R.L) {
-        if (I_next == R.J) {
-            const int I0 = I_next * BLK;
-            const int64_t toff = off_next;
-            if (R.count > 1) { I_next = tile_I[R.first + 1]; off_next = tile_off[R.first + 1]; }
-            if (PAIR && A.pair_sync) __syncthreads();   // the two waves of a pair stay within one tile of each other: the second reader hits L2
-            jk_digest_tile<WITH_J, WITH_K, NT, true, true, KJLT>(A, lane, i, k, I0, J0, K0, L0, ld, bk, toff, dKL, dJK, kjl, jkl, kjk);
-            t = 1;
-        }
-        for (; t < R.count; t++) {
-            const int I0 = I_next * BLK;
-            const int64_t toff = off_next;
-            if (t + 1 < R.count) { I_next = tile_I[R.first + t + 1]; off_next = tile_off[R.first + t + 1]; }
-            if (PAIR && A.pair_sync) __syncthreads();   // the two waves of a pair stay within one tile of each other: the second reader hits L2
-            jk_digest_tile<WITH_J, WITH_K, NT, false, true, KJLT>(A, lane, i, k, I0, J0, K0, L0, ld, bk, toff, dKL, dJK, kjl, jkl, kjk);
-        }
-    } else {
-        if (A.tri && I_next == R.J) {
-            const int I0 = I_next * BLK;
-            const int64_t toff = off_next;
-            if (R.count > 1) { I_next = tile_I[R.first + 1]; off_next = tile_off[R.first + 1]; }
-            if (PAIR && A.pair_sync) __syncthreads();   // the two waves of a pair stay within one tile of each other: the second reader hits L2
-            jk_digest_tile<WITH_J, WITH_K, NT, true, false, KJLT>(A, lane, i, k, I0, J0, K0, L0, ld, bk, toff, dKL, dJK, kjl, jkl, kjk);
-            t = 1;
-        }
-        for (; t < R.count; t++) {
-            const int I0 = I_next * BLK;
-            const int64_t toff = off_next;
-            if (t + 1 < R.count) { I_next = tile_I[R.first + t + 1]; off_next = tile_off[R.first + t + 1]; }
-            if (PAIR && A.pair_sync) __syncthreads();   // the two waves of a pair stay within one tile of each other: the second reader hits L2
-            jk_digest_tile<WITH_J, WITH_K, NT, false, false, KJLT>(A, lane, i, k, I0, J0, K0, L0, ld, bk, toff, dKL, dJK, kjl, jkl, kjk);
-        }
-    }
-    // per-run outputs
+// per-run outputs
+template <bool WITH_J, bool WITH_K, bool KJLT>
+__device__ __forceinline__ void jk_run_end(const JkArgs &A, const RunHead &R, const int lane, const double (&kjl)[8][8],
+                                           const double (&jkl)[8], const double (&kjk)[8])
+{
+    const int i = lane >> 3, k = lane & 7, ld = A.ld;
     if (WITH_J) {
         double r = reduce8(jkl, lane, 32, 16, 8); // lane holds l = i
-        atomicAdd(&A.Jacc[(size_t)(K0 + k) * ld + L0 + i], r);
+        atomicAdd(&A.Jacc[(size_t)(R.K0 + k) * ld + R.L0 + i], r);
     }
     if (WITH_K) {
         double r = reduce8(kjk, lane, 32, 16, 8); // lane holds j = i
-        atomicAdd(&A.Kacc[(size_t)(J0 + i) * ld + K0 + k], r);
+        atomicAdd(&A.Kacc[(size_t)(R.J0 + i) * ld + R.K0 + k], r);
         // K_JL: 64 values over 64 lanes; first over i-lanes for each l-row... do it as 8 x reduce8 then reduce8
         if (KJLT) return;   // (already added per tile)
         double s[8];
@@ -3513,25 +3527,51 @@ __device__ __forceinline__ void jk_segment(const JkArgs &A, const int seg)
             s[l] = reduce8(col, lane, 32, 16, 8); // lane holds j = i, summed over i-lanes, for this l
         }
         double r2 = reduce8(s, lane, 4, 2, 1); // lane holds l = k, summed over k-lanes
-        atomicAdd(&A.Kacc[(size_t)(J0 + i) * ld + L0 + k], r2);
+        atomicAdd(&A.Kacc[(size_t)(R.J0 + i) * ld + R.L0 + k], r2);
     }
-  }
 }
 
-// The first `n_cached` work items (the longest segments) are read with the default cache policy, everything else with
-// nontemporal loads: on a tensor larger than the 256 MiB Infinity Cache the nontemporal stream does not evict them, so that
-// share of the tiles is served on-die in every SCF cycle after the first instead of from HBM.
+template <bool WITH_J, bool WITH_K, bool NT, bool PAIR = false, bool KJLT = false>
+__device__ __forceinline__ void jk_segment(const JkArgs &A, const int seg)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = lane >> 3, k = lane & 7;
+    const RunHead R = run_head(A.dir, seg, A.nao, A.tri);
+    double dKL[8], dJK[8], kjl[8][8], jkl[8], kjk[8];
+    jk_run_begin(A.D, R, A.ld, k, dKL, dJK, kjl, jkl, kjk);
+    TileEntry next = tile_entry(A.dir, R.first);
+    auto step = [&](const int t, auto dij, auto dkl) __attribute__((always_inline)) {
+        const TileHead H = tile_step(A.dir, R, t, next, A.nao, dij());
+        if (PAIR && A.pair_sync) __syncthreads();   // the two waves of a pair stay within one tile of each other: the second reader hits L2
+        jk_digest_tile<WITH_J, WITH_K, NT, dij(), dkl(), KJLT>(A, lane, i, k, R, H, dKL, dJK, kjl, jkl, kjk);
+    };
+    // only the first tile of a run can lie on the I == J diagonal (tiles of a run are ordered by I >= J); K == L holds for
+    // the whole run or not at all
+    auto tiles = [&](auto dkl) __attribute__((always_inline)) {
+        int t = 0;
+        if (A.tri && next.I == R.J) step(t++, std::true_type{}, dkl);
+        for (; t < R.count; t++) step(t, std::false_type{}, dkl);
+    };
+    if (R.dkl) tiles(std::true_type{}); else tiles(std::false_type{});
+    jk_run_end<WITH_J, WITH_K, KJLT>(A, R, lane, kjl, jkl, kjk);
+}
+
 template <bool WITH_J, bool WITH_K, bool NT>
 __global__ __launch_bounds__(64) void jk_tiles_kernel(JkArgs A)
 {
-    const MI_CONST_AS int *wave_seg = as_const(A.wave_seg);
-    const int seg_end = wave_seg[blockIdx.x + 1];
-    for (int seg = wave_seg[blockIdx.x]; seg < seg_end; seg++) {
-        if (NT && seg < A.n_cached) jk_segment<WITH_J, WITH_K, false>(A, seg);
-        else jk_segment<WITH_J, WITH_K, NT>(A, seg);
-    }
+    for_work_items<NT, true>(A.dir, A.n_cached, [&](const int seg, auto nt) __attribute__((always_inline)) {
+        jk_segment<WITH_J, WITH_K, nt()>(A, seg);
+    });
 }
 
+// J+K with K_JL reduced per tile (KJLT): 128 registers fewer, so two waves fit a SIMD (jk_kjlt option)
+template <bool NT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void jk_tiles_kjlt_kernel(JkArgs A)
+{
+    for_work_items<NT, true>(A.dir, A.n_cached, [&](const int seg, auto nt) __attribute__((always_inline)) {
+        jk_segment<true, true, nt(), false, true>(A, seg);
+    });
+}
 
 // Two densities in ONE pass over the tiles (the spin pair of UHF / UKS).  A single wave cannot hold two sets of
 // run-wide accumulators (2 x 64 K_JL + ... : the compiler spills, section 3.1 of DESIGN.md), so a workgroup of TWO waves
@@ -3539,17 +3579,6 @@ __global__ __launch_bounds__(64) void jk_tiles_kernel(JkArgs A)
 // single-density kernel, on two SIMDs of one CU.  Both read the same tiles; a barrier per tile keeps them within one tile of
 // each other, so the second reader of a 16-byte chunk finds it in L2 (default cache policy: no nontemporal hint here) and
 // HBM is read once for both densities.
-// J+K with K_JL reduced per tile (KJLT): 128 registers fewer, so two waves fit a SIMD (jk_kjlt option)
-template <bool NT>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void jk_tiles_kjlt_kernel(JkArgs A)
-{
-    const MI_CONST_AS int *wave_seg = as_const(A.wave_seg);
-    const int seg_end = wave_seg[blockIdx.x + 1];
-    for (int seg = wave_seg[blockIdx.x]; seg < seg_end; seg++) {
-        if (NT && seg < A.n_cached) jk_segment<true, true, false, false, true>(A, seg);
-        else jk_segment<true, true, NT, false, true>(A, seg);
-    }
-}
 template <bool WITH_J, bool WITH_K, bool NT>
 __global__ __launch_bounds__(128) void jk_tiles_pair_kernel(JkArgs A)
 {
@@ -3558,12 +3587,9 @@ __global__ __launch_bounds__(128) void jk_tiles_pair_kernel(JkArgs A)
     B.D = A.D + wave * A.pair_stride;
     B.Jacc = A.Jacc + wave * A.pair_stride;
     B.Kacc = A.Kacc + wave * A.pair_stride;
-    const MI_CONST_AS int *wave_seg = as_const(A.wave_seg);
-    const int seg_end = wave_seg[blockIdx.x + 1];
-    for (int seg = wave_seg[blockIdx.x]; seg < seg_end; seg++) {
-        if (NT && seg < A.n_cached) jk_segment<WITH_J, WITH_K, false, true>(B, seg);
-        else jk_segment<WITH_J, WITH_K, NT, true>(B, seg);
-    }
+    for_work_items<NT, true>(A.dir, A.n_cached, [&](const int seg, auto nt) __attribute__((always_inline)) {
+        jk_segment<WITH_J, WITH_K, nt(), true>(B, seg);
+    });
 }
 
 // Software-pipelined variant for the K-carrying builds (one wave per SIMD, so a wave has to overlap its own
@@ -3592,59 +3618,34 @@ __device__ __forceinline__ void jk_load_half(d2_t (&buf)[16], const d2_t *__rest
 }
 
 template <bool WITH_J, bool NT, bool TRI>
-__global__ __launch_bounds__(64) void jk_tiles_pipe_kernel(JkArgs A)
+__device__ __forceinline__ void jk_pipe_segment(const JkArgs &A, const int seg)
 {
     const int lane = threadIdx.x;
     const int i = lane >> 3, k = lane & 7;
-    const MI_CONST_AS int *wave_seg = as_const(A.wave_seg);
-    const MI_CONST_AS int *tile_I = as_const(A.tile_I);
-    const MI_CONST_AS int64_t *tile_off = as_const(A.tile_off);
     const MI_CONST_AS double *Du = as_const(A.D);
-    const int seg_end = wave_seg[blockIdx.x + 1];
-  for (int seg = wave_seg[blockIdx.x]; seg < seg_end; seg++) {
-    const MI_CONST_AS RunRec *rr = as_const(A.runs) + seg;
-    const RunRec R{rr->J, rr->K, rr->L, rr->first, rr->count};
-    const int J0 = R.J * BLK, K0 = R.K * BLK, L0 = R.L * BLK;
-    const int ld = A.ld;
-    const int bk = min(BLK, A.nao - K0);
     const double *__restrict__ D = A.D;
-
-    double dKL[8], dJK[8];
-#pragma unroll
-    for (int l = 0; l < 8; l++) dKL[l] = D[(size_t)(K0 + k) * ld + L0 + l];
-#pragma unroll
-    for (int j = 0; j < 8; j++) dJK[j] = D[(size_t)(J0 + j) * ld + K0 + k];
-    double kjl[8][8], jkl[8], kjk[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        jkl[j] = 0.0; kjk[j] = 0.0;
-#pragma unroll
-        for (int l = 0; l < 8; l++) kjl[j][l] = 0.0;
-    }
+    const RunHead R = run_head(A.dir, seg, A.nao, TRI);
+    const int J0 = R.J0, K0 = R.K0, L0 = R.L0, ld = A.ld, bk = R.bk;
+    double dKL[8], dJK[8], kjl[8][8], jkl[8], kjk[8];
+    jk_run_begin(D, R, ld, k, dKL, dJK, kjl, jkl, kjk);
 
     d2_t bufA[16], bufB[16];
-    const bool dkl = TRI && R.K == R.L;
-    int I_cur = tile_I[R.first];
-    int64_t off_cur = tile_off[R.first];
+    TileEntry next = tile_entry(A.dir, R.first);
     {
-        const int bi0 = min(BLK, A.nao - I_cur * BLK);
-        jk_load_half<NT>(bufA, reinterpret_cast<const d2_t *>(A.tiles + off_cur), bi0, bk, i, k, TRI && I_cur == R.J, dkl, 0);
+        const TileHead H = tile_head(R, next, A.nao, TRI);
+        jk_load_half<NT>(bufA, reinterpret_cast<const d2_t *>(A.dir.tiles + H.toff), H.bi, bk, i, k, H.dij, R.dkl, 0);
     }
     for (int t = 0; t < R.count; t++) {
-        const int tid = R.first + t;
-        const int I0 = I_cur * BLK;
-        const int bi = min(BLK, A.nao - I0);
         const bool more = t + 1 < R.count;
-        int I_nx = I_cur;
-        int64_t off_nx = off_cur;
-        if (more) { I_nx = tile_I[tid + 1]; off_nx = tile_off[tid + 1]; }
+        const TileHead H = tile_step(A.dir, R, t, next, A.nao, TRI);
+        const int I0 = H.I0;
         double dIJ[8], dIL[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) dIJ[j] = D[(size_t)(I0 + i) * ld + J0 + j];
 #pragma unroll
         for (int l = 0; l < 8; l++) dIL[l] = D[(size_t)(I0 + i) * ld + L0 + l];
         const double dIK = D[(size_t)(I0 + i) * ld + K0 + k];
-        jk_load_half<NT>(bufB, reinterpret_cast<const d2_t *>(A.tiles + off_cur), bi, bk, i, k, TRI && I_cur == R.J, dkl, 1);
+        jk_load_half<NT>(bufB, reinterpret_cast<const d2_t *>(A.dir.tiles + H.toff), H.bi, bk, i, k, H.dij, R.dkl, 1);
 
         double kik = 0.0, jij[8], kil[8];
 #pragma unroll
@@ -3670,8 +3671,8 @@ __global__ __launch_bounds__(64) void jk_tiles_pipe_kernel(JkArgs A)
                 }
             }
             if (half == 0 && more) {
-                const int bin = min(BLK, A.nao - I_nx * BLK);
-                jk_load_half<NT>(bufA, reinterpret_cast<const d2_t *>(A.tiles + off_nx), bin, bk, i, k, false, dkl, 0);   // only a run's first tile can have I == J
+                const int bin = min(BLK, A.nao - next.I * BLK);
+                jk_load_half<NT>(bufA, reinterpret_cast<const d2_t *>(A.dir.tiles + next.off), bin, bk, i, k, false, R.dkl, 0);   // only a run's first tile can have I == J
             }
         }
         atomicAdd(&A.Kacc[(size_t)(I0 + i) * ld + K0 + k], kik);
@@ -3683,27 +3684,17 @@ __global__ __launch_bounds__(64) void jk_tiles_pipe_kernel(JkArgs A)
             double r = reduce8(jij, lane, 4, 2, 1);
             atomicAdd(&A.Jacc[(size_t)(I0 + i) * ld + J0 + k], r);
         }
-        I_cur = I_nx; off_cur = off_nx;
     }
-    if (WITH_J) {
-        double r = reduce8(jkl, lane, 32, 16, 8);
-        atomicAdd(&A.Jacc[(size_t)(K0 + k) * ld + L0 + i], r);
-    }
-    {
-        double r = reduce8(kjk, lane, 32, 16, 8);
-        atomicAdd(&A.Kacc[(size_t)(J0 + i) * ld + K0 + k], r);
-        double s8[8];
-#pragma unroll
-        for (int l = 0; l < 8; l++) {
-            double col[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) col[j] = kjl[j][l];
-            s8[l] = reduce8(col, lane, 32, 16, 8);
-        }
-        double r2 = reduce8(s8, lane, 4, 2, 1);
-        atomicAdd(&A.Kacc[(size_t)(J0 + i) * ld + L0 + k], r2);
-    }
-  }
+    jk_run_end<WITH_J, true, false>(A, R, lane, kjl, jkl, kjk);
+}
+
+// (no default-policy prefix here: every work item is read with the policy of the launch, as mi_jk_describe documents)
+template <bool WITH_J, bool NT, bool TRI>
+__global__ __launch_bounds__(64) void jk_tiles_pipe_kernel(JkArgs A)
+{
+    for_work_items<NT, false>(A.dir, 0, [&](const int seg, auto) __attribute__((always_inline)) {
+        jk_pipe_segment<WITH_J, NT, TRI>(A, seg);
+    });
 }
 
 // Dense (nao^4) copy of the resident tiles for post-SCF methods on small molecules (MP2 behind `pyscf.mp`): every stored
@@ -3797,16 +3788,8 @@ extern "C" int mi_eri_read_quartet(mi_ctx *c, int ish, int jsh, int ksh, int lsh
     return 0;
 }
 
-// `iperm`: tile AO -> caller AO (the padded copy is in the tile order of the ERI store)
-__global__ void pad_density_kernel(const double *D, double *Dp, int nao, int ld, const int *__restrict__ iperm)
-{
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= ld * ld) return;
-    int r = idx / ld, c = idx - r * ld;
-    Dp[idx] = (r < nao && c < nao) ? D[(size_t)iperm[r] * nao + iperm[c]] : 0.0;
-}
-
-// D -> zero-padded [ld][ld] copy, and the J/K accumulators cleared in the same launch (one kernel instead of three per build)
+// D -> zero-padded [ld][ld] copy, and the J/K accumulators (where given) cleared in the same launch (one kernel instead of three
+// per build).  `iperm`: tile AO -> caller AO (the padded copy is in the tile order of the ERI store)
 __global__ void pad_density_clear_kernel(const double *D, double *Dp, double *Jacc, double *Kacc, int nao, int ld, const int *__restrict__ iperm)
 {
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3855,33 +3838,45 @@ static JkPlan jk_plan(const mi_ctx *c, bool wj, bool wk, int n_dm)
     return P;
 }
 
+// Runtime flags -> template arguments: f(std::bool_constant<flag>...), and f(std::integral_constant<int, W>) for the smallest
+// batch width W of 1, 2, 4, 8 that holds n.  A kernel is instantiated where f names it, so f guards the combinations that are
+// never launched with `if constexpr`.
+template <class F> static void with_flags(F &&f) { f(); }
+template <class F, class... B> static void with_flags(F &&f, bool flag, B... rest)
+{
+    if (flag) with_flags([&](auto... r) { f(std::true_type{}, r...); }, rest...);
+    else with_flags([&](auto... r) { f(std::false_type{}, r...); }, rest...);
+}
+template <class F> static void with_width(int n, F &&f)
+{
+    if (n <= 1) f(std::integral_constant<int, 1>{});
+    else if (n <= 2) f(std::integral_constant<int, 2>{});
+    else if (n <= 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
+}
+
 static int launch_jk_plan(mi_ctx *c, const JkPlan &P, bool wj, bool wk, hipStream_t st)
 {
     const bool pair = P.family == JK_PAIR;
-    JkArgs A{c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg, c->n_jk_waves, c->d_Dpad, c->d_Jacc, c->d_Kacc, c->ldp, c->nao,
+    JkArgs A{tile_dir(c), c->n_jk_waves, c->d_Dpad, c->d_Jacc, c->d_Kacc, c->ldp, c->nao,
              c->n_jk_cached, c->tri, (size_t)c->ldp * c->ldp, pair ? 1 : 0, P.dpp ? 1 : 0};
     if (c->n_tiles == 0) return 0;
-    dim3 g(A.nruns), b(pair ? 128 : 64);
-    const bool nt = P.nt;
+    if (!wj && !wk) return fail("launch_jk_plan: neither J nor K");
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(A.nruns), dim3(pair ? 128 : 64), 0, st, A); };
     switch (P.family) {
     case JK_PAIR:
         // same cache policy as the single-density kernel: nontemporal stream + default-policy prefix for tensors beyond the
         // Infinity Cache (an all-default-policy stream of 4.9 GB made the launch time erratic: 1.65 ... 2.75 ms)
-        if (wj && wk) { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<true, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<true, true, false>), g, b, 0, st, A); }
-        else if (wj) { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<true, false, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<true, false, false>), g, b, 0, st, A); }
-        else { if (nt) hipLaunchKernelGGL((jk_tiles_pair_kernel<false, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pair_kernel<false, true, false>), g, b, 0, st, A); }
+        with_flags([&](auto J, auto K, auto NT) { if constexpr (J() || K()) launch(jk_tiles_pair_kernel<J(), K(), NT()>); }, wj, wk, P.nt);
         break;
-    case JK_PIPE:
-        if (wj) { if (nt) hipLaunchKernelGGL((jk_tiles_pipe_kernel<true, true, false>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_pipe_kernel<true, false, false>), g, b, 0, st, A); }
-        else hipLaunchKernelGGL((jk_tiles_pipe_kernel<false, true, false>), g, b, 0, st, A);
+    case JK_PIPE:   // full-row tiles only (jk_plan); the K-only form is built with the nontemporal stream only, whatever P.nt says
+        with_flags([&](auto J, auto NT) { launch(jk_tiles_pipe_kernel<J(), J() ? NT() : true, false>); }, wj, P.nt);
         break;
     case JK_KJLT:
-        if (nt) hipLaunchKernelGGL((jk_tiles_kjlt_kernel<true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kjlt_kernel<false>), g, b, 0, st, A);
+        with_flags([&](auto NT) { launch(jk_tiles_kjlt_kernel<NT()>); }, P.nt);
         break;
     case JK_PLAIN:
-        if (wj && wk) { if (nt) hipLaunchKernelGGL((jk_tiles_kernel<true, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kernel<true, true, false>), g, b, 0, st, A); }
-        else if (wj) { if (nt) hipLaunchKernelGGL((jk_tiles_kernel<true, false, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kernel<true, false, false>), g, b, 0, st, A); }
-        else { if (nt) hipLaunchKernelGGL((jk_tiles_kernel<false, true, true>), g, b, 0, st, A); else hipLaunchKernelGGL((jk_tiles_kernel<false, true, false>), g, b, 0, st, A); }
+        with_flags([&](auto J, auto K, auto NT) { if constexpr (J() || K()) launch(jk_tiles_kernel<J(), K(), NT()>); }, wj, wk, P.nt);
         break;
     }
     HIPCHK(hipGetLastError());
@@ -3912,23 +3907,16 @@ extern "C" int mi_build_jk(mi_ctx *c, const double *d_D, int n_dm, double *d_J, 
     hipStream_t st = (hipStream_t)stream;
     size_t nn = (size_t)c->nao * c->nao, pp = (size_t)c->ldp * c->ldp;
     const JkPlan P = jk_plan(c, d_J != nullptr, d_K != nullptr, n_dm);
-    if (P.family == JK_PAIR && c->n_tiles > 0) {
-        for (int m = 0; m < 2; m++)
-            hipLaunchKernelGGL(pad_density_clear_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_D + m * nn, c->d_Dpad + m * pp,
+    const int per = P.family == JK_PAIR ? 2 : 1;   // densities per pass over the tiles (jk_plan: the pair family only for n_dm == 2)
+    for (int m0 = 0; m0 < n_dm; m0 += per) {
+        const int n = std::min(per, n_dm - m0);
+        for (int m = 0; m < n; m++)
+            hipLaunchKernelGGL(pad_density_clear_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_D + (m0 + m) * nn, c->d_Dpad + m * pp,
                                d_J ? c->d_Jacc + m * pp : nullptr, d_K ? c->d_Kacc + m * pp : nullptr, c->nao, c->ldp, c->d_iperm);
         if (launch_jk_plan(c, P, d_J != nullptr, d_K != nullptr, st)) return -1;
-        for (int m = 0; m < 2; m++)
+        for (int m = 0; m < n; m++)
             hipLaunchKernelGGL(finalize_jk_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, c->d_Jacc + m * pp, c->d_Kacc + m * pp,
-                               d_J ? d_J + m * nn : nullptr, d_K ? d_K + m * nn : nullptr, c->nao, c->ldp, c->d_perm);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    for (int m = 0; m < n_dm; m++) {
-        hipLaunchKernelGGL(pad_density_clear_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_D + m * nn, c->d_Dpad,
-                           d_J ? c->d_Jacc : nullptr, d_K ? c->d_Kacc : nullptr, c->nao, c->ldp, c->d_iperm);
-        if (launch_jk(c, d_J != nullptr, d_K != nullptr, st)) return -1;
-        hipLaunchKernelGGL(finalize_jk_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, c->d_Jacc, c->d_Kacc,
-                           d_J ? d_J + m * nn : nullptr, d_K ? d_K + m * nn : nullptr, c->nao, c->ldp, c->d_perm);
+                               d_J ? d_J + (m0 + m) * nn : nullptr, d_K ? d_K + (m0 + m) * nn : nullptr, c->nao, c->ldp, c->d_perm);
         HIPCHK(hipGetLastError());
     }
     return 0;
@@ -3961,11 +3949,7 @@ constexpr int JKM_SI = 537, JKM_SJ = 67, JKM_SK = 8;
 constexpr int JKM_LDS = 7 * JKM_SI + 7 * JKM_SJ + 7 * JKM_SK + 8;
 
 struct JkmArgs {
-    const double *tiles;
-    const int64_t *tile_off;
-    const int *tile_I;
-    const RunRec *runs;
-    const int *wave_seg;
+    TileDir dir;
     const double *D;           // [n][ld][ld] padded densities in tile order
     double *Jacc, *Kacc;       // [n][ld][ld]
     size_t pp;                 // ld * ld
@@ -4027,12 +4011,8 @@ __device__ __forceinline__ void jkm_segment(const JkmArgs &A, double *__restrict
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int a = lane >> 3, b = lane & 7;
-    const MI_CONST_AS RunRec *rr = as_const(A.runs) + seg;
-    const RunRec R{rr->J, rr->K, rr->L, rr->first, rr->count};
-    const int J0 = R.J * BLK, K0 = R.K * BLK, L0 = R.L * BLK;
-    const int ld = A.ld;
-    const int bk = min(BLK, A.nao - K0);
-    const bool dkl = A.tri && R.K == R.L;
+    const RunHead R = run_head(A.dir, seg, A.nao, A.tri);
+    const int J0 = R.J0, K0 = R.K0, L0 = R.L0, ld = A.ld;
     // density slots of this wave: m = 2q + wave; slots beyond n repeat density 0 and add nothing
     int mq[NPW];
     bool live[NPW], wantj[NPW];
@@ -4049,15 +4029,11 @@ __device__ __forceinline__ void jkm_segment(const JkmArgs &A, double *__restrict
     double jkl[NPW], kjl[NPW], kjk[NPW];
 #pragma unroll
     for (int q = 0; q < NPW; q++) { jkl[q] = 0.0; kjl[q] = 0.0; kjk[q] = 0.0; }
-    const MI_CONST_AS int *tile_I = as_const(A.tile_I);
-    const MI_CONST_AS int64_t *tile_off = as_const(A.tile_off);
     for (int t = 0; t < R.count; t++) {
-        const int I = tile_I[R.first + t];
-        const int64_t toff = tile_off[R.first + t];
-        const int I0 = I * BLK;
-        const int bi = min(BLK, A.nao - I0);
+        const TileHead H = tile_head(R, tile_entry(A.dir, R.first + t), A.nao, A.tri);
+        const int I0 = H.I0;
         __syncthreads();   // the previous tile's image is no longer read
-        load_tile_image<NT, 128>(A.tiles, Tl, toff, bi, bk, A.tri && I == R.J, dkl);
+        load_tile_image<NT, 128>(A.dir.tiles, Tl, H.toff, H.bi, R.bk, H.dij, R.dkl);
         __syncthreads();
         const MI_CONST_AS double *Dq[NPW];
         double acc[NPW];
@@ -4112,12 +4088,9 @@ template <bool NT, int NPW>
 __global__ __launch_bounds__(128) void jk_multi_kernel(JkmArgs A)
 {
     __shared__ double Tl[JKM_LDS];
-    const MI_CONST_AS int *wave_seg = as_const(A.wave_seg);
-    const int seg_end = wave_seg[blockIdx.x + 1];
-    for (int seg = wave_seg[blockIdx.x]; seg < seg_end; seg++) {
-        if (NT && seg < A.n_cached) jkm_segment<false, NPW>(A, Tl, seg);
-        else jkm_segment<NT, NPW>(A, Tl, seg);
-    }
+    for_work_items<NT, true>(A.dir, A.n_cached, [&](const int seg, auto nt) __attribute__((always_inline)) {
+        jkm_segment<nt(), NPW>(A, Tl, seg);
+    });
 }
 
 // n densities -> zero-padded [ld][ld] copies in tile order, their accumulators cleared
@@ -4182,17 +4155,10 @@ extern "C" int mi_build_jk_multi(mi_ctx *c, const double *d_D, int n_dm, const i
                            c->d_mJacc, c->d_mKacc, n, c->nao, c->ldp, c->d_iperm);
         HIPCHK(hipGetLastError());
         if (c->n_tiles > 0) {
-            JkmArgs A{c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg, c->d_mDpad, c->d_mJacc, c->d_mKacc, pp,
-                      c->ldp, c->nao, n, d_J ? jmask : 0, d_K ? 1 : 0, c->n_jk_cached, c->tri};
-            dim3 g(c->n_jk_waves), b(128);
-            const int npw = (n + 1) / 2;
-#define JKM_LAUNCH(P) do { if (nt) hipLaunchKernelGGL((jk_multi_kernel<true, P>), g, b, 0, st, A); \
-                           else hipLaunchKernelGGL((jk_multi_kernel<false, P>), g, b, 0, st, A); } while (0)
-            if (npw <= 1) JKM_LAUNCH(1);
-            else if (npw <= 2) JKM_LAUNCH(2);
-            else if (npw <= 4) JKM_LAUNCH(4);
-            else JKM_LAUNCH(8);
-#undef JKM_LAUNCH
+            JkmArgs A{tile_dir(c), c->d_mDpad, c->d_mJacc, c->d_mKacc, pp, c->ldp, c->nao, n, d_J ? jmask : 0, d_K ? 1 : 0, c->n_jk_cached, c->tri};
+            with_width((n + 1) / 2, [&](auto NPW) {   // densities per wave
+                with_flags([&](auto NT) { hipLaunchKernelGGL((jk_multi_kernel<NT(), NPW()>), dim3(c->n_jk_waves), dim3(128), 0, st, A); }, nt);
+            });
             HIPCHK(hipGetLastError());
         }
         hipLaunchKernelGGL(finalize_jk_multi_kernel, dim3((unsigned)((nn * n + 255) / 256)), dim3(256), 0, st, c->d_mJacc, c->d_mKacc,
@@ -4224,11 +4190,7 @@ constexpr int QT_BATCH = 8;                    // orbitals per pass
 constexpr int QT_THREADS = 256;
 
 struct QtArgs {
-    const double *tiles;
-    const int64_t *tile_off;
-    const int *tile_I;
-    const RunRec *runs;
-    const int *wave_seg;
+    TileDir dir;
     const double *C;           // [ld][QT_BATCH] coefficient rows in tile order, zero-padded
     double *A;                 // [n][ld][ld][ld]
     size_t p3;                 // ld^3
@@ -4256,27 +4218,20 @@ __device__ __forceinline__ void qt_segment(const QtArgs &A, double *__restrict__
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int a = lane >> 3, b = lane & 7;
-    const MI_CONST_AS RunRec *rr = as_const(A.runs) + seg;
-    const RunRec R{rr->J, rr->K, rr->L, rr->first, rr->count};
-    const int J0 = R.J * BLK, K0 = R.K * BLK, L0 = R.L * BLK;
+    const RunHead R = run_head(A.dir, seg, A.nao, A.tri);
+    const int J0 = R.J0, K0 = R.K0, L0 = R.L0;
     const size_t ld = A.ld;
-    const int bk = min(BLK, A.nao - K0);
-    const bool dkl = A.tri && R.K == R.L;
     const MI_CONST_AS double *Cc = as_const(A.C);
-    const MI_CONST_AS int *tile_I = as_const(A.tile_I);
-    const MI_CONST_AS int64_t *tile_off = as_const(A.tile_off);
     double run[2][NB];
 #pragma unroll
     for (int s = 0; s < 2; s++)
 #pragma unroll
         for (int o = 0; o < NB; o++) run[s][o] = 0.0;
     for (int t = 0; t < R.count; t++) {
-        const int I = tile_I[R.first + t];
-        const int64_t toff = tile_off[R.first + t];
-        const int I0 = I * BLK;
-        const int bi = min(BLK, A.nao - I0);
+        const TileHead H = tile_head(R, tile_entry(A.dir, R.first + t), A.nao, A.tri);
+        const int I0 = H.I0;
         __syncthreads();   // the previous tile's image is no longer read
-        load_tile_image<NT, QT_THREADS>(A.tiles, Tl, toff, bi, bk, A.tri && I == R.J, dkl);
+        load_tile_image<NT, QT_THREADS>(A.dir.tiles, Tl, H.toff, H.bi, R.bk, H.dij, R.dkl);
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < 2; s++) {
@@ -4318,12 +4273,9 @@ template <bool NT, int NB>
 __global__ __launch_bounds__(QT_THREADS) void eri_qtrans_kernel(QtArgs A)
 {
     __shared__ double Tl[JKM_LDS];
-    const MI_CONST_AS int *wave_seg = as_const(A.wave_seg);
-    const int seg_end = wave_seg[blockIdx.x + 1];
-    for (int seg = wave_seg[blockIdx.x]; seg < seg_end; seg++) {
-        if (NT && seg < A.n_cached) qt_segment<false, NB>(A, Tl, seg);
-        else qt_segment<NT, NB>(A, Tl, seg);
-    }
+    for_work_items<NT, true>(A.dir, A.n_cached, [&](const int seg, auto nt) __attribute__((always_inline)) {
+        qt_segment<nt(), NB>(A, Tl, seg);
+    });
 }
 
 // Cp[r][o] = C[iperm[r]][o0 + o] for r < nao, o < n; zero elsewhere (tile AO order, QT_BATCH columns)
@@ -4372,15 +4324,10 @@ extern "C" int mi_eri_qtrans(mi_ctx *c, const double *d_C, int nb, int ldc, doub
                            (int)ld, d_Cp.get(), c->d_iperm);
         if (hipMemsetAsync(d_A, 0, sizeof(double) * p3 * n, st) != hipSuccess) { rc = fail("mi_eri_qtrans: memset failed"); break; }
         if (c->n_tiles > 0) {
-            QtArgs A{c->d_tiles, c->d_tile_off, c->d_tile_I, c->d_segs, c->d_wave_seg, d_Cp, d_A, p3, (int)ld, c->nao, c->n_jk_cached, c->tri, n};
-            dim3 g(c->n_jk_waves), b(QT_THREADS);
-#define QT_LAUNCH(P) do { if (nt) hipLaunchKernelGGL((eri_qtrans_kernel<true, P>), g, b, 0, st, A); \
-                          else hipLaunchKernelGGL((eri_qtrans_kernel<false, P>), g, b, 0, st, A); } while (0)
-            if (n <= 1) QT_LAUNCH(1);
-            else if (n <= 2) QT_LAUNCH(2);
-            else if (n <= 4) QT_LAUNCH(4);
-            else QT_LAUNCH(8);
-#undef QT_LAUNCH
+            QtArgs A{tile_dir(c), d_Cp, d_A, p3, (int)ld, c->nao, c->n_jk_cached, c->tri, n};
+            with_width(n, [&](auto NB) {
+                with_flags([&](auto NT) { hipLaunchKernelGGL((eri_qtrans_kernel<NT(), NB()>), dim3(c->n_jk_waves), dim3(QT_THREADS), 0, st, A); }, nt);
+            });
         }
         hipLaunchKernelGGL(qt_finalize_kernel, dim3((unsigned)((n3 + 255) / 256), (unsigned)n), dim3(256), 0, st, d_A.get(), d_Y + (size_t)m0 * n3,
                            c->nao, (int)ld, p3, c->d_perm);
@@ -4393,27 +4340,27 @@ extern "C" int mi_eri_qtrans(mi_ctx *c, const double *d_C, int nb, int ldc, doub
 extern "C" int mi_time_jk_variant(mi_ctx *c, const double *d_D, int with_j, int with_k, int reps, double *ms, void *stream)
 {
     if (!c || !d_D || !ms || reps < 1 || (!with_j && !with_k)) return fail("mi_time_jk_variant: bad argument");
-    if (!c->eri_ready) return fail("mi_time_jk_kernel: call mi_eri_prepare first");
+    if (!c->eri_ready) return fail("mi_time_jk_variant: call mi_eri_prepare first");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     size_t pp = (size_t)c->ldp * c->ldp;
-    hipLaunchKernelGGL(pad_density_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_D, c->d_Dpad, c->nao, c->ldp, c->d_iperm);
-    HIPCHK(hipMemsetAsync(c->d_Jacc, 0, sizeof(double) * pp, st));
-    HIPCHK(hipMemsetAsync(c->d_Kacc, 0, sizeof(double) * pp, st));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    hipLaunchKernelGGL(pad_density_clear_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_D, c->d_Dpad, c->d_Jacc, c->d_Kacc,
+                       c->nao, c->ldp, c->d_iperm);
+    struct Event {   // released on every return
+        hipEvent_t e = nullptr;
+        ~Event() { if (e) hipEventDestroy(e); }
+    } e0, e1;
+    HIPCHK(hipEventCreate(&e0.e));
+    HIPCHK(hipEventCreate(&e1.e));
     if (launch_jk(c, with_j != 0, with_k != 0, st)) return -1; // warm
-    HIPCHK(hipEventRecord(e0, st));
+    HIPCHK(hipEventRecord(e0.e, st));
     for (int r = 0; r < reps; r++)
         if (launch_jk(c, with_j != 0, with_k != 0, st)) return -1;
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
+    HIPCHK(hipEventRecord(e1.e, st));
+    HIPCHK(hipEventSynchronize(e1.e));
     float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
+    HIPCHK(hipEventElapsedTime(&t, e0.e, e1.e));
     *ms = (double)t / reps;
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     return 0;
 }
 
@@ -7515,10 +7462,11 @@ extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d
     GradState G;
     G.c = c; G.st = st; G.hyb = hyb; G.rank = rank; G.nranks = nranks; G.natm3 = c->natm * 3;
     size_t pp = (size_t)c->ldp * c->ldp;
-    hipLaunchKernelGGL(pad_density_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_D, c->d_Dpad, c->nao, c->ldp, c->d_iperm);
+    double *const none = nullptr;   // no accumulators to clear
+    hipLaunchKernelGGL(pad_density_clear_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_D, c->d_Dpad, none, none, c->nao, c->ldp, c->d_iperm);
     if (d_Dspin) {
         HIPCHK(G.d_Mpad.alloc(pp));
-        hipLaunchKernelGGL(pad_density_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_Dspin, G.d_Mpad.get(), c->nao, c->ldp, c->d_iperm);
+        hipLaunchKernelGGL(pad_density_clear_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_Dspin, G.d_Mpad.get(), none, none, c->nao, c->ldp, c->d_iperm);
     }
     std::vector<int> shell_atom(c->nbas);
     for (int i = 0; i < c->nbas; i++) shell_atom[i] = c->shells[i].atom;
