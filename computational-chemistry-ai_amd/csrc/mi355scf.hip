@@ -8922,3 +8922,8 @@ extern "C" int mi_pcm_fock(mi_ctx *c, const double *d_B, int npts, int64_t ld, c
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// =================================================================================================
+// Determinant full CI inside an active space (mi_fci_*): gather / GEMM / gather over string link tables.
+// =================================================================================================
+#include "fci_kernels.h"

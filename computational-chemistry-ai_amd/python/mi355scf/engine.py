@@ -42,7 +42,7 @@ def build_library(force=False):
     src = os.path.join(_CSRC, "mi355scf.hip")
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.getmtime(os.path.join(_CSRC, f)) > os.path.getmtime(LIB_PATH)
-        for f in ("mi355scf.hip", "rys_tables.h", "Makefile") if os.path.exists(os.path.join(_CSRC, f)))
+        for f in ("mi355scf.hip", "rys_tables.h", "fci_kernels.h", "Makefile") if os.path.exists(os.path.join(_CSRC, f)))
     if force or stale:
         subprocess.check_call(["make", "-C", _CSRC, "-s"] + (["-B"] if force else []))
     return LIB_PATH
@@ -132,6 +132,10 @@ def lib():
         L.mi_pcm_potential.argtypes = [vp, vp, ctypes.c_int, i64, vp, vp, vp, vp, vp]
         L.mi_pcm_fock_chunks.argtypes = [ctypes.c_int, i64]
         L.mi_pcm_fock.argtypes = [vp, vp, ctypes.c_int, i64, vp, ctypes.c_double, ctypes.c_int, vp, vp, vp]
+        ci = ctypes.c_int
+        L.mi_fci_gather_d.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, vp, vp]
+        L.mi_fci_gather_sigma.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp]
+        L.mi_fci_hdiag.argtypes = [vp, vp, vp, ci, vp, ci, vp, ci, vp, vp]
         _lib = L
     return _lib
 

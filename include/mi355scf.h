@@ -419,6 +419,27 @@ int mi_pcm_fock(mi_ctx *ctx, const double *d_B, int npts, int64_t ld, const doub
 int mi_pcm_grad(mi_ctx *ctx, const double *d_pts, int npts, const int32_t *d_blk, int nblk, const double *d_D, const double *d_q,
                 double *d_part, void *stream);
 
+/* ---- determinant full CI in an active space (additions; ABI version unchanged; no context: nothing depends on the molecule) ----
+ * `mcscf.CASCI(mf, ncas, nelecas).kernel()` -> fcisolver.kernel (templates/calculate_casscf.py:126-131); stands in for
+ * pyscf.fci.direct_spin1's FCIcontract_2e_spin1 / FCImake_hdiag_uhf / FCIrdm12kern_sf of libfci [MEM].
+ * norb <= 16 orbitals; strings are occupation bit masks numbered in ascending integer order; the determinant |Ia Ib> is (alpha
+ * creators ascending)(beta creators ascending)|0>; CI vectors d_c / d_sigma are [nvec][nsa][nsb], beta string fastest.
+ * Link tables (mi355scf/fci.py builds them): a link a+_cre a_ann |J> = sgn |T> is the pair (ann * norb + cre, sgn * (T + 1));
+ * d_alink[nsa][nla][2] lists the nla links of every alpha string, d_btab[norb^2][nsb] holds the beta links densely (0 = none).
+ * Work arrays cover alpha rows [a0, a0 + nrow) of every vector: W[(plane * nvec + v) * (nrow * nsb) + (Ia - a0) * nsb + Ib],
+ * norb^2 + 1 planes.
+ * mi_fci_gather_d:     D[r * norb + s] = <J|E_rs|c_v> (mode 1: alpha part, 2: beta part, 3: spin-summed); D[norb^2] = c_v.
+ * mi_fci_gather_sigma: d_sigma[v][I] += sum_pq sum_{K in rows} <I|E_pq|K> F[p * norb + q][v][K] for EVERY I (planes 0..norb^2-1
+ *                      of F); the caller zeroes d_sigma and calls once per chunk of rows.  Gather only, no atomics.
+ * mi_fci_hdiag:        d_out[Ia][Ib] = <Ia Ib|H|Ia Ib> from h1[norb][norb], jdiag[p][q] = (pp|qq), kdiag[p][q] = (pq|qp) and the
+ *                      string masks d_astr[nsa], d_bstr[nsb]. */
+int mi_fci_gather_d(const double *d_c, int nvec, int nsa, int nsb, int norb, int a0, int nrow, const int32_t *d_alink, int nla,
+                    const int32_t *d_btab, int mode, double *d_D, void *stream);
+int mi_fci_gather_sigma(const double *d_F, int nvec, int nsa, int nsb, int norb, int a0, int nrow, const int32_t *d_alink, int nla,
+                        const int32_t *d_btab, double *d_sigma, void *stream);
+int mi_fci_hdiag(const double *d_h1, const double *d_jdiag, const double *d_kdiag, int norb, const int32_t *d_astr, int nsa,
+                 const int32_t *d_bstr, int nsb, double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
