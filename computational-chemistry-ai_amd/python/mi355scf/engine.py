@@ -624,7 +624,8 @@ class Engine:
                                      self._stream()))
 
     def pcm_grad(self, pts, blk, D, q, part):
-        """part[pair, block, 3] = -2 sum_g q_g sum D_mn <d m|erf/r|n> (pairs of `pcm_pairs(ordered=True)`)."""
+        """part[pair (i, j), block, 3] = -2 sum_{g in block} q_g sum_{m in i, n in j} D_mn <d_A m|erf/r|n>_g for the pairs of
+        `pcm_pairs(ordered=True)`: d_A = d/d(centre of shell i) of the bra function alone, D as given (not symmetrised)."""
         self._pcm_points(pts, blk)
         assert D.is_contiguous() and D.shape == (self.nao, self.nao) and q.is_contiguous() and q.numel() == pts.shape[0]
         assert part.is_contiguous() and part.numel() == len(self.pcm_pairs(True)) * blk.shape[0] * 3

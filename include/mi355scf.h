@@ -407,7 +407,9 @@ int mi_rys_roots_host(int nroots, double x, double *roots, double *weights);
  *                   mi_pcm_fock_chunks(npts, ld) * ld doubles of per-chunk column sums (added in index order, no atomics).
  * mi_pcm_pairs:     the shell pairs of the launches (ordered = 1: all (i, j), the gradient's rows); returns their number,
  *                   fills out[n][2] when out is not NULL.
- * mi_pcm_grad:      d_part[n_ordered_pairs][nblk][3] = -2 sum_{g in block} q_g sum_{m in i, n in j} D_mn d/dA_i B[g]_mn:
+ * mi_pcm_grad:      d_part[n_ordered_pairs][nblk][3] = -2 sum_{g in block} q_g sum_{m in i, n in j} D_mn <d_A m|erf/r|n>_g, d_A the
+ *                   derivative with respect to the centre of shell i acting on the bra function m alone (also when j sits on
+ *                   the same centre: the ket's derivative is the row (j, i)); D is read as given, not symmetrised.  The row is
  *                   the share of the atom of shell i; the block's owning atom takes minus it (translational invariance). */
 int mi_pcm_pairs(mi_ctx *ctx, int ordered, int32_t *out);
 int mi_pcm_eval(mi_ctx *ctx, const double *d_pts, int npts, const int32_t *d_blk, int nblk, int64_t ld, double *d_B, void *stream);
