@@ -8927,3 +8927,8 @@ extern "C" int mi_pcm_fock(mi_ctx *c, const double *d_B, int npts, int64_t ld, c
 // Determinant full CI inside an active space (mi_fci_*): gather / GEMM / gather over string link tables.
 // =================================================================================================
 #include "fci_kernels.h"
+
+// =================================================================================================
+// Closed-shell coupled cluster (mi_cc_*): the CCSD amplitude update and the (T) permutation / energy pass.
+// =================================================================================================
+#include "cc_kernels.h"

@@ -24,22 +24,28 @@ import torch
 from . import fci
 
 
+def check_rhf_reference(mf, who, unrestricted="UHF / UKS references are not supported (closed-shell RHF only)"):
+    """Refuse every reference but a closed-shell RHF of this engine on one GPU (shared by `CASCI` and `ccsd.CCSD`)."""
+    if not getattr(mf, "_spin_restricted", True):
+        raise NotImplementedError(f"{who}: {unrestricted}")
+    if getattr(mf, "xc", None) is not None:
+        raise NotImplementedError(f"{who}: Kohn-Sham references (xc = {mf.xc!r}) are not supported (closed-shell RHF only)")
+    if getattr(mf, "with_df", None) is not None:
+        raise NotImplementedError(f"{who}: density-fitted references are not supported")
+    if getattr(mf, "_pcm", False) or getattr(mf, "with_solvent", None) is not None:
+        raise NotImplementedError(f"{who}: PCM-solvated references are not supported")
+    if getattr(mf, "_nranks", 1) > 1:
+        raise NotImplementedError(f"{who}: sharded references are not supported (one GPU, unsharded ERI store)")
+    if not all(hasattr(type(mf), a) for a in ("_jk", "_setup_once", "engine")) or not hasattr(mf, "mo_coeff"):    # `engine` is a property
+                                                                                                                  # that opens the GPU
+        raise NotImplementedError(f"{who}: {type(mf).__name__} is not an RHF object of this engine")
+
+
 class CASCI:
     natorb = False
 
     def __init__(self, mf, ncas, nelecas, ncore=None):
-        if not getattr(mf, "_spin_restricted", True):
-            raise NotImplementedError("CASCI: UHF / UKS references are not supported (closed-shell RHF only)")
-        if getattr(mf, "xc", None) is not None:
-            raise NotImplementedError(f"CASCI: Kohn-Sham references (xc = {mf.xc!r}) are not supported (closed-shell RHF only)")
-        if getattr(mf, "with_df", None) is not None:
-            raise NotImplementedError("CASCI: density-fitted references are not supported")
-        if getattr(mf, "_pcm", False) or getattr(mf, "with_solvent", None) is not None:
-            raise NotImplementedError("CASCI: PCM-solvated references are not supported")
-        if getattr(mf, "_nranks", 1) > 1:
-            raise NotImplementedError("CASCI: sharded references are not supported (one GPU, unsharded ERI store)")
-        if not all(hasattr(mf, a) for a in ("_jk", "_setup_once", "engine", "mo_coeff")):
-            raise NotImplementedError(f"CASCI: {type(mf).__name__} is not an RHF object of this engine")
+        check_rhf_reference(mf, "CASCI")
         self._scf = mf
         self.mol = mf.mol
         self.verbose = mf.verbose

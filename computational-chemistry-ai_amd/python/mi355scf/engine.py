@@ -42,7 +42,7 @@ def build_library(force=False):
     src = os.path.join(_CSRC, "mi355scf.hip")
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.getmtime(os.path.join(_CSRC, f)) > os.path.getmtime(LIB_PATH)
-        for f in ("mi355scf.hip", "rys_tables.h", "fci_kernels.h", "Makefile") if os.path.exists(os.path.join(_CSRC, f)))
+        for f in ("mi355scf.hip", "rys_tables.h", "fci_kernels.h", "cc_kernels.h", "Makefile") if os.path.exists(os.path.join(_CSRC, f)))
     if force or stale:
         subprocess.check_call(["make", "-C", _CSRC, "-s"] + (["-B"] if force else []))
     return LIB_PATH
@@ -136,6 +136,9 @@ def lib():
         L.mi_fci_gather_d.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, vp, vp]
         L.mi_fci_gather_sigma.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp]
         L.mi_fci_hdiag.argtypes = [vp, vp, vp, ci, vp, ci, vp, ci, vp, vp]
+        L.mi_cc_amp_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp]
+        L.mi_cc_t_blocks.argtypes = [ci]
+        L.mi_cc_t_energy.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -442,6 +442,25 @@ int mi_fci_gather_sigma(const double *d_F, int nvec, int nsa, int nsb, int norb,
 int mi_fci_hdiag(const double *d_h1, const double *d_jdiag, const double *d_kdiag, int norb, const int32_t *d_astr, int nsa,
                  const int32_t *d_bstr, int nsb, double *d_out, void *stream);
 
+/* Closed-shell coupled cluster (mi355scf/ccsd.py).  Context-free; all arrays FP64 on the device.
+ * `cc.CCSD(mf).kernel()` / `.ccsd_t()` (reference README, "adding a new method").
+ * mi_cc_amp_update: one pass over the stacked vector [t1 (nocc nvir) | t2 (nocc nocc nvir nvir, layout i j a b)] of a CCSD cycle:
+ *                   d_tnew = d_num / D (D = e_i - e_a, e_i + e_j - e_a - e_b), d_err = d_tnew - d_told, d_out[0] = sum |d_err|^2,
+ *                   d_out[1] = sum_ijab (t2 + t1 t1)(2 (ia|jb) - (ib|ja)) of the NEW amplitudes against d_ovov[i][a][j][b].  Sums are
+ *                   per workgroup, then in workgroup order (d_part: 2 * mi_cc_amp_blocks() doubles of work space): bit-reproducible.
+ * mi_cc_t_energy:   the (T) correction of `ntrip` occupied triples after the GEMMs.  d_raw[6][ntrip][nvir^3]: cube p of triple t is
+ *                   X(pi_p(i, j, k)) in its own index order, pi_p the p-th permutation of three objects in lexicographic order and
+ *                   X(i, j, k)[a][b][c] = sum_d (ia|bd) t2[k][j][c][d] - sum_l (ia|lj) t2[l][k][b][c].  d_ijk[ntrip][3], d_wt[ntrip] the
+ *                   triple's weight, d_t1[nocc][nvir], d_ovov[i][a][j][b], d_eo / d_ev the orbital energies.  d_et[t] = d_wt[t] * sum_abc
+ *                   (4 W_abc + W_bca + W_cab - 2 W_acb - 2 W_cba - 2 W_bac) V_abc / (3 D).  d_part: ntrip * mi_cc_t_blocks(nvir) doubles
+ *                   of work space (one partial sum per workgroup, added in workgroup order: no atomics, bit-reproducible). */
+int mi_cc_amp_blocks(void);
+int mi_cc_amp_update(const double *d_num, const double *d_told, double *d_tnew, double *d_err, const double *d_ovov, const double *d_eo,
+                     const double *d_ev, int nocc, int nvir, double *d_part, double *d_out, void *stream);
+int mi_cc_t_blocks(int nvir);
+int mi_cc_t_energy(const double *d_raw, int ntrip, int nvir, int nocc, const int32_t *d_ijk, const double *d_wt, const double *d_t1,
+                   const double *d_ovov, const double *d_eo, const double *d_ev, double *d_part, double *d_et, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
