@@ -8932,3 +8932,56 @@ extern "C" int mi_pcm_fock(mi_ctx *c, const double *d_B, int npts, int64_t ld, c
 // Closed-shell coupled cluster (mi_cc_*): the CCSD amplitude update and the (T) permutation / energy pass.
 // =================================================================================================
 #include "cc_kernels.h"
+
+// =================================================================================================
+// Restricted open-shell SCF (mi_rohf_fock): Roothaan's effective Fock operator, its orbital gradient and the gradient's norms.
+// =================================================================================================
+// Orbital classes in MO order: closed [0, ncore), open [ncore, ncore + nopen), virtual [ncore + nopen, nmo).  With Fc = (Fa + Fb) / 2
+// the element (i, j) of F_eff is Fc inside a class and between closed and virtual, Fb between closed and open, Fa between open
+// and virtual (PySCF's default Roothaan coefficients).  The inter-class elements are the ROHF orbital gradient; as the CDIIS
+// error vector they take the sign of the occupation commutator F n - n F:  G[i][j] = sgn(class(i) - class(j)) F_eff[i][j].
+// One thread per element and output (grid-stride over a fixed grid), plain loads and stores; sum |G|^2 and max |G| per workgroup
+// by wave shuffles and a fixed-order pass over the waves, so the figures are bit-reproducible.
+#define ROHF_BLOCKS 64
+
+__global__ __launch_bounds__(256) void rohf_fock_kernel(const double *__restrict__ fa, const double *__restrict__ fb, int64_t ld, int ncore, int nopen,
+                                                        int nmo, double *__restrict__ feff, double *__restrict__ g, double *__restrict__ part)
+{
+    __shared__ double red[4], redm[4];
+    const size_t n = (size_t)nmo * nmo;
+    const int nocc = ncore + nopen;
+    double s = 0.0, m = 0.0;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (size_t)gridDim.x * blockDim.x) {
+        const int i = (int)(idx / nmo), j = (int)(idx - (size_t)i * nmo);
+        const int ci = (i >= ncore) + (i >= nocc), cj = (j >= ncore) + (j >= nocc);
+        const size_t at = (size_t)i * ld + j;
+        const double a = fa[at], b = fb[at];
+        const int lo = ci < cj ? ci : cj, hi = ci < cj ? cj : ci;
+        const double f = (lo == 0 && hi == 1) ? b : ((lo == 1 && hi == 2) ? a : 0.5 * (a + b));
+        const double gv = ci > cj ? f : (ci < cj ? -f : 0.0);
+        feff[at] = f;
+        g[at] = gv;
+        s += gv * gv;
+        m = fmax(m, fabs(gv));
+    }
+    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
+    if ((threadIdx.x & 63) == 0) redm[threadIdx.x >> 6] = m;
+    s = cc_block_sum(s, red);       // (its barriers also publish redm)
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = s;
+        part[ROHF_BLOCKS + blockIdx.x] = fmax(fmax(redm[0], redm[1]), fmax(redm[2], redm[3]));
+    }
+}
+
+extern "C" int mi_rohf_fock_blocks(void) { return ROHF_BLOCKS; }
+
+extern "C" int mi_rohf_fock(const double *d_fa, const double *d_fb, int64_t ld, int ncore, int nopen, int nmo, double *d_feff, double *d_g,
+                            double *d_part, void *stream)
+{
+    if (nmo < 1 || nmo > 46340 || ncore < 0 || nopen < 0 || (int64_t)ncore + nopen > nmo || ld < nmo)
+        return fail("mi_rohf_fock: ncore = %d, nopen = %d, nmo = %d, ld = %lld", ncore, nopen, nmo, (long long)ld);
+    if (!d_fa || !d_fb || !d_feff || !d_g || !d_part) return fail("mi_rohf_fock: bad argument");
+    hipLaunchKernelGGL(rohf_fock_kernel, dim3(ROHF_BLOCKS), dim3(256), 0, (hipStream_t)stream, d_fa, d_fb, ld, ncore, nopen, nmo, d_feff, d_g, d_part);
+    HIPCHK(hipGetLastError());
+    return 0;
+}

@@ -1,3 +1,4 @@
-from . import rks, uks  # noqa: F401
+from . import rks, uks, roks  # noqa: F401
 RKS = rks.RKS
 UKS = uks.UKS
+ROKS = roks.ROKS

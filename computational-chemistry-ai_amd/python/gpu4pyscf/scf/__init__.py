@@ -1,3 +1,4 @@
-from . import hf, uhf  # noqa: F401
+from . import hf, uhf, rohf  # noqa: F401
 RHF = hf.RHF
 UHF = uhf.UHF
+ROHF = rohf.ROHF

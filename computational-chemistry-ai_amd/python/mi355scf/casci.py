@@ -1,5 +1,6 @@
 """Complete-active-space CI behind `pyscf.mcscf.CASCI(mf, ncas, nelecas)` (`templates/calculate_casscf.py:121-137`, the
-`--casci-only` branch) for a converged closed-shell RHF on one GPU with the resident, unsharded, full-Coulomb ERI store.
+`--casci-only` branch) for a converged closed-shell RHF, or an ROHF whose singly occupied orbitals all lie in the active block, on
+one GPU with the resident, unsharded, full-Coulomb ERI store.
 
     Dc     = 2 Cc Cc^T                                  density of the `ncore` doubly occupied orbitals
     Vc     = J(Dc) - 1/2 K(Dc)                          one J/K pass over the resident tiles
@@ -13,7 +14,7 @@ and `ci` a list.  `natorb = True` rotates the active block to the natural orbita
 CI again in them (so `ci` belongs to the returned `mo_coeff`) and fills `mo_occ`.  There is no canonicalisation: `mo_energy` is
 the diagonal of the reference's Fock matrix in the returned orbitals.
 
-Not implemented (refused with NotImplementedError, never approximated): RKS / UHF / UKS references, density fitting, PCM,
+Not implemented (refused with NotImplementedError, never approximated): RKS / ROKS / UHF / UKS references, an open-shell core, density fitting, PCM,
 sharded or direct-mode references, orbital optimisation (CASSCF), state averaging.
 """
 import sys
@@ -24,9 +25,13 @@ import torch
 from . import fci
 
 
-def check_rhf_reference(mf, who, unrestricted="UHF / UKS references are not supported (closed-shell RHF only)"):
-    """Refuse every reference but a closed-shell RHF of this engine on one GPU (shared by `CASCI` and `ccsd.CCSD`)."""
-    if not getattr(mf, "_spin_restricted", True):
+def check_rhf_reference(mf, who, unrestricted="UHF / UKS references are not supported (closed-shell RHF only)", rohf=False):
+    """Refuse every reference but a closed-shell RHF of this engine on one GPU (shared by `CASCI` and `ccsd.CCSD`); `rohf`: an
+    engine ROHF (one orbital set, occupations 2 / 1 / 0) passes too."""
+    if getattr(mf, "_rohf", False):
+        if not rohf:
+            raise NotImplementedError(f"{who}: restricted open-shell (ROHF / ROKS) references are not supported")
+    elif not getattr(mf, "_spin_restricted", True):
         raise NotImplementedError(f"{who}: {unrestricted}")
     if getattr(mf, "xc", None) is not None:
         raise NotImplementedError(f"{who}: Kohn-Sham references (xc = {mf.xc!r}) are not supported (closed-shell RHF only)")
@@ -45,12 +50,18 @@ class CASCI:
     natorb = False
 
     def __init__(self, mf, ncas, nelecas, ncore=None):
-        check_rhf_reference(mf, "CASCI")
+        check_rhf_reference(mf, "CASCI", rohf=True)
         self._scf = mf
         self.mol = mf.mol
         self.verbose = mf.verbose
         self.stdout = getattr(mf, "stdout", None)
         self.ncas = int(ncas)
+        spin = int(getattr(self.mol, "spin", 0))
+        if spin and isinstance(nelecas, (int, np.integer)):
+            # PySCF: an electron count on an open-shell molecule takes the molecule's 2 Ms
+            if (int(nelecas) + spin) % 2 or int(nelecas) < spin:
+                raise ValueError(f"CASCI: {nelecas} active electrons cannot carry the molecule's spin = {spin}")
+            nelecas = ((int(nelecas) + spin) // 2, (int(nelecas) - spin) // 2)
         self.nelecas = fci._unpack_nelec(nelecas)
         nel = int(self.mol.nelectron)
         ncore_el = nel - sum(self.nelecas)
@@ -68,6 +79,12 @@ class CASCI:
             raise NotImplementedError(f"CASCI: ncas = {self.ncas}; the FCI solver holds at most {fci.MAX_NORB} orbitals")
         if nmo is not None and self.ncore + self.ncas > nmo:
             raise NotImplementedError(f"CASCI: ncore + ncas = {self.ncore + self.ncas} exceeds the {nmo} molecular orbitals")
+        if getattr(mf, "_rohf", False):
+            na, nb = self.mol.nelec
+            for i in range(nb, na):          # the core density is built closed-shell: no singly occupied orbital may fall outside
+                if not self.ncore <= i < self.ncore + self.ncas:
+                    raise NotImplementedError(f"CASCI: the singly occupied orbital {i} of the ROHF reference lies outside the active "
+                                              f"block [{self.ncore}, {self.ncore + self.ncas}): an open-shell core is not supported")
         self.fcisolver = fci.FCISolver(self.mol)
         self.e_tot = self.e_cas = self.ci = None
         self.mo_coeff = mf.mo_coeff
@@ -131,6 +148,8 @@ class CASCI:
         reordering of its orbitals)."""
         mf = self._scf
         D = torch.as_tensor(np.asarray(mf.make_rdm1()), dtype=torch.float64, device=C.device)
+        if D.dim() == 3:                     # ROHF: the spin-summed density, RHF-style J - K / 2
+            D = (D[0] + D[1]).contiguous()
         J, K = mf._jk(D)
         return torch.einsum("pi,pq,qi->i", C, mf._h1 + J - 0.5 * K, C).cpu().numpy()
 

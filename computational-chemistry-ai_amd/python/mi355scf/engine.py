@@ -139,6 +139,7 @@ def lib():
         L.mi_cc_amp_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp]
         L.mi_cc_t_blocks.argtypes = [ci]
         L.mi_cc_t_energy.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.mi_rohf_fock.argtypes = [vp, vp, i64, ci, ci, ci, vp, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -53,6 +53,8 @@ class MP2:
     occ_batch = None        # occupied orbitals per batch of the streaming path (None: from free HBM)
 
     def __init__(self, mf, frozen=None):
+        if getattr(mf, "_rohf", False):
+            raise NotImplementedError("MP2: restricted open-shell (ROHF / ROKS) references are not supported (RHF -> RMP2, UHF -> UMP2)")
         self._scf = mf
         self.mol = mf.mol
         self.verbose = mf.verbose

@@ -68,6 +68,7 @@ class PairDIIS:
 class UHF(SCF):
     _spin_restricted = False
     sp2_min_nao = 200   # below this a per-cycle `eigh` of each spin is cheaper than the purification
+    _purify_spins = True   # the plain loop may purify each spin's Fock matrix instead of diagonalising it (ROHF: never)
 
     def __init__(self, mol):
         SCF.__init__(self, mol)
@@ -334,13 +335,36 @@ class UHF(SCF):
         return dm
 
     def _uorbitals(self, F):
-        """(mo_energy[2, N], mo_coeff[2, N, N]) on the device: one `eigh` of the Cholesky-orthogonalised Fock matrix per spin."""
+        """(mo_energy[2, N], mo_coeff[2, N, N]) on the device: one `eigh` of the Cholesky-orthogonalised Fock matrix per spin
+        (per matrix of the stack `F`: ROHF passes its one effective Fock matrix)."""
         Li = self._Linv
         es, cs = [], []
-        for s_ in range(2):
-            e_, c_ = torch.linalg.eigh(Li @ F[s_] @ Li.T)
+        for f in F:
+            e_, c_ = torch.linalg.eigh(Li @ f @ Li.T)
             es.append(e_); cs.append(Li.T @ c_)
         return torch.stack(es), torch.stack(cs)
+
+    # --- what the plain loop asks of its class (rohf.ROHF overrides them) --------------------
+    def _diis_pair(self, F, dm):
+        """(matrices CDIIS extrapolates and the orbitals come from, their AO error vectors, squared norm of the error vectors in
+        the orthonormal basis as a device scalar) for the Fock pair F of the spin densities dm: the pair itself with
+        F_s D_s S - S D_s F_s."""
+        S, Li = self._S, self._Linv
+        err = torch.stack([F[s_] @ dm[s_] @ S - S @ dm[s_] @ F[s_] for s_ in range(2)])
+        # |g| = |F_vo| of both spins = |[F', D']|_F / sqrt(2) in the orthonormal basis (D' is a projector)
+        eo = torch.stack([Li @ err[s_] @ Li.T for s_ in range(2)])
+        return F, err, torch.sum(eo * eo)
+
+    def _shift_densities(self, dm):
+        """Occupied-space projectors (AO densities of occupation 1) that `level_shift` leaves unshifted, one per matrix of
+        `_diis_pair`."""
+        return dm
+
+    def _n_rotations(self):
+        """Number of independent orbital rotations, the normalisation of |g|."""
+        n = self.engine.nao
+        na, nb = self.nelec
+        return max(na * (n - na) + nb * (n - nb), 1)
 
     def _uresult(self, dm, F, e_tot, mo_e, mo_c, t_start):
         """Results of a finished loop onto the object (host copies of the orbitals, aufbau occupations, plans for the next
@@ -433,12 +457,12 @@ class UHF(SCF):
         mo_e = mo_c = None
 
         def density(cs):
-            ca, cb = cs[0][:, :na], cs[1][:, :nb]
+            ca, cb = cs[0][:, :na], cs[-1][:, :nb]      # (one orbital set: the beta orbitals are the first n_beta of it)
             return torch.stack([ca @ ca.T, cb @ cb.T])
 
         # larger matrices: occupied projector of each spin by SP2 purification (same GEMM-only path as RHF, `scf.py`)
         # instead of a diagonalisation per cycle; orbitals are then only needed once, after convergence
-        use_sp2 = self.eig_method == "sp2" and n >= self.sp2_min_nao
+        use_sp2 = self._purify_spins and self.eig_method == "sp2" and n >= self.sp2_min_nao
         # one purifier per spin for this kernel() only (plans from the traces of its checked runs), starting from the object's
         # pass count
         pur = [Purifier(self, self._purifier.iters) for _ in range(2)]
@@ -476,16 +500,13 @@ class UHF(SCF):
             self._plain_projectors = xs
             return torch.stack(out), None
 
-        def commutator(Fx, dmx):
-            return torch.stack([Fx[s_] @ dmx[s_] @ S - S @ dmx[s_] @ Fx[s_] for s_ in range(2)])
-
-        nvo = max(na * (n - na) + nb * (n - nb), 1)
+        nvo = self._n_rotations()
         de = gnorm = 0.0
-        err = commutator(F, dm)
+        Fd, err, g2 = self._diis_pair(F, dm)
         while cycle < self.max_cycle:
-            Fx = diis.update(F, err) if cycle + 1 >= self.diis_start_cycle else F
+            Fx = diis.update(Fd, err) if cycle + 1 >= self.diis_start_cycle else Fd
             if self.level_shift:   # F_s + shift (S - S D_s S): virtual space of each spin raised (AO form of PySCF's level_shift)
-                Fx = Fx + self.level_shift * (S.unsqueeze(0) - torch.stack([S @ dm[s_] @ S for s_ in range(2)]))
+                Fx = Fx + self.level_shift * (S.unsqueeze(0) - torch.stack([S @ d @ S for d in self._shift_densities(dm)]))
             self._plain_projectors = None
             dm, mo = new_density(Fx)
             if mo is not None:
@@ -499,10 +520,8 @@ class UHF(SCF):
                 self._xc_projector_pair = None          # a failed factorisation poisons itself with NaN: full densities instead
                 F, e_el = self._fock_pair(dm)
             self._xc_projector_pair = None
-            err = commutator(F, dm)
-            # |g| = |F_vo| of both spins = |[F', D']|_F / sqrt(2) in the orthonormal basis (D' is a projector)
-            eo = torch.stack([Li @ err[s_] @ Li.T for s_ in range(2)])
-            ctrl = torch.stack([e_el.reshape(()), torch.sum(eo * eo)])
+            Fd, err, g2 = self._diis_pair(F, dm)
+            ctrl = torch.stack([e_el.reshape(()), g2.reshape(())])
             if sync is not None:
                 sync(ctrl)
             ctrl = ctrl.cpu().numpy()
@@ -520,7 +539,7 @@ class UHF(SCF):
         if use_sp2:
             self._purifier.iters = pur[1 if nb else 0].iters   # the count of the spin purified last carries over to the object
         if self.converged and self.conv_check:
-            mo_e, mo_c = self._uorbitals(F)
+            mo_e, mo_c = self._uorbitals(Fd)
             dm = density(mo_c)
             F, e_el = self._fock_pair(dm)
             e_el = e_el.reshape(1)
@@ -530,7 +549,7 @@ class UHF(SCF):
             self._log(4, f"Extra cycle  E= {e_new:.15g}  delta_E= {e_new - e_tot:.3g}")
             e_tot = e_new
         if mo_e is None or (use_sp2 and not (self.converged and self.conv_check)):
-            mo_e, mo_c = self._uorbitals(F)
+            mo_e, mo_c = self._uorbitals(Fd)
         return self._uresult(dm, F, e_tot, mo_e, mo_c, t_start)
 
     def dip_moment(self, mol=None, dm=None, unit="Debye", verbose=None, **kw):

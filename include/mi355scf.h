@@ -461,6 +461,20 @@ int mi_cc_t_blocks(int nvir);
 int mi_cc_t_energy(const double *d_raw, int ntrip, int nvir, int nocc, const int32_t *d_ijk, const double *d_wt, const double *d_t1,
                    const double *d_ovov, const double *d_eo, const double *d_ev, double *d_part, double *d_et, void *stream);
 
+/* Restricted open-shell SCF (mi355scf/rohf.py).  Context-free; all arrays FP64 on the device.
+ * mi_rohf_fock: Roothaan's effective Fock operator from the alpha and beta Fock matrices in the current MO basis, d_fa / d_fb
+ *               [nmo][ld] row-major (ld >= nmo).  Orbitals [0, ncore) are doubly occupied, [ncore, ncore + nopen) singly, the
+ *               rest empty; with Fc = (Fa + Fb) / 2
+ *                   d_feff[i][j] = Fb between closed and open, Fa between open and virtual, Fc everywhere else,
+ *                   d_g[i][j]    = sgn(class(i) - class(j)) d_feff[i][j]    (class: closed 0, open 1, virtual 2; 0 inside a class),
+ *               the ROHF orbital gradient with the sign pattern of F n - n F (the CDIIS error vector in the MO basis).  Both
+ *               outputs are [nmo][ld]; elements j >= nmo of a row are not touched.  d_part: 2 * mi_rohf_fock_blocks() doubles,
+ *               d_part[b] = partial sum of d_g^2 and d_part[mi_rohf_fock_blocks() + b] = partial max |d_g| of workgroup b (every
+ *               entry is written; the caller adds / maximises them).  No atomics, one writer per element: bit-reproducible. */
+int mi_rohf_fock_blocks(void);
+int mi_rohf_fock(const double *d_fa, const double *d_fb, int64_t ld, int ncore, int nopen, int nmo, double *d_feff, double *d_g,
+                 double *d_part, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
