@@ -441,7 +441,8 @@ struct mi_ctx {
     int opt_task_table = 1;  // wave-per-quartet kernels read (bra, ket) of a task from a table written once per class pair
     int opt_prim_lds = 0;    // Rys kernel: primitive-pair records of the quartet staged in LDS
     int opt_xcd_map = 1;     // ERI kernels: consecutive task chunks stay on one XCD (its L2 merges the pieces of a line)
-    int ao_order = 0;        // order of the current shells[].ao / d_perm
+    int opt_df_batch_max = 0; // mi_df_build / mi_df_grad: at most this many tasks per pass of a class (0: only the hand-over buffer limits a pass)
+    int ao_order = 0;       // order of the current shells[].ao / d_perm
     int *d_perm = nullptr, *d_iperm = nullptr;   // caller AO -> tile AO and back
     std::vector<int> perm, iperm;
     int opt_vmat_xcd = 1;    // xc_vmat: XCD-aware workgroup order (tiles of one split share an XCD's L2)
@@ -815,6 +816,10 @@ extern "C" int mi_set_option(mi_ctx *c, const char *key, double value)
     else if (k == "task_table") c->opt_task_table = (int)value;
     else if (k == "eri_fused") c->opt_eri_fused = (int)value;
     else if (k == "rys_fine") c->opt_rys_fine = (int)value;
+    else if (k == "df_batch_max") {
+        if (!(value >= 0.0) || value > 2147483647.0) return fail("mi_set_option: df_batch_max must be in [0, 2^31)");
+        c->opt_df_batch_max = (int)value;
+    }
     else if (k == "vmat_fold_mt") c->opt_vmat_fold_mt = (int)value;
     else if (k == "work_mb") c->opt_work_mb = (int)value;
     else if (k == "grad_work_mb") c->opt_grad_work_mb = (int)value;
@@ -1623,10 +1628,15 @@ __device__ __forceinline__ void xf_body(const XfArgs &A, const EriArgs *R)
     auto emit_dense = [&](int r, int c, double s) {   // density fitting: dense (ij|P) / (P|Q) output
         int sa = r / A.nsb, sb = r - sa * A.nsb, sc = c / A.nsd;
         int i = ab.ao_i + sa, j = ab.ao_j + sb, k = cd.ao_i + sc;
+        // An element and its mirror image get ONE value from ONE writer, so the output is symmetric to the bit and does not
+        // depend on store order: a pair of one shell with itself holds (a,b) and (b,a), and the two-index driver runs both
+        // (P|Q) and (Q|P) -- equal in exact arithmetic only.  The image with the larger first index writes both places.
         if (A.dense_mode == 1) {
+            if (ab.ao_i == ab.ao_j && i < j) return;
             A.dense_out[((size_t)i * A.nao + j) * A.dense_n + k] = s;
             A.dense_out[((size_t)j * A.nao + i) * A.dense_n + k] = s;
         } else {
+            if (i < k) return;
             A.dense_out[(size_t)i * A.dense_n + k] = s;
             A.dense_out[(size_t)k * A.dense_n + i] = s;
         }
@@ -3222,7 +3232,8 @@ extern "C" int mi_df_build(mi_ctx *c, mi_ctx *aux, double *d_int3c, double *d_in
         X.ni = E.ni; X.nj = E.nj; X.nk = E.nk; X.nl = 1;
         X.dense_out = out; X.dense_mode = mode; X.dense_n = naux;
         const size_t shm2 = sizeof(double) * ((size_t)X.ne * X.nf + (size_t)X.nsab * X.nf);
-        const int64_t per = std::min<int64_t>((int64_t)(WORK_DOUBLES / E.ncomp), (int64_t)1 << 22);
+        int64_t per = std::min<int64_t>((int64_t)(WORK_DOUBLES / E.ncomp), (int64_t)1 << 22);
+        if (c->opt_df_batch_max > 0) per = std::min<int64_t>(per, c->opt_df_batch_max);
         for (int64_t t0 = 0; t0 < ntask; t0 += per) {
             const int nb = (int)std::min<int64_t>(per, ntask - t0);
             E.t0 = t0; E.ntask = nb; X.t0 = t0; X.ntask = nb;
@@ -7645,6 +7656,7 @@ extern "C" int mi_df_grad(mi_ctx *c, mi_ctx *aux, const double *d_Z3, const doub
         if (shm > 160 * 1024) return fail("gradient contraction needs %zu bytes of LDS", shm);
         int64_t per = std::min<int64_t>((int64_t)(WORK_DOUBLES / Ep.ncomp), (int64_t)1 << 22);
         if (nranks > 1) per = std::min<int64_t>(per, std::max<int64_t>(1024, ntask / (8 * nranks)));
+        if (c->opt_df_batch_max > 0) per = std::min<int64_t>(per, c->opt_df_batch_max);
         for (int64_t t0 = 0; t0 < ntask; t0 += per) {
             if ((int)((batch_counter++) % nranks) != rank) continue;
             const int nb = (int)std::min<int64_t>(per, ntask - t0);

@@ -73,6 +73,9 @@ void mi_release_cache(void);
  *                 quartets; 0: every launch screens per wave
  *   "grad_rows", "grad_rows_min", "grad_rows_g32"  row gradient kernel for the mid / high classes (1 = on, default), for
  *                 derivative blocks of at least this many rows (20), two quartets per wave up to 64 rows (1)
+ *   "df_batch_max"  mi_df_build / mi_df_grad (set on the orbital context): at most this many (bra pair, auxiliary shell) tasks per
+ *                 pass of an angular class (0, default: a pass is limited only by the 32 Mi-double hand-over buffer).  The
+ *                 integrals do not depend on it to the bit; tests use a small value to run the several-pass loop
  *   "vmat_xcd"    xc_vmat: XCD-aware workgroup order (1, default: the tiles of one split share an XCD's L2; 0: natural order)
  *   "vmat_wgs"    xc_vmat: workgroups aimed at by the split over the grid points (0 = 1024, two full rounds; -1 = round-1 formula)
  *   "sp2_direct"  planned purification, one launch per pass, N <= 320: 1 = sp2_direct_kernel (MFMA operands loaded straight into

@@ -27,6 +27,13 @@ def test_df_integrals_and_jk_match_oracle(name, basis):
     assert d.naux > 2 * mol.nao
     j3o, j2o = odf.integrals(mol, d.auxmol)
     assert np.abs(d.int2c.cpu().numpy() - j2o).max() < 1e-9
+    # (ij|P) element by element (DF keeps only the whitened tensor: the driver is called again)
+    aux_eng = Engine(d._aux_packed, device=eng.device)
+    int3c = torch.zeros(mol.nao, mol.nao, d.naux, dtype=torch.float64, device=eng.device)
+    eng.df_build(aux_eng, int3c, None)
+    aux_eng.close()
+    assert np.abs(int3c.cpu().numpy() - j3o).max() < 1e-10 * max(1.0, np.abs(j3o).max())
+    del int3c
     D = _sym(mol.nao, 3)
     J, K = d.get_jk(torch.as_tensor(D, device=eng.device))
     Jo, Ko = odf.jk(j3o, j2o, D)
