@@ -4348,6 +4348,205 @@ extern "C" int mi_eri_qtrans(mi_ctx *c, const double *d_C, int nb, int ldc, doub
     return rc;
 }
 
+// =================================================================================================
+// Active-pair Coulomb operators of the resident tiles (mi_eri_active_j; the two-electron input of a CASSCF macro iteration):
+//   Jp[vw][p][q] = sum_rs (pq|rs) Ca[r][v] Ca[s][w],   v >= w packed as v (v + 1) / 2 + w,
+// for up to AJ_WIDTH pairs per pass over the store.  This is the J half of jk_multi_kernel for the symmetric densities
+// D_vw[r][s] = (Ca[r][v] Ca[s][w] + Ca[s][v] Ca[r][w]) / 2 (same weights, same accumulate-then-symmetrise rule, see there), with two
+// differences: the densities are never in memory, and the contractions run on the FP64 matrix unit.
+//
+// A tile read as the 64x64 matrix T[(ij)][(kl)] gives   Jacc[.][I J] += T D_KL   (per tile)   and   Jacc[.][K L] += T^T D_IJ
+// (shared by the tiles of a run: kept in the MFMA accumulators until the run ends), each a 64x64 by 64xN product with one
+// column per pair.  v_mfma_f64_16x16x4_f64 takes the 4x16 slice D[(kl) = 4 s + (lane >> 4)][pair = lane & 15] as ONE double per
+// lane, so a lane builds its density elements from the coefficient rows of its own pair (v, w) in registers -- lane-varying
+// operands are what the matrix unit wants and what the VALU form (wave-uniform operands from scalar loads, as qt_contract)
+// cannot take without first writing the densities to memory.  Wave `wave` of the four owns the 16 output rows
+// 16 wave .. 16 wave + 15 of both products; the A operand is one ds_read_b64 of the tile image per lane and k-step, shared by
+// the NB column blocks.  Result registers (guide: col = lane & 15, row = (lane >> 4) + 4 reg) go out with one FP64 atomic each
+// into the accumulator Jacc[ld][ld][AJ_WIDTH] (pair index fastest: the 16 lanes of a row group write 128 contiguous bytes).
+// =================================================================================================
+constexpr int AJ_WIDTH = 32;                   // pairs per pass: 2 column blocks of the 16-wide MFMA
+constexpr int AJ_MAXCAS = 16;
+constexpr int AJ_THREADS = 256;
+typedef double d4_t __attribute__((ext_vector_type(4)));
+
+struct AjArgs {
+    TileDir dir;
+    const double *C;           // two [ld][QT_BATCH] panels (orbitals 0..7, 8..15) in tile order, zero-padded
+    double *Jacc;              // [ld][ld][AJ_WIDTH]
+    int ld, nao, n_cached, tri;
+    int m0, n;                 // first pair and number of pairs of this pass (n <= 16 NB)
+};
+
+template <bool NT, int NB>
+__device__ __forceinline__ void aj_segment(const AjArgs &A, double *__restrict__ Tl, const int seg)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int col = lane & 15, g = lane >> 4;
+    const RunHead R = run_head(A.dir, seg, A.nao, A.tri);
+    const int J0 = R.J0, K0 = R.K0, L0 = R.L0;
+    const size_t ld = A.ld;
+    const size_t panel = ld * QT_BATCH;
+    // this lane's pair per column block: offsets of its two orbitals' columns in the coefficient panels; `h` = 1/2 (live) or 0
+    int ov[NB], ow[NB];
+    double h[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) {
+        const int ml = 16 * nb + col, m = A.m0 + ml;
+        int v = 0;
+        while ((v + 1) * (v + 2) / 2 <= m && v < AJ_MAXCAS - 1) v++;
+        const int w = min(m - v * (v + 1) / 2, v);
+        ov[nb] = (v >> 3) * (int)panel + (v & 7);
+        ow[nb] = (w >> 3) * (int)panel + (w & 7);
+        h[nb] = ml < A.n ? 0.5 : 0.0;
+    }
+    const double *__restrict__ Cp = A.C;
+    // D_KL in B-operand form, fixed over the run: k-step s holds (k, l) = (s >> 1, 4 (s & 1) + g)
+    double dkl[NB][16];
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) {
+        double lv[2], lw[2];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const size_t r = (size_t)(L0 + 4 * e + g) * QT_BATCH;
+            lv[e] = h[nb] * Cp[r + ov[nb]];
+            lw[e] = h[nb] * Cp[r + ow[nb]];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const size_t r = (size_t)(K0 + k) * QT_BATCH;
+            const double kv = Cp[r + ov[nb]], kw = Cp[r + ow[nb]];
+#pragma unroll
+            for (int e = 0; e < 2; e++) dkl[nb][2 * k + e] = fma(kv, lw[e], kw * lv[e]);
+        }
+    }
+    // the J rows of D_IJ are fixed over the run as well: j = 4 e + g
+    double jv[NB][2], jw[NB][2];
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++)
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const size_t r = (size_t)(J0 + 4 * e + g) * QT_BATCH;
+            jv[nb][e] = h[nb] * Cp[r + ov[nb]];
+            jw[nb][e] = h[nb] * Cp[r + ow[nb]];
+        }
+    d4_t run[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++) run[nb] = d4_t{0.0, 0.0, 0.0, 0.0};
+    // A-operand bases: row (lane & 15) of this wave's 16, i.e. (2 wave + (col >> 3), col & 7) of the leading index pair
+    const int hi = 2 * wave + (col >> 3), lo = col & 7;
+    const int base_ij = JKM_SI * hi + JKM_SJ * lo + g;           // + JKM_SK * k + 4 e   : T[(i j)][(k l)]
+    const int base_kl = JKM_SK * hi + lo + JKM_SJ * g;           // + JKM_SI * i + 4 JKM_SJ e : T[(i j)][(k l)] read by (k l)
+    for (int t = 0; t < R.count; t++) {
+        const TileHead H = tile_head(R, tile_entry(A.dir, R.first + t), A.nao, A.tri);
+        const int I0 = H.I0;
+        __syncthreads();   // the previous tile's image is no longer read
+        load_tile_image<NT, AJ_THREADS>(A.dir.tiles, Tl, H.toff, H.bi, R.bk, H.dij, R.dkl);
+        // D_IJ of this tile while the image settles: k-step s holds (i, j) = (s >> 1, 4 (s & 1) + g)
+        double dij[NB][16];
+#pragma unroll
+        for (int nb = 0; nb < NB; nb++)
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const size_t r = (size_t)(I0 + i) * QT_BATCH;
+                const double iv = Cp[r + ov[nb]], iw = Cp[r + ow[nb]];
+#pragma unroll
+                for (int e = 0; e < 2; e++) dij[nb][2 * i + e] = fma(iv, jw[nb][e], iw * jv[nb][e]);
+            }
+        __syncthreads();
+        d4_t acc[NB];
+#pragma unroll
+        for (int nb = 0; nb < NB; nb++) acc[nb] = d4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < 16; s++) {
+            const double x = Tl[base_ij + JKM_SK * (s >> 1) + 4 * (s & 1)];
+            const double y = Tl[base_kl + JKM_SI * (s >> 1) + 4 * JKM_SJ * (s & 1)];
+#pragma unroll
+            for (int nb = 0; nb < NB; nb++) {
+                acc[nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(x, dkl[nb][s], acc[nb], 0, 0, 0);
+                run[nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(y, dij[nb][s], run[nb], 0, 0, 0);
+            }
+        }
+        // result register q: row g + 4 q of the wave's 16 = (i, j) = (2 wave + (q >> 1), g + 4 (q & 1))
+#pragma unroll
+        for (int nb = 0; nb < NB; nb++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const double val = acc[nb][q];
+                if (16 * nb + col < A.n && val != 0.0)
+                    atomicAdd(&A.Jacc[((size_t)(I0 + 2 * wave + (q >> 1)) * ld + J0 + g + 4 * (q & 1)) * AJ_WIDTH + 16 * nb + col], val);
+            }
+    }
+#pragma unroll
+    for (int nb = 0; nb < NB; nb++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const double val = run[nb][q];
+            if (16 * nb + col < A.n && val != 0.0)
+                atomicAdd(&A.Jacc[((size_t)(K0 + 2 * wave + (q >> 1)) * ld + L0 + g + 4 * (q & 1)) * AJ_WIDTH + 16 * nb + col], val);
+        }
+}
+
+template <bool NT, int NB>
+__global__ __launch_bounds__(AJ_THREADS) void eri_active_j_kernel(AjArgs A)
+{
+    __shared__ double Tl[JKM_LDS];
+    for_work_items<NT, true>(A.dir, A.n_cached, [&](const int seg, auto nt) __attribute__((always_inline)) {
+        aj_segment<nt(), NB>(A, Tl, seg);
+    });
+}
+
+// Jp[m0 + m][p][q] = 2 (Jacc[p'][q'][m] + Jacc[q'][p'][m]) in the caller's AO order (x' = perm[x]): exactly symmetric
+__global__ void aj_finalize_kernel(const double *Jacc, double *Jp, int n, int nao, int ld, const int *__restrict__ perm)
+{
+    const size_t nn = (size_t)nao * nao;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nn * n) return;
+    const int m = (int)(idx % n);
+    const size_t e = idx / n;
+    const size_t r = perm[e / nao], c = perm[e % nao];
+    Jp[(size_t)m * nn + e] = 2.0 * (Jacc[(r * ld + c) * AJ_WIDTH + m] + Jacc[(c * ld + r) * AJ_WIDTH + m]);
+}
+
+extern "C" int mi_eri_active_j_width(void) { return AJ_WIDTH; }
+
+extern "C" int mi_eri_active_j(mi_ctx *c, const double *d_Ca, int ncas, int ldc, double *d_Jp, void *stream)
+{
+    if (!c || !d_Ca || !d_Jp || ncas < 1 || ncas > AJ_MAXCAS || ldc < ncas) return fail("mi_eri_active_j: bad argument (1 <= ncas <= 16, ldc >= ncas)");
+    if (!c->eri_ready) return fail("mi_eri_active_j: call mi_eri_prepare first");
+    if (c->nranks != 1) return fail("mi_eri_active_j: needs the whole (unsharded) tile store");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ld = c->ldp, nn = (size_t)c->nao * c->nao;
+    const int npair = ncas * (ncas + 1) / 2;
+    DevBuf<double> d_acc, d_Cp;
+    if (d_acc.alloc(ld * ld * AJ_WIDTH) != hipSuccess || d_Cp.alloc(2 * ld * QT_BATCH) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("mi_eri_active_j: no device memory");
+    }
+    for (int o0 = 0; o0 < AJ_MAXCAS; o0 += QT_BATCH)   // orbitals beyond ncas: zero columns
+        hipLaunchKernelGGL(qt_pad_coeff_kernel, dim3((unsigned)((ld * QT_BATCH + 255) / 256)), dim3(256), 0, st, d_Ca + std::min(o0, ncas - 1), ldc,
+                           std::max(0, std::min(QT_BATCH, ncas - o0)), c->nao, (int)ld, d_Cp.get() + (size_t)(o0 / QT_BATCH) * ld * QT_BATCH, c->d_iperm);
+    const bool nt = jk_stream_nt(c);
+    int rc = 0;
+    for (int m0 = 0; m0 < npair && !rc; m0 += AJ_WIDTH) {
+        const int n = std::min(AJ_WIDTH, npair - m0);
+        if (hipMemsetAsync(d_acc, 0, sizeof(double) * ld * ld * AJ_WIDTH, st) != hipSuccess) { rc = fail("mi_eri_active_j: memset failed"); break; }
+        if (c->n_tiles > 0) {
+            AjArgs A{tile_dir(c), d_Cp, d_acc, (int)ld, c->nao, c->n_jk_cached, c->tri, m0, n};
+            with_flags([&](auto NT, auto WIDE) {
+                hipLaunchKernelGGL((eri_active_j_kernel<NT(), WIDE() ? 2 : 1>), dim3(c->n_jk_waves), dim3(AJ_THREADS), 0, st, A);
+            }, nt, n > 16);
+        }
+        hipLaunchKernelGGL(aj_finalize_kernel, dim3((unsigned)((nn * n + 255) / 256)), dim3(256), 0, st, d_acc.get(), d_Jp + (size_t)m0 * nn, n,
+                           c->nao, (int)ld, c->d_perm);
+        if (hipGetLastError() != hipSuccess) rc = fail("mi_eri_active_j: kernel launch failed");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail("mi_eri_active_j: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
 extern "C" int mi_time_jk_variant(mi_ctx *c, const double *d_D, int with_j, int with_k, int reps, double *ms, void *stream)
 {
     if (!c || !d_D || !ms || reps < 1 || (!with_j && !with_k)) return fail("mi_time_jk_variant: bad argument");

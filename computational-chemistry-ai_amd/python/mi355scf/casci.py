@@ -15,7 +15,7 @@ CI again in them (so `ci` belongs to the returned `mo_coeff`) and fills `mo_occ`
 the diagonal of the reference's Fock matrix in the returned orbitals.
 
 Not implemented (refused with NotImplementedError, never approximated): RKS / ROKS / UHF / UKS references, an open-shell core, density fitting, PCM,
-sharded or direct-mode references, orbital optimisation (CASSCF), state averaging.
+sharded or direct-mode references.  Orbital optimisation and state averaging are `casscf.CASSCF` (re-exported here).
 """
 import sys
 
@@ -216,8 +216,9 @@ class CASCI:
         return 2.0 * Cc @ Cc.T + Ca @ dm_act @ Ca.T
 
 
-class CASSCF:
-    """Orbital optimisation is not implemented (`CASCI` is): constructing this raises."""
-
-    def __init__(self, *a, **kw):
-        raise NotImplementedError("mcscf.CASSCF: orbital optimisation is not implemented; mcscf.CASCI (fixed orbitals) is")
+def __getattr__(name):
+    """`CASSCF` (orbital optimisation, `casscf.py`) subclasses `CASCI` above, so it is imported on first use."""
+    if name == "CASSCF":
+        from .casscf import CASSCF
+        return CASSCF
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -71,6 +71,7 @@ def lib():
         L.mi_build_jk_multi.argtypes = [vp, vp, ctypes.c_int, ip, vp, vp, vp]
         L.mi_eri_unpack.argtypes = [vp, vp, vp]
         L.mi_eri_qtrans.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
+        L.mi_eri_active_j.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
         L.mi_time_jk_kernel.argtypes = [vp, vp, ctypes.c_int, dp, vp]
         L.mi_time_jk_variant.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, vp]
         L.mi_diis_errvec.argtypes = [vp, vp, vp, vp]
@@ -403,6 +404,30 @@ class Engine:
         if nb:
             with torch.cuda.device(self.device):
                 _check(lib().mi_eri_qtrans(self._h, C.data_ptr(), nb, nb, out.data_ptr(), self._stream()))
+        return out
+
+    @staticmethod
+    def active_pair_width():
+        """Pairs `active_pair_j` finishes per pass over the store (more run as several passes)."""
+        return int(lib().mi_eri_active_j_width())
+
+    def active_pair_j(self, Ca):
+        """Jp[vw, p, q] = sum_rs (pq|rs) Ca[r, v] Ca[s, w] for the pairs v >= w of the columns of Ca [N, ncas <= 16], packed as
+        vw = v (v + 1) / 2 + w (mi_eri_active_j): device tensor [ncas (ncas + 1) / 2, N, N], exactly symmetric in (p, q).
+        Unsharded resident store only."""
+        if not self.eri_ready:
+            self.prepare_eri()
+        C = torch.as_tensor(Ca, dtype=torch.float64, device=self.device)
+        if C.dim() == 1:
+            C = C[:, None]
+        C = C.contiguous()
+        n = self.nao
+        if C.dim() != 2 or C.shape[0] != n or not 1 <= C.shape[1] <= 16:
+            raise ValueError(f"active_pair_j: Ca must be [{n}, ncas] with 1 <= ncas <= 16")
+        nc = C.shape[1]
+        out = self._new(nc * (nc + 1) // 2, n, n)
+        with torch.cuda.device(self.device):
+            _check(lib().mi_eri_active_j(self._h, C.data_ptr(), nc, nc, out.data_ptr(), self._stream()))
         return out
 
     def time_jk_kernel(self, dm, reps=20, with_j=True, with_k=True):

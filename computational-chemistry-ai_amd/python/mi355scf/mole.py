@@ -266,6 +266,41 @@ class Mole:
                 out[ia] = (idx[0], idx[-1] + 1, loc[idx[0]], loc[idx[-1] + 1])
         return out
 
+    # --- AO labels ------------------------------------------------------------------------------
+    _AO_M = {0: [""], 1: ["x", "y", "z"], 2: ["xy", "yz", "z^2", "xz", "x2-y2"],
+             3: ["-3", "-2", "-1", "+0", "+1", "+2", "+3"], 4: ["-4", "-3", "-2", "-1", "+0", "+1", "+2", "+3", "+4"]}
+
+    def ao_labels(self, fmt=True):
+        """One label per AO in this engine's spherical order, PySCF's spelling [MEM]: "0 C 2px" = atom index, element, principal
+        number (counted per atom and angular momentum from l + 1), shell letter and component (p: x, y, z; d: xy, yz, z^2, xz,
+        x2-y2; f, g: m = -l .. +l).  fmt=False: tuples (atom, element, "2p", "x")."""
+        out = []
+        count = {}
+        for ia, l in zip(self._bas[:, ATOM_OF], self._bas[:, ANG_OF]):
+            ia, l = int(ia), int(l)
+            n = count.get((ia, l), l) + 1
+            count[(ia, l)] = n
+            sym = self.atom_pure_symbol(ia)
+            for m in self._AO_M[l]:
+                t = (ia, sym, f"{n}{'spdfg'[l]}", m)
+                out.append(f"{t[0]} {t[1]} {t[2]}{t[3]}" if fmt else t)
+        return out
+
+    def search_ao_label(self, label):
+        """Indices of the AOs whose label matches `label`: a string or a list of strings, each a regular expression searched in
+        the label (a plain substring such as "C 2p" is one; a string that is no valid expression is matched as a substring)."""
+        pats = [label] if isinstance(label, str) else list(label)
+        labs = self.ao_labels()
+        hit = np.zeros(len(labs), dtype=bool)
+        for pat in pats:
+            try:
+                rx = re.compile(str(pat))
+                test = lambda s: rx.search(s) is not None
+            except re.error:
+                test = lambda s, pat=str(pat): pat in s
+            hit |= np.array([test(s) for s in labs], dtype=bool)
+        return np.where(hit)[0]
+
     def energy_nuc(self):
         z = self.atom_charges().astype(np.float64)
         c = self.atom_coords()

@@ -191,6 +191,18 @@ int mi_eri_unpack(mi_ctx *ctx, double *d_out, void *stream);
 int mi_eri_qtrans(mi_ctx *ctx, const double *d_C, int nb, int ldc, double *d_Y, void *stream);
 int mi_eri_qtrans_batch(void);
 
+/* Active-pair Coulomb operators straight from the resident tiles (the two-electron input of a CASSCF macro iteration,
+ * `mcscf.CASSCF(mf, ncas, nelecas).kernel()` in templates/calculate_casscf.py):
+ *   Jp[vw][p][q] = sum_rs (pq|rs) Ca[r][v] Ca[s][w],  v >= w packed as vw = v (v + 1) / 2 + w,  npair = ncas (ncas + 1) / 2,
+ * d_Ca: [nao][ldc] device (column v of row r at d_Ca[r * ldc + v], ldc >= ncas, 1 <= ncas <= 16), d_Jp: [npair][nao][nao] device,
+ * caller's AO order, exactly symmetric in (p, q); screened-out tiles contribute zero.  The pair densities are formed on the
+ * chip from the coefficient rows, never read from memory; one streaming pass over the store per mi_eri_active_j_width() (= 32)
+ * pairs.  Allocates a padded accumulator of 32 (8 ceil(nao / 8) + 8)^2 doubles for the duration of the call and synchronises
+ * `stream` before returning.  Unsharded contexts only (error otherwise, and before mi_eri_prepare).  Project-defined; stands
+ * in for the (pq|vw) class of pyscf.mcscf.mc_ao2mo [MEM]. */
+int mi_eri_active_j(mi_ctx *ctx, const double *d_Ca, int ncas, int ldc, double *d_Jp, void *stream);
+int mi_eri_active_j_width(void);
+
 /* Time `reps` back-to-back launches of the J/K digestion kernel alone with HIP events on `stream`
  * and return the average milliseconds per launch (bench.py's roofline leg). */
 int mi_time_jk_kernel(mi_ctx *ctx, const double *d_D, int reps, double *ms_per_launch, void *stream);
