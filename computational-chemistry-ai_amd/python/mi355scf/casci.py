@@ -2,11 +2,10 @@
 `--casci-only` branch) for a converged closed-shell RHF, or an ROHF whose singly occupied orbitals all lie in the active block, on
 one GPU with the resident, unsharded, full-Coulomb ERI store.
 
-    Dc     = 2 Cc Cc^T                                  density of the `ncore` doubly occupied orbitals
-    Vc     = J(Dc) - 1/2 K(Dc)                          one J/K pass over the resident tiles
-    E_core = E_nuc + Tr[Dc (h + 1/2 Vc)]
-    h_act  = Ca^T (h + Vc) Ca
-    (tu|vw)  from Y[t,p,q,r] = sum_s Ca[s,t] (sp|qr)    (`Engine.eri_qtrans`) and three small GEMMs
+    F^I, E_core                                         frozen-core Fock matrix and energy of the `ncore` doubly occupied
+                                                        orbitals, one J/K pass over the resident tiles (`ao2mo.core_fock`)
+    h_act  = Ca^T F^I Ca
+    (tu|vw)                                             `ao2mo.transform` of the active block, then `ao2mo.symmetrize8`
     E_tot  = E_core + lowest eigenvalue(s) of the active-space Hamiltonian      (`fci.FCISolver`)
 
 `kernel()` returns PySCF's 5-tuple (e_tot, e_cas, ci, mo_coeff, mo_energy); with `fcisolver.nroots > 1` the energies are arrays
@@ -23,27 +22,7 @@ import numpy as np
 import torch
 
 from . import fci
-
-
-def check_rhf_reference(mf, who, unrestricted="UHF / UKS references are not supported (closed-shell RHF only)", rohf=False):
-    """Refuse every reference but a closed-shell RHF of this engine on one GPU (shared by `CASCI` and `ccsd.CCSD`); `rohf`: an
-    engine ROHF (one orbital set, occupations 2 / 1 / 0) passes too."""
-    if getattr(mf, "_rohf", False):
-        if not rohf:
-            raise NotImplementedError(f"{who}: restricted open-shell (ROHF / ROKS) references are not supported")
-    elif not getattr(mf, "_spin_restricted", True):
-        raise NotImplementedError(f"{who}: {unrestricted}")
-    if getattr(mf, "xc", None) is not None:
-        raise NotImplementedError(f"{who}: Kohn-Sham references (xc = {mf.xc!r}) are not supported (closed-shell RHF only)")
-    if getattr(mf, "with_df", None) is not None:
-        raise NotImplementedError(f"{who}: density-fitted references are not supported")
-    if getattr(mf, "_pcm", False) or getattr(mf, "with_solvent", None) is not None:
-        raise NotImplementedError(f"{who}: PCM-solvated references are not supported")
-    if getattr(mf, "_nranks", 1) > 1:
-        raise NotImplementedError(f"{who}: sharded references are not supported (one GPU, unsharded ERI store)")
-    if not all(hasattr(type(mf), a) for a in ("_jk", "_setup_once", "engine")) or not hasattr(mf, "mo_coeff"):    # `engine` is a property
-                                                                                                                  # that opens the GPU
-        raise NotImplementedError(f"{who}: {type(mf).__name__} is not an RHF object of this engine")
+from .ao2mo import check_rhf_reference, core_fock, resident_engine, symmetrize8, transform
 
 
 class CASCI:
@@ -111,35 +90,14 @@ class CASCI:
 
     # ---- integrals ------------------------------------------------------------------------------------------------------------
     def _prepare(self, mo):
-        mf = self._scf
-        mf._setup_once()
-        if getattr(mf, "_stream_groups", 1) > 1:
-            raise NotImplementedError("CASCI: the ERI store does not fit (direct mode); not supported")
-        eng = mf.engine
-        dev, n = eng.device, eng.nao
-        C = torch.as_tensor(np.ascontiguousarray(mo), dtype=torch.float64, device=dev)
-        if C.shape[0] != n or self.ncore + self.ncas > C.shape[1]:
-            raise ValueError(f"CASCI: mo_coeff of shape {tuple(C.shape)} for {n} AOs, ncore + ncas = {self.ncore + self.ncas}")
-        Cc, Ca = C[:, :self.ncore], C[:, self.ncore:self.ncore + self.ncas].contiguous()
-        h = mf._h1
-        e_core = float(self.mol.energy_nuc())
-        heff = h
-        if self.ncore:
-            Dc = 2.0 * Cc @ Cc.T
-            J, K = mf._jk(Dc)
-            Vc = J - 0.5 * K
-            e_core += float(torch.sum(Dc * (h + 0.5 * Vc)))
-            heff = h + Vc
+        eng = resident_engine(self._scf, "CASCI")
+        C = torch.as_tensor(np.ascontiguousarray(mo), dtype=torch.float64, device=eng.device)
+        if C.shape[0] != eng.nao or self.ncore + self.ncas > C.shape[1]:
+            raise ValueError(f"CASCI: mo_coeff of shape {tuple(C.shape)} for {eng.nao} AOs, ncore + ncas = {self.ncore + self.ncas}")
+        Ca = C[:, self.ncore:self.ncore + self.ncas].contiguous()
+        heff, e_core = core_fock(self._scf, C, self.ncore)
         h_act = Ca.T @ heff @ Ca
-        nc = self.ncas
-        Y = eng.eri_qtrans(Ca)                                            # [t, p, q, r]
-        X = torch.matmul(Ca.T, Y.view(nc, n, n * n))                      # (t u|q r)
-        del Y
-        X = torch.matmul(Ca.T, X.view(nc * nc, n, n))                     # (t u|v r)
-        eri = torch.matmul(X, Ca).view(nc, nc, nc, nc)                    # (t u|v w)
-        eri = 0.5 * (eri + eri.permute(2, 3, 0, 1))                       # the store is screened: restore the exact symmetry
-        eri = 0.5 * (eri + eri.permute(1, 0, 2, 3))
-        eri = 0.5 * (eri + eri.permute(0, 1, 3, 2))
+        eri = symmetrize8(transform(eng, Ca, Ca, [(Ca, Ca)])[0])          # (t u|v w); the store is screened
         h_act = 0.5 * (h_act + h_act.T)
         return h_act.cpu().numpy(), eri.cpu().numpy(), e_core, C
 

@@ -5,7 +5,7 @@ One macro iteration at the orbitals C = [Cc | Ca | Cv]:
 
     Jp[vw]   = sum_rs (pq|rs) Ca[r,v] Ca[s,w]          one pass over the resident tiles (`Engine.active_pair_j`)
     (tu|vw)  = Ca^T Jp[vw] Ca,   (pu|vw) = C^T Jp[vw] Ca
-    Dc = 2 Cc Cc^T,  F^I = h + J(Dc) - K(Dc) / 2,  E_core = E_nuc + Tr[Dc (h + F^I)] / 2,  h_act = Ca^T F^I Ca
+    F^I, E_core: frozen-core Fock matrix and energy (`ao2mo.core_fock`),  h_act = Ca^T F^I Ca
     CI       : `fcisolver.kernel`, warm-started from the previous vectors; gamma, Gamma from `make_rdm12`
     Da = Ca gamma Ca^T,  F^A = J(Da) - K(Da) / 2
     F        : generalised Fock matrix (`generalized_fock`),  g = 2 (F - F^T) on the non-redundant blocks (`orbital_gradient`)
@@ -34,7 +34,7 @@ averages, `e_tot` the weighted energy, `e_states` the per-state energies, `ci` t
 
 The gradient, rotation and step algebra are plain functions of NumPy arrays (tests/test_casscf_host.py drives them on a CPU).
 
-Not implemented (refused with NotImplementedError): everything `casci.check_rhf_reference` refuses, ROHF / ROKS references
+Not implemented (refused with NotImplementedError): everything `ao2mo.check_rhf_reference` refuses, ROHF / ROKS references
 (ROHF-based CASSCF), references that have not been run, direct-mode stores, state-specific excited states (`fcisolver.nroots > 1`
 without `state_average`), nuclear gradients.
 """
@@ -43,7 +43,8 @@ import copy
 import numpy as np
 import torch
 
-from .casci import CASCI, check_rhf_reference
+from .ao2mo import check_rhf_reference, core_fock, resident_engine, symmetrize8
+from .casci import CASCI
 
 RISE_NOISE = 1e-11        # Hartree: an energy "rise" below this is the CI eigenvalue's noise, not a rise
 HDIAG_FLOOR = 0.05        # smallest diagonal Hessian element the preconditioner divides by
@@ -261,9 +262,6 @@ class CASSCF(CASCI):
         return new.state_average_(weights)
 
     # ---- one macro iteration --------------------------------------------------------------------------------------------------
-    def _jk1(self, D):
-        return self._scf._jk(D)
-
     def _macro(self, mo, ci0):
         """Energy, CI, densities and generalised Fock matrix at the orbitals `mo`."""
         mf = self._scf
@@ -272,22 +270,11 @@ class CASSCF(CASCI):
         nocc = ncore + nc
         C = torch.as_tensor(np.ascontiguousarray(mo), dtype=torch.float64, device=eng.device)
         Ca = C[:, ncore:nocc].contiguous()
-        h = mf._h1
         Jp = eng.active_pair_j(Ca)                                         # [npair, N, N]
         puvw = unpack_pairs(torch.matmul(C.T, torch.matmul(Jp, Ca)).cpu().numpy(), nc).transpose(2, 3, 0, 1)   # [p, u, v, w]
         del Jp
-        eri = puvw[ncore:nocc].copy()
-        eri = 0.5 * (eri + eri.transpose(2, 3, 0, 1))                       # the store is screened: restore the exact symmetry
-        eri = 0.5 * (eri + eri.transpose(1, 0, 2, 3))
-        eri = 0.5 * (eri + eri.transpose(0, 1, 3, 2))
-        e_core = float(self.mol.energy_nuc())
-        FI = h
-        if ncore:
-            Cc = C[:, :ncore]
-            Dc = 2.0 * Cc @ Cc.T
-            J, K = self._jk1(Dc)
-            FI = h + J - 0.5 * K
-            e_core += 0.5 * float(torch.sum(Dc * (h + FI)))
+        eri = symmetrize8(torch.from_numpy(puvw[ncore:nocc].copy())).numpy()    # the store is screened
+        FI, e_core = core_fock(mf, C, ncore)
         FI_mo = (C.T @ FI @ C).cpu().numpy()
         FI_mo = 0.5 * (FI_mo + FI_mo.T)
         h_act = FI_mo[ncore:nocc, ncore:nocc].copy()
@@ -310,7 +297,7 @@ class CASSCF(CASCI):
             ci = cis
         gamma = 0.5 * (gamma + gamma.T)
         Da = Ca @ torch.as_tensor(gamma, dtype=torch.float64, device=eng.device) @ Ca.T
-        J, K = self._jk1(Da)
+        J, K = mf._jk(Da)
         FA = J - 0.5 * K
         FA_mo = (C.T @ FA @ C).cpu().numpy()
         FA_mo = 0.5 * (FA_mo + FA_mo.T)
@@ -323,9 +310,7 @@ class CASSCF(CASCI):
     # ---- driver ---------------------------------------------------------------------------------------------------------------
     def kernel(self, mo_coeff=None, ci0=None):
         mf = self._scf
-        mf._setup_once()
-        if getattr(mf, "_stream_groups", 1) > 1:
-            raise NotImplementedError("CASSCF: the ERI store does not fit (direct mode); not supported")
+        resident_engine(mf, "CASSCF")
         if not getattr(mf, "converged", True):
             self._log(2, "CASSCF: the reference SCF is not converged")
         if mo_coeff is None:

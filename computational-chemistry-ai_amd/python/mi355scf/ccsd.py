@@ -2,9 +2,9 @@
 method": `mycc = cc.CCSD(mf); mycc.kernel(); et = mycc.ccsd_t(); return mycc.e_tot + et`) for a converged canonical RHF on one
 GPU with the resident, unsharded ERI tile store.
 
-Integrals.  The active MO space is transformed once per `kernel()`: `Engine.eri_qtrans` batches (sized from free HBM) and three
-FP64 GEMMs per batch give (pq|rs) over the active orbitals, the exact 8-fold symmetry is restored (the store is screened), and
-the blocks oooo, ovoo, oovv, ovov, ovvo, ovvv, vvvv stay on the device.  Everything is held in core: there is NO AO-direct
+Integrals.  The active MO space is transformed once per `kernel()`: `ao2mo.transform` in batches sized from free HBM
+(`ao2mo.plan_qtrans_batch`) gives (pq|rs) over the active orbitals, `ao2mo.symmetrize8` restores the exact 8-fold symmetry (the
+store is screened), and the blocks oooo, ovoo, oovv, ovov, ovvo, ovvv, vvvv stay on the device.  Everything is held in core: there is NO AO-direct
 particle-particle ladder and NO vvvv-free algorithm here; a case whose integrals and work space exceed 80 % of the free HBM
 beside the store is refused with NotImplementedError.
 
@@ -24,7 +24,7 @@ per-workgroup then fixed-order reduction into one number per triple); no v^3 per
 `t_batch`: triples per launch (None: from free HBM).
 
 Settings keep PySCF's names; the defaults (conv_tol 1e-7, conv_tol_normt 1e-5, max_cycle 50, diis_space 6, diis_start_cycle 0)
-and the `frozen` convention (`mp2._active`) are written from memory, not pinned against PySCF.
+and the `frozen` convention (`ao2mo.active_mask`) are written from memory, not pinned against PySCF.
 
 Not implemented (refused with NotImplementedError, never approximated): UHF / UKS references (UCCSD), Kohn-Sham references,
 density fitting, PCM, sharded or direct-mode references, frozen natural orbitals, gradients, lambda equations.
@@ -37,8 +37,8 @@ import numpy as np
 import torch
 
 from . import engine
-from .casci import check_rhf_reference
-from .mp2 import _active
+from .ao2mo import (active_mask, check_rhf_reference, free_hbm, plan_qtrans_batch, qtrans_work_bytes, resident_engine, symmetrize8,
+                    transform)
 
 PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))     # lexicographic, as in csrc/cc_kernels.h
 _Z_COEFF = (4.0, -2.0, -2.0, 1.0, 1.0, -2.0)                                   # identity, transpositions, 3-cycles
@@ -234,7 +234,7 @@ class CCSD:
         mo_c, mo_e, occ = np.asarray(mf.mo_coeff), np.asarray(mf.mo_energy), np.asarray(mf.mo_occ)
         if mo_c.ndim != 2:
             raise NotImplementedError("CCSD: UCCSD is not implemented (closed-shell RHF only)")
-        act = _active(self.frozen, mo_c.shape[1])
+        act = active_mask(self.frozen, mo_c.shape[1])
         o, v = (occ > 0) & act, (occ == 0) & act
         if not o.any() or not v.any():
             raise ValueError(f"CCSD: {int(o.sum())} occupied and {int(v.sum())} virtual orbitals are correlated")
@@ -256,44 +256,25 @@ class CCSD:
             mf.kernel()
         if not getattr(mf, "converged", True):
             self._log(2, "CCSD: the reference SCF is not converged (a canonical, converged RHF is assumed: f_ov = 0)")
-        mf._setup_once()
-        if getattr(mf, "_nranks", 1) > 1:
-            raise NotImplementedError("CCSD: sharded references are not supported (one GPU, unsharded ERI store)")
-        if getattr(mf, "_stream_groups", 1) > 1:
-            raise NotImplementedError("CCSD: the ERI store does not fit (direct mode); not supported")
-        eng = mf.engine
+        eng = resident_engine(mf, "CCSD")
         dev, N = eng.device, eng.nao
         C, eo, ev = self._spaces()
         no, nv = len(eo), len(ev)
         n = no + nv
-        if not eng.eri_ready:
-            eng.prepare_eri()
-        torch.cuda.empty_cache()
-        free, _total = torch.cuda.mem_get_info(dev)
-        ldp = 8 * ((N + 7) // 8) + 8
-        per_orb = 8.0 * (N ** 3 + max(ldp ** 3, n * N * N))          # Y, and the kernel's accumulator or the first GEMM (MP2._plan_batch)
+        per_orb = qtrans_work_bytes(N, n)
         need = self._need_bytes(no, nv, self.diis_space)
-        if need + per_orb > 0.8 * free:
+        nb, free = plan_qtrans_batch(eng, n, per_orb, reserve_bytes=8 * n ** 4)
+        if need + per_orb > 0.8 * free:      # `need` exceeds the reserve, so below this line at least one orbital fits
             raise NotImplementedError(f"CCSD: o = {no}, v = {nv} needs {(need + per_orb) * 1e-9:.1f} GB for the MO integrals and the work "
                                       f"space; {0.8 * free * 1e-9:.1f} GB (80 % of the free HBM beside the ERI store) are available")
-        nb = int((0.8 * free - 8.0 * n ** 4) // per_orb)
-        q = eng.qtrans_batch()
-        nb = max(1, min(n, nb - nb % q if nb > q else nb))
         self._log(4, f"CCSD: o = {no}, v = {nv}; {need * 1e-9:.2f} GB of integrals and work space, qtrans batches of {nb} orbitals")
         t0 = time.perf_counter()
         Cd = torch.as_tensor(np.ascontiguousarray(C), dtype=torch.float64, device=dev)
         eri = torch.empty((n, n, n, n), dtype=torch.float64, device=dev)
         for p0 in range(0, n, nb):
             p1 = min(p0 + nb, n)
-            Y = eng.eri_qtrans(Cd[:, p0:p1])                                       # [p, s, q, r]
-            X = torch.matmul(Cd.T, Y.view(p1 - p0, N, N * N))                      # (p q'|q r)
-            del Y
-            X = torch.matmul(Cd.T, X.view((p1 - p0) * n, N, N))                    # (p q'|r' r)
-            eri[p0:p1] = torch.matmul(X, Cd).view(p1 - p0, n, n, n)
-            del X
-        eri = 0.5 * (eri + eri.permute(2, 3, 0, 1))                                # the store is screened: restore the exact symmetry
-        eri = 0.5 * (eri + eri.permute(1, 0, 2, 3))
-        eri = 0.5 * (eri + eri.permute(0, 1, 3, 2))
+            eri[p0:p1] = transform(eng, Cd[:, p0:p1], Cd, [(Cd, Cd)])[0]
+        eri = symmetrize8(eri)
         o, v = slice(0, no), slice(no, n)
         E = {k: eri[tuple(o if ch == "o" else v for ch in k)].contiguous() for k in ("oooo", "ovoo", "oovv", "ovov", "ovvo", "ovvv", "vvvv")}
         del eri
@@ -383,8 +364,7 @@ class CCSD:
     def _plan_triples(self, nv, ntrip, dev):
         if self.t_batch:
             return max(1, min(int(self.t_batch), ntrip))
-        torch.cuda.empty_cache()
-        free, _total = torch.cuda.mem_get_info(dev)
+        free = free_hbm(dev)
         per = 8.0 * (7 * nv ** 3 + nv * nv * 8)                  # six raw cubes, the gathered (ia|bd), small operands
         nb = int(0.5 * free // per)
         if nb < 1:

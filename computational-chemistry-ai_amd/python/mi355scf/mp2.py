@@ -5,14 +5,13 @@ reference: RHF -> RMP2, UHF -> UMP2).
 `algorithm = "stream"` (default): conventional (not density-fitted) MP2 for any molecule whose ERI tile store is resident
 and unsharded.  For each batch O of active occupied orbitals
 
-    Y[o,p,q,r] = sum_s C[s,o] (sp|qr)       one streaming pass over the resident tiles per 8 orbitals (`Engine.eri_qtrans`)
-    (oa|qr) -> (oa|jr) -> (oa|jb)           three FP64 GEMMs (rocBLAS), for ALL active occupied j
+    (oa|jb) for ALL active occupied j       `ao2mo.transform`: one pass over the resident tiles per 8 orbitals, three FP64 GEMMs
     E += sum_ajb (oa|jb) [2 (oa|jb) - (ob|ja)] / (e_o + e_j - e_a - e_b)
 
 needs only integrals of the batch's own o, so batches are independent and nothing of size N^4 exists.  Memory per orbital
-of a batch: 8 N^3 bytes of Y plus the larger of the kernel's padded accumulator (8 (N_pad + 8)^3) and the first GEMM's
-output (8 n_vir N^2); the batch size is the largest that fits in 80 % of the free HBM beside the store (`occ_batch`
-overrides it).  UMP2 runs alpha batches (alpha-alpha and alpha-beta energies from one Y) and beta batches (beta-beta).
+of a batch: the transformation's work space (`ao2mo.qtrans_work_bytes`) plus the amplitude-sized temporaries of the energy
+step; the batch size is the largest that fits in 80 % of the free HBM beside the store (`ao2mo.plan_qtrans_batch`;
+`occ_batch` overrides it).  UMP2 runs alpha batches (alpha-alpha and alpha-beta energies from one Y) and beta batches (beta-beta).
 
 `algorithm = "dense"`: the earlier path, kept as the cross-check -- the tiles are unpacked to a dense (ij|kl) tensor
 (`mi_eri_unpack`, 8 N^4 bytes, N <= 220) and transformed with torch contractions.
@@ -28,24 +27,10 @@ import time
 import numpy as np
 import torch
 
+from .ao2mo import active_mask as _active, plan_qtrans_batch, qtrans_work_bytes, resident_engine, transform
+
 MAX_NAO = 220   # dense path: 8 * 220^4 = 18.7 GB tensor
 T2_MAX_BYTES = 8 * (MAX_NAO // 2) ** 4   # 1.17 GB: the largest n_occ^2 n_vir^2 amplitude tensor of any N <= MAX_NAO basis
-
-
-def _active(frozen, nmo):
-    act = np.ones(nmo, dtype=bool)
-    if frozen is None:
-        return act
-    if isinstance(frozen, (int, np.integer)):
-        if frozen < 0 or frozen > nmo:
-            raise ValueError(f"frozen = {frozen}: between 0 and {nmo} orbitals can be frozen")
-        act[:int(frozen)] = False
-        return act
-    idx = np.asarray(list(frozen), dtype=int)
-    if idx.size and (idx.min() < 0 or idx.max() >= nmo):
-        raise ValueError(f"frozen: MO indices must lie in [0, {nmo})")
-    act[idx] = False
-    return act
 
 
 class MP2:
@@ -140,53 +125,18 @@ class MP2:
         """Occupied orbitals per batch: what fits in 80 % of the free HBM (see the module docstring), at most `nocc`."""
         eng = self._scf.engine
         n = eng.nao
-        ldp = 8 * ((n + 7) // 8) + 8
-        per_orb = 8.0 * (n ** 3 + max(ldp ** 3, nvir * n * n) + 6 * nvir * max(nocc, 1) * max(nvir, n))
-        if self.occ_batch:
-            nb = max(1, min(int(self.occ_batch), nocc))
-            self._scf._log(4, f"MP2: occupied batch {nb} of {nocc} (occ_batch), {per_orb * nb * 1e-9:.2f} GB of work space")
-            return nb
-        torch.cuda.empty_cache()
-        free, _total = torch.cuda.mem_get_info(eng.device)
-        nb = int(0.8 * free // per_orb)
+        per_orb = qtrans_work_bytes(n, nvir) + 8.0 * 6 * nvir * max(nocc, 1) * max(nvir, n)
+        nb, free = plan_qtrans_batch(eng, nocc, per_orb, forced=self.occ_batch)
         if nb < 1:
             raise MemoryError(f"MP2: one occupied orbital needs {per_orb * 1e-9:.1f} GB of work space (Y[N^3], accumulator, "
                               f"first GEMM), {free * 1e-9:.1f} GB of HBM are free beside the ERI store")
-        q = eng.qtrans_batch()
-        if nb > q:
-            nb -= nb % q        # whole kernel passes
-        nb = min(nb, nocc)
-        self._scf._log(4, f"MP2: occupied batch {nb} of {nocc}: {per_orb * nb * 1e-9:.2f} GB of work space, "
-                          f"{free * 1e-9:.1f} GB of HBM free")
+        self._scf._log(4, f"MP2: occupied batch {nb} of {nocc}: {per_orb * nb * 1e-9:.2f} GB of work space, " +
+                          ("set by occ_batch" if free is None else f"{free * 1e-9:.1f} GB of HBM free"))
         return nb
-
-    def _ovov_batch(self, co_batch, cv, targets):
-        """[(o a|j b) as [nb, nvir, nocc', nvir'] for every (C_occ', C_vir') of `targets`] from one pass over the store."""
-        eng = self._scf.engine
-        n, nb, nv = eng.nao, co_batch.shape[1], cv.shape[1]
-        t0 = time.perf_counter()
-        Y = eng.eri_qtrans(co_batch)                                   # synchronises
-        t1 = time.perf_counter()
-        X = torch.matmul(cv.T, Y.view(nb, n, n * n))                   # (o a|q r)
-        del Y
-        out = []
-        for co2, cv2 in targets:
-            X2 = torch.matmul(co2.T, X.view(nb * nv, n, n))            # (o a|j r)
-            out.append(torch.matmul(X2, cv2).view(nb, nv, co2.shape[1], cv2.shape[1]))
-            del X2
-        del X
-        torch.cuda.synchronize(eng.device)
-        t2 = time.perf_counter()
-        self.timing["qtrans_seconds"] += t1 - t0
-        self.timing["gemm_seconds"] += t2 - t1
-        self.timing["passes"] += -(-nb // eng.qtrans_batch())
-        return out
 
     def _kernel_stream(self, spaces):
         mf = self._scf
         eng = mf.engine
-        if getattr(mf, "_stream_groups", 1) > 1:
-            raise NotImplementedError("MP2 needs the resident ERI tile store: this reference runs in the direct mode")
         dev = eng.device
         self.timing.update(qtrans_seconds=0.0, gemm_seconds=0.0, energy_seconds=0.0, passes=0)
         zero = lambda: torch.zeros((), dtype=torch.float64, device=dev)
@@ -208,7 +158,7 @@ class MP2:
                 nb = self._plan_batch(no, nv)
                 for o0 in range(0, no, nb):
                     sl = slice(o0, min(o0 + nb, no))
-                    ovov, = self._ovov_batch(co[:, sl], cv, [(co, cv)])
+                    ovov, = transform(eng, co[:, sl], cv, [(co, cv)], self.timing)
                     t0 = time.perf_counter()
                     t = ovov / denom(eo[sl], ev, eo, ev)
                     e_os += torch.sum(t * ovov)
@@ -235,7 +185,7 @@ class MP2:
                 nb = self._plan_batch(no, max(nv, cvb.shape[1]))
                 for o0 in range(0, no, nb):
                     sl = slice(o0, min(o0 + nb, no))
-                    res = self._ovov_batch(co[:, sl], cv, targets)
+                    res = transform(eng, co[:, sl], cv, targets, self.timing)
                     t0 = time.perf_counter()
                     ovov = res[0]
                     anti = ovov - ovov.transpose(1, 3)
@@ -256,8 +206,7 @@ class MP2:
             mf.kernel()
         if self.algorithm not in ("stream", "dense"):
             raise ValueError(f"MP2.algorithm = {self.algorithm!r}: 'stream' or 'dense'")
-        if mf._nranks > 1:
-            raise NotImplementedError("MP2 is single-GPU (unsharded tile store)")
+        resident_engine(mf, "MP2")
         mo_c = np.asarray(mf.mo_coeff if mo_coeff is None else mo_coeff)
         mo_e = np.asarray(mf.mo_energy if mo_energy is None else mo_energy)
         occ = np.asarray(mf.mo_occ)

@@ -28,6 +28,8 @@ import warnings
 import numpy as np
 import torch
 
+from .ao2mo import resident_engine
+
 HARTREE2EV = 27.211386245988
 HARTREE2NM = 45.56335252907954   # nm * Hartree: lambda = 45.563... / E
 # Batches of symmetric densities below this size take the looped single-density build: measured per density on
@@ -193,8 +195,6 @@ class _TDBase:
             raise NotImplementedError("TDA/TDDFT: only closed-shell RHF/RKS references are supported (UHF/UKS are not)")
         if getattr(mf, "with_df", None) is not None:
             raise NotImplementedError("TDA/TDDFT: density-fitted references are not supported")
-        if getattr(mf, "_nranks", 1) > 1:
-            raise NotImplementedError("TDA/TDDFT: sharded references are not supported")
         xc = getattr(mf, "xc", None)
         self._omega, self._alpha = 0.0, 0.0
         if xc is None:
@@ -227,13 +227,10 @@ class _TDBase:
         mf = self._scf
         if mf.mo_coeff is None:
             mf.kernel()
-        if getattr(mf, "_stream_groups", 1) > 1:
-            raise NotImplementedError("TDA/TDDFT: the ERI store does not fit (direct mode); not supported")
+        eng = resident_engine(mf, "TDA/TDDFT")
         if self._omega != 0.0:
             from .dft import check_rsh_scf
             check_rsh_scf(mf)
-        mf._setup_once()
-        eng = mf.engine
         dev = eng.device
         occ = np.asarray(mf.mo_occ)
         C = torch.as_tensor(np.asarray(mf.mo_coeff), dtype=torch.float64, device=dev)
