@@ -5757,28 +5757,40 @@ template <class T> __device__ inline T xc_closed_sum(const XcSpec &X, T R, T S)
     return acc;
 }
 
-template <class T> __device__ inline T xc_spin_sum(const XcSpec &X, T Ra, T Rb, T Saa, T Sab, T Sbb)
+// One spin-polarised term e_t(rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb, tau_a, tau_b): the only spin dispatch, behind every
+// kernel that evaluates the spin forms.  MGGA compiles the meta-GGA terms in; without it they are not instantiated (the GGA
+// kernels and the second-order duals of xc_fxc_prep_kernel keep their registers) and the taus are dead.
+template <bool MGGA, class T>
+__device__ inline T xc_term_spin(int kind, double prm, T Ra, T Rb, T Saa, T Sab, T Sbb, T Ta, T Tb)
 {
-    T acc(0.0);
-    for (int t = 0; t < X.n; t++) {
-        T f(0.0);
-        switch (X.kind[t]) {
-        case XC_SLATER: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T) { return f_slater(r); }); break;
-        case XC_B88: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T s_) { return f_b88(r, s_); }); break;
-        case XC_PBE_X: f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T s_) { return f_pbe_x(r, s_); }); break;
-        case XC_B88_SR: {
-            const double om = X.param[t];
-            f = spin_scaled_exchange(Ra, Rb, Saa, Sbb, [om](T r, T s_) { return f_b88_sr(r, s_, om); });
-            break;
-        }
-        case XC_VWN_RPA: f = f_vwn_rpa_spin(Ra, Rb); break;
-        case XC_VWN5: f = f_vwn5_spin(Ra, Rb); break;
-        case XC_LYP: f = f_lyp_spin(Ra, Rb, Saa, Sab, Sbb); break;
-        case XC_PBE_C: f = f_pbe_c_spin(Ra, Rb, Saa, Sab, Sbb); break;
+    switch (kind) {
+    case XC_SLATER: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T) { return f_slater(r); });
+    case XC_B88: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T s_) { return f_b88(r, s_); });
+    case XC_PBE_X: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T s_) { return f_pbe_x(r, s_); });
+    case XC_B88_SR: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [prm](T r, T s_) { return f_b88_sr(r, s_, prm); });
+    case XC_VWN_RPA: return f_vwn_rpa_spin(Ra, Rb);
+    case XC_VWN5: return f_vwn5_spin(Ra, Rb);
+    case XC_LYP: return f_lyp_spin(Ra, Rb, Saa, Sab, Sbb);
+    case XC_PBE_C: return f_pbe_c_spin(Ra, Rb, Saa, Sab, Sbb);
+    default: break;
+    }
+    if constexpr (MGGA) {
+        switch (kind) {
+        case XC_TPSS_X: return f_tpss_x_spin(Ra, Rb, Saa, Sbb, Ta, Tb);
+        case XC_TPSS_C: return f_tpss_c_spin(Ra, Rb, Saa, Sab, Sbb, Ta, Tb);
+        case XC_M062X_X: return f_m062x_x_spin(Ra, Rb, Saa, Sbb, Ta, Tb);
+        case XC_M062X_C: return f_m062x_c_spin(Ra, Rb, Saa, Sbb, Ta, Tb);
         default: break;
         }
-        acc = acc + T(X.coef[t]) * f;
     }
+    return T(0.0);
+}
+
+template <bool MGGA = false, class T>
+__device__ inline T xc_spin_sum(const XcSpec &X, T Ra, T Rb, T Saa, T Sab, T Sbb, T Ta = T(0.0), T Tb = T(0.0))
+{
+    T acc(0.0);
+    for (int t = 0; t < X.n; t++) acc = acc + T(X.coef[t]) * xc_term_spin<MGGA>(X.kind[t], X.param[t], Ra, Rb, Saa, Sab, Sbb, Ta, Tb);
     return acc;
 }
 
@@ -5810,45 +5822,60 @@ __global__ __launch_bounds__(256) void xc_eval_kernel(XcSpec X, const double *rh
 
 // Spin-polarised evaluation (UKS): rho_s[0] = density, rho_s[1..3] = its gradient.  exc[g] = e per volume;
 // wv_s[0] = 0.5 w de/drho_s ; wv_s[1..3] = w (2 de/dsigma_ss grad rho_s + de/dsigma_ab grad rho_s')  (same consumer as the
-// closed-shell wv: V_s = ao^T aow_s + transpose)
-__global__ __launch_bounds__(256) void xc_eval_spin_kernel(XcSpec X, const double *rhoa, const double *rhob, const double *w, int64_t ng,
-                                                           int gga, double *exc, double *wva, double *wvb)
+// closed-shell wv: V_s = ao^T aow_s + transpose).  MGGA: dual numbers over tau_a, tau_b as well, wv_s[4] = 0.25 w de/dtau_s;
+// without it the taus are not read and `gga` chooses between LDA and GGA.
+template <bool MGGA>
+__global__ __launch_bounds__(256) void xc_eval_spin_kernel(XcSpec X, const double *rhoa, const double *rhob, const double *taua,
+                                                           const double *taub, const double *w, int64_t ng, int gga, double *exc,
+                                                           double *wva, double *wvb)
 {
+    constexpr int NV = MGGA ? 7 : 5;
+    typedef DN<NV> D;
     int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= ng) return;
     const double ra = fmax(rhoa[g], 0.0), rb = fmax(rhob[g], 0.0);
     double ga[3] = {0, 0, 0}, gb[3] = {0, 0, 0};
-    if (gga)
+    if (MGGA || gga)
         for (int k = 0; k < 3; k++) { ga[k] = rhoa[(k + 1) * ng + g]; gb[k] = rhob[(k + 1) * ng + g]; }
-    double e = 0.0, v[5] = {0, 0, 0, 0, 0};
+    double e = 0.0, v[NV] = {};
     if (ra + rb > 1e-10) {
-        D5 Ra = D5::var(ra, 0), Rb = D5::var(rb, 1);
-        D5 Saa = D5::var(ga[0] * ga[0] + ga[1] * ga[1] + ga[2] * ga[2], 2);
-        D5 Sab = D5::var(ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2], 3);
-        D5 Sbb = D5::var(gb[0] * gb[0] + gb[1] * gb[1] + gb[2] * gb[2], 4);
-        D5 acc = xc_spin_sum(X, Ra, Rb, Saa, Sab, Sbb);
+        D Ra = D::var(ra, 0), Rb = D::var(rb, 1);
+        D Saa = D::var(ga[0] * ga[0] + ga[1] * ga[1] + ga[2] * ga[2], 2);
+        D Sab = D::var(ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2], 3);
+        D Sbb = D::var(gb[0] * gb[0] + gb[1] * gb[1] + gb[2] * gb[2], 4);
+        D Ta(0.0), Tb(0.0);
+        if constexpr (MGGA) { Ta = D::var(fmax(taua[g], 0.0), 5); Tb = D::var(fmax(taub[g], 0.0), 6); }
+        D acc = xc_spin_sum<MGGA>(X, Ra, Rb, Saa, Sab, Sbb, Ta, Tb);
         e = acc.v;
-        for (int k = 0; k < 5; k++) v[k] = acc.d[k];
+        for (int k = 0; k < NV; k++) v[k] = acc.d[k];
     }
     if (exc) exc[g] = e;
     const double ww = w[g];
     wva[g] = 0.5 * ww * v[0];
     wvb[g] = 0.5 * ww * v[1];
-    if (gga)
+    if (MGGA || gga)
         for (int k = 0; k < 3; k++) {
             wva[(k + 1) * ng + g] = ww * (2.0 * v[2] * ga[k] + v[3] * gb[k]);
             wvb[(k + 1) * ng + g] = ww * (2.0 * v[4] * gb[k] + v[3] * ga[k]);
         }
+    if constexpr (MGGA) {
+        wva[4 * ng + g] = 0.25 * ww * v[5];
+        wvb[4 * ng + g] = 0.25 * ww * v[6];
+    }
 }
 
-// kinds / coefs / params -> XcSpec; `params` (may be NULL) carries each term's runtime parameter: the omega of XC_B88_SR
-static int fill_gga_spec(XcSpec &X, const int32_t *kinds, const double *coefs, const double *params, int nterms, const char *who)
+// kinds / coefs / params -> XcSpec, for every XC entry point.  `params` (may be NULL) carries each term's runtime parameter:
+// the omega of XC_B88_SR, without which that term is refused.  Meta-GGA ids pass only where the caller has tau.
+static int fill_xc_spec(XcSpec &X, const int32_t *kinds, const double *coefs, const double *params, int nterms, bool allow_mgga,
+                        const char *who)
 {
     if (nterms < 0 || nterms > 8) return fail("%s: at most 8 functional terms", who);
     X = XcSpec{};
     X.n = nterms;
     for (int i = 0; i < nterms; i++) {
-        if (!xc_gga_kind(kinds[i])) return fail("%s: unknown functional id %d", who, kinds[i]);
+        const bool mgga = kinds[i] >= XC_TPSS_X && kinds[i] <= XC_M062X_C;
+        if (!xc_gga_kind(kinds[i]) && !mgga) return fail("%s: unknown functional id %d", who, kinds[i]);
+        if (mgga && !allow_mgga) return fail("%s: functional id %d is a meta-GGA (needs tau: mi_xc_eval_mgga*)", who, kinds[i]);
         X.kind[i] = kinds[i]; X.coef[i] = coefs[i]; X.param[i] = params ? params[i] : 0.0;
         if (kinds[i] == XC_B88_SR && !(X.param[i] > 0.0 && std::isfinite(X.param[i])))
             return fail("%s: term %d (short-range B88) needs omega > 0 in params", who, i);
@@ -5856,18 +5883,33 @@ static int fill_gga_spec(XcSpec &X, const int32_t *kinds, const double *coefs, c
     return 0;
 }
 
+// The argument check of the per-point XC entry points: -1 on an error, 0 when there is nothing to launch (ng == 0), else 1.
+static int xc_entry(XcSpec &X, const int32_t *kinds, const double *coefs, const double *params, int nterms, bool allow_mgga,
+                    bool null_argument, int64_t ng, const char *who)
+{
+    if (null_argument) return fail("%s: null argument", who);
+    if (ng < 0) return fail("%s: negative number of grid points", who);
+    if (fill_xc_spec(X, kinds, coefs, params, nterms, allow_mgga, who)) return -1;
+    return ng > 0;
+}
+
+// ... and their launch: one thread per grid point
+template <class... P, class... A> static int xc_launch(void (*kernel)(P...), int64_t ng, void *stream, A... args)
+{
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, args...);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int mi_xc_eval_spin_p(const int32_t *kinds, const double *coefs, const double *params, int nterms, const double *d_rhoa,
                                  const double *d_rhob, const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wva, double *d_wvb,
                                  void *stream)
 {
-    if (!d_rhoa || !d_rhob || !d_w || !d_wva || !d_wvb) return fail("mi_xc_eval_spin: null argument");
     XcSpec X;
-    if (fill_gga_spec(X, kinds, coefs, params, nterms, "mi_xc_eval_spin")) return -1;
-    if (ng <= 0) return 0;
-    hipLaunchKernelGGL(xc_eval_spin_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, d_rhoa, d_rhob, d_w,
-                       ng, gga, d_exc, d_wva, d_wvb);
-    HIPCHK(hipGetLastError());
-    return 0;
+    const int go = xc_entry(X, kinds, coefs, params, nterms, false, !d_rhoa || !d_rhob || !d_w || !d_wva || !d_wvb, ng, "mi_xc_eval_spin");
+    if (go <= 0) return go;
+    return xc_launch(xc_eval_spin_kernel<false>, ng, stream, X, d_rhoa, d_rhob, (const double *)nullptr, (const double *)nullptr, d_w,
+                     ng, gga, d_exc, d_wva, d_wvb);
 }
 
 extern "C" int mi_xc_eval_spin(const int32_t *kinds, const double *coefs, int nterms, const double *d_rhoa, const double *d_rhob,
@@ -5880,13 +5922,10 @@ extern "C" int mi_xc_eval_p(const int32_t *kinds, const double *coefs, const dou
                             const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wv, double *d_vrho, double *d_vsigma,
                             void *stream)
 {
-    if (!d_rho || (d_wv && !d_w)) return fail("mi_xc_eval: null argument");
     XcSpec X;
-    if (fill_gga_spec(X, kinds, coefs, params, nterms, "mi_xc_eval")) return -1;
-    hipLaunchKernelGGL(xc_eval_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, d_rho, d_w, ng, gga,
-                       d_exc, d_wv, d_vrho, d_vsigma);
-    HIPCHK(hipGetLastError());
-    return 0;
+    const int go = xc_entry(X, kinds, coefs, params, nterms, false, !d_rho || (d_wv && !d_w), ng, "mi_xc_eval");
+    if (go <= 0) return go;
+    return xc_launch(xc_eval_kernel, ng, stream, X, d_rho, d_w, ng, gga, d_exc, d_wv, d_vrho, d_vsigma);
 }
 
 extern "C" int mi_xc_eval(const int32_t *kinds, const double *coefs, int nterms, const double *d_rho, const double *d_w,
@@ -5972,19 +6011,10 @@ __global__ __launch_bounds__(256) void xc_fxc_apply_kernel(const double *__restr
 extern "C" int mi_xc_fxc_prep(const int32_t *kinds, const double *coefs, const double *params, int nterms, const double *d_rho,
                               const double *d_w, int64_t ng, int gga, int triplet, double *d_coef, void *stream)
 {
-    if (!d_rho || !d_w || !d_coef) return fail("mi_xc_fxc_prep: null argument");
-    if (ng < 0) return fail("mi_xc_fxc_prep: negative number of grid points");
     XcSpec X;
-    if (fill_gga_spec(X, kinds, coefs, params, nterms, "mi_xc_fxc_prep")) return -1;
-    if (ng == 0) return 0;
-    if (triplet)
-        hipLaunchKernelGGL(xc_fxc_prep_kernel<true>, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, d_rho, d_w,
-                           ng, gga ? 1 : 0, d_coef);
-    else
-        hipLaunchKernelGGL(xc_fxc_prep_kernel<false>, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, d_rho, d_w,
-                           ng, gga ? 1 : 0, d_coef);
-    HIPCHK(hipGetLastError());
-    return 0;
+    const int go = xc_entry(X, kinds, coefs, params, nterms, false, !d_rho || !d_w || !d_coef, ng, "mi_xc_fxc_prep");
+    if (go <= 0) return go;
+    return xc_launch(triplet ? xc_fxc_prep_kernel<true> : xc_fxc_prep_kernel<false>, ng, stream, X, d_rho, d_w, ng, gga ? 1 : 0, d_coef);
 }
 
 extern "C" int mi_xc_fxc_apply(const double *d_rho0, const double *d_coef, const double *d_rho1, int m, int64_t ng, int gga,
@@ -6002,28 +6032,8 @@ extern "C" int mi_xc_fxc_apply(const double *d_rho0, const double *d_coef, const
 // ---- meta-GGA evaluation.  Closed shell: rho[0..3] = density and gradient, tau = 1/2 sum_i |grad phi_i|^2 (all electrons);
 // wv[0] = 0.5 w de/drho, wv[1..3] = 2 w de/dsigma grad rho, wv[4] = 0.25 w de/dtau  (V = vmat + vmat^T with
 // vmat = ao0^T (wv0 ao0 + wv_k ao_k) + sum_k ao_k^T (wv4 ao_k)).
+// The spin forms at half densities (xc_term_spin), not the closed-form functionals of xc_eval_kernel.
 typedef DN<3> D3;
-typedef DN<7> D7;
-template <class T>
-__device__ inline T xc_term_spin(int kind, double prm, T Ra, T Rb, T Saa, T Sab, T Sbb, T Ta, T Tb)
-{
-    switch (kind) {
-    case XC_SLATER: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T) { return f_slater(r); });
-    case XC_B88: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T s_) { return f_b88(r, s_); });
-    case XC_PBE_X: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [](T r, T s_) { return f_pbe_x(r, s_); });
-    case XC_B88_SR: return spin_scaled_exchange(Ra, Rb, Saa, Sbb, [prm](T r, T s_) { return f_b88_sr(r, s_, prm); });
-    case XC_VWN_RPA: return f_vwn_rpa_spin(Ra, Rb);
-    case XC_VWN5: return f_vwn5_spin(Ra, Rb);
-    case XC_LYP: return f_lyp_spin(Ra, Rb, Saa, Sab, Sbb);
-    case XC_PBE_C: return f_pbe_c_spin(Ra, Rb, Saa, Sab, Sbb);
-    case XC_TPSS_X: return f_tpss_x_spin(Ra, Rb, Saa, Sbb, Ta, Tb);
-    case XC_TPSS_C: return f_tpss_c_spin(Ra, Rb, Saa, Sab, Sbb, Ta, Tb);
-    case XC_M062X_X: return f_m062x_x_spin(Ra, Rb, Saa, Sbb, Ta, Tb);
-    case XC_M062X_C: return f_m062x_c_spin(Ra, Rb, Saa, Sbb, Ta, Tb);
-    default: return T(0.0);
-    }
-}
-
 __global__ __launch_bounds__(256) void xc_eval_mgga_kernel(XcSpec X, const double *rho, const double *tau, const double *w, int64_t ng,
                                                            double *exc, double *wv)
 {
@@ -6034,8 +6044,7 @@ __global__ __launch_bounds__(256) void xc_eval_mgga_kernel(XcSpec X, const doubl
     if (r > 1e-10) {
         D3 R = D3::var(r, 0), S = D3::var(gx * gx + gy * gy + gz * gz, 1), Tt = D3::var(fmax(t, 0.0), 2);
         D3 Rh = R * D3(0.5), S4 = S * D3(0.25), Th = Tt * D3(0.5);
-        D3 acc(0.0);
-        for (int q = 0; q < X.n; q++) acc = acc + D3(X.coef[q]) * xc_term_spin(X.kind[q], X.param[q], Rh, Rh, S4, S4, S4, Th, Th);
+        D3 acc = xc_spin_sum<true>(X, Rh, Rh, S4, S4, S4, Th, Th);
         e = acc.v; vr = acc.d[0]; vs = acc.d[1]; vt = acc.d[2];
     }
     if (exc) exc[g] = e;
@@ -6047,76 +6056,25 @@ __global__ __launch_bounds__(256) void xc_eval_mgga_kernel(XcSpec X, const doubl
     }
 }
 
-__global__ __launch_bounds__(256) void xc_eval_mgga_spin_kernel(XcSpec X, const double *rhoa, const double *rhob, const double *taua,
-                                                                const double *taub, const double *w, int64_t ng, double *exc, double *wva,
-                                                                double *wvb)
-{
-    int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= ng) return;
-    const double ra = fmax(rhoa[g], 0.0), rb = fmax(rhob[g], 0.0);
-    double ga[3], gb[3];
-    for (int k = 0; k < 3; k++) { ga[k] = rhoa[(k + 1) * ng + g]; gb[k] = rhob[(k + 1) * ng + g]; }
-    double e = 0.0, v[7] = {0, 0, 0, 0, 0, 0, 0};
-    if (ra + rb > 1e-10) {
-        D7 Ra = D7::var(ra, 0), Rb = D7::var(rb, 1);
-        D7 Saa = D7::var(ga[0] * ga[0] + ga[1] * ga[1] + ga[2] * ga[2], 2);
-        D7 Sab = D7::var(ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2], 3);
-        D7 Sbb = D7::var(gb[0] * gb[0] + gb[1] * gb[1] + gb[2] * gb[2], 4);
-        D7 Ta = D7::var(fmax(taua[g], 0.0), 5), Tb = D7::var(fmax(taub[g], 0.0), 6);
-        D7 acc(0.0);
-        for (int q = 0; q < X.n; q++) acc = acc + D7(X.coef[q]) * xc_term_spin(X.kind[q], X.param[q], Ra, Rb, Saa, Sab, Sbb, Ta, Tb);
-        e = acc.v;
-        for (int k = 0; k < 7; k++) v[k] = acc.d[k];
-    }
-    if (exc) exc[g] = e;
-    const double ww = w[g];
-    wva[g] = 0.5 * ww * v[0];
-    wvb[g] = 0.5 * ww * v[1];
-    for (int k = 0; k < 3; k++) {
-        wva[(k + 1) * ng + g] = ww * (2.0 * v[2] * ga[k] + v[3] * gb[k]);
-        wvb[(k + 1) * ng + g] = ww * (2.0 * v[4] * gb[k] + v[3] * ga[k]);
-    }
-    wva[4 * ng + g] = 0.25 * ww * v[5];
-    wvb[4 * ng + g] = 0.25 * ww * v[6];
-}
-
-static int fill_xc_spec(XcSpec &X, const int32_t *kinds, const double *coefs, int nterms)
-{
-    if (nterms < 0 || nterms > 8) return fail("xc: at most 8 functional terms");
-    X = XcSpec{};
-    X.n = nterms;
-    for (int i = 0; i < nterms; i++) {
-        if (kinds[i] < XC_SLATER || kinds[i] > XC_M062X_C) return fail("xc: unknown functional id %d", kinds[i]);
-        X.kind[i] = kinds[i]; X.coef[i] = coefs[i];
-    }
-    return 0;
-}
-
+// No term of a meta-GGA takes a runtime parameter: params = NULL, so a short-range B88 term is refused here.
 extern "C" int mi_xc_eval_mgga(const int32_t *kinds, const double *coefs, int nterms, const double *d_rho, const double *d_tau,
                                const double *d_w, int64_t ng, double *d_exc, double *d_wv, void *stream)
 {
-    if (!d_rho || !d_tau || (d_wv && !d_w)) return fail("mi_xc_eval_mgga: null argument");
     XcSpec X;
-    if (fill_xc_spec(X, kinds, coefs, nterms)) return -1;
-    if (ng <= 0) return 0;
-    hipLaunchKernelGGL(xc_eval_mgga_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, d_rho, d_tau, d_w, ng,
-                       d_exc, d_wv);
-    HIPCHK(hipGetLastError());
-    return 0;
+    const int go = xc_entry(X, kinds, coefs, nullptr, nterms, true, !d_rho || !d_tau || (d_wv && !d_w), ng, "mi_xc_eval_mgga");
+    if (go <= 0) return go;
+    return xc_launch(xc_eval_mgga_kernel, ng, stream, X, d_rho, d_tau, d_w, ng, d_exc, d_wv);
 }
 
 extern "C" int mi_xc_eval_mgga_spin(const int32_t *kinds, const double *coefs, int nterms, const double *d_rhoa, const double *d_rhob,
                                     const double *d_taua, const double *d_taub, const double *d_w, int64_t ng, double *d_exc, double *d_wva,
                                     double *d_wvb, void *stream)
 {
-    if (!d_rhoa || !d_rhob || !d_taua || !d_taub || !d_w || !d_wva || !d_wvb) return fail("mi_xc_eval_mgga_spin: null argument");
     XcSpec X;
-    if (fill_xc_spec(X, kinds, coefs, nterms)) return -1;
-    if (ng <= 0) return 0;
-    hipLaunchKernelGGL(xc_eval_mgga_spin_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, d_rhoa, d_rhob,
-                       d_taua, d_taub, d_w, ng, d_exc, d_wva, d_wvb);
-    HIPCHK(hipGetLastError());
-    return 0;
+    const int go = xc_entry(X, kinds, coefs, nullptr, nterms, true, !d_rhoa || !d_rhob || !d_taua || !d_taub || !d_w || !d_wva || !d_wvb,
+                            ng, "mi_xc_eval_mgga_spin");
+    if (go <= 0) return go;
+    return xc_launch(xc_eval_spin_kernel<true>, ng, stream, X, d_rhoa, d_rhob, d_taua, d_taub, d_w, ng, 1, d_exc, d_wva, d_wvb);
 }
 
 // aow[mu][g] = ao0*wv0 + sum_k ao_k*wv_k

@@ -187,7 +187,7 @@ class KSMixin:
 
     def _ao_blocks(self, gga):
         """(weights, ao) of each grid block of this rank, in order: the one loop over the grid that the SCF quadrature
-        (`_nr_rks_raw`, `_nr_uks_raw`) and the XC response of tdscf share.  AO values come from the resident cache where it
+        (`_nr_raw`) and the XC response of tdscf share.  AO values come from the resident cache where it
         holds them and are put there otherwise, so every caller has to walk the same `_xc_block_size` blocks."""
         eng = self.engine
         n = eng.nao
@@ -257,6 +257,85 @@ class KSMixin:
         st[(key, "G")] = self.engine.nystrom_warm(Zp_t, _info, G0, Gn)
         return Zp_t @ self._Linv                            # (L^-T Zp)^T
 
+    # --- the one block body of the quadrature: RKS and UKS (`_nr_raw`), the XC gradients (grad.py) and the TDDFT spin potential
+    # (tdscf.py) are these five pieces over `_ao_blocks` (or the gradient's own AO blocks)
+    def _xc_functional(self):
+        """(hyb, terms, level, params) of `self.xc`: parse_xc and the runtime parameter of each term (xc_params)."""
+        hyb, terms, gga = parse_xc(self.xc)
+        return hyb, terms, gga, xc_params(self.xc)
+
+    def _padded_factor(self, Zt, gga, key):
+        """Zt [nocc, nao] -> Zp [nao, ldz], orbital index fastest, zero-padded to the density kernel's chunk (24 GGA / 32 LDA).
+        One buffer per `key` kept between cycles: the padding is zeroed when the buffer is made, not every cycle, so a changed
+        occupied count (stale columns) makes a new one as a changed shape or device does."""
+        nocc, n = Zt.shape
+        ch = 24 if gga else 32
+        ldz = (nocc + ch - 1) // ch * ch
+        bufs = self.__dict__.setdefault("_zp_bufs", {})
+        Zp, had = bufs.get(key, (None, None))
+        if Zp is None or Zp.shape != (n, ldz) or Zp.device != Zt.device or had != nocc:
+            Zp = torch.zeros(n, ldz, dtype=torch.float64, device=Zt.device)
+            bufs[key] = (Zp, nocc)
+        Zp[:, :nocc].copy_(Zt.T)
+        return Zp
+
+    def _block_density(self, ao, dm, Zp, gga, C=None):
+        """(rho, tau) of one density on one block: from its padded factor (D = Z Z^T: nao / n_occ times fewer flops and bytes
+        than D.ao, one pass over ao), else from `dm` (C = dm.ao0 if the caller has it).  tau is None below meta-GGA."""
+        eng = self.engine
+        if Zp is not None:
+            if gga == 2:
+                return eng.xc_rho_lowrank(ao, Zp, deriv=1, with_tau=True)
+            return eng.xc_rho_lowrank(ao, Zp, deriv=1 if gga else 0), None
+        rho = eng.xc_rho(ao, dm @ ao[0] if C is None else C, deriv=1 if gga else 0)
+        return rho, (eng.xc_tau(ao, dm) if gga == 2 else None)
+
+    def _block_functional(self, xcf, rho, tau, w):
+        """(e, [wv per density]) of one density (closed-shell entry points) or two (spin-polarised ones) on one block."""
+        eng = self.engine
+        _hyb, terms, gga, params = xcf
+        if len(rho) == 1:
+            if gga == 2:
+                e, wv = eng.xc_eval_mgga(terms, rho[0], tau[0], w)
+            else:
+                e, wv = eng.xc_eval(terms, rho[0], w, gga, params=params)
+            return e, [wv]
+        if gga == 2:
+            e, wva, wvb = eng.xc_eval_mgga_spin(terms, rho[0], rho[1], tau[0], tau[1], w)
+        else:
+            e, wva, wvb = eng.xc_eval_spin(terms, rho[0], rho[1], w, gga, params=params)
+        return e, [wva, wvb]
+
+    def _block_vmat(self, ao, wv, gga, vmat, fold=False):
+        """vmat += ao0 . (sum_c wv_c ao_c)^T (unsymmetrised V_xc of one density on one block), plus the kinetic-energy-density
+        term sum_k ao_k . (w/4 vtau ao_k)^T of a meta-GGA.  `fold`: weighted AOs formed inside the MFMA kernel."""
+        eng = self.engine
+        if fold:
+            eng.xc_vmat_fold(ao, wv, gga, vmat)
+        else:
+            eng.xc_vmat(ao[0], eng.xc_aow(ao, wv, gga), vmat)      # split-K FP64 MFMA kernel
+        if gga == 2:
+            for k in (1, 2, 3):
+                eng.xc_vmat(ao[k], wv[4] * ao[k], vmat)
+
+    def _nr_raw(self, dms, Zts, keys, vmats, tail, fold=False):
+        """The quadrature of one (RKS) or two (UKS) densities: the unsymmetrised XC matrix of each into `vmats`, the electron
+        count of each and then E_xc into `tail` -- views of a caller-owned (zeroed) buffer, e.g. the fused all-reduce buffer of
+        `_fock_energy`.  `Zts`: the low-rank factor of each density or None; `keys` name their padded buffers.  Returns the
+        exact-exchange fraction of the functional."""
+        eng = self.engine
+        xcf = self._xc_functional()
+        gga = xcf[2]
+        Zps = [None if Zt is None else self._padded_factor(Zt, gga, key) for Zt, key in zip(Zts, keys)]
+        for w, ao in self._ao_blocks(gga):
+            dens = [self._block_density(ao, dm, Zp, gga) for dm, Zp in zip(dms, Zps)]
+            rho, tau = [d[0] for d in dens], [d[1] for d in dens]
+            e, wvs = self._block_functional(xcf, rho, tau, w)
+            eng.xc_tail(w, (*(r[0] for r in rho), e), tail)     # N_elec per density and E_xc of the block: one deterministic launch
+            for wv, vmat in zip(wvs, vmats):
+                self._block_vmat(ao, wv, gga, vmat, fold)
+        return xcf[0]
+
     def _ao_cache_for(self, nao, npts, ncomp):
         """AO values on this rank's grid points are kept resident between SCF cycles when they fit in a quarter
         of the free HBM (benzene/cc-pVTZ 1.2 GB, ibuprofen/def2-TZVP 7.1 GB); invalidated with the grid."""
@@ -292,50 +371,12 @@ class RKS(KSMixin, RHF):
         return tail[0], tail[1], vmat + vmat.T, hyb
 
     def _nr_rks_raw(self, dm, vmat, tail):
-        """Accumulate the UNsymmetrised XC matrix (V_xc = vmat + vmat^T) into `vmat` and [N_elec, E_xc] into `tail` -- views of
-        a caller-owned (zeroed) buffer, e.g. the fused all-reduce buffer of `_fock_energy`.  Returns the exact-exchange
-        fraction of the functional."""
-        eng = self.engine
-        hyb, terms, gga = parse_xc(self.xc)
-        params = xc_params(self.xc)
-        n = eng.nao
-        Zt = self._occ_factor(dm)
-        if Zt is not None:   # [nao, ldz] with the orbital index fastest, zero-padded to the kernel's chunk (24 GGA / 32 LDA)
-            ch = 24 if gga else 32
-            ldz = (Zt.shape[0] + ch - 1) // ch * ch
-            Zp = getattr(self, "_zp_buf", None)      # persistent: the padding columns are zeroed once, not every cycle
-            if Zp is None or Zp.shape != (n, ldz) or Zp.device != Zt.device or self._zp_nocc != Zt.shape[0]:
-                Zp = self._zp_buf = torch.zeros(n, ldz, dtype=torch.float64, device=Zt.device)
-                self._zp_nocc = Zt.shape[0]
-            Zp[:, :Zt.shape[0]].copy_(Zt.T)
-        for w, ao in self._ao_blocks(gga):
-            if Zt is not None:
-                # D = Z Z^T: densities from the occupied orbitals on the grid (nao / n_occ times fewer flops and bytes than D.ao)
-                if gga == 2:
-                    rho, tau = eng.xc_rho_lowrank(ao, Zp, deriv=1, with_tau=True)
-                else:
-                    rho, tau = eng.xc_rho_lowrank(ao, Zp, deriv=1 if gga else 0), None
-            else:
-                C = dm @ ao[0]
-                rho = eng.xc_rho(ao, C, deriv=1 if gga else 0)
-                tau = eng.xc_tau(ao, dm) if gga == 2 else None
-            if gga == 2:
-                e, wv = eng.xc_eval_mgga(terms, rho, tau, w)
-            else:
-                e, wv = eng.xc_eval(terms, rho, w, gga, params=params)
-            eng.xc_tail(w, (rho[0], e), tail)     # tail[0] += w.rho (N_elec), tail[1] += w.e (E_xc): one deterministic launch
-            if os.environ.get("MI355_VMAT_MT") and not getattr(self, "_vmat_mt_set", False):
-                eng.set_option("vmat_fold_mt", float(os.environ["MI355_VMAT_MT"]))
-                self._vmat_mt_set = True
-            if self.xc_vmat_fold or os.environ.get("MI355_XC_FOLD", "0") == "1":
-                eng.xc_vmat_fold(ao, wv, gga, vmat)    # vmat += ao0 . (sum_c wv_c ao_c)^T, weighted AOs formed inside the MFMA kernel
-            else:
-                aow = eng.xc_aow(ao, wv, gga)
-                eng.xc_vmat(ao[0], aow, vmat)      # vmat += ao0 . aow^T  (split-K FP64 MFMA kernel)
-            if gga == 2:                        # kinetic-energy-density term: sum_k ao_k . (w/4 vtau ao_k)^T
-                for k in (1, 2, 3):
-                    eng.xc_vmat(ao[k], wv[4] * ao[k], vmat)
-        return hyb
+        """`KSMixin._nr_raw` of the closed-shell density: V_xc = vmat + vmat^T, tail = [N_elec, E_xc]."""
+        if os.environ.get("MI355_VMAT_MT") and not getattr(self, "_vmat_mt_set", False):
+            self.engine.set_option("vmat_fold_mt", float(os.environ["MI355_VMAT_MT"]))
+            self._vmat_mt_set = True
+        fold = self.xc_vmat_fold or os.environ.get("MI355_XC_FOLD", "0") == "1"
+        return self._nr_raw([dm], [self._occ_factor(dm)], ["rks"], [vmat], tail, fold)
 
     xc_vmat_fold = False  # V_xc product with the weighted AOs formed on the fly (round 3 experiment: 0.88-1.8 ms against 0.75 ms for the xc_aow pass + xc_vmat; DESIGN.md 8.8)
 

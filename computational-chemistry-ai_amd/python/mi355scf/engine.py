@@ -478,45 +478,39 @@ class Engine:
                                        tau.data_ptr() if tau is not None else None, self._stream()))
         return (rho, tau) if with_tau else rho
 
+    @staticmethod
+    def _xc_spec(terms, params=None):
+        """terms [(coef, kind_id)] and params (one per term, or None) -> the (kinds, coefs, params-or-NULL, n) arguments of the
+        mi_xc_* entry points, and the arrays behind them, which the caller holds until the call has returned."""
+        kinds = np.array([k for _c, k in terms], dtype=np.int32)
+        coefs = np.array([c for c, _k in terms], dtype=np.float64)
+        prm = None if params is None else np.ascontiguousarray(params, dtype=np.float64)
+        assert prm is None or prm.shape == (len(kinds),)
+        args = (kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _dp(coefs), None if prm is None else _dp(prm), len(kinds))
+        return args, (kinds, coefs, prm)
+
     def xc_eval_spin(self, terms, rhoa, rhob, weights, gga=True, params=None):
         """Spin-polarised functionals: (exc[ng], wva[(1|4)][ng], wvb[(1|4)][ng]).  `params`: one runtime parameter per term
         (the omega of a short-range B88 term, `dft.xc_params`), None for functionals without one."""
         ng = rhoa.shape[-1]
-        kinds = np.array([k for _c, k in terms], dtype=np.int32)
-        coefs = np.array([c for c, _k in terms], dtype=np.float64)
         exc = self._new(ng)
         wva = self._new(4 if gga else 1, ng)
         wvb = self._new(4 if gga else 1, ng)
-        kp = kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        if params is None:
-            _check(lib().mi_xc_eval_spin(kp, _dp(coefs), len(kinds), rhoa.data_ptr(), rhob.data_ptr(), weights.data_ptr(), ng,
-                                         int(gga), exc.data_ptr(), wva.data_ptr(), wvb.data_ptr(), self._stream()))
-        else:
-            prm = np.ascontiguousarray(params, dtype=np.float64)
-            assert prm.shape == (len(kinds),)
-            _check(lib().mi_xc_eval_spin_p(kp, _dp(coefs), _dp(prm), len(kinds), rhoa.data_ptr(), rhob.data_ptr(),
-                                           weights.data_ptr(), ng, int(gga), exc.data_ptr(), wva.data_ptr(), wvb.data_ptr(),
-                                           self._stream()))
+        spec, _keep = self._xc_spec(terms, params)
+        _check(lib().mi_xc_eval_spin_p(*spec, rhoa.data_ptr(), rhob.data_ptr(), weights.data_ptr(), ng, int(gga), exc.data_ptr(),
+                                       wva.data_ptr(), wvb.data_ptr(), self._stream()))
         return exc, wva, wvb
 
     def xc_eval(self, terms, rho, weights, gga=True, want_raw=False, params=None):
         """terms: [(coef, kind_id)] -> (exc[ng], wv[(1|4)][ng]) (+ vrho, vsigma if want_raw).  `params` as in xc_eval_spin."""
         ng = rho.shape[-1]
-        kinds = np.array([k for _c, k in terms], dtype=np.int32)
-        coefs = np.array([c for c, _k in terms], dtype=np.float64)
         exc = self._new(ng)
         wv = self._new(4 if gga else 1, ng)
         vr = self._new(ng) if want_raw else None
         vs = self._new(ng) if want_raw else None
-        kp = kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        outs = (rho.data_ptr(), weights.data_ptr(), ng, int(gga), exc.data_ptr(), wv.data_ptr(),
-                vr.data_ptr() if want_raw else None, vs.data_ptr() if want_raw else None, self._stream())
-        if params is None:
-            _check(lib().mi_xc_eval(kp, _dp(coefs), len(kinds), *outs))
-        else:
-            prm = np.ascontiguousarray(params, dtype=np.float64)
-            assert prm.shape == (len(kinds),)
-            _check(lib().mi_xc_eval_p(kp, _dp(coefs), _dp(prm), len(kinds), *outs))
+        spec, _keep = self._xc_spec(terms, params)
+        _check(lib().mi_xc_eval_p(*spec, rho.data_ptr(), weights.data_ptr(), ng, int(gga), exc.data_ptr(), wv.data_ptr(),
+                                  vr.data_ptr() if want_raw else None, vs.data_ptr() if want_raw else None, self._stream()))
         return (exc, wv, vr, vs) if want_raw else (exc, wv)
 
     def xc_fxc_prep(self, terms, rho, weights, gga=True, triplet=False, params=None):
@@ -524,14 +518,10 @@ class Engine:
         closed-shell functional; triplet: spin-difference kernel of the spin-polarised one).  `params` as in xc_eval."""
         ng = rho.shape[-1]
         assert rho.is_contiguous() and weights.is_contiguous() and rho.shape[0] == (4 if gga else 1)
-        kinds = np.array([k for _c, k in terms], dtype=np.int32)
-        coefs = np.array([c for c, _k in terms], dtype=np.float64)
-        prm = None if params is None else np.ascontiguousarray(params, dtype=np.float64)
-        assert prm is None or prm.shape == (len(kinds),)
         coef = self._new(4 if gga else 1, ng)
-        _check(lib().mi_xc_fxc_prep(kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _dp(coefs),
-                                    _dp(prm) if prm is not None else None, len(kinds), rho.data_ptr(), weights.data_ptr(), ng,
-                                    int(bool(gga)), int(bool(triplet)), coef.data_ptr(), self._stream()))
+        spec, _keep = self._xc_spec(terms, params)
+        _check(lib().mi_xc_fxc_prep(*spec, rho.data_ptr(), weights.data_ptr(), ng, int(bool(gga)), int(bool(triplet)),
+                                    coef.data_ptr(), self._stream()))
         return coef
 
     def xc_fxc_apply(self, rho0, coef, rho1, gga=True):
@@ -556,21 +546,18 @@ class Engine:
     def xc_eval_mgga(self, terms, rho, tau, weights):
         """meta-GGA: (exc[ng], wv[5][ng]); wv[4] = w/4 de/dtau."""
         ng = rho.shape[-1]
-        kinds = np.array([k for _c, k in terms], dtype=np.int32)
-        coefs = np.array([c for c, _k in terms], dtype=np.float64)
         exc, wv = self._new(ng), self._new(5, ng)
-        _check(lib().mi_xc_eval_mgga(kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _dp(coefs), len(kinds), rho.data_ptr(),
-                                     tau.data_ptr(), weights.data_ptr(), ng, exc.data_ptr(), wv.data_ptr(), self._stream()))
+        (kp, cp, _no_params, n), _keep = self._xc_spec(terms)
+        _check(lib().mi_xc_eval_mgga(kp, cp, n, rho.data_ptr(), tau.data_ptr(), weights.data_ptr(), ng, exc.data_ptr(), wv.data_ptr(),
+                                     self._stream()))
         return exc, wv
 
     def xc_eval_mgga_spin(self, terms, rhoa, rhob, taua, taub, weights):
         ng = rhoa.shape[-1]
-        kinds = np.array([k for _c, k in terms], dtype=np.int32)
-        coefs = np.array([c for c, _k in terms], dtype=np.float64)
         exc, wva, wvb = self._new(ng), self._new(5, ng), self._new(5, ng)
-        _check(lib().mi_xc_eval_mgga_spin(kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _dp(coefs), len(kinds), rhoa.data_ptr(),
-                                          rhob.data_ptr(), taua.data_ptr(), taub.data_ptr(), weights.data_ptr(), ng, exc.data_ptr(),
-                                          wva.data_ptr(), wvb.data_ptr(), self._stream()))
+        (kp, cp, _no_params, n), _keep = self._xc_spec(terms)
+        _check(lib().mi_xc_eval_mgga_spin(kp, cp, n, rhoa.data_ptr(), rhob.data_ptr(), taua.data_ptr(), taub.data_ptr(),
+                                          weights.data_ptr(), ng, exc.data_ptr(), wva.data_ptr(), wvb.data_ptr(), self._stream()))
         return exc, wva, wvb
 
     def xc_tail(self, w, vals, tail):

@@ -60,26 +60,27 @@ class Gradients:
 
     def grad_xc(self, dm):
         """XC gradient of RKS: `_add_xc_force` of the closed-shell density over this rank's grid, summed per atom."""
-        from .dft import parse_xc
+        return self._grad_xc([dm])
+
+    def _grad_xc(self, dms):
+        """XC gradient of one density (closed shell) or two (spin): per grid block the densities and the functional of the SCF's
+        block body (`dft.KSMixin`), on AO values with second derivatives, then `_add_xc_force` of each (D_s, wv_s)."""
         mf = self.base
         eng = mf.engine
-        hyb, terms, gga = parse_xc(mf.xc)
-        n = eng.nao
+        xcf = mf._xc_functional()
+        gga = xcf[2]
         coords, weights = mf.grids.coords, mf.grids.weights
         lo, hi = mf._grid_range(coords.shape[0])
-        fmu = torch.zeros(n, 3, dtype=torch.float64, device=eng.device)
+        fmu = torch.zeros(eng.nao, 3, dtype=torch.float64, device=eng.device)
         B = max(4096, mf.grid_block // 4)
         for p0 in range(lo, hi, B):
             p1 = min(p0 + B, hi)
-            c, w = coords[p0:p1], weights[p0:p1]
-            ao = eng.eval_ao(c, deriv=2 if gga else 1)
-            C = dm @ ao[0]
-            rho = eng.xc_rho(ao, C, deriv=1 if gga else 0)
-            if gga == 2:
-                _e, wv = eng.xc_eval_mgga(terms, rho, eng.xc_tau(ao, dm), w)
-            else:
-                _e, wv = eng.xc_eval(terms, rho, w, gga)
-            _add_xc_force(fmu, ao, dm, C, wv, gga)
+            ao = eng.eval_ao(coords[p0:p1], deriv=2 if gga else 1)
+            Cs = [dm @ ao[0] for dm in dms]
+            dens = [mf._block_density(ao, dm, None, gga, C) for dm, C in zip(dms, Cs)]
+            _e, wvs = mf._block_functional(xcf, [d[0] for d in dens], [d[1] for d in dens], weights[p0:p1])
+            for dm, C, wv in zip(dms, Cs, wvs):
+                _add_xc_force(fmu, ao, dm, C, wv, gga)
         if mf._nranks > 1:
             from . import parallel
             parallel.all_reduce_sum(fmu, mf._pg)
@@ -87,33 +88,36 @@ class Gradients:
         sl = mf.mol.aoslice_by_atom()
         return np.array([f[sl[ia, 2]:sl[ia, 3]].sum(axis=0) for ia in range(mf.mol.natm)])
 
+    def _densities(self):
+        """What `kernel` contracts, from the converged SCF: (densities of the XC term, total density D, spin density M or None,
+        energy-weighted density W, densities handed to the fitted `grad_jk`)."""
+        mf = self.base
+        dm = mf._dm
+        W = 0.5 * dm @ (mf._h1 + mf._vhf) @ dm
+        return [dm], dm.contiguous(), None, W.contiguous(), dm
+
     def kernel(self, mo_energy=None, mo_coeff=None, mo_occ=None, atmlst=None):
         mf = self.base
         if mf._dm is None or not mf.converged:
             mf.kernel()
         eng = mf.engine
         mol = mf.mol
-        dm = mf._dm
-        fock = mf._h1 + mf._vhf
-        W = 0.5 * dm @ fock @ dm
+        dms, D, M, W, dm_fit = self._densities()
         import time
         tm = {}
         t0 = time.time()
         g = torch.zeros(mol.natm, 3, dtype=torch.float64, device=eng.device)
-        eng.grad_1e(dm.contiguous(), W.contiguous(), g)
+        eng.grad_1e(D, W, g)
         torch.cuda.synchronize()
         tm["grad_1e"] = time.time() - t0
         is_ks = getattr(mf, "xc", None) is not None and hasattr(mf, "grids")
-        hyb = 1.0
-        if is_ks:
-            from .dft import parse_xc
-            hyb = parse_xc(mf.xc)[0]
+        hyb = mf._xc_functional()[0] if is_ks else 1.0
         t0 = time.time()
         if getattr(mf, "with_df", None) is not None:
-            g2 = _fitted_tensor(mf).grad_jk(dm, hyb, rank=mf._rank, nranks=mf._nranks)
+            g2 = _fitted_tensor(mf).grad_jk(dm_fit, hyb, rank=mf._rank, nranks=mf._nranks)
         else:
             g2 = torch.zeros_like(g)
-            eng.grad_eri(dm.contiguous(), hyb, g2, rank=mf._rank, nranks=mf._nranks)
+            eng.grad_eri(D, hyb, g2, spin_density=M, rank=mf._rank, nranks=mf._nranks)
         tm["grad_eri"] = time.time() - t0
         if mf._nranks > 1:   # derivative-quartet batches are dealt round-robin to ranks inside mi_grad_eri
             from . import parallel
@@ -121,7 +125,7 @@ class Gradients:
         de = (g + g2).cpu().numpy() + grad_nuc(mol)
         if is_ks:
             t0 = time.time()
-            de = de + self.grad_xc(dm)
+            de = de + self._grad_xc(dms)
             torch.cuda.synchronize()
             tm["grad_xc"] = time.time() - t0
         if mf._nranks > 1:
@@ -158,78 +162,16 @@ class UGradients(Gradients):
     """Analytic UHF gradient: the restricted pieces with D = Da + Db, W = sum_s Ds Fs Ds, and the exchange part of
     the two-particle density from both spins (`mi_grad_eri_spin`, spin density M = Da - Db)."""
 
-    def kernel(self, mo_energy=None, mo_coeff=None, mo_occ=None, atmlst=None):
+    def _densities(self):
         mf = self.base
-        if mf._dm is None or not mf.converged:
-            mf.kernel()
-        eng = mf.engine
-        mol = mf.mol
         dma, dmb = mf._dm[0], mf._dm[1]
         F = mf._fock
-        D = (dma + dmb).contiguous()
-        M = (dma - dmb).contiguous()
         W = (dma @ F[0] @ dma + dmb @ F[1] @ dmb).contiguous()
-        g = torch.zeros(mol.natm, 3, dtype=torch.float64, device=eng.device)
-        eng.grad_1e(D, W, g)
-        is_ks = getattr(mf, "xc", None) is not None and hasattr(mf, "grids")
-        hyb = 1.0
-        if is_ks:
-            from .dft import parse_xc
-            hyb = parse_xc(mf.xc)[0]
-        if getattr(mf, "with_df", None) is not None:
-            g2 = _fitted_tensor(mf).grad_jk([dma, dmb], hyb, rank=mf._rank, nranks=mf._nranks)
-        else:
-            g2 = torch.zeros_like(g)
-            eng.grad_eri(D, hyb, g2, spin_density=M, rank=mf._rank, nranks=mf._nranks)
-        if mf._nranks > 1:
-            from . import parallel
-            parallel.all_reduce_sum(g2, mf._pg)
-        de = (g + g2).cpu().numpy() + grad_nuc(mol)
-        if is_ks:
-            de = de + self.grad_xc_spin(mf._dm)
-        if mf._nranks > 1:
-            from . import parallel
-            dt = torch.as_tensor(de, device=eng.device)
-            parallel.broadcast0(dt, mf._pg)
-            de = dt.cpu().numpy()
-        self.de = de
-        if self.verbose >= 4:
-            mf._log(4, "--------------- gradients ---------------")
-            for ia in range(mol.natm):
-                mf._log(4, "%d %s  %16.10f %16.10f %16.10f" % (ia, mol.atom_pure_symbol(ia), *de[ia]))
-        return de
-
-    grad = kernel
+        return [dma, dmb], (dma + dmb).contiguous(), (dma - dmb).contiguous(), W, [dma, dmb]
 
     def grad_xc_spin(self, dm):
         """XC gradient of UKS: `_add_xc_force` per spin with (D_s, wv_s) from the spin-polarised functional."""
-        from .dft import parse_xc
-        mf = self.base
-        eng = mf.engine
-        hyb, terms, gga = parse_xc(mf.xc)
-        n = eng.nao
-        coords, weights = mf.grids.coords, mf.grids.weights
-        lo, hi = mf._grid_range(coords.shape[0])
-        fmu = torch.zeros(n, 3, dtype=torch.float64, device=eng.device)
-        B = max(4096, mf.grid_block // 4)
-        for p0 in range(lo, hi, B):
-            p1 = min(p0 + B, hi)
-            c, w = coords[p0:p1], weights[p0:p1]
-            ao = eng.eval_ao(c, deriv=2 if gga else 1)
-            Cs = [dm[s_] @ ao[0] for s_ in range(2)]
-            rho = [eng.xc_rho(ao, Cs[s_], deriv=1 if gga else 0) for s_ in range(2)]
-            if gga == 2:
-                _e, wva, wvb = eng.xc_eval_mgga_spin(terms, rho[0], rho[1], eng.xc_tau(ao, dm[0]), eng.xc_tau(ao, dm[1]), w)
-            else:
-                _e, wva, wvb = eng.xc_eval_spin(terms, rho[0], rho[1], w, gga)
-            for s_, wv in ((0, wva), (1, wvb)):
-                _add_xc_force(fmu, ao, dm[s_], Cs[s_], wv, gga)
-        if mf._nranks > 1:
-            from . import parallel
-            parallel.all_reduce_sum(fmu, mf._pg)
-        f = fmu.cpu().numpy()
-        sl = mf.mol.aoslice_by_atom()
-        return np.array([f[sl[ia, 2]:sl[ia, 3]].sum(axis=0) for ia in range(mf.mol.natm)])
+        return self._grad_xc([dm[0], dm[1]])
 
 
 class FDGradients:

@@ -307,33 +307,28 @@ class _TDBase:
         return out
 
     def _vxc_alpha(self, Da, Db):
-        """V_xc of spin alpha of the spin densities (Da, Db) on the SCF's grid (Engine.xc_eval_spin)."""
-        from .dft import parse_xc, xc_params
+        """V_xc of spin alpha of the spin densities (Da, Db) on the SCF's grid: the SCF's block body (dft.KSMixin) with the
+        spin-polarised functional, of which only the alpha matrix is folded."""
         mf = self._scf
-        eng = mf.engine
-        _hyb, terms, gga = parse_xc(mf.xc)
-        params = xc_params(mf.xc)
-        deriv = 1 if gga else 0
+        xcf = mf._xc_functional()
+        gga = xcf[2]
         vmat = torch.zeros_like(Da)
         for w, ao in mf._ao_blocks(gga):
-            ra = eng.xc_rho(ao, Da @ ao[0], deriv)
-            rb = eng.xc_rho(ao, Db @ ao[0], deriv)
-            _e, wva, _wvb = eng.xc_eval_spin(terms, ra, rb, w, gga, params=params)
-            eng.xc_vmat(ao[0], eng.xc_aow(ao, wva, gga), vmat)
+            dens = [mf._block_density(ao, dm, None, gga) for dm in (Da, Db)]
+            _e, (wva, _wvb) = mf._block_functional(xcf, [d[0] for d in dens], [d[1] for d in dens], w)
+            mf._block_vmat(ao, wva, gga, vmat)
         return vmat + vmat.T
 
     def _fxc_blocks(self, triplet):
         """[(rho0, coef)] per grid block: the ground-state density and its XC kernel coefficients for the channel, made once
         per run (Engine.xc_fxc_prep)."""
         if self._fxc is None or self._fxc[0] != bool(triplet):
-            from .dft import parse_xc, xc_params
             mf = self._scf
             eng = mf.engine
-            _hyb, terms, gga = parse_xc(mf.xc)
-            params = xc_params(mf.xc)
+            _hyb, terms, gga, params = mf._xc_functional()
             blocks = []
             for w, ao in mf._ao_blocks(gga):
-                rho0 = eng.xc_rho(ao, self._D0 @ ao[0], 1 if gga else 0)
+                rho0, _tau = mf._block_density(ao, self._D0, None, gga)
                 blocks.append((rho0, eng.xc_fxc_prep(terms, rho0, w, gga, triplet=triplet, params=params)))
             self._fxc = (bool(triplet), blocks)
         return self._fxc[1]

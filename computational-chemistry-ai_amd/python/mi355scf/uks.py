@@ -1,15 +1,17 @@
 """Spin-unrestricted Kohn-Sham behind `pyscf.dft.UKS` / `gpu4pyscf.dft.UKS` (call sites
 `templates/calculate_bde.py:128,140,197,215`: `mf = UKS(mol); mf.xc = method` for the radical fragments).
 
-Same grid, AO, density and V_xc HIP kernels as RKS; the functional is evaluated by `mi_xc_eval_spin` (forward-mode
-dual numbers over rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb: spin-scaled exchange, VWN/PW92 spin interpolation,
-open-shell LYP, PBE correlation with phi(zeta)).  Meta-GGAs (TPSS; the template's default M06-2X, parameter tables unverified-memory) go through `mi_xc_eval_mgga_spin` (dual numbers incl. tau_a, tau_b).
+Same grid, AO, density and V_xc HIP kernels as RKS, and the same block body (`dft.KSMixin._nr_raw`, over two densities); the
+functional is evaluated by `xc_eval_spin_kernel` (forward-mode dual numbers over rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb:
+spin-scaled exchange, VWN/PW92 spin interpolation, open-shell LYP, PBE correlation with phi(zeta)) through `mi_xc_eval_spin_p`.
+Meta-GGAs (TPSS; the template's default M06-2X, parameter tables unverified-memory) go through `mi_xc_eval_mgga_spin`: the same
+kernel instantiated with tau_a, tau_b among the dual variables.
 The grid is not pruned by density (PySCF's `small_rho_cutoff` step is RKS-only here).
 """
 import numpy as np
 import torch
 
-from .dft import KSMixin, check_rsh_scf, is_rsh, lr_engine, parse_xc, rsh_coeff, xc_params
+from .dft import KSMixin, check_rsh_scf, is_rsh, lr_engine, parse_xc, rsh_coeff
 from .uhf import UHF
 
 
@@ -29,45 +31,13 @@ class UKS(KSMixin, UHF):
         return tail[:2], tail[2], vmat + vmat.transpose(1, 2), hyb
 
     def _nr_uks_raw(self, dm, vmat, tail):
-        """Unsymmetrised V_xc,s into `vmat[2,N,N]`, [N_alpha, N_beta, E_xc] into `tail` (views of a zeroed caller buffer)."""
-        eng = self.engine
-        hyb, terms, gga = parse_xc(self.xc)
-        params = xc_params(self.xc)
-        n = eng.nao
+        """`KSMixin._nr_raw` of the spin densities: unsymmetrised V_xc,s into `vmat[2,N,N]`, [N_alpha, N_beta, E_xc] into `tail`."""
         # spin densities declared projectors by the fast UHF/UKS loop (`_xc_projector_pair`): D_s = Z_s Z_s^T without orbitals
-        Zps = [None, None]
+        Zts = [None, None]
         proj = getattr(self, "_xc_projector_pair", None)
         if self.xc_lowrank and proj is not None and proj[0] is dm:
-            ch = 24 if gga else 32
-            for s_ in range(2):
-                Zt = self._lowrank_factor(proj[1][s_], proj[2][s_], ("uks", s_)) if proj[2][s_] > 0 else None
-                if Zt is not None:
-                    Zp = torch.zeros(n, (Zt.shape[0] + ch - 1) // ch * ch, dtype=torch.float64, device=Zt.device)
-                    Zp[:, :Zt.shape[0]] = Zt.T
-                    Zps[s_] = Zp
-        for w, ao in self._ao_blocks(gga):
-            rho, tau = [None, None], [None, None]
-            for s_ in range(2):
-                if Zps[s_] is not None:      # spin density from its low-rank factor (dft.KSMixin._lowrank_factor), one pass over ao
-                    if gga == 2:
-                        rho[s_], tau[s_] = eng.xc_rho_lowrank(ao, Zps[s_], deriv=1, with_tau=True)
-                    else:
-                        rho[s_] = eng.xc_rho_lowrank(ao, Zps[s_], deriv=1 if gga else 0)
-                else:
-                    rho[s_] = eng.xc_rho(ao, dm[s_] @ ao[0], deriv=1 if gga else 0)
-                    if gga == 2:
-                        tau[s_] = eng.xc_tau(ao, dm[s_])
-            if gga == 2:
-                e, wva, wvb = eng.xc_eval_mgga_spin(terms, rho[0], rho[1], tau[0], tau[1], w)
-            else:
-                e, wva, wvb = eng.xc_eval_spin(terms, rho[0], rho[1], w, gga, params=params)
-            eng.xc_tail(w, (rho[0][0], rho[1][0], e), tail)   # N_alpha, N_beta, E_xc of the block: one deterministic launch
-            for s_, wv in ((0, wva), (1, wvb)):
-                eng.xc_vmat(ao[0], eng.xc_aow(ao, wv, gga), vmat[s_])
-                if gga == 2:
-                    for k in (1, 2, 3):
-                        eng.xc_vmat(ao[k], wv[4] * ao[k], vmat[s_])
-        return hyb
+            Zts = [self._lowrank_factor(proj[1][s_], proj[2][s_], ("uks", s_)) if proj[2][s_] > 0 else None for s_ in range(2)]
+        return self._nr_raw(dm, Zts, [("uks", 0), ("uks", 1)], vmat, tail)
 
     def _fock_pair(self, dm):
         """One collective per Fock build: [J(2) | K(2) | Vxc(2) | N_alpha N_beta E_xc] partial sums in one flat buffer."""

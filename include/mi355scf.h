@@ -321,7 +321,7 @@ int mi_xc_rho_lowrank(mi_ctx *ctx, const double *d_ao, const double *d_Zp, int l
                       double *d_tau, void *stream);
 
 /* Closed-shell XC energy density and potential on the grid.  kinds[]: 1 Slater, 2 B88, 3 VWN-RPA,
- * 4 VWN5, 5 LYP, 6 PBE-x, 7 PBE-c, 12 short-range B88 (mi_xc_eval_p only) with weights coefs[].  Outputs (any may be NULL): d_exc[ng] energy
+ * 4 VWN5, 5 LYP, 6 PBE-x, 7 PBE-c, 12 short-range B88 (needs its omega in params: the _p entry points) with weights coefs[].  Outputs (any may be NULL): d_exc[ng] energy
  * per volume; d_wv[(1|4)][ng] = {w*vrho/2, 2*w*vsigma*grad rho}; d_vrho, d_vsigma raw derivatives.
  * Replaces libxc (HYB_GGA_XC_B3LYP etc.) reached through mf.xc (templates/calculate_energy.py:149). */
 int mi_xc_eval(const int32_t *kinds, const double *coefs, int nterms, const double *d_rho,
@@ -335,7 +335,9 @@ int mi_xc_eval_spin(const int32_t *kinds, const double *coefs, int nterms, const
  * Kind 12 = short-range B88 of CAM-B3LYP, params[i] = omega > 0 (required): per spin channel e_s^B88 F(a_s), ITYH attenuation
  * (Iikura, Tsuneda, Yanai, Hirao 2001) with a_s = omega / (2 k_s), k_s = sqrt(9 pi / K_s) rho_s^(1/3), e_s^B88 = -1/2
  * rho_s^(4/3) K_s; F(a) in closed form below a = 4 and by its asymptotic series from there (the closed form cancels in FP64).
- * The spin form applies it per channel by spin scaling.  Other kinds ignore their parameter. */
+ * The spin form applies it per channel by spin scaling.  Other kinds ignore their parameter.  Every XC entry point checks its
+ * terms the same way: at most 8, known ids, a meta-GGA id only in mi_xc_eval_mgga*, kind 12 only with its omega (so never in
+ * an entry point without params); ng < 0 is an error and ng == 0 returns 0 without a launch. */
 int mi_xc_eval_p(const int32_t *kinds, const double *coefs, const double *params, int nterms, const double *d_rho,
                  const double *d_w, int64_t ng, int gga, double *d_exc, double *d_wv, double *d_vrho, double *d_vsigma, void *stream);
 int mi_xc_eval_spin_p(const int32_t *kinds, const double *coefs, const double *params, int nterms, const double *d_rhoa,
@@ -385,7 +387,7 @@ int mi_grad_eri_sharded(mi_ctx *ctx, const double *d_D, const double *d_Dspin, d
                         int nranks, void *stream);
 
 /* meta-GGA evaluation (functional ids 8 TPSS exchange, 9 TPSS correlation, 10 M06-2X exchange, 11 M06-2X correlation; ids
- * 1-7 may be mixed in): d_tau[ng] = 1/2 sum_i |grad phi_i|^2; d_wv[5][ng] as mi_xc_eval plus d_wv[4] = w/4 de/dtau (the caller
+ * 1-7 may be mixed in; 12 is refused, there is no params argument): d_tau[ng] = 1/2 sum_i |grad phi_i|^2; d_wv[5][ng] as mi_xc_eval plus d_wv[4] = w/4 de/dtau (the caller
  * adds sum_k ao_k^T (wv4 ao_k) to the unsymmetrised V_xc).  `--method M06-2X` at templates/calculate_energy.py:263;
  * default functional of templates/calculate_bde.py:105.  Stands in for libxc MGGA_X/C_TPSS, HYB_MGGA_X_M06_2X, MGGA_C_M06_2X
  * [MEM]; the M06-2X parameter tables are entered from memory (unverified). */
