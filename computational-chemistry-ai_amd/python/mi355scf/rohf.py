@@ -13,15 +13,15 @@ empty.  Da = C[:, :na] C[:, :na]^T, Db = C[:, :nb] C[:, :nb]^T; the Fock pair (F
     virtual     Fc      Fa      Fc
 
 and into the orbital gradient G (the closed-open block of Fb, the open-virtual block of Fa, the closed-virtual block of Fc, signed
-like F n - n F) with the partial sums of |G|^2.  The loop is `UHF._kernel_plain`: CDIIS (`PairDIIS`) extrapolates the one matrix
-S C F_eff C^T S with the error vector S C G C^T S, and the new orbitals come from one `eigh` of it per cycle in the
-Cholesky-orthogonalised basis.  The two nested densities are not purified (DESIGN.md section 14 names that as the follow-up).
+like F n - n F) with the partial sums of |G|^2.  The loop is UHF's plain loop (`UHF._plain_start`, `_plain_step`, `_ufinal`): CDIIS
+(`PairDIIS`) extrapolates the one matrix S C F_eff C^T S with the error vector S C G C^T S, and the new orbitals come from one
+`eigh` of it per cycle in the Cholesky-orthogonalised basis.  The two nested densities are not purified (DESIGN.md section 14 names
+that as the follow-up).
 
 Refused (NotImplementedError, never approximated): range-separated hybrids, density fitting, sharded runs; PCM, TDA / TDDFT, MP2
 and CCSD refuse an ROHF reference themselves.  `mcscf.CASCI` accepts ROHF (not ROKS).
 """
 import ctypes
-import time
 
 import numpy as np
 import torch
@@ -106,7 +106,7 @@ class ROHF(UHF):
             raise NotImplementedError(f"ROKS: the range-separated hybrid {self.xc} is not implemented (RKS / UKS only)")
         if getattr(self, "with_df", None) is not None or getattr(self, "with_solvent", None) is not None:
             raise NotImplementedError("ROHF / ROKS: density fitting and PCM solvation are not implemented")
-        return self._kernel_plain(dm0)
+        return self._run(dm0, fast=False)
 
     scf = kernel
 
@@ -145,10 +145,9 @@ class ROHF(UHF):
         nvir = n - ncore - nopen
         return max(ncore * nopen + nopen * nvir + ncore * nvir, 1)
 
-    def _uresult(self, dm, F, e_tot, mo_e, mo_c, t_start):
+    def _set_orbitals(self, dm, F, mo_e, mo_c):
+        """The one orbital set with occupations 2 / 1 / 0; `mo_energy` carries the per-spin diagonals of the Fock pair F."""
         ncore, nopen = self._classes()
-        self._dm, self._fock = dm, F
-        self.e_tot = e_tot
         C = mo_c[0]
         e = mo_e[0].cpu().numpy().view(_MOEnergy)
         e.mo_ea, e.mo_eb = (torch.einsum("pi,spq,qi->si", C, F, C).cpu().numpy())
@@ -158,13 +157,6 @@ class ROHF(UHF):
         occ[:ncore] = 2.0
         occ[ncore:ncore + nopen] = 1.0
         self.mo_occ = occ
-        self.timing["total_seconds"] = time.time() - t_start
-        if self.converged:
-            ss, mult = self.spin_square()
-            self._log(3, f"converged SCF energy = {self.e_tot:.15g}  <S^2> = {ss:.8g}  2S+1 = {mult:.8g}")
-        else:
-            self._log(3, f"SCF not converged.\nSCF energy = {self.e_tot:.15g} after {self.max_cycle} cycles")
-        return self.e_tot
 
 
 class ROKS(ROHF, UKS):

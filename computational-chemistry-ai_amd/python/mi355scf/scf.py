@@ -950,17 +950,17 @@ class SCF:
         st["cycle"] += 1
         return st
 
-    def kernel(self, dm0=None, **kw):
-        t_start = time.time()
-        st = self._start(dm0)
-        eng = self.engine
+    def _iterate(self, st, step):
+        """The outer loop of every SCF driver here: `step(st)` runs one cycle and leaves `cycle`, `e_tot`, `de` and `gnorm` in the
+        state `st`, until |delta E| < conv_tol and |g| < conv_tol_grad or `max_cycle` cycles have run.  Sets `converged`, `cycles`
+        and `timing["loop_seconds"]`."""
         conv_tol = self.conv_tol
         conv_tol_grad = self.conv_tol_grad if self.conv_tol_grad is not None else np.sqrt(conv_tol)
         self._log(4, f"init E= {st['e_tot']:.15g}")
         self.converged = False
         t_loop = time.time()
         while st["cycle"] < self.max_cycle:
-            self._step(st)
+            step(st)
             self._log(4, f"cycle= {st['cycle']} E= {st['e_tot']:.15g}  delta_E= {st['de']:.3g}  |g|= {st['gnorm']:.3g}")
             if abs(st["de"]) < conv_tol and st["gnorm"] < conv_tol_grad:
                 self.converged = True
@@ -968,6 +968,12 @@ class SCF:
         st.pop("front", None)                            # the speculative head of a cycle that will not run
         self.cycles = st["cycle"]
         self.timing["loop_seconds"] = time.time() - t_loop
+
+    def kernel(self, dm0=None, **kw):
+        t_start = time.time()
+        st = self._start(dm0)
+        eng = self.engine
+        self._iterate(st, self._step)
         t_final = time.time()
         if self.converged and self.conv_check:
             self._step(st, use_diis=False, want_mo=True)

@@ -154,9 +154,17 @@ class UHF(SCF):
         small = n < self.sp2_min_nao or self.eig_method != "sp2"
         warm = all(no == 0 or sp.plan is not None for sp, no in zip(self._spin_states(n), (na, nb)))
         use_fast = self.fast_loop and (small or (self.fast_loop == "always" and warm))
-        if use_fast:
-            return self._kernel_fast(dm0)
-        return self._kernel_plain(dm0)
+        return self._run(dm0, use_fast)
+
+    def _run(self, dm0, fast):
+        """One SCF on the fast or the plain loop: the loop's start state, the outer loop of every driver, the common finish."""
+        t_start = time.time()
+        self._setup_once()
+        na, nb = self.mol.nelec
+        self.nelec = (na, nb)
+        st = self._fast_start(dm0) if fast else self._plain_start(dm0)
+        self._iterate(st, self._ustep if fast else self._plain_step)
+        return self._ufinal(st, t_start)
 
     # Plain loop (round 3): once a spin's checked, trace-correcting purification has run with |g| below `sp2_trace_plan_gnorm`, its
     # trace history gives the bounds of a purification PLAN for that spin (sp2plan.bounds_from_traces, as in the closed-shell
@@ -366,12 +374,9 @@ class UHF(SCF):
         na, nb = self.nelec
         return max(na * (n - na) + nb * (n - nb), 1)
 
-    def _uresult(self, dm, F, e_tot, mo_e, mo_c, t_start):
-        """Results of a finished loop onto the object (host copies of the orbitals, aufbau occupations, plans for the next
-        kernel()); returns e_tot."""
+    def _set_orbitals(self, dm, F, mo_e, mo_c):
+        """Host copies of the final orbitals with aufbau occupations, and the purification plans of the next kernel()."""
         na, nb = self.nelec
-        self._dm, self._fock = dm, F
-        self.e_tot = e_tot
         self.mo_energy = mo_e.cpu().numpy()
         self._seed_plans(mo_e)
         self.mo_coeff = mo_c.cpu().numpy()
@@ -379,6 +384,12 @@ class UHF(SCF):
         occ[0, :na] = 1.0
         occ[1, :nb] = 1.0
         self.mo_occ = occ
+
+    def _uresult(self, dm, F, e_tot, mo_e, mo_c, t_start):
+        """Results of a finished loop onto the object; returns e_tot."""
+        self._dm, self._fock = dm, F
+        self.e_tot = e_tot
+        self._set_orbitals(dm, F, mo_e, mo_c)
         self.timing["total_seconds"] = time.time() - t_start
         if self.converged:
             ss, mult = self.spin_square()
@@ -387,59 +398,45 @@ class UHF(SCF):
             self._log(3, f"SCF not converged.\nSCF energy = {self.e_tot:.15g} after {self.max_cycle} cycles")
         return self.e_tot
 
-    def _kernel_fast(self, dm0=None):
-        t_start = time.time()
-        mol = self.mol
-        self._setup_once()
-        eng = self.engine
-        L = self._L
-        na, nb = mol.nelec
-        self.nelec = (na, nb)
-        n = eng.nao
-        dm = self._udm0(dm0)
-        st = {"nocc": (na, nb), "enuc": mol.energy_nuc(), "cycle": 0, "diis": DeviceDIIS(eng, self.diis_space, nmat=2),
-              "spin": self._spin_states(n), "nvo": max(na * (n - na) + nb * (n - nb), 1), "e_tot": None}
-        dmo0 = torch.stack([L.T @ dm[0] @ L, L.T @ dm[1] @ L])
-        ctx = self._ulaunch(st, dm, dmo0, 0, [None, None])
-        self._ufinish(st, ctx, [None, None], None)
-        conv_tol = self.conv_tol
-        conv_tol_grad = self.conv_tol_grad if self.conv_tol_grad is not None else np.sqrt(conv_tol)
-        self._log(4, f"init E= {st['e_tot']:.15g}")
-        self.converged = False
-        t_loop = time.time()
-        while st["cycle"] < self.max_cycle:
-            self._ustep(st)
-            self._log(4, f"cycle= {st['cycle']} E= {st['e_tot']:.15g}  delta_E= {st['de']:.3g}  |g|= {st['gnorm']:.3g}")
-            if abs(st["de"]) < conv_tol and st["gnorm"] < conv_tol_grad:
-                self.converged = True
-                break
-        st.pop("front", None)
-        self.cycles = st["cycle"]
-        self.timing["loop_seconds"] = time.time() - t_loop
-        F, dm, e_tot = st["F"], st["dm"], st["e_tot"]
-        mo_e, mo_c = self._uorbitals(F)
-        if self.converged and self.conv_check:
-            ca, cb = mo_c[0][:, :na], mo_c[1][:, :nb]
-            dm = torch.stack([ca @ ca.T, cb @ cb.T])
+    def _occupied_density(self, mo_c):
+        na, nb = self.nelec
+        ca, cb = mo_c[0][:, :na], mo_c[-1][:, :nb]      # (one orbital set: the beta orbitals are the first n_beta of it)
+        return torch.stack([ca @ ca.T, cb @ cb.T])
+
+    def _ufinal(self, st, t_start):
+        """After `_iterate`, for both loops: the final orbitals, the `conv_check` extra cycle (density of those orbitals, one Fock
+        build, no extrapolation), the results.  Where the two loops differ they do so on purpose:"""
+        plain = st["plain"]
+        check = self.converged and self.conv_check
+        if plain and st["use_sp2"]:
+            # the pass count of the spin purified last carries over to the object (the fast loop's purifiers live on the object)
+            self._purifier.iters = st["pur"][1 if self.nelec[1] else 0].iters
+        if plain:
+            # plain loop: the matrix CDIIS extrapolates (ROHF: F_eff) is diagonalised for the extra cycle, when the loop has made no
+            # orbitals (max_cycle = 0) and when it purified; otherwise -- not converged, or conv_check off -- the orbitals of the
+            # last in-loop `eigh` are kept, which belong to the last EXTRAPOLATED (and level-shifted) matrix, not to `Fd`
+            Fd, fresh = st["Fd"], check or st["mo_e"] is None or st["use_sp2"]
+        else:
+            # fast loop: always the orbitals of the last Fock pair (its cycles keep projectors, not orbitals)
+            Fd, fresh = st["F"], True
+        mo_e, mo_c = self._uorbitals(Fd) if fresh else (st["mo_e"], st["mo_c"])
+        dm, F, e_tot = st["dm"], st["F"], st["e_tot"]
+        if check:
+            dm = self._occupied_density(mo_c)
             F, e_el = self._fock_pair(dm)
+            if st.get("sync") is not None:        # plain loop, sharded: rank 0's energy on every rank, like the cycles' scalars
+                e_el = e_el.reshape(1)
+                st["sync"](e_el)
             e_new = float(e_el) + st["enuc"]
             self._log(4, f"Extra cycle  E= {e_new:.15g}  delta_E= {e_new - e_tot:.3g}")
             e_tot = e_new
         return self._uresult(dm, F, e_tot, mo_e, mo_c, t_start)
 
-    def _kernel_plain(self, dm0=None, **kw):
-        t_start = time.time()
-        mol = self.mol
-        self._setup_once()
-        eng = self.engine
-        S, L, Li = self._S, self._L, self._Linv
-        na, nb = mol.nelec
-        self.nelec = (na, nb)
-        n = eng.nao
+    # --- the plain loop: AO basis, host-side pair DIIS, one host sync per cycle -------------------------------------------
+    def _plain_start(self, dm0):
+        """State of the plain loop after the first Fock build (`self.nelec` set)."""
         dm = self._udm0(dm0)
-        enuc = mol.energy_nuc()
-        conv_tol = self.conv_tol
-        conv_tol_grad = self.conv_tol_grad if self.conv_tol_grad is not None else np.sqrt(conv_tol)
+        enuc = self.mol.energy_nuc()
         # sharded runs: the all-reduced J/K(/Vxc) are identical on every rank and the replicated algebra below is made of
         # deterministic library reductions, so the ranks stay bit-identical without broadcasting control scalars;
         # `sync_control` (auto-on for sharded runs, see scf.SCF) makes rank 0's Gram row / scalars authoritative
@@ -447,110 +444,101 @@ class UHF(SCF):
         if self._sync_control_on():
             from . import parallel
             sync = lambda t: parallel.broadcast0(t, self._pg)
-        diis = PairDIIS(self.diis_space, sync)
         F, e_el = self._fock_pair(dm)
-        e_tot = float(e_el) + enuc
-        self._log(4, f"init E= {e_tot:.15g}")
-        self.converged = False
-        cycle = 0
-        t_loop = time.time()
-        mo_e = mo_c = None
-
-        def density(cs):
-            ca, cb = cs[0][:, :na], cs[-1][:, :nb]      # (one orbital set: the beta orbitals are the first n_beta of it)
-            return torch.stack([ca @ ca.T, cb @ cb.T])
-
+        st = {"plain": True, "enuc": enuc, "cycle": 0, "diis": PairDIIS(self.diis_space, sync), "sync": sync,
+              "nvo": self._n_rotations(), "dm": dm, "F": F, "e_tot": float(e_el) + enuc, "de": 0.0, "gnorm": 0.0,
+              "mo_e": None, "mo_c": None}
         # larger matrices: occupied projector of each spin by SP2 purification (same GEMM-only path as RHF, `scf.py`)
         # instead of a diagonalisation per cycle; orbitals are then only needed once, after convergence
-        use_sp2 = self._purify_spins and self.eig_method == "sp2" and n >= self.sp2_min_nao
+        st["use_sp2"] = self._purify_spins and self.eig_method == "sp2" and self.engine.nao >= self.sp2_min_nao
         # one purifier per spin for this kernel() only (plans from the traces of its checked runs), starting from the object's
         # pass count
-        pur = [Purifier(self, self._purifier.iters) for _ in range(2)]
+        st["pur"] = [Purifier(self, self._purifier.iters) for _ in range(2)]
+        st["Fd"], st["err"], _g2 = self._diis_pair(F, dm)
+        return st
 
-        def new_density(Fx):
-            if not use_sp2:
-                e_, c_ = self._uorbitals(Fx)
-                return density(c_), (e_, c_)
-            out = []
-            xs = []        # spin projectors X_s in the orthonormal basis (UKS: rho_s from a low-rank factor, `_xc_projector_pair`)
-            for s_, no in ((0, na), (1, nb)):
-                if no == 0:
-                    out.append(torch.zeros(n, n, dtype=torch.float64, device=eng.device))
-                    xs.append(out[-1])
-                    continue
-                fo = (Li @ Fx[s_] @ Li.T).contiguous()
-                p = pur[s_]
-                dmo = self._planned_spin_density(fo, no, p)
-                if dmo is None:
-                    dmo = p.checked(fo, no)
-                    g_prev = gnorm if cycle > 0 else 1.0e9          # (no orbital gradient before the first cycle has finished)
-                    if (p.trace_bounds is not None and self.sp2_planned and self.sp2_trace_plan
-                            and g_prev <= self.sp2_trace_plan_gnorm):
-                        p.plan_from_traces()
-                    p.trace_bounds = None
-                if dmo is None:      # purification did not converge (vanishing gap): diagonalise this spin
-                    e_, c_ = torch.linalg.eigh(fo)
-                    co = Li.T @ c_[:, :no]
-                    out.append(co @ co.T)
-                    xs = None
-                else:
-                    out.append(0.5 * (Li.T @ dmo @ Li))
-                    if xs is not None:
-                        xs.append(0.5 * dmo)
-            self._plain_projectors = xs
-            return torch.stack(out), None
+    def _plain_density(self, st, Fx):
+        """(spin densities, spin projectors X_s in the orthonormal basis or None, (mo_e, mo_c) or None) from the matrices `Fx`:
+        by `eigh` (orbitals, no projectors) or by purifying each spin (projectors unless a spin fell back to `eigh`; no
+        orbitals)."""
+        if not st["use_sp2"]:
+            mo = self._uorbitals(Fx)
+            return self._occupied_density(mo[1]), None, mo
+        n, Li = self.engine.nao, self._Linv
+        out = []
+        xs = []        # (UKS takes rho_s from a low-rank factor of X_s, `_xc_projector_pair`)
+        for s_, no in enumerate(self.nelec):
+            if no == 0:
+                out.append(torch.zeros(n, n, dtype=torch.float64, device=self.engine.device))
+                xs.append(out[-1])
+                continue
+            fo = (Li @ Fx[s_] @ Li.T).contiguous()
+            p = st["pur"][s_]
+            dmo = self._planned_spin_density(fo, no, p)
+            if dmo is None:
+                dmo = p.checked(fo, no)
+                g_prev = st["gnorm"] if st["cycle"] > 0 else 1.0e9      # (no orbital gradient before the first cycle has finished)
+                if (p.trace_bounds is not None and self.sp2_planned and self.sp2_trace_plan
+                        and g_prev <= self.sp2_trace_plan_gnorm):
+                    p.plan_from_traces()
+                p.trace_bounds = None
+            if dmo is None:      # purification did not converge (vanishing gap): diagonalise this spin
+                e_, c_ = torch.linalg.eigh(fo)
+                co = Li.T @ c_[:, :no]
+                out.append(co @ co.T)
+                xs = None
+            else:
+                out.append(0.5 * (Li.T @ dmo @ Li))
+                if xs is not None:
+                    xs.append(0.5 * dmo)
+        return torch.stack(out), xs, None
 
-        nvo = self._n_rotations()
-        de = gnorm = 0.0
-        Fd, err, g2 = self._diis_pair(F, dm)
-        while cycle < self.max_cycle:
-            Fx = diis.update(Fd, err) if cycle + 1 >= self.diis_start_cycle else Fd
-            if self.level_shift:   # F_s + shift (S - S D_s S): virtual space of each spin raised (AO form of PySCF's level_shift)
-                Fx = Fx + self.level_shift * (S.unsqueeze(0) - torch.stack([S @ d @ S for d in self._shift_densities(dm)]))
-            self._plain_projectors = None
-            dm, mo = new_density(Fx)
-            if mo is not None:
-                mo_e, mo_c = mo
-            # purified spin densities are projectors of known rank: UKS takes rho_s from their low-rank factors (one pass over
-            # the AO values instead of an N x N x n_grid product per spin), exactly as in the fast loop
-            xs = self._plain_projectors
-            self._xc_projector_pair = (dm, xs, (na, nb)) if xs is not None else None
-            F, e_el = self._fock_pair(dm)
-            if self._xc_projector_pair is not None and not bool(torch.isfinite(e_el).all()):
-                self._xc_projector_pair = None          # a failed factorisation poisons itself with NaN: full densities instead
-                F, e_el = self._fock_pair(dm)
+    def _fock_pair_of_projectors(self, dm, xs):
+        """`_fock_pair(dm)` with the spin densities declared projectors `xs` of known rank: UKS takes rho_s from their low-rank
+        factors (one pass over the AO values instead of an N x N x n_grid product per spin), exactly as in the fast loop.  A
+        failed factorisation poisons itself with NaN: the pair is then rebuilt from the full densities."""
+        self._xc_projector_pair = (dm, xs, self.nelec) if xs is not None else None
+        F, e_el = self._fock_pair(dm)
+        if xs is not None and not bool(torch.isfinite(e_el).all()):
             self._xc_projector_pair = None
-            Fd, err, g2 = self._diis_pair(F, dm)
-            ctrl = torch.stack([e_el.reshape(()), g2.reshape(())])
-            if sync is not None:
-                sync(ctrl)
-            ctrl = ctrl.cpu().numpy()
-            e_new = float(ctrl[0]) + enuc
-            gnorm = float(np.sqrt(max(ctrl[1], 0.0) / 2.0)) / np.sqrt(nvo)
-            de = e_new - e_tot
-            e_tot = e_new
-            cycle += 1
-            self._log(4, f"cycle= {cycle} E= {e_tot:.15g}  delta_E= {de:.3g}  |g|= {gnorm:.3g}")
-            if abs(de) < conv_tol and gnorm < conv_tol_grad:
-                self.converged = True
-                break
-        self.cycles = cycle
-        self.timing["loop_seconds"] = time.time() - t_loop
-        if use_sp2:
-            self._purifier.iters = pur[1 if nb else 0].iters   # the count of the spin purified last carries over to the object
-        if self.converged and self.conv_check:
-            mo_e, mo_c = self._uorbitals(Fd)
-            dm = density(mo_c)
             F, e_el = self._fock_pair(dm)
-            e_el = e_el.reshape(1)
-            if sync is not None:
-                sync(e_el)
-            e_new = float(e_el) + enuc
-            self._log(4, f"Extra cycle  E= {e_new:.15g}  delta_E= {e_new - e_tot:.3g}")
-            e_tot = e_new
-        if mo_e is None or (use_sp2 and not (self.converged and self.conv_check)):
-            mo_e, mo_c = self._uorbitals(Fd)
-        return self._uresult(dm, F, e_tot, mo_e, mo_c, t_start)
+        self._xc_projector_pair = None
+        return F, e_el
+
+    def _plain_step(self, st):
+        """One cycle: CDIIS extrapolation (and level shift) -> spin densities -> Fock pair -> energy and |g|, one host sync."""
+        S = self._S
+        Fx = st["diis"].update(st["Fd"], st["err"]) if st["cycle"] + 1 >= self.diis_start_cycle else st["Fd"]
+        if self.level_shift:   # F_s + shift (S - S D_s S): virtual space of each spin raised (AO form of PySCF's level_shift)
+            Fx = Fx + self.level_shift * (S.unsqueeze(0) - torch.stack([S @ d @ S for d in self._shift_densities(st["dm"])]))
+        dm, xs, mo = self._plain_density(st, Fx)
+        if mo is not None:
+            st["mo_e"], st["mo_c"] = mo
+        F, e_el = self._fock_pair_of_projectors(dm, xs)
+        Fd, err, g2 = self._diis_pair(F, dm)
+        ctrl = torch.stack([e_el.reshape(()), g2.reshape(())])
+        if st["sync"] is not None:
+            st["sync"](ctrl)
+        ctrl = ctrl.cpu().numpy()
+        e_tot = float(ctrl[0]) + st["enuc"]
+        gnorm = float(np.sqrt(max(ctrl[1], 0.0) / 2.0)) / np.sqrt(st["nvo"])
+        st.update(dm=dm, F=F, Fd=Fd, err=err, de=e_tot - st["e_tot"], e_tot=e_tot, gnorm=gnorm, cycle=st["cycle"] + 1)
+        return st
+
+    # --- the fast loop: orthonormal basis, device-side pair DIIS, pipelined step (`_ustep`) -------------------------------
+    def _fast_start(self, dm0):
+        """State of the fast loop after the first Fock build (`self.nelec` set)."""
+        eng, L = self.engine, self._L
+        n = eng.nao
+        na, nb = self.nelec
+        dm = self._udm0(dm0)
+        st = {"plain": False, "nocc": (na, nb), "enuc": self.mol.energy_nuc(), "cycle": 0,
+              "diis": DeviceDIIS(eng, self.diis_space, nmat=2), "spin": self._spin_states(n),
+              "nvo": max(na * (n - na) + nb * (n - nb), 1), "e_tot": None}
+        dmo0 = torch.stack([L.T @ dm[0] @ L, L.T @ dm[1] @ L])
+        ctx = self._ulaunch(st, dm, dmo0, 0, [None, None])
+        self._ufinish(st, ctx, [None, None], None)
+        return st
 
     def dip_moment(self, mol=None, dm=None, unit="Debye", verbose=None, **kw):
         if dm is None:

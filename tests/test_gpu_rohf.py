@@ -110,7 +110,7 @@ def test_closed_shell_limit():
 
 
 def test_rohf_never_takes_the_purification_branch_of_the_shared_loop():
-    """`UHF._kernel_plain` purifies each spin's Fock matrix from `sp2_min_nao` basis functions on; ROHF has one effective Fock
+    """`UHF._plain_density` purifies each spin's Fock matrix from `sp2_min_nao` basis functions on; ROHF has one effective Fock
     matrix and must diagonalise it at every size.  With the threshold lowered to 1 the run must be the default run."""
     from pyscf import scf
     mol, ref = _rohf("oh")

@@ -100,6 +100,94 @@ def test_uhf_sp2_path_matches_diagonalisation():
     print("UHF C6H6+ cc-pVTZ:", res)
 
 
+def _plain_oh(cls, method, **settings):
+    """OH / 6-31G* (16 AOs) on the plain loop with the per-spin purification switched on at every size."""
+    mf = cls(_mol(OH, "6-31G*", 1)).to_gpu()
+    mf.fast_loop, mf.sp2_min_nao, mf.conv_tol, mf.eig_method = False, 0, 1e-10, method
+    for k, v in settings.items():
+        setattr(mf, k, v)
+    return mf
+
+
+@pytest.fixture(scope="module")
+def oh_eigh_energy():
+    """Energy of the plain loop that diagonalises both spins every cycle: the reference of the purification branches."""
+    import gpu4pyscf
+    mf = _plain_oh(gpu4pyscf.scf.UHF, "eigh")
+    e = mf.kernel()
+    assert mf.converged
+    return e
+
+
+def test_plain_loop_purification_branch_plans_from_its_traces(oh_eigh_energy, monkeypatch):
+    """Smallest case that reaches the plain loop's purification branch: checked recursion per spin, a plan from its traces once
+    |g| is small, planned passes after that; the pass count of the spin purified last (beta) carries over to the object."""
+    import gpu4pyscf
+    from mi355scf import uhf
+    made, base = [], uhf.Purifier
+
+    class Spy(base):
+        def __init__(self, *a, **kw):
+            base.__init__(self, *a, **kw)
+            made.append(self)
+
+    monkeypatch.setattr(uhf, "Purifier", Spy)
+    mf = _plain_oh(gpu4pyscf.scf.UHF, "sp2")
+    mf._purifier.iters = 8                   # too few passes for any spectrum: the checked recursion has to raise the count
+    e = mf.kernel()
+    print(f"purified {e:.12f} eigh {oh_eigh_energy:.12f} diff {e - oh_eigh_energy:.2e} cycles {mf.cycles} paths {mf.path_counts} "
+          f"iters {mf._purifier.iters} per-kernel {[p.iters for p in made[-2:]]}")
+    assert mf.converged and abs(e - oh_eigh_energy) < 1e-9
+    assert mf.path_counts.get("planned_spin", 0) > 0
+    # (the loop makes its two purifiers last, after the object's own pair of `_spin_states`)
+    assert all(p.iters > 8 for p in made[-2:]) and mf._purifier.iters == made[-1].iters
+    assert abs(mf.spin_square()[0] - 0.75) < 0.02 and mf.mo_energy.shape == (2, mf.mol.nao)
+
+
+def test_plain_loop_diagonalises_a_spin_whose_purification_fails(oh_eigh_energy):
+    """`sp2_tol = 0` lets no checked purification pass: every spin of every cycle falls back to its own `eigh`."""
+    import gpu4pyscf
+    mf = _plain_oh(gpu4pyscf.scf.UHF, "sp2", sp2_tol=0.0)
+    e = mf.kernel()
+    print(f"fallback {e:.12f} eigh {oh_eigh_energy:.12f} diff {e - oh_eigh_energy:.2e} cycles {mf.cycles}")
+    assert mf.converged and abs(e - oh_eigh_energy) < 1e-9
+    assert getattr(mf, "path_counts", {}).get("planned_spin", 0) == 0
+
+
+def test_plain_loop_purifies_with_an_empty_spin_channel():
+    """H atom / cc-pVDZ, n_beta = 0: the purification branch with a spin that has nothing to purify."""
+    import gpu4pyscf
+    mf = gpu4pyscf.scf.UHF(_mol("H 0 0 0", "cc-pVDZ", 1)).to_gpu()
+    mf.fast_loop, mf.sp2_min_nao = False, 0
+    e = mf.kernel()
+    print(f"H atom {e:.10f} cycles {mf.cycles}")
+    assert mf.converged and abs(e + 0.49927840) < 2e-8
+    assert abs(mf.spin_square()[0] - 0.75) < 1e-10 and np.abs(mf.make_rdm1()[1]).max() == 0.0
+
+
+def test_plain_uks_loop_hands_purified_spin_densities_to_the_quadrature_as_projectors():
+    """UKS B3LYP with the low-rank density route open at every size: the plain loop declares its purified spin densities
+    projectors and the quadrature takes rho_s from their factors.  The bound is 3.98e-7, not the 1e-8 of the benzene comparison
+    below: the quadrature is not rotationally invariant and the pi hole of this radical is degenerate, so already the `eigh`-mode
+    energy moves by about 2e-7 from run to run (the UHF energies of the tests above repeat to 1e-13)."""
+    import gpu4pyscf
+    ref = _plain_oh(gpu4pyscf.dft.UKS, "eigh", xc="B3LYP", xc_lowrank_min_nao=0)
+    e_ref = ref.kernel()
+    mf = _plain_oh(gpu4pyscf.dft.UKS, "sp2", xc="B3LYP", xc_lowrank_min_nao=0)
+    seen, factor = [], mf._lowrank_factor
+
+    def counted(*a, **kw):
+        zt = factor(*a, **kw)
+        seen.append(zt is not None)
+        return zt
+
+    mf._lowrank_factor = counted
+    e = mf.kernel()
+    print(f"UKS purified {e:.12f} eigh {e_ref:.12f} diff {e - e_ref:.2e} cycles {mf.cycles} factorisations {sum(seen)}")
+    assert ref.converged and mf.converged and abs(e - e_ref) < 2 * 1.99e-7
+    assert sum(seen) >= 2            # (both spins of at least one cycle went through the factorisation)
+
+
 def test_uhf_fast_loop_with_per_spin_purifiers_equals_the_plain_loop():
     """The orthonormal-basis UHF/UKS loop (device-side pair DIIS, planned purification per spin, pipelined step) against the
     plain loop: benzene cation / cc-pVDZ with the purification forced on (sp2_min_nao = 0).  The first kernel() of an object is
