@@ -1044,6 +1044,7 @@ struct EriArgs {
     int ni, nj, nk, nl;       // spherical shell sizes (for the ownership test)
     // gradient only: density-weighted Schwarz screening  q_ab q_cd max|G| < dtol  (dmax == nullptr: off)
     const double *q_bra, *q_ket, *dmax; // Schwarz factors of the two pair lists; max |D| per shell pair [nbas][nbas]
+    const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
     int nbas_d;
     double dtol, hyb;
     // host side only (kernel choice): primitive-pair statistics of the shared (bra) and the varying (ket) pair list
@@ -1084,11 +1085,30 @@ static inline unsigned eri_grid(int64_t nblocks, unsigned C)
 }
 
 // Upper bound of |G| = |D_ab D_cd - hyb/4 (D_ac D_bd + D_ad D_bc)| over the AO quadruples of a shell quartet.
-__device__ inline double quartet_density_bound(const double *dmax, int nb, int a, int b, int c, int d, double hyb)
+// qmax (pair mode, mi_grad_eri_pairs): G has the extra term sum_k s_k Q^k_ab Q^k_cd, bounded by qmax_ab qmax_cd with
+// qmax_ab = sqrt(sum_k |s_k| max_ab |Q^k|^2) (Cauchy-Schwarz over k).
+__device__ inline double quartet_density_bound(const double *dmax, int nb, int a, int b, int c, int d, double hyb, const double *qmax = nullptr)
 {
     double coul = dmax[a * nb + b] * dmax[c * nb + d];
     double exch = dmax[a * nb + c] * dmax[b * nb + d] + dmax[a * nb + d] * dmax[b * nb + c];
-    return coul + 0.25 * hyb * exch;
+    double pairs = qmax ? qmax[a * nb + b] * qmax[c * nb + d] : 0.0;
+    return coul + 0.25 * hyb * exch + pairs;
+}
+
+// Pair mode of the gradient (mi_grad_eri_pairs): the two-particle density has the extra term sum_k s_k Q^k_ab Q^k_cd.  The Q^k
+// are kept as P[(a * ld + b) * K + k] = sqrt|s_k| Q^k_ab (padded tile order like D, k fastest: one AO pair's K values are one
+// contiguous run), the `npos` positive s_k first, so the term is a dot product of two runs with one change of sign.
+struct PairTerm {
+    const double *P;   // nullptr: no pair term
+    int K, npos;
+};
+__device__ inline double pair_term(const PairTerm &T, size_t ab, size_t cd)
+{
+    const double *x = T.P + ab * T.K, *y = T.P + cd * T.K;
+    double pos = 0.0, neg = 0.0;
+    for (int k = 0; k < T.npos; k++) pos = fma(x[k], y[k], pos);
+    for (int k = T.npos; k < T.K; k++) neg = fma(x[k], y[k], neg);
+    return pos - neg;
 }
 
 // Task t of a class pair -> (bra pair index, ket index).  `prefix` holds the nbra+1 cumulative task counts followed by
@@ -1137,12 +1157,13 @@ struct LiveArgs {
     const double *q_bra, *q_ket, *dmax;
     int nbas_d;
     double hyb, dtol;
+    const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
 };
 __device__ inline bool task_is_live(const LiveArgs &A, int64_t t, int &ib, int &ik)
 {
     find_task(A.prefix, A.nbra, t, ib, ik);
     const int a = A.bra[ib].sh_i, b = A.bra[ib].sh_j, c = A.ket[ik].sh_i, d = A.ket[ik].sh_j;
-    return !(A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, a, b, c, d, A.hyb) < A.dtol);
+    return !(A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, a, b, c, d, A.hyb, A.qmax) < A.dtol);
 }
 __global__ __launch_bounds__(256) void live_count_kernel(LiveArgs A, int *block_counts)
 {
@@ -1235,11 +1256,11 @@ __global__ __launch_bounds__(64) void eri_rys_kernel(EriArgs A)
     if (A.qtol > 0.0 && A.q_bra[ib] * A.q_ket[ik] < A.qtol) { if (QPW == 1) return; live = false; }
     if (QPW == 1) { // one quartet per wave: negligible / non-resident quartets leave at once
         if (A.own_table && !quartet_has_resident_tile(A.own_table, ab.ao_i, A.ni, ab.ao_j, A.nj, cd.ao_i, A.nk, cd.ao_j, A.nl, lane)) return;
-        if (A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j, A.hyb) < A.dtol) return;
+        if (A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax) < A.dtol) return;
     } else {
         if (A.own_table)
             live = quartet_has_resident_tile(A.own_table, ab.ao_i, A.ni, ab.ao_j, A.nj, cd.ao_i, A.nk, cd.ao_j, A.nl, lane, GSZ, grp) && live;
-        if (A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j, A.hyb) < A.dtol) live = false;
+        if (A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax) < A.dtol) live = false;
     }
     const int n = A.nroots, tsz = A.tsz, M1 = A.mmax + 1;
     const int ncd = cd.nprim, nPQ = live ? ab.nprim * ncd : 0;
@@ -6515,6 +6536,7 @@ struct GradXfArgs {
     int64_t nbatch;      // tasks in this launch
     const TaskIdx *tasks; // non-null: (bra, ket) per task, precomputed (get_task)
     const double *q_bra, *q_ket, *dmax; // same screening as EriArgs (the Rys kernel left these quartets' blocks unwritten)
+    const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
     int nbas_d;
     double dtol;
     // density fitting (mi_df_grad, template flag DF): the two-particle density is not a product of D's but a dense tensor,
@@ -6524,12 +6546,13 @@ struct GradXfArgs {
     int64_t zs_i, zs_j;
     const int *ket_atom;
     double w0;
+    PairTerm pt;         // pair mode (template flag PAIRS): G += sum_k s_k Q^k_ab Q^k_cd
 };
 #define GRAD_COPIES 4096
 
 // GSZ = lanes per quartet: 16 (four quartets per wave, small angular classes) or 64 (256 = four waves sharing one
 // quartet's LDS blocks is supported by the code but was measured slower and is not launched).
-template <int GSZ, bool MFMA, bool DF = false>
+template <int GSZ, bool MFMA, bool DF = false, bool PAIRS = false>
 __global__ __launch_bounds__(GSZ > 64 ? GSZ : 64) void eri_grad_contract(GradXfArgs A)
 {
     // sum_{x-independent part first}:  g[x] = sum_{r,e} M^x[r][e] * Z[r][e],  Z[r][e] = sum_f E0[e][f] Y[r][f],
@@ -6556,7 +6579,7 @@ __global__ __launch_bounds__(GSZ > 64 ? GSZ : 64) void eri_grad_contract(GradXfA
     if (A.swap) { int t_ = ib; ib = ik; ik = t_; }
     const PairRec dp = A.dplus[ib], cd = A.ket[ik];
     const bool live = in_batch && !(A.dmax && A.q_bra[ib] * A.q_ket[ik] *
-                                    quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb) < A.dtol);
+                                    quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax) < A.dtol);
     int m_off_m = 0;
     const double *D = A.D;
     const int ld = A.ld;
@@ -6585,7 +6608,9 @@ __global__ __launch_bounds__(GSZ > 64 ? GSZ : 64) void eri_grad_contract(GradXfA
             double ex = D[(size_t)i * ld + k] * D[(size_t)j * ld + l] + D[(size_t)i * ld + l] * D[(size_t)j * ld + k];
             if (A.Dm) // sum_s Ds x Ds = (D x D + M x M) / 2
                 ex += A.Dm[(size_t)i * ld + k] * A.Dm[(size_t)j * ld + l] + A.Dm[(size_t)i * ld + l] * A.Dm[(size_t)j * ld + k];
-            G[o] = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * A.hyb * ex;
+            double gv = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * A.hyb * ex;
+            if (PAIRS) gv += pair_term(A.pt, (size_t)i * ld + j, (size_t)k * ld + l);
+            G[o] = gv;
         }
     }
     __syncthreads();
@@ -6718,13 +6743,15 @@ struct GradRowsArgs {
     double *grad;
     int natm3, inv_from_second;
     const double *q_bra, *q_ket, *dmax;
+    const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
     int nbas_d;
     double dtol;
+    PairTerm pt;                        // pair mode (template flag PAIRS)
 };
 
 // GSZ lanes per quartet (64 / GSZ quartets per wave): the Rys phases keep 2 n .. 3 n lanes per primitive quartet busy and the
 // rows of the low bra classes fill a fraction of a wave, so the small classes run two or four latency chains side by side.
-template <int LC, int LD, int ROWS, int GSZ>
+template <int LC, int LD, int ROWS, int GSZ, bool PAIRS = false>
 __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
 {
     constexpr int NF = c_ne(LC, LD), MMAX = LC + LD, M1 = MMAX + 1;
@@ -6741,7 +6768,7 @@ __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
     if (A.swap) { int t_ = ib; ib = ik; ik = t_; }
     const bool has_m = A.ne_m > 0;
     const PairRec dp = A.dplus[ib], cd = A.ket[ik];
-    if (live && A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb) < A.dtol)
+    if (live && A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax) < A.dtol)
         live = false;
     if (QPW == 1 && !live) return;
     int m_prim = dp.prim_off, m_off_m = 0;
@@ -6766,7 +6793,9 @@ __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
             double ex = D[(size_t)i * ld + k] * D[(size_t)j * ld + l] + D[(size_t)i * ld + l] * D[(size_t)j * ld + k];
             if (A.Dm) // sum_s Ds x Ds = (D x D + M x M) / 2
                 ex += A.Dm[(size_t)i * ld + k] * A.Dm[(size_t)j * ld + l] + A.Dm[(size_t)i * ld + l] * A.Dm[(size_t)j * ld + k];
-            G[o] = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * A.hyb * ex;
+            double gv = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * A.hyb * ex;
+            if (PAIRS) gv += pair_term(A.pt, (size_t)i * ld + j, (size_t)k * ld + l);
+            G[o] = gv;
         }
     }
     const int ne = A.ne_p + A.ne_m;
@@ -6918,26 +6947,31 @@ static RowsGeom rows_geometry(int ne)
     if (ne <= 192) return {3, 64};
     return {0, 0};
 }
-template <int LC, int LD, int ROWS, int GSZ>
+template <int LC, int LD, int ROWS, int GSZ, bool PAIRS>
 static int launch_grad_rows_g(const GradRowsArgs &R, size_t shm_per_quartet, hipStream_t st)
 {
     constexpr int QPW = 64 / GSZ;
     const size_t shm = shm_per_quartet * QPW;
     if (shm > 160 * 1024) return 0;
     if (shm > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)eri_grad_rows_kernel<LC, LD, ROWS, GSZ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((eri_grad_rows_kernel<LC, LD, ROWS, GSZ>), dim3((unsigned)((R.ntask + QPW - 1) / QPW)), dim3(64), shm, st, R);
+        HIPCHK(hipFuncSetAttribute((const void *)eri_grad_rows_kernel<LC, LD, ROWS, GSZ, PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL((eri_grad_rows_kernel<LC, LD, ROWS, GSZ, PAIRS>), dim3((unsigned)((R.ntask + QPW - 1) / QPW)), dim3(64), shm, st, R);
     HIPCHK(hipGetLastError());
     return 1;
+}
+template <int LC, int LD, bool PAIRS>
+static int launch_grad_rows_p(RowsGeom gm, const GradRowsArgs &R, size_t shm_q, hipStream_t st)
+{
+    if (gm.rows == 2 && gm.gsz == 32) return launch_grad_rows_g<LC, LD, 2, 32, PAIRS>(R, shm_q, st);
+    if (gm.rows == 1 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 1, 64, PAIRS>(R, shm_q, st);
+    if (gm.rows == 2 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 2, 64, PAIRS>(R, shm_q, st);
+    if (gm.rows == 3 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 3, 64, PAIRS>(R, shm_q, st);
+    return 0;
 }
 template <int LC, int LD>
 static int launch_grad_rows_t(RowsGeom gm, const GradRowsArgs &R, size_t shm_q, hipStream_t st)
 {
-    if (gm.rows == 2 && gm.gsz == 32) return launch_grad_rows_g<LC, LD, 2, 32>(R, shm_q, st);
-    if (gm.rows == 1 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 1, 64>(R, shm_q, st);
-    if (gm.rows == 2 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 2, 64>(R, shm_q, st);
-    if (gm.rows == 3 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 3, 64>(R, shm_q, st);
-    return 0;
+    return R.pt.P ? launch_grad_rows_p<LC, LD, true>(gm, R, shm_q, st) : launch_grad_rows_p<LC, LD, false>(gm, R, shm_q, st);
 }
 // 1: launched, 0: no row kernel for this (other pair, number of rows), -1: error.  dry: only answers the question.
 static int launch_grad_rows(int lc, int ld, int ne, const GradRowsArgs &R, size_t shm_q, hipStream_t st, bool dry = false)
@@ -6978,12 +7012,14 @@ struct TpqGradArgs {
     double *grad;             // GRAD_COPIES private copies of [natm3]
     int natm3, inv_from_second;
     const double *q_bra, *q_ket, *dmax;
+    const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
     int nbas_d;
     double dtol;
     const TaskIdx *tasks;     // non-null: the compacted list of live quartets (already screened: dmax is null then)
+    PairTerm pt;              // pair mode (template flag PAIRS)
 };
 
-template <int L1, int L2, int LC, int LD>
+template <int L1, int L2, int LC, int LD, bool PAIRS = false>
 __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_grad_kernel(TpqGradArgs A)
 {
     constexpr bool HASM = L1 > 0;
@@ -7008,7 +7044,7 @@ __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_grad_kernel(TpqGradArgs A)
     const bool same_pair = A.same_class && ib == ik;
     if (A.swap) { int t_ = ib; ib = ik; ik = t_; }
     const PairRec dp = A.dplus[ib], cd = A.ket[ik];
-    if (live && A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb) < A.dtol)
+    if (live && A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax) < A.dtol)
         live = false;
     double force[3] = {0.0, 0.0, 0.0};
     if (live) {
@@ -7177,6 +7213,7 @@ __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_grad_kernel(TpqGradArgs A)
                     double ex = D[(size_t)i * ld + k] * D[(size_t)j * ld + l] + D[(size_t)i * ld + l] * D[(size_t)j * ld + k];
                     if (A.Dm) ex += A.Dm[(size_t)i * ld + k] * A.Dm[(size_t)j * ld + l] + A.Dm[(size_t)i * ld + l] * A.Dm[(size_t)j * ld + k];
                     Gd[sa * NS2 + sb] = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * A.hyb * ex;
+                    if (PAIRS) Gd[sa * NS2 + sb] += pair_term(A.pt, (size_t)i * ld + j, (size_t)k * ld + l);
                 }
             // Gc[a][b] = sum_{sa,sb} c1[a][sa] c2[b][sb] Gd[sa][sb]   (density back-transformed to cartesians: 3x fewer products)
             double h2[NS1 * NK2];
@@ -7254,7 +7291,9 @@ static int launch_eri_tpq_grad_t(const TpqGradArgs &Q, hipStream_t st)
     constexpr int NR = (L1 + 1 + L2 + LC + LD) / 2 + 1;
     const size_t shm = sizeof(double) * (size_t)RYS_NINT_H[NR] * 2 * NR * (RYS_DEG + 1);
     if (Q.ntask <= 0) return 1;   // nothing in this rank's share of the class (the class is still "handled")
-    hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD>), dim3((unsigned)((Q.ntask + TPQ_BLOCK - 1) / TPQ_BLOCK)), dim3(TPQ_BLOCK), shm, st, Q);
+    const dim3 grid((unsigned)((Q.ntask + TPQ_BLOCK - 1) / TPQ_BLOCK));
+    if (Q.pt.P) hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD, true>), grid, dim3(TPQ_BLOCK), shm, st, Q);
+    else hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD>), grid, dim3(TPQ_BLOCK), shm, st, Q);
     if (hipGetLastError() != hipSuccess) return fail("eri_tpq_grad_kernel launch failed");
     return 1;
 }
@@ -7311,6 +7350,32 @@ __global__ void shell_dmax_kernel(const double *D, const double *Dm, int ld, con
     out[idx] = m;
 }
 
+// pair mode: P[(r * ld + c) * K + k] = w[k] * Q[src[k]][iperm[r]][iperm[c]] (w = sqrt|s|, zero in the padding)
+__global__ void pad_pairs_kernel(const double *Q, const int *src, const double *w, int K, double *P, int nao, int ld, const int *__restrict__ iperm)
+{
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)ld * ld * K) return;
+    const int k = (int)(idx % K);
+    const int64_t rc = idx / K;
+    const int r = (int)(rc / ld), c = (int)(rc - (int64_t)r * ld);
+    P[idx] = (r < nao && c < nao) ? w[k] * Q[((size_t)src[k] * nao + iperm[r]) * nao + iperm[c]] : 0.0;
+}
+// qmax_ab = sqrt(sum_k max_{ab} P_k^2) per shell pair (see quartet_density_bound)
+__global__ void shell_qmax_kernel(const double *P, int K, int ld, const int *sh_ao, const int *sh_n, int nbas, double *out)
+{
+    int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nbas * nbas) return;
+    int a = idx / nbas, b = idx - a * nbas;
+    double sum = 0.0;
+    for (int k = 0; k < K; k++) {
+        double m = 0.0;
+        for (int i = 0; i < sh_n[a]; i++)
+            for (int j = 0; j < sh_n[b]; j++) m = fmax(m, fabs(P[((size_t)(sh_ao[a] + i) * ld + sh_ao[b] + j) * K + k]));
+        sum += m * m;
+    }
+    out[idx] = sqrt(sum);
+}
+
 __global__ void grad_reduce_copies_kernel(const double *copies, int natm3, double *grad)
 {
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -7334,7 +7399,12 @@ static int launch_grad_contract(bool df, const GradXfArgs &X, bool has_m, int nb
             HIPCHK(hipFuncSetAttribute((const void *)eri_grad_contract<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
         hipLaunchKernelGGL((eri_grad_contract<__VA_ARGS__>), dim3(nb), dim3(64), shm, st, X);                                             \
     } while (0)
-    if (!df && big <= 48 && shm * 4 <= 64 * 1024) { // small classes: four quartets per wave (16 lanes each)
+    if (!df && X.pt.P) {   // pair mode: the same three geometries with the pair term in the G gather
+        if (big <= 48 && shm * 4 <= 64 * 1024)
+            hipLaunchKernelGGL((eri_grad_contract<16, false, false, true>), dim3((nb + 3) / 4), dim3(64), shm * 4, st, X);
+        else if (mfma) GRAD_CONTRACT(64, true, false, true);
+        else GRAD_CONTRACT(64, false, false, true);
+    } else if (!df && big <= 48 && shm * 4 <= 64 * 1024) { // small classes: four quartets per wave (16 lanes each)
         hipLaunchKernelGGL((eri_grad_contract<16, false>), dim3((nb + 3) / 4), dim3(64), shm * 4, st, X);
     } else if (!df) {
         // (two or four waves sharing one quartet's LDS blocks -- eri_grad_contract<128|256, true> -- were measured at
@@ -7363,6 +7433,8 @@ struct GradState {
     DevBuf<int> d_shell_atom, d_sh_ao, d_sh_n;
     DevBuf<double> d_dmax;                   // max |D| per shell pair (null: no density-weighted screening)
     DevBuf<double> d_gcopies;
+    DevBuf<double> d_P, d_qmax;              // pair mode: sqrt|s_k| Q^k, k fastest (PairTerm), and its per-shell-pair bound
+    PairTerm pt{nullptr, 0, 0};
     Scratch scr_wp, scr_wm, scr_gtasks, scr_live;
     DevBuf<uint32_t> d_comp_p, d_comp_m;
     DevBuf<int64_t> d_prefix;
@@ -7409,7 +7481,8 @@ static int grad_ensure_live(GradState &G, GradClassPair &CP)
     }
     if (G.scr_live.ensure(c->device, SCR_GRAD_LIVE, sizeof(TaskIdx) * (size_t)ntask)) return -1;
     TaskIdx *d_live_tasks = (TaskIdx *)G.scr_live.p;
-    LiveArgs L{B.d_recs, Kc.d_recs, G.d_prefix, (int)B.recs.size(), ntask, B.d_q, Kc.d_q, G.d_dmax, c->nbas, G.hyb, c->opt_grad_dtol};
+    LiveArgs L{B.d_recs, Kc.d_recs, G.d_prefix, (int)B.recs.size(), ntask, B.d_q, Kc.d_q, G.d_dmax, c->nbas, G.hyb, c->opt_grad_dtol,
+               G.d_qmax.get()};
     hipLaunchKernelGGL(live_count_kernel, dim3(nblk), dim3(256), 0, st, L, G.d_live_counts.get());
     hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, st, G.d_live_counts.get(), nblk, G.d_live_off.get());
     hipLaunchKernelGGL(live_fill_kernel, dim3(nblk), dim3(256), 0, st, L, G.d_live_off.get(), d_live_tasks);
@@ -7448,6 +7521,7 @@ static int grad_route_tpq(GradState &G, GradClassPair &CP, const GradPerm &M)
     Q.rys = c->rys; Q.shell_xyz = c->d_shell_xyz; Q.D = c->d_Dpad; Q.Dm = G.d_Mpad; Q.ld = c->ldp; Q.hyb = G.hyb;
     Q.shell_atom = G.d_shell_atom; Q.grad = G.d_gcopies; Q.natm3 = G.natm3; Q.inv_from_second = M.swap ? 0 : 1;
     Q.q_bra = Dc.d_q; Q.q_ket = Oc.d_q; Q.dmax = live_q ? nullptr : G.d_dmax.get(); Q.nbas_d = c->nbas; Q.dtol = c->opt_grad_dtol;
+    Q.qmax = G.d_qmax; Q.pt = G.pt;
     const bool dbg1 = getenv("MI355_DEBUG") != nullptr;
     auto tq0 = std::chrono::steady_clock::now();
     if (dbg1) hipStreamSynchronize(st);
@@ -7483,6 +7557,7 @@ static int grad_route_rows(GradState &G, const GradClassPair &CP, const GradPerm
     R.D = c->d_Dpad; R.Dm = G.d_Mpad; R.ld = c->ldp; R.hyb = G.hyb; R.shell_atom = G.d_shell_atom; R.grad = G.d_gcopies; R.natm3 = G.natm3;
     R.inv_from_second = M.swap ? 0 : 1;
     R.q_bra = Dc.d_q; R.q_ket = Oc.d_q; R.dmax = M.dmax_w; R.nbas_d = c->nbas; R.dtol = c->opt_grad_dtol;
+    R.qmax = G.d_qmax; R.pt = G.pt;
     const int nscd_ = Oc.nsab, nf_ = Oc.ne;
     const size_t shm_q = sizeof(double) * ((size_t)R.PB * R.nroots * 3 * R.tsz + (size_t)R.PB * 2 * R.nroots + (size_t)R.PB +
                                            (size_t)nscd_ * nf_ + (size_t)R.nsab * nscd_);
@@ -7514,9 +7589,11 @@ static int grad_route_pipeline(GradState &G, const GradClassPair &CP, GradPerm &
     Ep.h_shared_np = B.mean_np; Ep.h_vary_mean = Kc.mean_np; Ep.h_vary_max4 = Kc.max4_np;
     Em.h_shared_np = B.mean_np; Em.h_vary_mean = Kc.mean_np; Em.h_vary_max4 = Kc.max4_np;
     Ep.q_bra = Dc.d_q; Ep.q_ket = Oc.d_q; Ep.dmax = M.dmax_w; Ep.nbas_d = c->nbas; Ep.dtol = c->opt_grad_dtol; Ep.hyb = hyb;
-    if (has_m) { Em.q_bra = Ep.q_bra; Em.q_ket = Ep.q_ket; Em.dmax = M.dmax_w; Em.nbas_d = c->nbas; Em.dtol = Ep.dtol; Em.hyb = hyb; }
+    Ep.qmax = G.d_qmax;
+    if (has_m) { Em.q_bra = Ep.q_bra; Em.q_ket = Ep.q_ket; Em.dmax = M.dmax_w; Em.nbas_d = c->nbas; Em.dtol = Ep.dtol; Em.hyb = hyb; Em.qmax = Ep.qmax; }
     GradXfArgs X{};
     X.q_bra = Ep.q_bra; X.q_ket = Ep.q_ket; X.dmax = M.dmax_w; X.nbas_d = c->nbas; X.dtol = Ep.dtol;
+    X.qmax = G.d_qmax; X.pt = G.pt;
     X.dplus = Dc.d_g_recs[M.orient][0]; X.dminus = has_m ? Dc.d_g_recs[M.orient][1] : nullptr; X.ket = Oc.d_recs;
     X.Mbuf = c->d_M; X.prefix = G.d_prefix; X.nbra = Ep.nbra; X.swap = Ep.swap; X.same_class = CP.same;
     X.ne_p = ne_of(l1 + 1, l2); X.ne_m = has_m ? ne_of(l1 - 1, l2) : 0; X.nf = Oc.ne;
@@ -7615,8 +7692,9 @@ static int grad_class_pair(GradState &G, PairClass &B, PairClass &Kc, bool same)
 // (rank, nranks): which share of the derivative-quartet batches this call evaluates.  It is an ARGUMENT, not the split of
 // the last mi_eri_prepare: in direct mode the tile store is prepared group by group (rank*ng + v of nranks*ng) while the
 // gradient is still shared between the nranks processes only.
-extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, double *d_grad, int rank, int nranks,
-                                   void *stream)
+// d_Q / s / K: the pair term of mi_grad_eri_pairs (K = 0: none, the plain Hartree-Fock form)
+static int grad_eri_run(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, const double *d_Q, const double *s, int K,
+                        double *d_grad, int rank, int nranks, void *stream)
 {
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail("mi_grad_eri: bad rank/nranks");
     if (!c || !d_D || !d_grad) return fail("mi_grad_eri: null argument");
@@ -7639,11 +7717,37 @@ extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d
     std::vector<int> shell_atom(c->nbas);
     for (int i = 0; i < c->nbas; i++) shell_atom[i] = c->shells[i].atom;
     if (G.d_shell_atom.upload(shell_atom)) return -1;
+    // pair mode: the terms with s_k != 0, positive ones first, scaled by sqrt|s_k| and laid out k fastest (PairTerm)
+    DevBuf<int> d_psrc;
+    DevBuf<double> d_pw;
+    {
+        std::vector<int> src;
+        std::vector<double> w;
+        for (int sign = 0; sign < 2; sign++)
+            for (int k = 0; k < K; k++)
+                if (sign == 0 ? s[k] > 0.0 : s[k] < 0.0) { src.push_back(k); w.push_back(sqrt(fabs(s[k]))); }
+        const int Ke = (int)src.size();
+        if (Ke > 0) {
+            int npos = 0;
+            for (int k = 0; k < K; k++) npos += s[k] > 0.0;
+            if (d_psrc.upload(src) || d_pw.upload(w)) return -1;
+            if (G.d_P.alloc(pp * Ke) != hipSuccess) return fail("mi_grad_eri_pairs: no memory for %d pair matrices", Ke);
+            hipLaunchKernelGGL(pad_pairs_kernel, dim3((unsigned)((pp * Ke + 255) / 256)), dim3(256), 0, st, d_Q, d_psrc.get(), d_pw.get(), Ke,
+                               G.d_P.get(), c->nao, c->ldp, c->d_iperm);
+            HIPCHK(hipGetLastError());
+            G.pt = PairTerm{G.d_P.get(), Ke, npos};
+        }
+    }
     // density-weighted screening: q_ab q_cd max|G| < grad_dtol skips the quartet (0 disables)
     if (c->opt_grad_dtol > 0.0) {
         std::vector<int> sh_ao(c->nbas), sh_n(c->nbas);
         for (int i = 0; i < c->nbas; i++) { sh_ao[i] = c->shells[i].ao; sh_n[i] = 2 * c->shells[i].l + 1; }
         if (G.d_sh_ao.upload(sh_ao) || G.d_sh_n.upload(sh_n)) return -1;
+        if (G.pt.P) {
+            HIPCHK(G.d_qmax.alloc((size_t)c->nbas * c->nbas));
+            hipLaunchKernelGGL(shell_qmax_kernel, dim3((c->nbas * c->nbas + 255) / 256), dim3(256), 0, st, G.pt.P, G.pt.K, c->ldp, G.d_sh_ao.get(),
+                               G.d_sh_n.get(), c->nbas, G.d_qmax.get());
+        }
         HIPCHK(G.d_dmax.alloc((size_t)c->nbas * c->nbas));
         hipLaunchKernelGGL(shell_dmax_kernel, dim3((c->nbas * c->nbas + 255) / 256), dim3(256), 0, st, c->d_Dpad, G.d_Mpad.get(), c->ldp,
                            G.d_sh_ao.get(), G.d_sh_n.get(), c->nbas, G.d_dmax.get());
@@ -7679,6 +7783,25 @@ extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d
                 std::chrono::duration<double>(tg1 - tg0).count(),
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - tg1).count());
     return 0;   // (the buffers of G go back to the pool, its Scratch handles to the per-device cache)
+}
+
+extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, double *d_grad, int rank, int nranks,
+                                   void *stream)
+{
+    return grad_eri_run(c, d_D, d_Dspin, hyb, nullptr, nullptr, 0, d_grad, rank, nranks, stream);
+}
+
+// Gradient of  1/2 D.J[D] - hyb/4 (D.K[D] + M.K[M]) + 1/2 sum_k s_k (Q^k|Q^k)  in one pass over the derivative quartets: the
+// two-particle density of every quartet is the Hartree-Fock form plus sum_k s_k Q^k_ab Q^k_cd (symmetric Q^k; the active-space
+// cumulant of a CAS wavefunction, casscf_grad.py).  K = 0 is mi_grad_eri_sharded.
+extern "C" int mi_grad_eri_pairs(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, const double *d_Q, const double *s, int K,
+                                 double *d_grad, int rank, int nranks, void *stream)
+{
+    if (K < 0 || K > 136) return fail("mi_grad_eri_pairs: K = %d outside 0 .. 136", K);
+    if (K > 0 && (!d_Q || !s)) return fail("mi_grad_eri_pairs: null argument");
+    for (int k = 0; k < K; k++)
+        if (!std::isfinite(s[k])) return fail("mi_grad_eri_pairs: s[%d] is not finite", k);
+    return grad_eri_run(c, d_D, d_Dspin, hyb, d_Q, s, K, d_grad, rank, nranks, stream);
 }
 
 extern "C" int mi_grad_eri(mi_ctx *c, const double *d_D, double hyb, double *d_grad, void *stream)

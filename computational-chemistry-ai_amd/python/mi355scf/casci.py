@@ -173,6 +173,13 @@ class CASCI:
         Cc, Ca = mo[:, :self.ncore], mo[:, self.ncore:self.ncore + self.ncas]
         return 2.0 * Cc @ Cc.T + Ca @ dm_act @ Ca.T
 
+    # ---- nuclear gradients (casscf_grad.py: state-specific CASSCF only; a CASCI or state-averaged object is refused there) -----
+    def nuc_grad_method(self):
+        from . import casscf_grad
+        return casscf_grad.Gradients(self)
+
+    Gradients = nuc_grad_method
+
 
 def __getattr__(name):
     """`CASSCF` (orbital optimisation, `casscf.py`) subclasses `CASCI` above, so it is imported on first use."""

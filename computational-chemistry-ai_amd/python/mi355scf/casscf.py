@@ -36,7 +36,8 @@ The gradient, rotation and step algebra are plain functions of NumPy arrays (tes
 
 Not implemented (refused with NotImplementedError): everything `ao2mo.check_rhf_reference` refuses, ROHF / ROKS references
 (ROHF-based CASSCF), references that have not been run, direct-mode stores, state-specific excited states (`fcisolver.nroots > 1`
-without `state_average`), nuclear gradients.
+without `state_average`).  Nuclear gradients (`nuc_grad_method()`, casscf_grad.py) exist for the state-specific wavefunction only:
+state-averaged objects are refused there.
 """
 import copy
 
@@ -303,7 +304,7 @@ class CASSCF(CASCI):
         FA_mo = 0.5 * (FA_mo + FA_mo.T)
         F = generalized_fock(FI_mo, FA_mo, gamma, Gamma, puvw, ncore, nc)
         g = pack(orbital_gradient(F, ncore, nc), ncore, nc)
-        return dict(mo=np.array(mo), e_tot=e_tot, e_states=e_states, e_core=e_core, ci=ci, gamma=gamma, g=g,
+        return dict(mo=np.array(mo), e_tot=e_tot, e_states=e_states, e_core=e_core, ci=ci, gamma=gamma, Gamma=Gamma, F=F, g=g,
                     hdiag=hessian_diagonal(FI_mo, FA_mo, F, gamma, ncore, nc), fock_ao=FI + FA, h_act=h_act, eri=eri,
                     ci_converged=bool(np.all(sol.converged)))
 

@@ -112,6 +112,7 @@ def lib():
         L.mi_grad_eri.argtypes = [vp, vp, ctypes.c_double, vp, vp]
         L.mi_grad_eri_spin.argtypes = [vp, vp, vp, ctypes.c_double, vp, vp]
         L.mi_grad_eri_sharded.argtypes = [vp, vp, vp, ctypes.c_double, vp, ctypes.c_int, ctypes.c_int, vp]
+        L.mi_grad_eri_pairs.argtypes = [vp, vp, vp, ctypes.c_double, vp, dp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp]
         L.mi_eri_get_memory.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
         L.mi_eri_release.argtypes = [vp]
         L.mi_tile_store_allocations.restype = ctypes.c_int64
@@ -606,11 +607,26 @@ class Engine:
     def grad_1e(self, D, W, grad):
         _check(lib().mi_grad_1e(self._h, D.data_ptr(), W.data_ptr(), grad.data_ptr(), self._stream()))
 
-    def grad_eri(self, D, hyb, grad, spin_density=None, rank=0, nranks=1):
+    def grad_eri(self, D, hyb, grad, spin_density=None, rank=0, nranks=1, pairs=None):
         """D: total density; spin_density: Da - Db for UHF/UKS (None: closed shell); (rank, nranks): this process's share
-        of the derivative-quartet batches (explicit: in direct mode the last prepare_eri split is a tile group, not a rank)."""
+        of the derivative-quartet batches (explicit: in direct mode the last prepare_eri split is a tile group, not a rank).
+        pairs = (Q [K, N, N] device tensor of symmetric matrices, s [K]): the same pass with sum_k s_k Q^k_ab Q^k_cd added to
+        every quartet's two-particle density (`mi_grad_eri_pairs`), i.e. plus the gradient of 1/2 sum_k s_k (Q^k|Q^k)."""
         if not self.eri_ready:
             self.prepare_eri()
+        if pairs is not None:
+            Q, s = pairs
+            s = np.ascontiguousarray(np.asarray(s, dtype=np.float64).ravel())
+            K = int(s.size)
+            if K > 0:
+                if not (torch.is_tensor(Q) and Q.dtype == torch.float64 and Q.device == D.device and Q.is_contiguous()
+                        and tuple(Q.shape) == (K, self.nao, self.nao)):
+                    raise ValueError(f"grad_eri: pairs needs a contiguous float64 [{K}, {self.nao}, {self.nao}] tensor on {D.device}")
+            _check(lib().mi_grad_eri_pairs(self._h, D.data_ptr(), spin_density.data_ptr() if spin_density is not None else None,
+                                           float(hyb), Q.data_ptr() if K > 0 else None,
+                                           s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if K > 0 else None, K,
+                                           grad.data_ptr(), int(rank), int(nranks), self._stream()))
+            return
         _check(lib().mi_grad_eri_sharded(self._h, D.data_ptr(), spin_density.data_ptr() if spin_density is not None else None,
                                          float(hyb), grad.data_ptr(), int(rank), int(nranks), self._stream()))
 

@@ -385,6 +385,14 @@ int mi_grad_eri_spin(mi_ctx *ctx, const double *d_D, const double *d_Dspin, doub
  * (rank, nranks) of the last mi_eri_prepare, which in direct mode is a tile GROUP index, not the process's rank). */
 int mi_grad_eri_sharded(mi_ctx *ctx, const double *d_D, const double *d_Dspin, double hyb, double *d_grad, int rank,
                         int nranks, void *stream);
+/* The same pass with an extra pair term in the two-particle density of every quartet,
+ *   G_abcd = D_ab D_cd - hyb/4 (D_ac D_bd + D_ad D_bc) (+ spin term) + sum_k s_k Q^k_ab Q^k_cd,
+ * i.e. the gradient of 1/2 D.J[D] - hyb/4 (D.K[D] + M.K[M]) + 1/2 sum_k s_k (Q^k|Q^k): d_Q[K][nao][nao] symmetric
+ * matrices on the device, s[K] on the host (finite), 0 <= K <= 136.  The density-weighted screening bound gains
+ * qmax_ab qmax_cd, qmax_ab = sqrt(sum_k |s_k| max_ab |Q^k|^2).  K = 0 is mi_grad_eri_sharded.  Used for the active-space
+ * cumulant of a CASSCF wavefunction (mcscf.CASSCF.nuc_grad_method). */
+int mi_grad_eri_pairs(mi_ctx *ctx, const double *d_D, const double *d_Dspin, double hyb, const double *d_Q, const double *s,
+                      int K, double *d_grad, int rank, int nranks, void *stream);
 
 /* meta-GGA evaluation (functional ids 8 TPSS exchange, 9 TPSS correlation, 10 M06-2X exchange, 11 M06-2X correlation; ids
  * 1-7 may be mixed in; 12 is refused, there is no params argument): d_tau[ng] = 1/2 sum_i |grad phi_i|^2; d_wv[5][ng] as mi_xc_eval plus d_wv[4] = w/4 de/dtau (the caller
