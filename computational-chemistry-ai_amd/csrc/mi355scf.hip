@@ -1045,6 +1045,7 @@ struct EriArgs {
     // gradient only: density-weighted Schwarz screening  q_ab q_cd max|G| < dtol  (dmax == nullptr: off)
     const double *q_bra, *q_ket, *dmax; // Schwarz factors of the two pair lists; max |D| per shell pair [nbas][nbas]
     const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
+    const double *xmax;                 // exchange-pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
     int nbas_d;
     double dtol, hyb;
     // host side only (kernel choice): primitive-pair statistics of the shared (bra) and the varying (ket) pair list
@@ -1087,11 +1088,15 @@ static inline unsigned eri_grid(int64_t nblocks, unsigned C)
 // Upper bound of |G| = |D_ab D_cd - hyb/4 (D_ac D_bd + D_ad D_bc)| over the AO quadruples of a shell quartet.
 // qmax (pair mode, mi_grad_eri_pairs): G has the extra term sum_k s_k Q^k_ab Q^k_cd, bounded by qmax_ab qmax_cd with
 // qmax_ab = sqrt(sum_k |s_k| max_ab |Q^k|^2) (Cauchy-Schwarz over k).
-__device__ inline double quartet_density_bound(const double *dmax, int nb, int a, int b, int c, int d, double hyb, const double *qmax = nullptr)
+// xmax (exchange-pair mode, mi_grad_eri_xpairs): G has the extra term sum_m t_m (R^m_ac R^m_bd + R^m_ad R^m_bc), bounded by
+// xmax_ac xmax_bd + xmax_ad xmax_bc with xmax_ab = sqrt(sum_m |t_m| max_ab |R^m|^2) (|R^m| of the block and of its transpose).
+__device__ inline double quartet_density_bound(const double *dmax, int nb, int a, int b, int c, int d, double hyb, const double *qmax = nullptr,
+                                               const double *xmax = nullptr)
 {
     double coul = dmax[a * nb + b] * dmax[c * nb + d];
     double exch = dmax[a * nb + c] * dmax[b * nb + d] + dmax[a * nb + d] * dmax[b * nb + c];
     double pairs = qmax ? qmax[a * nb + b] * qmax[c * nb + d] : 0.0;
+    if (xmax) pairs += xmax[a * nb + c] * xmax[b * nb + d] + xmax[a * nb + d] * xmax[b * nb + c];
     return coul + 0.25 * hyb * exch + pairs;
 }
 
@@ -1108,6 +1113,18 @@ __device__ inline double pair_term(const PairTerm &T, size_t ab, size_t cd)
     double pos = 0.0, neg = 0.0;
     for (int k = 0; k < T.npos; k++) pos = fma(x[k], y[k], pos);
     for (int k = T.npos; k < T.K; k++) neg = fma(x[k], y[k], neg);
+    return pos - neg;
+}
+// Exchange-pair mode (mi_grad_eri_xpairs): the extra term sum_m t_m (R^m_ik R^m_jl + R^m_il R^m_jk), the R^m kept like the Q^k
+// (sqrt|t_m| R^m, m fastest, positive t_m first).  (i, j) is one pair of the quartet and (k, l) the other: every factor is read
+// as [index of the (i, j) pair][index of the (k, l) pair], so for an antisymmetric R^m exchanging the two pairs changes the sign
+// of both factors of a product and exchanging i, j or k, l exchanges the two products -- the term has the 8-fold symmetry of G.
+__device__ inline double xpair_term(const PairTerm &T, size_t ik, size_t jl, size_t il, size_t jk)
+{
+    const double *a = T.P + ik * T.K, *b = T.P + jl * T.K, *c = T.P + il * T.K, *d = T.P + jk * T.K;
+    double pos = 0.0, neg = 0.0;
+    for (int m = 0; m < T.npos; m++) pos = fma(a[m], b[m], fma(c[m], d[m], pos));
+    for (int m = T.npos; m < T.K; m++) neg = fma(a[m], b[m], fma(c[m], d[m], neg));
     return pos - neg;
 }
 
@@ -1158,12 +1175,13 @@ struct LiveArgs {
     int nbas_d;
     double hyb, dtol;
     const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
+    const double *xmax;                 // exchange-pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
 };
 __device__ inline bool task_is_live(const LiveArgs &A, int64_t t, int &ib, int &ik)
 {
     find_task(A.prefix, A.nbra, t, ib, ik);
     const int a = A.bra[ib].sh_i, b = A.bra[ib].sh_j, c = A.ket[ik].sh_i, d = A.ket[ik].sh_j;
-    return !(A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, a, b, c, d, A.hyb, A.qmax) < A.dtol);
+    return !(A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, a, b, c, d, A.hyb, A.qmax, A.xmax) < A.dtol);
 }
 __global__ __launch_bounds__(256) void live_count_kernel(LiveArgs A, int *block_counts)
 {
@@ -1256,11 +1274,11 @@ __global__ __launch_bounds__(64) void eri_rys_kernel(EriArgs A)
     if (A.qtol > 0.0 && A.q_bra[ib] * A.q_ket[ik] < A.qtol) { if (QPW == 1) return; live = false; }
     if (QPW == 1) { // one quartet per wave: negligible / non-resident quartets leave at once
         if (A.own_table && !quartet_has_resident_tile(A.own_table, ab.ao_i, A.ni, ab.ao_j, A.nj, cd.ao_i, A.nk, cd.ao_j, A.nl, lane)) return;
-        if (A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax) < A.dtol) return;
+        if (A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax, A.xmax) < A.dtol) return;
     } else {
         if (A.own_table)
             live = quartet_has_resident_tile(A.own_table, ab.ao_i, A.ni, ab.ao_j, A.nj, cd.ao_i, A.nk, cd.ao_j, A.nl, lane, GSZ, grp) && live;
-        if (A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax) < A.dtol) live = false;
+        if (A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax, A.xmax) < A.dtol) live = false;
     }
     const int n = A.nroots, tsz = A.tsz, M1 = A.mmax + 1;
     const int ncd = cd.nprim, nPQ = live ? ab.nprim * ncd : 0;
@@ -6537,6 +6555,7 @@ struct GradXfArgs {
     const TaskIdx *tasks; // non-null: (bra, ket) per task, precomputed (get_task)
     const double *q_bra, *q_ket, *dmax; // same screening as EriArgs (the Rys kernel left these quartets' blocks unwritten)
     const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
+    const double *xmax;                 // exchange-pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
     int nbas_d;
     double dtol;
     // density fitting (mi_df_grad, template flag DF): the two-particle density is not a product of D's but a dense tensor,
@@ -6547,12 +6566,13 @@ struct GradXfArgs {
     const int *ket_atom;
     double w0;
     PairTerm pt;         // pair mode (template flag PAIRS): G += sum_k s_k Q^k_ab Q^k_cd
+    PairTerm xt;         // exchange-pair mode (template flag XPAIRS): G += sum_m t_m (R^m_ac R^m_bd + R^m_ad R^m_bc)
 };
 #define GRAD_COPIES 4096
 
 // GSZ = lanes per quartet: 16 (four quartets per wave, small angular classes) or 64 (256 = four waves sharing one
 // quartet's LDS blocks is supported by the code but was measured slower and is not launched).
-template <int GSZ, bool MFMA, bool DF = false, bool PAIRS = false>
+template <int GSZ, bool MFMA, bool DF = false, bool PAIRS = false, bool XPAIRS = false>
 __global__ __launch_bounds__(GSZ > 64 ? GSZ : 64) void eri_grad_contract(GradXfArgs A)
 {
     // sum_{x-independent part first}:  g[x] = sum_{r,e} M^x[r][e] * Z[r][e],  Z[r][e] = sum_f E0[e][f] Y[r][f],
@@ -6579,7 +6599,7 @@ __global__ __launch_bounds__(GSZ > 64 ? GSZ : 64) void eri_grad_contract(GradXfA
     if (A.swap) { int t_ = ib; ib = ik; ik = t_; }
     const PairRec dp = A.dplus[ib], cd = A.ket[ik];
     const bool live = in_batch && !(A.dmax && A.q_bra[ib] * A.q_ket[ik] *
-                                    quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax) < A.dtol);
+                                    quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax, A.xmax) < A.dtol);
     int m_off_m = 0;
     const double *D = A.D;
     const int ld = A.ld;
@@ -6610,6 +6630,7 @@ __global__ __launch_bounds__(GSZ > 64 ? GSZ : 64) void eri_grad_contract(GradXfA
                 ex += A.Dm[(size_t)i * ld + k] * A.Dm[(size_t)j * ld + l] + A.Dm[(size_t)i * ld + l] * A.Dm[(size_t)j * ld + k];
             double gv = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * A.hyb * ex;
             if (PAIRS) gv += pair_term(A.pt, (size_t)i * ld + j, (size_t)k * ld + l);
+            if (XPAIRS) gv += xpair_term(A.xt, (size_t)i * ld + k, (size_t)j * ld + l, (size_t)i * ld + l, (size_t)j * ld + k);
             G[o] = gv;
         }
     }
@@ -6744,14 +6765,16 @@ struct GradRowsArgs {
     int natm3, inv_from_second;
     const double *q_bra, *q_ket, *dmax;
     const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
+    const double *xmax;                 // exchange-pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
     int nbas_d;
     double dtol;
     PairTerm pt;                        // pair mode (template flag PAIRS)
+    PairTerm xt;                        // exchange-pair mode (template flag XPAIRS)
 };
 
 // GSZ lanes per quartet (64 / GSZ quartets per wave): the Rys phases keep 2 n .. 3 n lanes per primitive quartet busy and the
 // rows of the low bra classes fill a fraction of a wave, so the small classes run two or four latency chains side by side.
-template <int LC, int LD, int ROWS, int GSZ, bool PAIRS = false>
+template <int LC, int LD, int ROWS, int GSZ, bool PAIRS = false, bool XPAIRS = false>
 __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
 {
     constexpr int NF = c_ne(LC, LD), MMAX = LC + LD, M1 = MMAX + 1;
@@ -6768,7 +6791,7 @@ __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
     if (A.swap) { int t_ = ib; ib = ik; ik = t_; }
     const bool has_m = A.ne_m > 0;
     const PairRec dp = A.dplus[ib], cd = A.ket[ik];
-    if (live && A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax) < A.dtol)
+    if (live && A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax, A.xmax) < A.dtol)
         live = false;
     if (QPW == 1 && !live) return;
     int m_prim = dp.prim_off, m_off_m = 0;
@@ -6795,6 +6818,7 @@ __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
                 ex += A.Dm[(size_t)i * ld + k] * A.Dm[(size_t)j * ld + l] + A.Dm[(size_t)i * ld + l] * A.Dm[(size_t)j * ld + k];
             double gv = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * A.hyb * ex;
             if (PAIRS) gv += pair_term(A.pt, (size_t)i * ld + j, (size_t)k * ld + l);
+            if (XPAIRS) gv += xpair_term(A.xt, (size_t)i * ld + k, (size_t)j * ld + l, (size_t)i * ld + l, (size_t)j * ld + k);
             G[o] = gv;
         }
     }
@@ -6947,30 +6971,31 @@ static RowsGeom rows_geometry(int ne)
     if (ne <= 192) return {3, 64};
     return {0, 0};
 }
-template <int LC, int LD, int ROWS, int GSZ, bool PAIRS>
+template <int LC, int LD, int ROWS, int GSZ, bool PAIRS, bool XPAIRS>
 static int launch_grad_rows_g(const GradRowsArgs &R, size_t shm_per_quartet, hipStream_t st)
 {
     constexpr int QPW = 64 / GSZ;
     const size_t shm = shm_per_quartet * QPW;
     if (shm > 160 * 1024) return 0;
     if (shm > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)eri_grad_rows_kernel<LC, LD, ROWS, GSZ, PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((eri_grad_rows_kernel<LC, LD, ROWS, GSZ, PAIRS>), dim3((unsigned)((R.ntask + QPW - 1) / QPW)), dim3(64), shm, st, R);
+        HIPCHK(hipFuncSetAttribute((const void *)eri_grad_rows_kernel<LC, LD, ROWS, GSZ, PAIRS, XPAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL((eri_grad_rows_kernel<LC, LD, ROWS, GSZ, PAIRS, XPAIRS>), dim3((unsigned)((R.ntask + QPW - 1) / QPW)), dim3(64), shm, st, R);
     HIPCHK(hipGetLastError());
     return 1;
 }
-template <int LC, int LD, bool PAIRS>
+template <int LC, int LD, bool PAIRS, bool XPAIRS = false>
 static int launch_grad_rows_p(RowsGeom gm, const GradRowsArgs &R, size_t shm_q, hipStream_t st)
 {
-    if (gm.rows == 2 && gm.gsz == 32) return launch_grad_rows_g<LC, LD, 2, 32, PAIRS>(R, shm_q, st);
-    if (gm.rows == 1 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 1, 64, PAIRS>(R, shm_q, st);
-    if (gm.rows == 2 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 2, 64, PAIRS>(R, shm_q, st);
-    if (gm.rows == 3 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 3, 64, PAIRS>(R, shm_q, st);
+    if (gm.rows == 2 && gm.gsz == 32) return launch_grad_rows_g<LC, LD, 2, 32, PAIRS, XPAIRS>(R, shm_q, st);
+    if (gm.rows == 1 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 1, 64, PAIRS, XPAIRS>(R, shm_q, st);
+    if (gm.rows == 2 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 2, 64, PAIRS, XPAIRS>(R, shm_q, st);
+    if (gm.rows == 3 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 3, 64, PAIRS, XPAIRS>(R, shm_q, st);
     return 0;
 }
 template <int LC, int LD>
 static int launch_grad_rows_t(RowsGeom gm, const GradRowsArgs &R, size_t shm_q, hipStream_t st)
 {
+    if (R.xt.P) return launch_grad_rows_p<LC, LD, true, true>(gm, R, shm_q, st);   // exchange pairs: with the pair term (K may be 0)
     return R.pt.P ? launch_grad_rows_p<LC, LD, true>(gm, R, shm_q, st) : launch_grad_rows_p<LC, LD, false>(gm, R, shm_q, st);
 }
 // 1: launched, 0: no row kernel for this (other pair, number of rows), -1: error.  dry: only answers the question.
@@ -7013,13 +7038,15 @@ struct TpqGradArgs {
     int natm3, inv_from_second;
     const double *q_bra, *q_ket, *dmax;
     const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
+    const double *xmax;                 // exchange-pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
     int nbas_d;
     double dtol;
     const TaskIdx *tasks;     // non-null: the compacted list of live quartets (already screened: dmax is null then)
     PairTerm pt;              // pair mode (template flag PAIRS)
+    PairTerm xt;              // exchange-pair mode (template flag XPAIRS)
 };
 
-template <int L1, int L2, int LC, int LD, bool PAIRS = false>
+template <int L1, int L2, int LC, int LD, bool PAIRS = false, bool XPAIRS = false>
 __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_grad_kernel(TpqGradArgs A)
 {
     constexpr bool HASM = L1 > 0;
@@ -7044,7 +7071,7 @@ __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_grad_kernel(TpqGradArgs A)
     const bool same_pair = A.same_class && ib == ik;
     if (A.swap) { int t_ = ib; ib = ik; ik = t_; }
     const PairRec dp = A.dplus[ib], cd = A.ket[ik];
-    if (live && A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax) < A.dtol)
+    if (live && A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax, A.xmax) < A.dtol)
         live = false;
     double force[3] = {0.0, 0.0, 0.0};
     if (live) {
@@ -7214,6 +7241,7 @@ __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_grad_kernel(TpqGradArgs A)
                     if (A.Dm) ex += A.Dm[(size_t)i * ld + k] * A.Dm[(size_t)j * ld + l] + A.Dm[(size_t)i * ld + l] * A.Dm[(size_t)j * ld + k];
                     Gd[sa * NS2 + sb] = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * A.hyb * ex;
                     if (PAIRS) Gd[sa * NS2 + sb] += pair_term(A.pt, (size_t)i * ld + j, (size_t)k * ld + l);
+                    if (XPAIRS) Gd[sa * NS2 + sb] += xpair_term(A.xt, (size_t)i * ld + k, (size_t)j * ld + l, (size_t)i * ld + l, (size_t)j * ld + k);
                 }
             // Gc[a][b] = sum_{sa,sb} c1[a][sa] c2[b][sb] Gd[sa][sb]   (density back-transformed to cartesians: 3x fewer products)
             double h2[NS1 * NK2];
@@ -7292,7 +7320,8 @@ static int launch_eri_tpq_grad_t(const TpqGradArgs &Q, hipStream_t st)
     const size_t shm = sizeof(double) * (size_t)RYS_NINT_H[NR] * 2 * NR * (RYS_DEG + 1);
     if (Q.ntask <= 0) return 1;   // nothing in this rank's share of the class (the class is still "handled")
     const dim3 grid((unsigned)((Q.ntask + TPQ_BLOCK - 1) / TPQ_BLOCK));
-    if (Q.pt.P) hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD, true>), grid, dim3(TPQ_BLOCK), shm, st, Q);
+    if (Q.xt.P) hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD, true, true>), grid, dim3(TPQ_BLOCK), shm, st, Q);
+    else if (Q.pt.P) hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD, true>), grid, dim3(TPQ_BLOCK), shm, st, Q);
     else hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD>), grid, dim3(TPQ_BLOCK), shm, st, Q);
     if (hipGetLastError() != hipSuccess) return fail("eri_tpq_grad_kernel launch failed");
     return 1;
@@ -7399,7 +7428,12 @@ static int launch_grad_contract(bool df, const GradXfArgs &X, bool has_m, int nb
             HIPCHK(hipFuncSetAttribute((const void *)eri_grad_contract<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
         hipLaunchKernelGGL((eri_grad_contract<__VA_ARGS__>), dim3(nb), dim3(64), shm, st, X);                                             \
     } while (0)
-    if (!df && X.pt.P) {   // pair mode: the same three geometries with the pair term in the G gather
+    if (!df && X.xt.P) {   // exchange-pair mode: the pair-mode instantiations with the exchange-pair term as well (pt.K may be 0)
+        if (big <= 48 && shm * 4 <= 64 * 1024)
+            hipLaunchKernelGGL((eri_grad_contract<16, false, false, true, true>), dim3((nb + 3) / 4), dim3(64), shm * 4, st, X);
+        else if (mfma) GRAD_CONTRACT(64, true, false, true, true);
+        else GRAD_CONTRACT(64, false, false, true, true);
+    } else if (!df && X.pt.P) {   // pair mode: the same three geometries with the pair term in the G gather
         if (big <= 48 && shm * 4 <= 64 * 1024)
             hipLaunchKernelGGL((eri_grad_contract<16, false, false, true>), dim3((nb + 3) / 4), dim3(64), shm * 4, st, X);
         else if (mfma) GRAD_CONTRACT(64, true, false, true);
@@ -7435,6 +7469,8 @@ struct GradState {
     DevBuf<double> d_gcopies;
     DevBuf<double> d_P, d_qmax;              // pair mode: sqrt|s_k| Q^k, k fastest (PairTerm), and its per-shell-pair bound
     PairTerm pt{nullptr, 0, 0};
+    DevBuf<double> d_X, d_xmax;              // exchange-pair mode: sqrt|t_m| R^m, m fastest, and its per-shell-pair bound
+    PairTerm xt{nullptr, 0, 0};
     Scratch scr_wp, scr_wm, scr_gtasks, scr_live;
     DevBuf<uint32_t> d_comp_p, d_comp_m;
     DevBuf<int64_t> d_prefix;
@@ -7482,7 +7518,7 @@ static int grad_ensure_live(GradState &G, GradClassPair &CP)
     if (G.scr_live.ensure(c->device, SCR_GRAD_LIVE, sizeof(TaskIdx) * (size_t)ntask)) return -1;
     TaskIdx *d_live_tasks = (TaskIdx *)G.scr_live.p;
     LiveArgs L{B.d_recs, Kc.d_recs, G.d_prefix, (int)B.recs.size(), ntask, B.d_q, Kc.d_q, G.d_dmax, c->nbas, G.hyb, c->opt_grad_dtol,
-               G.d_qmax.get()};
+               G.d_qmax.get(), G.d_xmax.get()};
     hipLaunchKernelGGL(live_count_kernel, dim3(nblk), dim3(256), 0, st, L, G.d_live_counts.get());
     hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, st, G.d_live_counts.get(), nblk, G.d_live_off.get());
     hipLaunchKernelGGL(live_fill_kernel, dim3(nblk), dim3(256), 0, st, L, G.d_live_off.get(), d_live_tasks);
@@ -7521,7 +7557,7 @@ static int grad_route_tpq(GradState &G, GradClassPair &CP, const GradPerm &M)
     Q.rys = c->rys; Q.shell_xyz = c->d_shell_xyz; Q.D = c->d_Dpad; Q.Dm = G.d_Mpad; Q.ld = c->ldp; Q.hyb = G.hyb;
     Q.shell_atom = G.d_shell_atom; Q.grad = G.d_gcopies; Q.natm3 = G.natm3; Q.inv_from_second = M.swap ? 0 : 1;
     Q.q_bra = Dc.d_q; Q.q_ket = Oc.d_q; Q.dmax = live_q ? nullptr : G.d_dmax.get(); Q.nbas_d = c->nbas; Q.dtol = c->opt_grad_dtol;
-    Q.qmax = G.d_qmax; Q.pt = G.pt;
+    Q.qmax = G.d_qmax; Q.pt = G.pt; Q.xmax = G.d_xmax; Q.xt = G.xt;
     const bool dbg1 = getenv("MI355_DEBUG") != nullptr;
     auto tq0 = std::chrono::steady_clock::now();
     if (dbg1) hipStreamSynchronize(st);
@@ -7557,7 +7593,7 @@ static int grad_route_rows(GradState &G, const GradClassPair &CP, const GradPerm
     R.D = c->d_Dpad; R.Dm = G.d_Mpad; R.ld = c->ldp; R.hyb = G.hyb; R.shell_atom = G.d_shell_atom; R.grad = G.d_gcopies; R.natm3 = G.natm3;
     R.inv_from_second = M.swap ? 0 : 1;
     R.q_bra = Dc.d_q; R.q_ket = Oc.d_q; R.dmax = M.dmax_w; R.nbas_d = c->nbas; R.dtol = c->opt_grad_dtol;
-    R.qmax = G.d_qmax; R.pt = G.pt;
+    R.qmax = G.d_qmax; R.pt = G.pt; R.xmax = G.d_xmax; R.xt = G.xt;
     const int nscd_ = Oc.nsab, nf_ = Oc.ne;
     const size_t shm_q = sizeof(double) * ((size_t)R.PB * R.nroots * 3 * R.tsz + (size_t)R.PB * 2 * R.nroots + (size_t)R.PB +
                                            (size_t)nscd_ * nf_ + (size_t)R.nsab * nscd_);
@@ -7589,11 +7625,11 @@ static int grad_route_pipeline(GradState &G, const GradClassPair &CP, GradPerm &
     Ep.h_shared_np = B.mean_np; Ep.h_vary_mean = Kc.mean_np; Ep.h_vary_max4 = Kc.max4_np;
     Em.h_shared_np = B.mean_np; Em.h_vary_mean = Kc.mean_np; Em.h_vary_max4 = Kc.max4_np;
     Ep.q_bra = Dc.d_q; Ep.q_ket = Oc.d_q; Ep.dmax = M.dmax_w; Ep.nbas_d = c->nbas; Ep.dtol = c->opt_grad_dtol; Ep.hyb = hyb;
-    Ep.qmax = G.d_qmax;
-    if (has_m) { Em.q_bra = Ep.q_bra; Em.q_ket = Ep.q_ket; Em.dmax = M.dmax_w; Em.nbas_d = c->nbas; Em.dtol = Ep.dtol; Em.hyb = hyb; Em.qmax = Ep.qmax; }
+    Ep.qmax = G.d_qmax; Ep.xmax = G.d_xmax;
+    if (has_m) { Em.q_bra = Ep.q_bra; Em.q_ket = Ep.q_ket; Em.dmax = M.dmax_w; Em.nbas_d = c->nbas; Em.dtol = Ep.dtol; Em.hyb = hyb; Em.qmax = Ep.qmax; Em.xmax = Ep.xmax; }
     GradXfArgs X{};
     X.q_bra = Ep.q_bra; X.q_ket = Ep.q_ket; X.dmax = M.dmax_w; X.nbas_d = c->nbas; X.dtol = Ep.dtol;
-    X.qmax = G.d_qmax; X.pt = G.pt;
+    X.qmax = G.d_qmax; X.pt = G.pt; X.xmax = G.d_xmax; X.xt = G.xt;
     X.dplus = Dc.d_g_recs[M.orient][0]; X.dminus = has_m ? Dc.d_g_recs[M.orient][1] : nullptr; X.ket = Oc.d_recs;
     X.Mbuf = c->d_M; X.prefix = G.d_prefix; X.nbra = Ep.nbra; X.swap = Ep.swap; X.same_class = CP.same;
     X.ne_p = ne_of(l1 + 1, l2); X.ne_m = has_m ? ne_of(l1 - 1, l2) : 0; X.nf = Oc.ne;
@@ -7693,8 +7729,9 @@ static int grad_class_pair(GradState &G, PairClass &B, PairClass &Kc, bool same)
 // the last mi_eri_prepare: in direct mode the tile store is prepared group by group (rank*ng + v of nranks*ng) while the
 // gradient is still shared between the nranks processes only.
 // d_Q / s / K: the pair term of mi_grad_eri_pairs (K = 0: none, the plain Hartree-Fock form)
+// d_R / t / Kx: the exchange-pair term of mi_grad_eri_xpairs (Kx = 0: none)
 static int grad_eri_run(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, const double *d_Q, const double *s, int K,
-                        double *d_grad, int rank, int nranks, void *stream)
+                        double *d_grad, int rank, int nranks, void *stream, const double *d_R = nullptr, const double *t = nullptr, int Kx = 0)
 {
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail("mi_grad_eri: bad rank/nranks");
     if (!c || !d_D || !d_grad) return fail("mi_grad_eri: null argument");
@@ -7738,6 +7775,26 @@ static int grad_eri_run(mi_ctx *c, const double *d_D, const double *d_Dspin, dou
             G.pt = PairTerm{G.d_P.get(), Ke, npos};
         }
     }
+    // exchange-pair mode: the same layout for the R^m with t_m != 0
+    DevBuf<int> d_xsrc;
+    DevBuf<double> d_xw;
+    {
+        std::vector<int> src;
+        std::vector<double> w;
+        int npos = 0;
+        for (int sign = 0; sign < 2; sign++)
+            for (int m = 0; m < Kx; m++)
+                if (sign == 0 ? t[m] > 0.0 : t[m] < 0.0) { src.push_back(m); w.push_back(sqrt(fabs(t[m]))); npos += sign == 0; }
+        const int Ke = (int)src.size();
+        if (Ke > 0) {
+            if (d_xsrc.upload(src) || d_xw.upload(w)) return -1;
+            if (G.d_X.alloc(pp * Ke) != hipSuccess) return fail("mi_grad_eri_xpairs: no memory for %d exchange-pair matrices", Ke);
+            hipLaunchKernelGGL(pad_pairs_kernel, dim3((unsigned)((pp * Ke + 255) / 256)), dim3(256), 0, st, d_R, d_xsrc.get(), d_xw.get(), Ke,
+                               G.d_X.get(), c->nao, c->ldp, c->d_iperm);
+            HIPCHK(hipGetLastError());
+            G.xt = PairTerm{G.d_X.get(), Ke, npos};
+        }
+    }
     // density-weighted screening: q_ab q_cd max|G| < grad_dtol skips the quartet (0 disables)
     if (c->opt_grad_dtol > 0.0) {
         std::vector<int> sh_ao(c->nbas), sh_n(c->nbas);
@@ -7747,6 +7804,11 @@ static int grad_eri_run(mi_ctx *c, const double *d_D, const double *d_Dspin, dou
             HIPCHK(G.d_qmax.alloc((size_t)c->nbas * c->nbas));
             hipLaunchKernelGGL(shell_qmax_kernel, dim3((c->nbas * c->nbas + 255) / 256), dim3(256), 0, st, G.pt.P, G.pt.K, c->ldp, G.d_sh_ao.get(),
                                G.d_sh_n.get(), c->nbas, G.d_qmax.get());
+        }
+        if (G.xt.P) {   // |R^m_ab| = |R^m_ba| (symmetric or antisymmetric): one bound serves both orientations of a quartet
+            HIPCHK(G.d_xmax.alloc((size_t)c->nbas * c->nbas));
+            hipLaunchKernelGGL(shell_qmax_kernel, dim3((c->nbas * c->nbas + 255) / 256), dim3(256), 0, st, G.xt.P, G.xt.K, c->ldp, G.d_sh_ao.get(),
+                               G.d_sh_n.get(), c->nbas, G.d_xmax.get());
         }
         HIPCHK(G.d_dmax.alloc((size_t)c->nbas * c->nbas));
         hipLaunchKernelGGL(shell_dmax_kernel, dim3((c->nbas * c->nbas + 255) / 256), dim3(256), 0, st, c->d_Dpad, G.d_Mpad.get(), c->ldp,
@@ -7802,6 +7864,28 @@ extern "C" int mi_grad_eri_pairs(mi_ctx *c, const double *d_D, const double *d_D
     for (int k = 0; k < K; k++)
         if (!std::isfinite(s[k])) return fail("mi_grad_eri_pairs: s[%d] is not finite", k);
     return grad_eri_run(c, d_D, d_Dspin, hyb, d_Q, s, K, d_grad, rank, nranks, stream);
+}
+
+// The pass of mi_grad_eri_pairs with signed exchange-type terms as well: the gradient, at fixed matrices, of
+//   1/2 (D|D) - hyb/4 [tr(D K[D]) + tr(M K[M])] + 1/2 sum_k s_k (Q^k|Q^k) + sum_m t_m sum_ijkl (ik|jl) R^m_ij R^m_kl.
+// Every quartet's two-particle density gains sum_m t_m (R^m_ac R^m_bd + R^m_ad R^m_bc); each R^m is symmetric (sym[m] = +1) or
+// antisymmetric (-1) (xpair_term: the same element formula serves both).  Kx = 0 is mi_grad_eri_pairs.
+extern "C" int mi_grad_eri_xpairs(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, const double *d_Q, const double *s, int K,
+                                  const double *d_R, const double *t, const int *sym, int Kx, double *d_grad, int rank, int nranks, void *stream)
+{
+    if (Kx < 0 || Kx > 8) return fail("mi_grad_eri_xpairs: Kx = %d outside 0 .. 8", Kx);
+    if (Kx > 0 && (!d_R || !t || !sym)) return fail("mi_grad_eri_xpairs: null argument");
+    for (int m = 0; m < Kx; m++) {
+        if (!std::isfinite(t[m])) return fail("mi_grad_eri_xpairs: t[%d] is not finite", m);
+        if (sym[m] != 1 && sym[m] != -1) return fail("mi_grad_eri_xpairs: sym[%d] = %d is neither +1 (symmetric) nor -1 (antisymmetric)", m, sym[m]);
+    }
+    if (K < 0 || K > 136) return fail("mi_grad_eri_xpairs: K = %d outside 0 .. 136", K);
+    if (K > 0 && (!d_Q || !s)) return fail("mi_grad_eri_xpairs: null argument");
+    for (int k = 0; k < K; k++)
+        if (!std::isfinite(s[k])) return fail("mi_grad_eri_xpairs: s[%d] is not finite", k);
+    if (c && (c->opt_omega != 0.0 || c->eri_omega != 0.0))
+        return fail("mi_grad_eri_xpairs: no derivative integrals for a long-range (omega != 0) context");
+    return grad_eri_run(c, d_D, d_Dspin, hyb, d_Q, s, K, d_grad, rank, nranks, stream, d_R, t, Kx);
 }
 
 extern "C" int mi_grad_eri(mi_ctx *c, const double *d_D, double hyb, double *d_grad, void *stream)

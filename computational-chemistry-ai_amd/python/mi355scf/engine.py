@@ -113,6 +113,8 @@ def lib():
         L.mi_grad_eri_spin.argtypes = [vp, vp, vp, ctypes.c_double, vp, vp]
         L.mi_grad_eri_sharded.argtypes = [vp, vp, vp, ctypes.c_double, vp, ctypes.c_int, ctypes.c_int, vp]
         L.mi_grad_eri_pairs.argtypes = [vp, vp, vp, ctypes.c_double, vp, dp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp]
+        L.mi_grad_eri_xpairs.argtypes = [vp, vp, vp, ctypes.c_double, vp, dp, ctypes.c_int, vp, dp, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                         vp, ctypes.c_int, ctypes.c_int, vp]
         L.mi_eri_get_memory.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
         L.mi_eri_release.argtypes = [vp]
         L.mi_tile_store_allocations.restype = ctypes.c_int64
@@ -190,6 +192,33 @@ def rys_roots(n, x):
     r, w = np.zeros(n), np.zeros(n)
     _check(lib().mi_rys_roots_host(n, float(x), _dp(r), _dp(w)))
     return r, w
+
+
+XPAIRS_MAX = 8
+
+
+def xpairs_args(xpairs, nao, device):
+    """(R, t [Kx] float64, sym [Kx] intc, Kx) of the `xpairs` argument of `Engine.grad_eri`, or ValueError: what the C entry point
+    cannot see of a device tensor (shape, type, contiguity, device), and what it refuses itself, before any launch."""
+    try:
+        R, t, sym = xpairs
+    except (TypeError, ValueError):
+        raise ValueError("grad_eri: xpairs must be (R, t, sym)") from None
+    t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).ravel())
+    sym = np.asarray(sym).ravel()
+    Kx = int(t.size)
+    if Kx > XPAIRS_MAX:
+        raise ValueError(f"grad_eri: xpairs takes at most {XPAIRS_MAX} matrices, got {Kx}")
+    if sym.size != Kx:
+        raise ValueError(f"grad_eri: xpairs has {Kx} weights and {sym.size} symmetry flags")
+    if not np.all(np.isfinite(t)):
+        raise ValueError("grad_eri: xpairs weights must be finite")
+    if not all(v == 1 or v == -1 for v in sym.tolist()):
+        raise ValueError(f"grad_eri: xpairs symmetry flags must be +1 (symmetric) or -1 (antisymmetric), got {sym.tolist()}")
+    if Kx > 0 and not (torch.is_tensor(R) and R.dtype == torch.float64 and R.device == torch.device(device) and R.is_contiguous()
+                       and tuple(R.shape) == (Kx, nao, nao)):
+        raise ValueError(f"grad_eri: xpairs needs a contiguous float64 [{Kx}, {nao}, {nao}] tensor on {device}")
+    return R, t, np.ascontiguousarray(sym.astype(np.intc)), Kx
 
 
 class Engine:
@@ -607,28 +636,38 @@ class Engine:
     def grad_1e(self, D, W, grad):
         _check(lib().mi_grad_1e(self._h, D.data_ptr(), W.data_ptr(), grad.data_ptr(), self._stream()))
 
-    def grad_eri(self, D, hyb, grad, spin_density=None, rank=0, nranks=1, pairs=None):
+    def grad_eri(self, D, hyb, grad, spin_density=None, rank=0, nranks=1, pairs=None, xpairs=None):
         """D: total density; spin_density: Da - Db for UHF/UKS (None: closed shell); (rank, nranks): this process's share
         of the derivative-quartet batches (explicit: in direct mode the last prepare_eri split is a tile group, not a rank).
         pairs = (Q [K, N, N] device tensor of symmetric matrices, s [K]): the same pass with sum_k s_k Q^k_ab Q^k_cd added to
-        every quartet's two-particle density (`mi_grad_eri_pairs`), i.e. plus the gradient of 1/2 sum_k s_k (Q^k|Q^k)."""
+        every quartet's two-particle density (`mi_grad_eri_pairs`), i.e. plus the gradient of 1/2 sum_k s_k (Q^k|Q^k).
+        xpairs = (R [Kx, N, N] device tensor, t [Kx], sym [Kx] of +1 / -1): the same pass with sum_m t_m (R^m_ac R^m_bd +
+        R^m_ad R^m_bc) added as well (`mi_grad_eri_xpairs`), i.e. plus the gradient of sum_m t_m sum_ijkl (ik|jl) R^m_ij R^m_kl;
+        R^m is symmetric (sym +1) or antisymmetric (-1) as declared, Kx <= 8."""
+        xp = xpairs_args(xpairs, self.nao, D.device) if xpairs is not None else None
         if not self.eri_ready:
             self.prepare_eri()
-        if pairs is not None:
-            Q, s = pairs
+        M = spin_density.data_ptr() if spin_density is not None else None
+        pd = ctypes.POINTER(ctypes.c_double)
+        if pairs is not None or xp is not None:
+            Q, s = pairs if pairs is not None else (None, ())
             s = np.ascontiguousarray(np.asarray(s, dtype=np.float64).ravel())
             K = int(s.size)
-            if K > 0:
-                if not (torch.is_tensor(Q) and Q.dtype == torch.float64 and Q.device == D.device and Q.is_contiguous()
-                        and tuple(Q.shape) == (K, self.nao, self.nao)):
-                    raise ValueError(f"grad_eri: pairs needs a contiguous float64 [{K}, {self.nao}, {self.nao}] tensor on {D.device}")
-            _check(lib().mi_grad_eri_pairs(self._h, D.data_ptr(), spin_density.data_ptr() if spin_density is not None else None,
-                                           float(hyb), Q.data_ptr() if K > 0 else None,
-                                           s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if K > 0 else None, K,
-                                           grad.data_ptr(), int(rank), int(nranks), self._stream()))
+            if K > 0 and not (torch.is_tensor(Q) and Q.dtype == torch.float64 and Q.device == D.device and Q.is_contiguous()
+                              and tuple(Q.shape) == (K, self.nao, self.nao)):
+                raise ValueError(f"grad_eri: pairs needs a contiguous float64 [{K}, {self.nao}, {self.nao}] tensor on {D.device}")
+            qs = (Q.data_ptr() if K > 0 else None, s.ctypes.data_as(pd) if K > 0 else None, K)
+            if xp is None:
+                _check(lib().mi_grad_eri_pairs(self._h, D.data_ptr(), M, float(hyb), *qs, grad.data_ptr(), int(rank), int(nranks),
+                                               self._stream()))
+                return
+            R, t, sym, Kx = xp
+            _check(lib().mi_grad_eri_xpairs(self._h, D.data_ptr(), M, float(hyb), *qs, R.data_ptr() if Kx > 0 else None,
+                                            t.ctypes.data_as(pd) if Kx > 0 else None,
+                                            sym.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if Kx > 0 else None, Kx,
+                                            grad.data_ptr(), int(rank), int(nranks), self._stream()))
             return
-        _check(lib().mi_grad_eri_sharded(self._h, D.data_ptr(), spin_density.data_ptr() if spin_density is not None else None,
-                                         float(hyb), grad.data_ptr(), int(rank), int(nranks), self._stream()))
+        _check(lib().mi_grad_eri_sharded(self._h, D.data_ptr(), M, float(hyb), grad.data_ptr(), int(rank), int(nranks), self._stream()))
 
     # --- C-PCM (pcm.py): surface-charge integrals and the two per-cycle passes over them -----------------------------------
     def pcm_pairs(self, ordered=False):

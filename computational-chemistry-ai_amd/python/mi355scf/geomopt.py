@@ -211,7 +211,12 @@ def optimize(mf, maxsteps=100, callback=None, coordsys="internal", **kw):
     """Drop-in for `pyscf.geomopt.geometric_solver.optimize(mf, maxsteps=...)`: returns a `Mole` at the
     optimised geometry.  `coordsys="internal"` (default; redundant primitive internals, Cartesian fallback) or
     "cart"."""
-    gs = mf.nuc_grad_method().as_scanner()
+    if callable(mf) and hasattr(mf, "base") and not hasattr(mf, "nuc_grad_method"):
+        gs, mf = mf, mf.base                      # a gradient scanner, e.g. td.nuc_grad_method().as_scanner(state=2)
+    elif hasattr(mf, "as_scanner") and not hasattr(mf, "nuc_grad_method"):
+        gs, mf = mf.as_scanner(), mf.base         # a gradient object, e.g. td.nuc_grad_method()
+    else:
+        gs = mf.nuc_grad_method().as_scanner()
     # forces inside the optimisation loop: derivative quartets screened at 1e-10 instead of 1e-13.  Measured on ibuprofen /
     # def2-TZVP with one density (tools/eri_bench.py, GRAD_DTOLS): 1e-13 1.30 s; 1e-11 1.03 s, forces change by 1.5e-7 Ha/Bohr;
     # 1e-10 0.87 s, 1.3e-6 (0.3 % of geomeTRIC's 4.5e-4 max-gradient criterion); 1e-9 0.72 s, 1.5e-5 (too close to it).

@@ -449,6 +449,34 @@ class _TDBase:
                     out.write(f"    {i + 1:4d} -> {a + self._nocc + 1:4d} {x[i, a]:12.5f}\n")
         return self
 
+    def _guess(self, x0):
+        """Trial vectors [m, nov] from `x0` (a previous `td.xy`, or arrays [m, nocc, nvir]): X of every state and Y where it is
+        not zero.  None when x0 is None or does not fit the current orbital spaces (the default unit-vector guess is used)."""
+        if x0 is None:
+            return None
+        rows = []
+        for item in x0:
+            parts = item if isinstance(item, (tuple, list)) else (item,)
+            for p in parts:
+                p = np.asarray(p, dtype=np.float64)
+                if p.size != self._nocc * self._nvir:
+                    return None
+                if np.abs(p).max() > 0.0:
+                    rows.append(p.ravel())
+        if not rows:
+            return None
+        V = torch.as_tensor(np.array(rows), dtype=torch.float64, device=self._de.device)
+        if V.shape[0] < min(int(self.nstates), self._de.numel()):      # fewer vectors than roots: topped up with unit vectors
+            V = torch.cat([V, initial_guess(self._de, int(self.nstates))])
+        return V
+
+    # --- nuclear gradients (tdscf_grad.py) ----------------------------------------------------------
+    def nuc_grad_method(self):
+        from .tdscf_grad import Gradients
+        return Gradients(self)
+
+    Gradients = nuc_grad_method
+
     def _finish(self, w, X, Y, conv):
         no, nv = self._nocc, self._nvir
         self.e = w.cpu().numpy()
@@ -472,7 +500,7 @@ class TDA(_TDBase):
         n = min(int(self.nstates), dim)
         self.nstates = n
         w, X, conv = davidson_tda(self._tda_matvec, self._de, n, self.conv_tol, self.max_cycle, self.max_space,
-                                  log=(lambda s: self._log(4, s)))
+                                  guess=self._guess(x0), log=(lambda s: self._log(4, s)))
         # X.X = 1/2 (PySCF's normalisation of restricted states)
         X = X * np.sqrt(0.5)
         return self._finish(w, X, None, conv)
@@ -500,7 +528,7 @@ class TDHF(_TDBase):
             return M if M is not None else self._rpa_products(V)[1]
 
         w, X, Y, conv = davidson_rpa(apb, amb, self._de, n, self.conv_tol, self.max_cycle, self.max_space,
-                                     log=(lambda s: self._log(4, s)))
+                                     guess=self._guess(x0), log=(lambda s: self._log(4, s)))
         return self._finish(w, X, Y, conv)
 
 

@@ -393,6 +393,17 @@ int mi_grad_eri_sharded(mi_ctx *ctx, const double *d_D, const double *d_Dspin, d
  * cumulant of a CASSCF wavefunction (mcscf.CASSCF.nuc_grad_method). */
 int mi_grad_eri_pairs(mi_ctx *ctx, const double *d_D, const double *d_Dspin, double hyb, const double *d_Q, const double *s,
                       int K, double *d_grad, int rank, int nranks, void *stream);
+/* The same pass with signed exchange-type terms as well: the gradient, at fixed matrices, of
+ *   1/2 (D|D) - hyb/4 [tr(D K[D]) + tr(M K[M])] + 1/2 sum_k s_k (Q^k|Q^k) + sum_m t_m sum_ijkl (ik|jl) R^m_ij R^m_kl,
+ * i.e. every quartet's two-particle density gains sum_m t_m (R^m_ac R^m_bd + R^m_ad R^m_bc).  d_R[Kx][nao][nao] on the
+ * device, each matrix symmetric (sym[m] = +1) or antisymmetric (sym[m] = -1) as declared (not verified: a matrix that is
+ * neither gives a wrong gradient); t[Kx] (finite, either sign) and sym[Kx] on the host; 0 <= Kx <= 8.  D, M, Q, s, K as in
+ * mi_grad_eri_pairs.  The screening bound gains xmax_ac xmax_bd + xmax_ad xmax_bc, xmax_ab = sqrt(sum_m |t_m| max_ab |R^m|^2).
+ * Kx = 0 is mi_grad_eri_pairs.  Refused on a context with "omega" != 0.  Used for the relaxed two-particle density of a
+ * TDA/TDDFT excited state (tdscf.TDA.nuc_grad_method). */
+int mi_grad_eri_xpairs(mi_ctx *ctx, const double *d_D, const double *d_Dspin, double hyb, const double *d_Q, const double *s,
+                       int K, const double *d_R, const double *t, const int *sym, int Kx, double *d_grad, int rank, int nranks,
+                       void *stream);
 
 /* meta-GGA evaluation (functional ids 8 TPSS exchange, 9 TPSS correlation, 10 M06-2X exchange, 11 M06-2X correlation; ids
  * 1-7 may be mixed in; 12 is refused, there is no params argument): d_tau[ng] = 1/2 sum_i |grad phi_i|^2; d_wv[5][ng] as mi_xc_eval plus d_wv[4] = w/4 de/dtau (the caller
