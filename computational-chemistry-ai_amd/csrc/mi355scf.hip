@@ -1016,6 +1016,95 @@ extern "C" int mi_int1e(mi_ctx *c, double *d_S, double *d_T, double *d_V, double
     return 0;
 }
 
+// Upper bound of |G| = |D_ab D_cd - hyb/4 (D_ac D_bd + D_ad D_bc)| over the AO quadruples of a shell quartet.
+// qmax (pair mode, mi_grad_eri_pairs): G has the extra term sum_k s_k Q^k_ab Q^k_cd, bounded by qmax_ab qmax_cd with
+// qmax_ab = sqrt(sum_k |s_k| max_ab |Q^k|^2) (Cauchy-Schwarz over k).
+// xmax (exchange-pair mode, mi_grad_eri_xpairs): G has the extra term sum_m t_m (R^m_ac R^m_bd + R^m_ad R^m_bc), bounded by
+// xmax_ac xmax_bd + xmax_ad xmax_bc with xmax_ab = sqrt(sum_m |t_m| max_ab |R^m|^2) (|R^m| of the block and of its transpose).
+__device__ inline double quartet_density_bound(const double *dmax, int nb, int a, int b, int c, int d, double hyb, const double *qmax, const double *xmax)
+{
+    double coul = dmax[a * nb + b] * dmax[c * nb + d];
+    double exch = dmax[a * nb + c] * dmax[b * nb + d] + dmax[a * nb + d] * dmax[b * nb + c];
+    double pairs = qmax ? qmax[a * nb + b] * qmax[c * nb + d] : 0.0;
+    if (xmax) pairs += xmax[a * nb + c] * xmax[b * nb + d] + xmax[a * nb + d] * xmax[b * nb + c];
+    return coul + 0.25 * hyb * exch + pairs;
+}
+
+// Pair mode of the gradient (mi_grad_eri_pairs): the two-particle density has the extra term sum_k s_k Q^k_ab Q^k_cd.  The Q^k
+// are kept as P[(a * ld + b) * K + k] = sqrt|s_k| Q^k_ab (padded tile order like D, k fastest: one AO pair's K values are one
+// contiguous run), the `npos` positive s_k first, so the term is a dot product of two runs with one change of sign.
+struct PairTerm {
+    const double *P;   // nullptr: no pair term
+    int K, npos;
+};
+__device__ inline double pair_term(const PairTerm &T, size_t ab, size_t cd)
+{
+    const double *x = T.P + ab * T.K, *y = T.P + cd * T.K;
+    double pos = 0.0, neg = 0.0;
+    for (int k = 0; k < T.npos; k++) pos = fma(x[k], y[k], pos);
+    for (int k = T.npos; k < T.K; k++) neg = fma(x[k], y[k], neg);
+    return pos - neg;
+}
+// Exchange-pair mode (mi_grad_eri_xpairs): the extra term sum_m t_m (R^m_ik R^m_jl + R^m_il R^m_jk), the R^m kept like the Q^k
+// (sqrt|t_m| R^m, m fastest, positive t_m first).  (i, j) is one pair of the quartet and (k, l) the other: every factor is read
+// as [index of the (i, j) pair][index of the (k, l) pair], so for an antisymmetric R^m exchanging the two pairs changes the sign
+// of both factors of a product and exchanging i, j or k, l exchanges the two products -- the term has the 8-fold symmetry of G.
+__device__ inline double xpair_term(const PairTerm &T, size_t ik, size_t jl, size_t il, size_t jk)
+{
+    const double *a = T.P + ik * T.K, *b = T.P + jl * T.K, *c = T.P + il * T.K, *d = T.P + jk * T.K;
+    double pos = 0.0, neg = 0.0;
+    for (int m = 0; m < T.npos; m++) pos = fma(a[m], b[m], fma(c[m], d[m], pos));
+    for (int m = T.npos; m < T.K; m++) neg = fma(a[m], b[m], fma(c[m], d[m], neg));
+    return pos - neg;
+}
+
+// The two-particle density of one derivative quartet, the ONE place its element formula lives (gradient kernels
+// eri_grad_contract, eri_grad_rows_kernel, eri_tpq_grad_kernel):
+//   G_ijkl = D_ij D_kl - hyb/4 (D_ik D_jl + D_il D_jk [+ M_ik M_jl + M_il M_jk]) [+ pair_term(pt)] [+ xpair_term(xt)]
+// Which optional terms are compiled in is the template argument GradTerms of those kernels, chosen once on the host
+// (with_grad_terms); XPAIRS includes the pair term (pt.K may be 0).
+enum class GradTerms { PLAIN, PAIRS, XPAIRS };
+struct QuartetDensity {
+    const double *D, *Dm;   // padded total density; padded spin density Da - Db (UHF/UKS) or nullptr
+    int ld;
+    double hyb;
+    PairTerm pt;            // pair mode: G += sum_k s_k Q^k_ij Q^k_kl
+    PairTerm xt;            // exchange-pair mode: G += sum_m t_m (R^m_ik R^m_jl + R^m_il R^m_jk)
+    template <GradTerms T>
+    __device__ double element(int i, int j, int k, int l) const
+    {
+        double ex = D[(size_t)i * ld + k] * D[(size_t)j * ld + l] + D[(size_t)i * ld + l] * D[(size_t)j * ld + k];
+        if (Dm) // sum_s Ds x Ds = (D x D + M x M) / 2
+            ex += Dm[(size_t)i * ld + k] * Dm[(size_t)j * ld + l] + Dm[(size_t)i * ld + l] * Dm[(size_t)j * ld + k];
+        double gv = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * hyb * ex;
+        if (T != GradTerms::PLAIN) gv += pair_term(pt, (size_t)i * ld + j, (size_t)k * ld + l);
+        if (T == GradTerms::XPAIRS) gv += xpair_term(xt, (size_t)i * ld + k, (size_t)j * ld + l, (size_t)i * ld + l, (size_t)j * ld + k);
+        return gv;
+    }
+};
+// host: f(std::integral_constant<GradTerms, ...>) for the terms that `d` carries -- the one mode dispatch of the gradient launches
+template <class F>
+static int with_grad_terms(const QuartetDensity &d, F &&f)
+{
+    if (d.xt.P) return f(std::integral_constant<GradTerms, GradTerms::XPAIRS>{});
+    if (d.pt.P) return f(std::integral_constant<GradTerms, GradTerms::PAIRS>{});
+    return f(std::integral_constant<GradTerms, GradTerms::PLAIN>{});
+}
+
+// Density-weighted Schwarz screening of the derivative quartets: q_ab q_cd max|G| < dtol skips the quartet (dmax == nullptr:
+// off -- the SCF's ERI evaluation, or a list of live quartets that is already screened).
+struct QuartetScreen {
+    const double *q_bra, *q_ket, *dmax; // Schwarz factors of the two pair lists; max |D| per shell pair [nbas_d][nbas_d]
+    const double *qmax, *xmax;          // pair / exchange-pair mode: see quartet_density_bound (nullptr otherwise)
+    int nbas_d;
+    double dtol, hyb;
+    // (ib, ik) index q_bra / q_ket; a, b | c, d are the shells of the two pairs
+    __device__ bool negligible(int ib, int ik, int a, int b, int c, int d) const
+    {
+        return dmax && q_bra[ib] * q_ket[ik] * quartet_density_bound(dmax, nbas_d, a, b, c, d, hyb, qmax, xmax) < dtol;
+    }
+};
+
 // =================================================================================================
 // ERI generation, kernel 1: contracted [e0|f0] integrals by Rys quadrature.
 //
@@ -1042,12 +1131,7 @@ struct EriArgs {
     int swap;                // 1: the task's (bra index, ket index) address (ket[], bra[]) instead
     const int32_t *own_table; // non-null on a sharded context: skip quartets none of whose tiles live on this rank
     int ni, nj, nk, nl;       // spherical shell sizes (for the ownership test)
-    // gradient only: density-weighted Schwarz screening  q_ab q_cd max|G| < dtol  (dmax == nullptr: off)
-    const double *q_bra, *q_ket, *dmax; // Schwarz factors of the two pair lists; max |D| per shell pair [nbas][nbas]
-    const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
-    const double *xmax;                 // exchange-pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
-    int nbas_d;
-    double dtol, hyb;
+    QuartetScreen scr;        // scr.q_bra / scr.q_ket: Schwarz factors (qtol); the rest is the gradient's screening (dmax == nullptr: off)
     // host side only (kernel choice): primitive-pair statistics of the shared (bra) and the varying (ket) pair list
     double h_shared_np, h_vary_mean, h_vary_max4;
     const TaskIdx *tasks;    // non-null: (bra, ket) per task, precomputed (get_task)
@@ -1083,49 +1167,6 @@ static inline unsigned eri_grid(int64_t nblocks, unsigned C)
     if (C == 0u) return (unsigned)nblocks;
     const int64_t m = 8 * (int64_t)C;
     return (unsigned)((nblocks + m - 1) / m * m);
-}
-
-// Upper bound of |G| = |D_ab D_cd - hyb/4 (D_ac D_bd + D_ad D_bc)| over the AO quadruples of a shell quartet.
-// qmax (pair mode, mi_grad_eri_pairs): G has the extra term sum_k s_k Q^k_ab Q^k_cd, bounded by qmax_ab qmax_cd with
-// qmax_ab = sqrt(sum_k |s_k| max_ab |Q^k|^2) (Cauchy-Schwarz over k).
-// xmax (exchange-pair mode, mi_grad_eri_xpairs): G has the extra term sum_m t_m (R^m_ac R^m_bd + R^m_ad R^m_bc), bounded by
-// xmax_ac xmax_bd + xmax_ad xmax_bc with xmax_ab = sqrt(sum_m |t_m| max_ab |R^m|^2) (|R^m| of the block and of its transpose).
-__device__ inline double quartet_density_bound(const double *dmax, int nb, int a, int b, int c, int d, double hyb, const double *qmax = nullptr,
-                                               const double *xmax = nullptr)
-{
-    double coul = dmax[a * nb + b] * dmax[c * nb + d];
-    double exch = dmax[a * nb + c] * dmax[b * nb + d] + dmax[a * nb + d] * dmax[b * nb + c];
-    double pairs = qmax ? qmax[a * nb + b] * qmax[c * nb + d] : 0.0;
-    if (xmax) pairs += xmax[a * nb + c] * xmax[b * nb + d] + xmax[a * nb + d] * xmax[b * nb + c];
-    return coul + 0.25 * hyb * exch + pairs;
-}
-
-// Pair mode of the gradient (mi_grad_eri_pairs): the two-particle density has the extra term sum_k s_k Q^k_ab Q^k_cd.  The Q^k
-// are kept as P[(a * ld + b) * K + k] = sqrt|s_k| Q^k_ab (padded tile order like D, k fastest: one AO pair's K values are one
-// contiguous run), the `npos` positive s_k first, so the term is a dot product of two runs with one change of sign.
-struct PairTerm {
-    const double *P;   // nullptr: no pair term
-    int K, npos;
-};
-__device__ inline double pair_term(const PairTerm &T, size_t ab, size_t cd)
-{
-    const double *x = T.P + ab * T.K, *y = T.P + cd * T.K;
-    double pos = 0.0, neg = 0.0;
-    for (int k = 0; k < T.npos; k++) pos = fma(x[k], y[k], pos);
-    for (int k = T.npos; k < T.K; k++) neg = fma(x[k], y[k], neg);
-    return pos - neg;
-}
-// Exchange-pair mode (mi_grad_eri_xpairs): the extra term sum_m t_m (R^m_ik R^m_jl + R^m_il R^m_jk), the R^m kept like the Q^k
-// (sqrt|t_m| R^m, m fastest, positive t_m first).  (i, j) is one pair of the quartet and (k, l) the other: every factor is read
-// as [index of the (i, j) pair][index of the (k, l) pair], so for an antisymmetric R^m exchanging the two pairs changes the sign
-// of both factors of a product and exchanging i, j or k, l exchanges the two products -- the term has the 8-fold symmetry of G.
-__device__ inline double xpair_term(const PairTerm &T, size_t ik, size_t jl, size_t il, size_t jk)
-{
-    const double *a = T.P + ik * T.K, *b = T.P + jl * T.K, *c = T.P + il * T.K, *d = T.P + jk * T.K;
-    double pos = 0.0, neg = 0.0;
-    for (int m = 0; m < T.npos; m++) pos = fma(a[m], b[m], fma(c[m], d[m], pos));
-    for (int m = T.npos; m < T.K; m++) neg = fma(a[m], b[m], fma(c[m], d[m], neg));
-    return pos - neg;
 }
 
 // Task t of a class pair -> (bra pair index, ket index).  `prefix` holds the nbra+1 cumulative task counts followed by
@@ -1171,17 +1212,12 @@ struct LiveArgs {
     const int64_t *prefix;
     int nbra;
     int64_t ntask;
-    const double *q_bra, *q_ket, *dmax;
-    int nbas_d;
-    double hyb, dtol;
-    const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
-    const double *xmax;                 // exchange-pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
+    QuartetScreen scr;
 };
 __device__ inline bool task_is_live(const LiveArgs &A, int64_t t, int &ib, int &ik)
 {
     find_task(A.prefix, A.nbra, t, ib, ik);
-    const int a = A.bra[ib].sh_i, b = A.bra[ib].sh_j, c = A.ket[ik].sh_i, d = A.ket[ik].sh_j;
-    return !(A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, a, b, c, d, A.hyb, A.qmax, A.xmax) < A.dtol);
+    return !A.scr.negligible(ib, ik, A.bra[ib].sh_i, A.bra[ib].sh_j, A.ket[ik].sh_i, A.ket[ik].sh_j);
 }
 __global__ __launch_bounds__(256) void live_count_kernel(LiveArgs A, int *block_counts)
 {
@@ -1271,14 +1307,14 @@ __global__ __launch_bounds__(64) void eri_rys_kernel(EriArgs A)
     else get_task(A.tasks, A.prefix, A.nbra, task, ib, ik);
     if (A.swap) { int t_ = ib; ib = ik; ik = t_; }
     const PairRec ab = A.bra[ib], cd = A.ket[ik];
-    if (A.qtol > 0.0 && A.q_bra[ib] * A.q_ket[ik] < A.qtol) { if (QPW == 1) return; live = false; }
+    if (A.qtol > 0.0 && A.scr.q_bra[ib] * A.scr.q_ket[ik] < A.qtol) { if (QPW == 1) return; live = false; }
     if (QPW == 1) { // one quartet per wave: negligible / non-resident quartets leave at once
         if (A.own_table && !quartet_has_resident_tile(A.own_table, ab.ao_i, A.ni, ab.ao_j, A.nj, cd.ao_i, A.nk, cd.ao_j, A.nl, lane)) return;
-        if (A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax, A.xmax) < A.dtol) return;
+        if (A.scr.negligible(ib, ik, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j)) return;
     } else {
         if (A.own_table)
             live = quartet_has_resident_tile(A.own_table, ab.ao_i, A.ni, ab.ao_j, A.nj, cd.ao_i, A.nk, cd.ao_j, A.nl, lane, GSZ, grp) && live;
-        if (A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax, A.xmax) < A.dtol) live = false;
+        if (A.scr.negligible(ib, ik, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j)) live = false;
     }
     const int n = A.nroots, tsz = A.tsz, M1 = A.mmax + 1;
     const int ncd = cd.nprim, nPQ = live ? ab.nprim * ncd : 0;
@@ -2949,7 +2985,7 @@ static int prepare_evaluate_class_pair(PrepareState &S, PairClass &B, PairClass 
     E.ni = 2 * B.la + 1; E.nj = 2 * B.lb + 1; E.nk = 2 * Kc.la + 1; E.nl = 2 * Kc.lb + 1;
     E.own_table = nranks > 1 ? c->d_tile_table : nullptr;
     E.h_shared_np = B.mean_np; E.h_vary_mean = Kc.mean_np; E.h_vary_max4 = Kc.max4_np;
-    E.q_bra = B.d_q; E.q_ket = Kc.d_q; E.qtol = c->opt_ket_cluster ? tol : 0.0;
+    E.scr.q_bra = B.d_q; E.scr.q_ket = Kc.d_q; E.qtol = c->opt_ket_cluster ? tol : 0.0;
     E.prim_lds = (c->opt_prim_lds && B.max_np + Kc.max_np <= 160) ? B.max_np + Kc.max_np : 0;
     P.xcd_wave = c->opt_xcd_map ? 32u : 0u; P.xcd_tpq = c->opt_xcd_map ? 8u : 0u;
     E.xcd = P.xcd_wave;
@@ -2959,7 +2995,7 @@ static int prepare_evaluate_class_pair(PrepareState &S, PairClass &B, PairClass 
     X.work = d_work; X.ncomp = E.ncomp; X.tile_table = c->d_tile_table; X.tile_off = c->d_tile_off;
     X.tiles = c->d_tiles; X.nao = c->nao; X.tri = c->tri;
     X.check_owner = nranks > 1; X.ni = E.ni; X.nj = E.nj; X.nk = E.nk; X.nl = E.nl;
-    X.q_bra = E.q_bra; X.q_ket = E.q_ket; X.qtol = E.qtol; X.xcd = P.xcd_wave; X.tasks = E.tasks;
+    X.q_bra = E.scr.q_bra; X.q_ket = E.scr.q_ket; X.qtol = E.qtol; X.xcd = P.xcd_wave; X.tasks = E.tasks;
     P.shm2 = sizeof(double) * ((size_t)X.ne * X.nf + (size_t)X.nsab * X.nf);
     {
         const size_t with_m = P.shm2 + sizeof(double) * ((size_t)2 * X.nsab * X.ne + (size_t)2 * X.nscd * X.nf);
@@ -2997,7 +3033,7 @@ static int eval_route_tpq(PrepareState &S, const ClassPairEval &P)
     Q.c2s = c->d_c2s;
     for (int q = 0; q <= LMAX + 1; q++) Q.c2s_off[q] = c->c2s_off[q];
     Q.rys = c->rys; Q.X = P.X; Q.shell_xyz = c->d_shell_xyz; Q.check_owner = S.nranks > 1;
-    Q.q_bra = E.q_bra; Q.q_ket = E.q_ket; Q.qtol = E.qtol; Q.xcd = P.xcd_tpq; Q.omega = E.omega;
+    Q.q_bra = E.scr.q_bra; Q.q_ket = E.scr.q_ket; Q.qtol = E.qtol; Q.xcd = P.xcd_tpq; Q.omega = E.omega;
     auto ta = std::chrono::steady_clock::now();
     if (P.dbg) hipStreamSynchronize(st);
     const int used = launch_eri_tpq(B.la, B.lb, Kc.la, Kc.lb, Q, st);
@@ -3023,7 +3059,7 @@ static int eval_route_fused(PrepareState &S, const ClassPairEval &P)
     FusedArgs F;
     F.R = E; F.X = X;
     F.R.PB = std::max(1, std::min(E.PB, B.max_np * Kc.max_np));   // uncontracted d / f shells: one primitive quartet per batch
-    F.R.prim_lds = 0; F.R.own_table = nullptr; F.R.qtol = 0.0; F.R.dmax = nullptr;   // (the transform half screens: check_owner, qtol)
+    F.R.prim_lds = 0; F.R.own_table = nullptr; F.R.qtol = 0.0; F.R.scr.dmax = nullptr;   // (the transform half screens: check_owner, qtol)
     F.X.m_lds = 0;
     const size_t scratch = (size_t)F.R.PB * E.nroots * 3 * E.tsz + (size_t)F.R.PB * 2 * E.nroots;
     const size_t shmf = sizeof(double) * ((size_t)X.ne * X.nf + std::max((size_t)X.nsab * X.nf, scratch));
@@ -6543,21 +6579,14 @@ struct GradXfArgs {
     int ne_p, ne_m, nf, ns1, ns2, nscd, nsd;
     const double *work_p, *work_m;
     int ncomp_p, ncomp_m;
-    const double *D; // padded total density
-    const double *Dm; // padded spin density Da - Db (UHF/UKS) or nullptr
-    int ld;
-    double hyb;
+    QuartetDensity dens; // the two-particle density G (unused with DF)
     const int *shell_atom;
     double *grad;
     int inv_from_second; // translational invariance: 1: the skipped shell is dp.sh_j, 0: it is cd.sh_i
     int natm3;           // grad points to GRAD_COPIES private copies of [natm*3] (atomic contention relief)
     int64_t nbatch;      // tasks in this launch
     const TaskIdx *tasks; // non-null: (bra, ket) per task, precomputed (get_task)
-    const double *q_bra, *q_ket, *dmax; // same screening as EriArgs (the Rys kernel left these quartets' blocks unwritten)
-    const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
-    const double *xmax;                 // exchange-pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
-    int nbas_d;
-    double dtol;
+    QuartetScreen scr;    // same screening as EriArgs (the Rys kernel left these quartets' blocks unwritten)
     // density fitting (mi_df_grad, template flag DF): the two-particle density is not a product of D's but a dense tensor,
     // G[(a b), (P)] = Z[a * zs_i + b * zs_j + P]  (three-index: Z3[a][b][P]; two-index: Z2[P][Q], zs_j = 0), the ket is an
     // auxiliary "pair" (P, unit function) whose atoms come from `ket_atom`, and the weight is w0 instead of 4.
@@ -6565,14 +6594,12 @@ struct GradXfArgs {
     int64_t zs_i, zs_j;
     const int *ket_atom;
     double w0;
-    PairTerm pt;         // pair mode (template flag PAIRS): G += sum_k s_k Q^k_ab Q^k_cd
-    PairTerm xt;         // exchange-pair mode (template flag XPAIRS): G += sum_m t_m (R^m_ac R^m_bd + R^m_ad R^m_bc)
 };
 #define GRAD_COPIES 4096
 
 // GSZ = lanes per quartet: 16 (four quartets per wave, small angular classes) or 64 (256 = four waves sharing one
 // quartet's LDS blocks is supported by the code but was measured slower and is not launched).
-template <int GSZ, bool MFMA, bool DF = false, bool PAIRS = false, bool XPAIRS = false>
+template <int GSZ, bool MFMA, bool DF = false, GradTerms TERMS = GradTerms::PLAIN>
 __global__ __launch_bounds__(GSZ > 64 ? GSZ : 64) void eri_grad_contract(GradXfArgs A)
 {
     // sum_{x-independent part first}:  g[x] = sum_{r,e} M^x[r][e] * Z[r][e],  Z[r][e] = sum_f E0[e][f] Y[r][f],
@@ -6598,11 +6625,8 @@ __global__ __launch_bounds__(GSZ > 64 ? GSZ : 64) void eri_grad_contract(GradXfA
     const bool same_pair = A.same_class && ib == ik;
     if (A.swap) { int t_ = ib; ib = ik; ik = t_; }
     const PairRec dp = A.dplus[ib], cd = A.ket[ik];
-    const bool live = in_batch && !(A.dmax && A.q_bra[ib] * A.q_ket[ik] *
-                                    quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax, A.xmax) < A.dtol);
+    const bool live = in_batch && !A.scr.negligible(ib, ik, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j);
     int m_off_m = 0;
-    const double *D = A.D;
-    const int ld = A.ld;
     // the first E0PRE x GSZ elements of the plus block travel through registers: their loads are issued here and land in LDS only
     // after the Y product, so the HBM round trip of the hand-over block overlaps the G gather and the first matrix product
     constexpr int E0PRE = (GSZ >= 64 && MFMA) ? 8 : 0;
@@ -6624,14 +6648,7 @@ __global__ __launch_bounds__(GSZ > 64 ? GSZ : 64) void eri_grad_contract(GradXfA
             int r = o / A.nscd, c = o - r * A.nscd;
             int sa = r / A.ns2, sb = r - sa * A.ns2, sc = c / A.nsd, sd = c - sc * A.nsd;
             int i = dp.ao_i + sa, j = dp.ao_j + sb, k = cd.ao_i + sc, l = cd.ao_j + sd;
-            if (DF) { G[o] = A.Z[(int64_t)i * A.zs_i + (int64_t)j * A.zs_j + k]; continue; }
-            double ex = D[(size_t)i * ld + k] * D[(size_t)j * ld + l] + D[(size_t)i * ld + l] * D[(size_t)j * ld + k];
-            if (A.Dm) // sum_s Ds x Ds = (D x D + M x M) / 2
-                ex += A.Dm[(size_t)i * ld + k] * A.Dm[(size_t)j * ld + l] + A.Dm[(size_t)i * ld + l] * A.Dm[(size_t)j * ld + k];
-            double gv = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * A.hyb * ex;
-            if (PAIRS) gv += pair_term(A.pt, (size_t)i * ld + j, (size_t)k * ld + l);
-            if (XPAIRS) gv += xpair_term(A.xt, (size_t)i * ld + k, (size_t)j * ld + l, (size_t)i * ld + l, (size_t)j * ld + k);
-            G[o] = gv;
+            G[o] = DF ? A.Z[(int64_t)i * A.zs_i + (int64_t)j * A.zs_j + k] : A.dens.template element<TERMS>(i, j, k, l);
         }
     }
     __syncthreads();
@@ -6757,24 +6774,16 @@ struct GradRowsArgs {
     int ne_p, ne_m, nsab, ns2;
     const uint32_t *comp_p, *comp_m;    // component tables of the two variants (row bases: entry e * NF)
     RysDev rys;
-    const double *D, *Dm;
-    int ld;
-    double hyb;
+    QuartetDensity dens;
     const int *shell_atom;
     double *grad;
     int natm3, inv_from_second;
-    const double *q_bra, *q_ket, *dmax;
-    const double *qmax;                 // pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
-    const double *xmax;                 // exchange-pair mode of the gradient: see quartet_density_bound (nullptr otherwise)
-    int nbas_d;
-    double dtol;
-    PairTerm pt;                        // pair mode (template flag PAIRS)
-    PairTerm xt;                        // exchange-pair mode (template flag XPAIRS)
+    QuartetScreen scr;
 };
 
 // GSZ lanes per quartet (64 / GSZ quartets per wave): the Rys phases keep 2 n .. 3 n lanes per primitive quartet busy and the
 // rows of the low bra classes fill a fraction of a wave, so the small classes run two or four latency chains side by side.
-template <int LC, int LD, int ROWS, int GSZ, bool PAIRS = false, bool XPAIRS = false>
+template <int LC, int LD, int ROWS, int GSZ, GradTerms TERMS = GradTerms::PLAIN>
 __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
 {
     constexpr int NF = c_ne(LC, LD), MMAX = LC + LD, M1 = MMAX + 1;
@@ -6791,7 +6800,7 @@ __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
     if (A.swap) { int t_ = ib; ib = ik; ik = t_; }
     const bool has_m = A.ne_m > 0;
     const PairRec dp = A.dplus[ib], cd = A.ket[ik];
-    if (live && A.dmax && A.q_bra[ib] * A.q_ket[ik] * quartet_density_bound(A.dmax, A.nbas_d, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j, A.hyb, A.qmax, A.xmax) < A.dtol)
+    if (live && A.scr.negligible(ib, ik, dp.sh_i, dp.sh_j, cd.sh_i, cd.sh_j))
         live = false;
     if (QPW == 1 && !live) return;
     int m_prim = dp.prim_off, m_off_m = 0;
@@ -6807,19 +6816,11 @@ __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
     if (live) {
         const double *Mcd = A.Mbuf + cd.m_off;
         for (int q = lane; q < NSCD * NF; q += GSZ) McdL[q] = Mcd[q];
-        const double *D = A.D;
-        const int ld = A.ld, ns2 = A.ns2;
+        const int ns2 = A.ns2;
         for (int o = lane; o < nsab * NSCD; o += GSZ) {      // G[r][c], r = (sa, sb) of the differentiated pair, c = (sc, sd) of the other
             const int r = o / NSCD, c = o - r * NSCD;
             const int sa = r / ns2, sb = r - sa * ns2, sc = c / NSD, sd = c - sc * NSD;
-            const int i = dp.ao_i + sa, j = dp.ao_j + sb, k = cd.ao_i + sc, l = cd.ao_j + sd;
-            double ex = D[(size_t)i * ld + k] * D[(size_t)j * ld + l] + D[(size_t)i * ld + l] * D[(size_t)j * ld + k];
-            if (A.Dm) // sum_s Ds x Ds = (D x D + M x M) / 2
-                ex += A.Dm[(size_t)i * ld + k] * A.Dm[(size_t)j * ld + l] + A.Dm[(size_t)i * ld + l] * A.Dm[(size_t)j * ld + k];
-            double gv = D[(size_t)i * ld + j] * D[(size_t)k * ld + l] - 0.25 * A.hyb * ex;
-            if (PAIRS) gv += pair_term(A.pt, (size_t)i * ld + j, (size_t)k * ld + l);
-            if (XPAIRS) gv += xpair_term(A.xt, (size_t)i * ld + k, (size_t)j * ld + l, (size_t)i * ld + l, (size_t)j * ld + k);
-            G[o] = gv;
+            G[o] = A.dens.template element<TERMS>(dp.ao_i + sa, dp.ao_j + sb, cd.ao_i + sc, cd.ao_j + sd);
         }
     }
     const int ne = A.ne_p + A.ne_m;
@@ -6971,32 +6972,29 @@ static RowsGeom rows_geometry(int ne)
     if (ne <= 192) return {3, 64};
     return {0, 0};
 }
-template <int LC, int LD, int ROWS, int GSZ, bool PAIRS, bool XPAIRS>
+template <int LC, int LD, int ROWS, int GSZ, GradTerms TERMS>
 static int launch_grad_rows_g(const GradRowsArgs &R, size_t shm_per_quartet, hipStream_t st)
 {
     constexpr int QPW = 64 / GSZ;
     const size_t shm = shm_per_quartet * QPW;
     if (shm > 160 * 1024) return 0;
     if (shm > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)eri_grad_rows_kernel<LC, LD, ROWS, GSZ, PAIRS, XPAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    hipLaunchKernelGGL((eri_grad_rows_kernel<LC, LD, ROWS, GSZ, PAIRS, XPAIRS>), dim3((unsigned)((R.ntask + QPW - 1) / QPW)), dim3(64), shm, st, R);
+        HIPCHK(hipFuncSetAttribute((const void *)eri_grad_rows_kernel<LC, LD, ROWS, GSZ, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL((eri_grad_rows_kernel<LC, LD, ROWS, GSZ, TERMS>), dim3((unsigned)((R.ntask + QPW - 1) / QPW)), dim3(64), shm, st, R);
     HIPCHK(hipGetLastError());
     return 1;
-}
-template <int LC, int LD, bool PAIRS, bool XPAIRS = false>
-static int launch_grad_rows_p(RowsGeom gm, const GradRowsArgs &R, size_t shm_q, hipStream_t st)
-{
-    if (gm.rows == 2 && gm.gsz == 32) return launch_grad_rows_g<LC, LD, 2, 32, PAIRS, XPAIRS>(R, shm_q, st);
-    if (gm.rows == 1 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 1, 64, PAIRS, XPAIRS>(R, shm_q, st);
-    if (gm.rows == 2 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 2, 64, PAIRS, XPAIRS>(R, shm_q, st);
-    if (gm.rows == 3 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 3, 64, PAIRS, XPAIRS>(R, shm_q, st);
-    return 0;
 }
 template <int LC, int LD>
 static int launch_grad_rows_t(RowsGeom gm, const GradRowsArgs &R, size_t shm_q, hipStream_t st)
 {
-    if (R.xt.P) return launch_grad_rows_p<LC, LD, true, true>(gm, R, shm_q, st);   // exchange pairs: with the pair term (K may be 0)
-    return R.pt.P ? launch_grad_rows_p<LC, LD, true>(gm, R, shm_q, st) : launch_grad_rows_p<LC, LD, false>(gm, R, shm_q, st);
+    return with_grad_terms(R.dens, [&](auto terms) {
+        constexpr GradTerms T = decltype(terms)::value;
+        if (gm.rows == 2 && gm.gsz == 32) return launch_grad_rows_g<LC, LD, 2, 32, T>(R, shm_q, st);
+        if (gm.rows == 1 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 1, 64, T>(R, shm_q, st);
+        if (gm.rows == 2 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 2, 64, T>(R, shm_q, st);
+        if (gm.rows == 3 && gm.gsz == 64) return launch_grad_rows_g<LC, LD, 3, 64, T>(R, shm_q, st);
+        return 0;
+    });
 }
 // 1: launched, 0: no row kernel for this (other pair, number of rows), -1: error.  dry: only answers the question.
 static int launch_grad_rows(int lc, int ld, int ne, const GradRowsArgs &R, size_t shm_q, hipStream_t st, bool dry = false)
@@ -7019,6 +7017,11 @@ static int launch_grad_rows(int lc, int ld, int ne, const GradRowsArgs &R, size_
 //   and is contracted at once with G = D_ab D_cd - hyb/4 (D_ac D_bd + D_ad D_bc) (+ spin term): no derivative block is stored.
 // L1 = differentiated shell, L2 = its partner (either order), (LC >= LD) the other pair.
 // =================================================================================================
+// NOT folded onto QuartetDensity / QuartetScreen: this kernel keeps the fields, the screening test and the element formula in its
+// own text (and two template booleans for GradTerms).  Its larger classes sit at the 512-register limit, and every folded form
+// tried -- embedded structs in three member orders, by-value copies, forced inlining, a static element() on hoisted locals --
+// moved VGPRs or scratch in a third of the plain classes and slowed the plain gradient by 0.6 %; with this text the compiler's
+// resource figures are the unfolded ones.  The formula below must stay equal to QuartetDensity::element.
 struct TpqGradArgs {
     const PairRec *dplus, *dminus, *ket;
     const double *prim;
@@ -7320,11 +7323,11 @@ static int launch_eri_tpq_grad_t(const TpqGradArgs &Q, hipStream_t st)
     const size_t shm = sizeof(double) * (size_t)RYS_NINT_H[NR] * 2 * NR * (RYS_DEG + 1);
     if (Q.ntask <= 0) return 1;   // nothing in this rank's share of the class (the class is still "handled")
     const dim3 grid((unsigned)((Q.ntask + TPQ_BLOCK - 1) / TPQ_BLOCK));
-    if (Q.xt.P) hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD, true, true>), grid, dim3(TPQ_BLOCK), shm, st, Q);
-    else if (Q.pt.P) hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD, true>), grid, dim3(TPQ_BLOCK), shm, st, Q);
-    else hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD>), grid, dim3(TPQ_BLOCK), shm, st, Q);
-    if (hipGetLastError() != hipSuccess) return fail("eri_tpq_grad_kernel launch failed");
-    return 1;
+    return with_grad_terms(QuartetDensity{Q.D, Q.Dm, Q.ld, Q.hyb, Q.pt, Q.xt}, [&](auto terms) {
+        constexpr GradTerms T = decltype(terms)::value;
+        hipLaunchKernelGGL((eri_tpq_grad_kernel<L1, L2, LC, LD, T != GradTerms::PLAIN, T == GradTerms::XPAIRS>), grid, dim3(TPQ_BLOCK), shm, st, Q);
+        return hipGetLastError() != hipSuccess ? fail("eri_tpq_grad_kernel launch failed") : 1;
+    });
 }
 
 // returns 1 if the class (l1 = differentiated shell, l2 = partner | lc >= ld) has a thread-per-quartet kernel, 0 otherwise
@@ -7422,35 +7425,22 @@ static int launch_grad_contract(bool df, const GradXfArgs &X, bool has_m, int nb
     const int big = std::max({X.ns1 * X.ns2 * X.nscd, X.ns1 * X.ns2 * X.nf, X.ns1 * X.ns2 * X.ne_p});
     const bool mfma = mfma_worthwhile(X.ns1 * X.ns2, X.nf, X.nscd) || mfma_worthwhile(X.ns1 * X.ns2, X.ne_p, X.nf) ||
                       (has_m && mfma_worthwhile(X.ns1 * X.ns2, X.ne_m, X.nf));
-#define GRAD_CONTRACT(...)                                                                                                                 \
-    do {                                                                                                                                   \
-        if (shm > 64 * 1024)                                                                                                               \
-            HIPCHK(hipFuncSetAttribute((const void *)eri_grad_contract<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
-        hipLaunchKernelGGL((eri_grad_contract<__VA_ARGS__>), dim3(nb), dim3(64), shm, st, X);                                             \
-    } while (0)
-    if (!df && X.xt.P) {   // exchange-pair mode: the pair-mode instantiations with the exchange-pair term as well (pt.K may be 0)
-        if (big <= 48 && shm * 4 <= 64 * 1024)
-            hipLaunchKernelGGL((eri_grad_contract<16, false, false, true, true>), dim3((nb + 3) / 4), dim3(64), shm * 4, st, X);
-        else if (mfma) GRAD_CONTRACT(64, true, false, true, true);
-        else GRAD_CONTRACT(64, false, false, true, true);
-    } else if (!df && X.pt.P) {   // pair mode: the same three geometries with the pair term in the G gather
-        if (big <= 48 && shm * 4 <= 64 * 1024)
-            hipLaunchKernelGGL((eri_grad_contract<16, false, false, true>), dim3((nb + 3) / 4), dim3(64), shm * 4, st, X);
-        else if (mfma) GRAD_CONTRACT(64, true, false, true);
-        else GRAD_CONTRACT(64, false, false, true);
-    } else if (!df && big <= 48 && shm * 4 <= 64 * 1024) { // small classes: four quartets per wave (16 lanes each)
-        hipLaunchKernelGGL((eri_grad_contract<16, false>), dim3((nb + 3) / 4), dim3(64), shm * 4, st, X);
-    } else if (!df) {
+    auto launch = [&](auto kernel, int grid, size_t bytes) {
+        if (bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), bytes, st, X);
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    if (df) return mfma ? launch(eri_grad_contract<64, true, true>, nb, shm) : launch(eri_grad_contract<64, false, true>, nb, shm);
+    return with_grad_terms(X.dens, [&](auto terms) {   // the same three geometries in every mode
+        constexpr GradTerms T = decltype(terms)::value;
+        // small classes: four quartets per wave (16 lanes each)
+        if (big <= 48 && shm * 4 <= 64 * 1024) return launch(eri_grad_contract<16, false, false, T>, (nb + 3) / 4, shm * 4);
         // (two or four waves sharing one quartet's LDS blocks -- eri_grad_contract<128|256, true> -- were measured at
         // -2 % / +8 %, the six density sub-blocks of G staged in LDS first at +2 %: the kernel is parked 70 % of its
         // wave cycles, but neither on a shortage of lanes nor on the G gather)
-        if (mfma) GRAD_CONTRACT(64, true); else GRAD_CONTRACT(64, false);
-    } else {
-        if (mfma) GRAD_CONTRACT(64, true, true); else GRAD_CONTRACT(64, false, true);
-    }
-#undef GRAD_CONTRACT
-    HIPCHK(hipGetLastError());
-    return 0;
+        return mfma ? launch(eri_grad_contract<64, true, false, T>, nb, shm) : launch(eri_grad_contract<64, false, false, T>, nb, shm);
+    });
 }
 
 // ---- mi_grad_eri_sharded: the per-call buffers (GradState), one (bra class, ket class) pair (GradClassPair), one of its role
@@ -7459,7 +7449,6 @@ static int launch_grad_contract(bool df, const GradXfArgs &X, bool has_m, int nb
 struct GradState {
     mi_ctx *c;
     hipStream_t st;
-    double hyb;
     int rank, nranks;
     int natm3;
     size_t work_doubles = 0;                 // per hand-over buffer (plus / minus)
@@ -7468,9 +7457,16 @@ struct GradState {
     DevBuf<double> d_dmax;                   // max |D| per shell pair (null: no density-weighted screening)
     DevBuf<double> d_gcopies;
     DevBuf<double> d_P, d_qmax;              // pair mode: sqrt|s_k| Q^k, k fastest (PairTerm), and its per-shell-pair bound
-    PairTerm pt{nullptr, 0, 0};
     DevBuf<double> d_X, d_xmax;              // exchange-pair mode: sqrt|t_m| R^m, m fastest, and its per-shell-pair bound
-    PairTerm xt{nullptr, 0, 0};
+    QuartetDensity dens{};                   // what every kernel of this call contracts with
+    QuartetScreen scr{};                     // prototype: q_bra, q_ket and dmax vary per route (screen)
+    // the screen of the launches over (differentiated pair class Dc | other pair class Oc); dmax null: the task list is already screened
+    QuartetScreen screen(const PairClass &Dc, const PairClass &Oc, const double *dmax) const
+    {
+        QuartetScreen s = scr;
+        s.q_bra = Dc.d_q; s.q_ket = Oc.d_q; s.dmax = dmax;
+        return s;
+    }
     Scratch scr_wp, scr_wm, scr_gtasks, scr_live;
     DevBuf<uint32_t> d_comp_p, d_comp_m;
     DevBuf<int64_t> d_prefix;
@@ -7517,8 +7513,7 @@ static int grad_ensure_live(GradState &G, GradClassPair &CP)
     }
     if (G.scr_live.ensure(c->device, SCR_GRAD_LIVE, sizeof(TaskIdx) * (size_t)ntask)) return -1;
     TaskIdx *d_live_tasks = (TaskIdx *)G.scr_live.p;
-    LiveArgs L{B.d_recs, Kc.d_recs, G.d_prefix, (int)B.recs.size(), ntask, B.d_q, Kc.d_q, G.d_dmax, c->nbas, G.hyb, c->opt_grad_dtol,
-               G.d_qmax.get(), G.d_xmax.get()};
+    LiveArgs L{B.d_recs, Kc.d_recs, G.d_prefix, (int)B.recs.size(), ntask, G.screen(B, Kc, G.d_dmax)};
     hipLaunchKernelGGL(live_count_kernel, dim3(nblk), dim3(256), 0, st, L, G.d_live_counts.get());
     hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, st, G.d_live_counts.get(), nblk, G.d_live_off.get());
     hipLaunchKernelGGL(live_fill_kernel, dim3(nblk), dim3(256), 0, st, L, G.d_live_off.get(), d_live_tasks);
@@ -7554,10 +7549,10 @@ static int grad_route_tpq(GradState &G, GradClassPair &CP, const GradPerm &M)
     Q.swap = M.swap ? 1 : 0; Q.same_class = CP.same;
     Q.c2s = c->d_c2s;
     for (int q = 0; q <= LMAX + 1; q++) Q.c2s_off[q] = c->c2s_off[q];
-    Q.rys = c->rys; Q.shell_xyz = c->d_shell_xyz; Q.D = c->d_Dpad; Q.Dm = G.d_Mpad; Q.ld = c->ldp; Q.hyb = G.hyb;
+    Q.rys = c->rys; Q.shell_xyz = c->d_shell_xyz; Q.D = G.dens.D; Q.Dm = G.dens.Dm; Q.ld = G.dens.ld; Q.hyb = G.dens.hyb;
     Q.shell_atom = G.d_shell_atom; Q.grad = G.d_gcopies; Q.natm3 = G.natm3; Q.inv_from_second = M.swap ? 0 : 1;
     Q.q_bra = Dc.d_q; Q.q_ket = Oc.d_q; Q.dmax = live_q ? nullptr : G.d_dmax.get(); Q.nbas_d = c->nbas; Q.dtol = c->opt_grad_dtol;
-    Q.qmax = G.d_qmax; Q.pt = G.pt; Q.xmax = G.d_xmax; Q.xt = G.xt;
+    Q.qmax = G.d_qmax; Q.pt = G.dens.pt; Q.xmax = G.d_xmax; Q.xt = G.dens.xt;
     const bool dbg1 = getenv("MI355_DEBUG") != nullptr;
     auto tq0 = std::chrono::steady_clock::now();
     if (dbg1) hipStreamSynchronize(st);
@@ -7590,10 +7585,9 @@ static int grad_route_rows(GradState &G, const GradClassPair &CP, const GradPerm
     R.nmax = M.Ep.nmax; R.nroots = M.Ep.nroots; R.tsz = M.Ep.tsz; R.PB = std::max(1, gm.gsz / (3 * M.Ep.nroots));
     R.ne_p = ne_p; R.ne_m = ne_m; R.nsab = (2 * l1 + 1) * (2 * l2 + 1); R.ns2 = 2 * l2 + 1;
     R.comp_p = G.d_comp_p; R.comp_m = G.d_comp_m; R.rys = c->rys;
-    R.D = c->d_Dpad; R.Dm = G.d_Mpad; R.ld = c->ldp; R.hyb = G.hyb; R.shell_atom = G.d_shell_atom; R.grad = G.d_gcopies; R.natm3 = G.natm3;
+    R.shell_atom = G.d_shell_atom; R.grad = G.d_gcopies; R.natm3 = G.natm3;
     R.inv_from_second = M.swap ? 0 : 1;
-    R.q_bra = Dc.d_q; R.q_ket = Oc.d_q; R.dmax = M.dmax_w; R.nbas_d = c->nbas; R.dtol = c->opt_grad_dtol;
-    R.qmax = G.d_qmax; R.pt = G.pt; R.xmax = G.d_xmax; R.xt = G.xt;
+    R.dens = G.dens; R.scr = G.screen(Dc, Oc, M.dmax_w);
     const int nscd_ = Oc.nsab, nf_ = Oc.ne;
     const size_t shm_q = sizeof(double) * ((size_t)R.PB * R.nroots * 3 * R.tsz + (size_t)R.PB * 2 * R.nroots + (size_t)R.PB +
                                            (size_t)nscd_ * nf_ + (size_t)R.nsab * nscd_);
@@ -7618,24 +7612,20 @@ static int grad_route_pipeline(GradState &G, const GradClassPair &CP, GradPerm &
     const PairClass &B = *CP.B, &Kc = *CP.Kc, &Dc = *M.Dc, &Oc = *M.Oc;
     const int l1 = M.l1, l2 = M.l2, lc = M.lc, ldd = M.ld, rank = G.rank, nranks = G.nranks;
     const bool has_m = M.has_m;
-    const double hyb = G.hyb;
     EriArgs &Ep = M.Ep, &Em = M.Em;
     Ep.tasks = Em.tasks = M.tasks_w;
     Ep.prim_lds = Em.prim_lds = (c->opt_prim_lds && B.max_np + Kc.max_np <= 160) ? B.max_np + Kc.max_np : 0;
     Ep.h_shared_np = B.mean_np; Ep.h_vary_mean = Kc.mean_np; Ep.h_vary_max4 = Kc.max4_np;
     Em.h_shared_np = B.mean_np; Em.h_vary_mean = Kc.mean_np; Em.h_vary_max4 = Kc.max4_np;
-    Ep.q_bra = Dc.d_q; Ep.q_ket = Oc.d_q; Ep.dmax = M.dmax_w; Ep.nbas_d = c->nbas; Ep.dtol = c->opt_grad_dtol; Ep.hyb = hyb;
-    Ep.qmax = G.d_qmax; Ep.xmax = G.d_xmax;
-    if (has_m) { Em.q_bra = Ep.q_bra; Em.q_ket = Ep.q_ket; Em.dmax = M.dmax_w; Em.nbas_d = c->nbas; Em.dtol = Ep.dtol; Em.hyb = hyb; Em.qmax = Ep.qmax; Em.xmax = Ep.xmax; }
     GradXfArgs X{};
-    X.q_bra = Ep.q_bra; X.q_ket = Ep.q_ket; X.dmax = M.dmax_w; X.nbas_d = c->nbas; X.dtol = Ep.dtol;
-    X.qmax = G.d_qmax; X.pt = G.pt; X.xmax = G.d_xmax; X.xt = G.xt;
+    X.dens = G.dens; X.scr = Ep.scr = G.screen(Dc, Oc, M.dmax_w);
+    if (has_m) Em.scr = Ep.scr;
     X.dplus = Dc.d_g_recs[M.orient][0]; X.dminus = has_m ? Dc.d_g_recs[M.orient][1] : nullptr; X.ket = Oc.d_recs;
     X.Mbuf = c->d_M; X.prefix = G.d_prefix; X.nbra = Ep.nbra; X.swap = Ep.swap; X.same_class = CP.same;
     X.ne_p = ne_of(l1 + 1, l2); X.ne_m = has_m ? ne_of(l1 - 1, l2) : 0; X.nf = Oc.ne;
     X.ns1 = 2 * l1 + 1; X.ns2 = 2 * l2 + 1; X.nscd = Oc.nsab; X.nsd = 2 * Oc.lb + 1;
     X.work_p = (double *)G.scr_wp.p; X.work_m = (double *)G.scr_wm.p; X.ncomp_p = Ep.ncomp; X.ncomp_m = has_m ? Em.ncomp : 0;
-    X.D = c->d_Dpad; X.Dm = G.d_Mpad; X.ld = c->ldp; X.hyb = hyb; X.shell_atom = G.d_shell_atom; X.grad = G.d_gcopies; X.natm3 = G.natm3;
+    X.shell_atom = G.d_shell_atom; X.grad = G.d_gcopies; X.natm3 = G.natm3;
     X.inv_from_second = M.swap ? 0 : 1;
     X.tasks = M.tasks_w;
     size_t shm = sizeof(double) * ((size_t)X.ne_p * X.nf + (size_t)X.ne_m * X.nf + (size_t)X.ns1 * X.ns2 * (X.nf + X.nscd));
@@ -7725,6 +7715,54 @@ static int grad_class_pair(GradState &G, PairClass &B, PairClass &Kc, bool same)
     return 0;
 }
 
+// Pair / exchange-pair mode: the matrices of `d_src` whose coefficient is not zero, the positive ones first, scaled by
+// sqrt|coef| and laid out term fastest in `store` (PairTerm).  No such matrix: `out` stays empty.
+static int stage_pair_term(mi_ctx *c, hipStream_t st, const double *d_src, const double *coef, int K, DevBuf<double> &store, PairTerm &out,
+                           const char *oom_fmt)
+{
+    std::vector<int> src;
+    std::vector<double> w;
+    int npos = 0;
+    for (int sign = 0; sign < 2; sign++)
+        for (int k = 0; k < K; k++)
+            if (sign == 0 ? coef[k] > 0.0 : coef[k] < 0.0) { src.push_back(k); w.push_back(sqrt(fabs(coef[k]))); npos += sign == 0; }
+    const int Ke = (int)src.size();
+    if (Ke == 0) return 0;
+    const size_t pp = (size_t)c->ldp * c->ldp;
+    DevBuf<int> d_idx;   // (these two are freed on return with pad_pairs_kernel possibly still queued: safe because dev_free
+    DevBuf<double> d_w;  // synchronises the device before it parks a block -- one synchronisation per staged term list)
+    if (d_idx.upload(src) || d_w.upload(w)) return -1;
+    if (store.alloc(pp * Ke) != hipSuccess) return fail(oom_fmt, Ke);
+    hipLaunchKernelGGL(pad_pairs_kernel, dim3((unsigned)((pp * Ke + 255) / 256)), dim3(256), 0, st, d_src, d_idx.get(), d_w.get(), Ke, store.get(),
+                       c->nao, c->ldp, c->d_iperm);
+    HIPCHK(hipGetLastError());
+    out = PairTerm{store.get(), Ke, npos};
+    return 0;
+}
+// the per-shell-pair bound of a staged term (see quartet_density_bound); no term: `out` stays null
+static int pair_term_bound(GradState &G, const PairTerm &T, DevBuf<double> &out)
+{
+    if (!T.P) return 0;
+    const int nb2 = G.c->nbas * G.c->nbas;
+    HIPCHK(out.alloc((size_t)nb2));
+    hipLaunchKernelGGL(shell_qmax_kernel, dim3((nb2 + 255) / 256), dim3(256), 0, G.st, T.P, T.K, G.c->ldp, G.d_sh_ao.get(), G.d_sh_n.get(),
+                       G.c->nbas, out.get());
+    return 0;
+}
+// what both public entries ask of a list of `K` signed terms (`names`: how the messages spell the count and the coefficients;
+// sym: the symmetry flags of exchange-pair terms, checked term by term with the coefficients)
+static int check_terms(const char *who, const char *const names[2], const void *ptr, const double *coef, int K, int Kmax, const int *sym = nullptr)
+{
+    if (K < 0 || K > Kmax) return fail("%s: %s = %d outside 0 .. %d", who, names[0], K, Kmax);
+    if (K > 0 && (!ptr || !coef)) return fail("%s: null argument", who);
+    for (int k = 0; k < K; k++) {
+        if (!std::isfinite(coef[k])) return fail("%s: %s[%d] is not finite", who, names[1], k);
+        if (sym && sym[k] != 1 && sym[k] != -1) return fail("%s: sym[%d] = %d is neither +1 (symmetric) nor -1 (antisymmetric)", who, k, sym[k]);
+    }
+    return 0;
+}
+static const char *const PAIR_NAMES[2] = {"K", "s"}, *const XPAIR_NAMES[2] = {"Kx", "t"};
+
 // (rank, nranks): which share of the derivative-quartet batches this call evaluates.  It is an ARGUMENT, not the split of
 // the last mi_eri_prepare: in direct mode the tile store is prepared group by group (rank*ng + v of nranks*ng) while the
 // gradient is still shared between the nranks processes only.
@@ -7743,7 +7781,7 @@ static int grad_eri_run(mi_ctx *c, const double *d_D, const double *d_Dspin, dou
     if (prepare_grad_records(c)) return -1;
     auto tg1 = std::chrono::steady_clock::now();
     GradState G;
-    G.c = c; G.st = st; G.hyb = hyb; G.rank = rank; G.nranks = nranks; G.natm3 = c->natm * 3;
+    G.c = c; G.st = st; G.rank = rank; G.nranks = nranks; G.natm3 = c->natm * 3;
     size_t pp = (size_t)c->ldp * c->ldp;
     double *const none = nullptr;   // no accumulators to clear
     hipLaunchKernelGGL(pad_density_clear_kernel, dim3((unsigned)((pp + 255) / 256)), dim3(256), 0, st, d_D, c->d_Dpad, none, none, c->nao, c->ldp, c->d_iperm);
@@ -7754,67 +7792,23 @@ static int grad_eri_run(mi_ctx *c, const double *d_D, const double *d_Dspin, dou
     std::vector<int> shell_atom(c->nbas);
     for (int i = 0; i < c->nbas; i++) shell_atom[i] = c->shells[i].atom;
     if (G.d_shell_atom.upload(shell_atom)) return -1;
-    // pair mode: the terms with s_k != 0, positive ones first, scaled by sqrt|s_k| and laid out k fastest (PairTerm)
-    DevBuf<int> d_psrc;
-    DevBuf<double> d_pw;
-    {
-        std::vector<int> src;
-        std::vector<double> w;
-        for (int sign = 0; sign < 2; sign++)
-            for (int k = 0; k < K; k++)
-                if (sign == 0 ? s[k] > 0.0 : s[k] < 0.0) { src.push_back(k); w.push_back(sqrt(fabs(s[k]))); }
-        const int Ke = (int)src.size();
-        if (Ke > 0) {
-            int npos = 0;
-            for (int k = 0; k < K; k++) npos += s[k] > 0.0;
-            if (d_psrc.upload(src) || d_pw.upload(w)) return -1;
-            if (G.d_P.alloc(pp * Ke) != hipSuccess) return fail("mi_grad_eri_pairs: no memory for %d pair matrices", Ke);
-            hipLaunchKernelGGL(pad_pairs_kernel, dim3((unsigned)((pp * Ke + 255) / 256)), dim3(256), 0, st, d_Q, d_psrc.get(), d_pw.get(), Ke,
-                               G.d_P.get(), c->nao, c->ldp, c->d_iperm);
-            HIPCHK(hipGetLastError());
-            G.pt = PairTerm{G.d_P.get(), Ke, npos};
-        }
-    }
-    // exchange-pair mode: the same layout for the R^m with t_m != 0
-    DevBuf<int> d_xsrc;
-    DevBuf<double> d_xw;
-    {
-        std::vector<int> src;
-        std::vector<double> w;
-        int npos = 0;
-        for (int sign = 0; sign < 2; sign++)
-            for (int m = 0; m < Kx; m++)
-                if (sign == 0 ? t[m] > 0.0 : t[m] < 0.0) { src.push_back(m); w.push_back(sqrt(fabs(t[m]))); npos += sign == 0; }
-        const int Ke = (int)src.size();
-        if (Ke > 0) {
-            if (d_xsrc.upload(src) || d_xw.upload(w)) return -1;
-            if (G.d_X.alloc(pp * Ke) != hipSuccess) return fail("mi_grad_eri_xpairs: no memory for %d exchange-pair matrices", Ke);
-            hipLaunchKernelGGL(pad_pairs_kernel, dim3((unsigned)((pp * Ke + 255) / 256)), dim3(256), 0, st, d_R, d_xsrc.get(), d_xw.get(), Ke,
-                               G.d_X.get(), c->nao, c->ldp, c->d_iperm);
-            HIPCHK(hipGetLastError());
-            G.xt = PairTerm{G.d_X.get(), Ke, npos};
-        }
-    }
+    G.dens = QuartetDensity{c->d_Dpad, G.d_Mpad, c->ldp, hyb, {nullptr, 0, 0}, {nullptr, 0, 0}};
+    if (stage_pair_term(c, st, d_Q, s, K, G.d_P, G.dens.pt, "mi_grad_eri_pairs: no memory for %d pair matrices") ||
+        stage_pair_term(c, st, d_R, t, Kx, G.d_X, G.dens.xt, "mi_grad_eri_xpairs: no memory for %d exchange-pair matrices"))
+        return -1;
     // density-weighted screening: q_ab q_cd max|G| < grad_dtol skips the quartet (0 disables)
     if (c->opt_grad_dtol > 0.0) {
         std::vector<int> sh_ao(c->nbas), sh_n(c->nbas);
         for (int i = 0; i < c->nbas; i++) { sh_ao[i] = c->shells[i].ao; sh_n[i] = 2 * c->shells[i].l + 1; }
         if (G.d_sh_ao.upload(sh_ao) || G.d_sh_n.upload(sh_n)) return -1;
-        if (G.pt.P) {
-            HIPCHK(G.d_qmax.alloc((size_t)c->nbas * c->nbas));
-            hipLaunchKernelGGL(shell_qmax_kernel, dim3((c->nbas * c->nbas + 255) / 256), dim3(256), 0, st, G.pt.P, G.pt.K, c->ldp, G.d_sh_ao.get(),
-                               G.d_sh_n.get(), c->nbas, G.d_qmax.get());
-        }
-        if (G.xt.P) {   // |R^m_ab| = |R^m_ba| (symmetric or antisymmetric): one bound serves both orientations of a quartet
-            HIPCHK(G.d_xmax.alloc((size_t)c->nbas * c->nbas));
-            hipLaunchKernelGGL(shell_qmax_kernel, dim3((c->nbas * c->nbas + 255) / 256), dim3(256), 0, st, G.xt.P, G.xt.K, c->ldp, G.d_sh_ao.get(),
-                               G.d_sh_n.get(), c->nbas, G.d_xmax.get());
-        }
+        // (|R^m_ab| = |R^m_ba|, symmetric or antisymmetric: one bound serves both orientations of a quartet)
+        if (pair_term_bound(G, G.dens.pt, G.d_qmax) || pair_term_bound(G, G.dens.xt, G.d_xmax)) return -1;
         HIPCHK(G.d_dmax.alloc((size_t)c->nbas * c->nbas));
         hipLaunchKernelGGL(shell_dmax_kernel, dim3((c->nbas * c->nbas + 255) / 256), dim3(256), 0, st, c->d_Dpad, G.d_Mpad.get(), c->ldp,
                            G.d_sh_ao.get(), G.d_sh_n.get(), c->nbas, G.d_dmax.get());
         HIPCHK(hipGetLastError());
     }
+    G.scr = QuartetScreen{nullptr, nullptr, nullptr, G.d_qmax, G.d_xmax, c->nbas, c->opt_grad_dtol, hyb};
     const int natm3 = G.natm3;
     HIPCHK(G.d_gcopies.alloc((size_t)GRAD_COPIES * natm3));
     HIPCHK(hipMemsetAsync(G.d_gcopies, 0, sizeof(double) * (size_t)GRAD_COPIES * natm3, st));
@@ -7859,10 +7853,7 @@ extern "C" int mi_grad_eri_sharded(mi_ctx *c, const double *d_D, const double *d
 extern "C" int mi_grad_eri_pairs(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, const double *d_Q, const double *s, int K,
                                  double *d_grad, int rank, int nranks, void *stream)
 {
-    if (K < 0 || K > 136) return fail("mi_grad_eri_pairs: K = %d outside 0 .. 136", K);
-    if (K > 0 && (!d_Q || !s)) return fail("mi_grad_eri_pairs: null argument");
-    for (int k = 0; k < K; k++)
-        if (!std::isfinite(s[k])) return fail("mi_grad_eri_pairs: s[%d] is not finite", k);
+    if (check_terms("mi_grad_eri_pairs", PAIR_NAMES, d_Q, s, K, 136)) return -1;
     return grad_eri_run(c, d_D, d_Dspin, hyb, d_Q, s, K, d_grad, rank, nranks, stream);
 }
 
@@ -7873,18 +7864,8 @@ extern "C" int mi_grad_eri_pairs(mi_ctx *c, const double *d_D, const double *d_D
 extern "C" int mi_grad_eri_xpairs(mi_ctx *c, const double *d_D, const double *d_Dspin, double hyb, const double *d_Q, const double *s, int K,
                                   const double *d_R, const double *t, const int *sym, int Kx, double *d_grad, int rank, int nranks, void *stream)
 {
-    if (Kx < 0 || Kx > 8) return fail("mi_grad_eri_xpairs: Kx = %d outside 0 .. 8", Kx);
-    if (Kx > 0 && (!d_R || !t || !sym)) return fail("mi_grad_eri_xpairs: null argument");
-    for (int m = 0; m < Kx; m++) {
-        if (!std::isfinite(t[m])) return fail("mi_grad_eri_xpairs: t[%d] is not finite", m);
-        if (sym[m] != 1 && sym[m] != -1) return fail("mi_grad_eri_xpairs: sym[%d] = %d is neither +1 (symmetric) nor -1 (antisymmetric)", m, sym[m]);
-    }
-    if (K < 0 || K > 136) return fail("mi_grad_eri_xpairs: K = %d outside 0 .. 136", K);
-    if (K > 0 && (!d_Q || !s)) return fail("mi_grad_eri_xpairs: null argument");
-    for (int k = 0; k < K; k++)
-        if (!std::isfinite(s[k])) return fail("mi_grad_eri_xpairs: s[%d] is not finite", k);
-    if (c && (c->opt_omega != 0.0 || c->eri_omega != 0.0))
-        return fail("mi_grad_eri_xpairs: no derivative integrals for a long-range (omega != 0) context");
+    if (check_terms("mi_grad_eri_xpairs", XPAIR_NAMES, sym ? d_R : nullptr, t, Kx, 8, sym)) return -1;   // (a null sym is a null argument too)
+    if (check_terms("mi_grad_eri_xpairs", PAIR_NAMES, d_Q, s, K, 136)) return -1;
     return grad_eri_run(c, d_D, d_Dspin, hyb, d_Q, s, K, d_grad, rank, nranks, stream, d_R, t, Kx);
 }
 

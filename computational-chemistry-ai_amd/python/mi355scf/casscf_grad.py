@@ -31,7 +31,7 @@ import time
 
 import numpy as np
 
-from .mole import Mole
+from .grad import _GradScanner, assemble, log_gradient
 
 ALGORITHMS = ("pairs", "loop")
 
@@ -108,7 +108,6 @@ class Gradients:
     def kernel(self, mo_coeff=None, ci=None, atmlst=None):
         import torch
         from .ao2mo import resident_engine
-        from .grad import grad_nuc
         mc = self.base
         if mc.weights is not None:
             raise NotImplementedError("state-averaged CASSCF nuclear gradients are not implemented: they need coupled-perturbed "
@@ -136,31 +135,18 @@ class Gradients:
         s, p = cumulant_pairs(cumulant(gamma, Gamma), nc)
         K = self.npairs = int(s.size)
         Q = torch.as_tensor(np.einsum("at,ktu,bu->kab", Ca, p, Ca, optimize=True), **dev).contiguous() if K else None
-        t0 = time.time()
-        g = torch.zeros(mol.natm, 3, **dev)
-        eng.grad_1e(D, W, g)
-        torch.cuda.synchronize()
-        tm["grad_1e"] = time.time() - t0
-        t0 = time.time()
-        g2 = torch.zeros_like(g)
-        if self.algorithm == "pairs":
-            eng.grad_eri(D, 1.0, g2, pairs=(Q, s))
-        else:
+
+        def two_electron(g2):
+            if self.algorithm == "pairs":
+                return eng.grad_eri(D, 1.0, g2, pairs=(Q, s))
             eng.grad_eri(D, 1.0, g2)
             for k in range(K):
-                gk = torch.zeros_like(g)
+                gk = torch.zeros_like(g2)
                 eng.grad_eri(Q[k].contiguous(), 0.0, gk)
                 g2 += float(s[k]) * gk
-        torch.cuda.synchronize()
-        tm["grad_eri"] = time.time() - t0
-        de = (g + g2).cpu().numpy() + grad_nuc(mol)
         self.timing = tm
-        mc._log(4, f"CASSCF gradient ({self.algorithm}, K = {K}) timings (s): " + ", ".join(f"{k} {v:.3f}" for k, v in tm.items()))
-        self.de = de
-        if self.verbose >= 4:
-            mc._log(4, "--------------- gradients ---------------")
-            for ia in range(mol.natm):
-                mc._log(4, "%d %s  %16.10f %16.10f %16.10f" % (ia, mol.atom_pure_symbol(ia), *de[ia]))
+        self.de = de = assemble(eng, mol, D, W, two_electron, timing=tm)
+        log_gradient(mc._log, mol, de, self.verbose >= 4, tm, f"CASSCF gradient ({self.algorithm}, K = {K})")
         return de
 
     grad = kernel
@@ -175,31 +161,18 @@ def lowdin_orthonormalize(C, S):
     return C @ ((U / np.sqrt(w)[None, :]) @ U.T)
 
 
-class _CASGradScanner:
+class _CASGradScanner(_GradScanner):
     """(e_tot, de) at a new geometry: the SCF from the previous density, the CASSCF from the previous orbitals (re-orthonormalised
     in the new overlap) and CI vector."""
 
-    def __init__(self, g):
-        self.g = g
-        self.base = g.base
-        self.mol = g.mol
-        self.converged = True
-
-    def __call__(self, mol_or_geom):
-        mc = self.g.base
+    def _energy(self, mol, dm0):
+        mc = self.base
         mf = mc._scf
-        mol = mol_or_geom if isinstance(mol_or_geom, Mole) else mc.mol.set_geom_(mol_or_geom, unit="Bohr", inplace=False)
-        dm0 = mf.make_rdm1() if mf.mo_coeff is not None else None
         warm = mc.ci is not None and mc.mo_coeff is not None
         mo_prev, ci_prev = (np.array(mc.mo_coeff), mc.ci) if warm else (None, None)
-        mf.reset(mol)
-        mf._grad_prefetch = True      # the gradient's host-side set-up overlaps the SCF and the CASSCF
-        mf.kernel(dm0=dm0)
-        mc.mol = self.g.mol = self.mol = mol
+        self._run_scf(mol, dm0)       # (the gradient's prefetch overlaps the CASSCF as well)
+        mc.mol = mol
         mo = lowdin_orthonormalize(mo_prev, mf.get_ovlp()) if warm else mf.mo_coeff
         mc.kernel(mo, ci0=ci_prev)
         self.converged = bool(mf.converged and mc.converged)
-        if getattr(self, "grad_dtol", None) is not None:
-            mf.engine.set_option("grad_dtol", self.grad_dtol)   # density-weighted screening of the derivative quartets
-        de = self.g.kernel()
-        return mc.e_tot, de
+        return mc.e_tot

@@ -197,6 +197,13 @@ def rys_roots(n, x):
 XPAIRS_MAX = 8
 
 
+def _term_matrices(name, A, K, nao, device):
+    """ValueError unless A holds the K matrices of the `pairs` / `xpairs` argument as the C entry point reads them."""
+    if K > 0 and not (torch.is_tensor(A) and A.dtype == torch.float64 and A.device == torch.device(device) and A.is_contiguous()
+                      and tuple(A.shape) == (K, nao, nao)):
+        raise ValueError(f"grad_eri: {name} needs a contiguous float64 [{K}, {nao}, {nao}] tensor on {device}")
+
+
 def xpairs_args(xpairs, nao, device):
     """(R, t [Kx] float64, sym [Kx] intc, Kx) of the `xpairs` argument of `Engine.grad_eri`, or ValueError: what the C entry point
     cannot see of a device tensor (shape, type, contiguity, device), and what it refuses itself, before any launch."""
@@ -215,9 +222,7 @@ def xpairs_args(xpairs, nao, device):
         raise ValueError("grad_eri: xpairs weights must be finite")
     if not all(v == 1 or v == -1 for v in sym.tolist()):
         raise ValueError(f"grad_eri: xpairs symmetry flags must be +1 (symmetric) or -1 (antisymmetric), got {sym.tolist()}")
-    if Kx > 0 and not (torch.is_tensor(R) and R.dtype == torch.float64 and R.device == torch.device(device) and R.is_contiguous()
-                       and tuple(R.shape) == (Kx, nao, nao)):
-        raise ValueError(f"grad_eri: xpairs needs a contiguous float64 [{Kx}, {nao}, {nao}] tensor on {device}")
+    _term_matrices("xpairs", R, Kx, nao, device)
     return R, t, np.ascontiguousarray(sym.astype(np.intc)), Kx
 
 
@@ -643,31 +648,21 @@ class Engine:
         every quartet's two-particle density (`mi_grad_eri_pairs`), i.e. plus the gradient of 1/2 sum_k s_k (Q^k|Q^k).
         xpairs = (R [Kx, N, N] device tensor, t [Kx], sym [Kx] of +1 / -1): the same pass with sum_m t_m (R^m_ac R^m_bd +
         R^m_ad R^m_bc) added as well (`mi_grad_eri_xpairs`), i.e. plus the gradient of sum_m t_m sum_ijkl (ik|jl) R^m_ij R^m_kl;
-        R^m is symmetric (sym +1) or antisymmetric (-1) as declared, Kx <= 8."""
-        xp = xpairs_args(xpairs, self.nao, D.device) if xpairs is not None else None
+        R^m is symmetric (sym +1) or antisymmetric (-1) as declared, Kx <= 8.
+        One C call serves all of it: an absent term is K = 0 / Kx = 0 of `mi_grad_eri_xpairs`."""
+        R, t, sym, Kx = xpairs_args(xpairs if xpairs is not None else (None, (), ()), self.nao, D.device)
+        Q, s = pairs if pairs is not None else (None, ())
+        s = np.ascontiguousarray(np.asarray(s, dtype=np.float64).ravel())
+        K = int(s.size)
+        _term_matrices("pairs", Q, K, self.nao, D.device)
         if not self.eri_ready:
             self.prepare_eri()
-        M = spin_density.data_ptr() if spin_density is not None else None
-        pd = ctypes.POINTER(ctypes.c_double)
-        if pairs is not None or xp is not None:
-            Q, s = pairs if pairs is not None else (None, ())
-            s = np.ascontiguousarray(np.asarray(s, dtype=np.float64).ravel())
-            K = int(s.size)
-            if K > 0 and not (torch.is_tensor(Q) and Q.dtype == torch.float64 and Q.device == D.device and Q.is_contiguous()
-                              and tuple(Q.shape) == (K, self.nao, self.nao)):
-                raise ValueError(f"grad_eri: pairs needs a contiguous float64 [{K}, {self.nao}, {self.nao}] tensor on {D.device}")
-            qs = (Q.data_ptr() if K > 0 else None, s.ctypes.data_as(pd) if K > 0 else None, K)
-            if xp is None:
-                _check(lib().mi_grad_eri_pairs(self._h, D.data_ptr(), M, float(hyb), *qs, grad.data_ptr(), int(rank), int(nranks),
-                                               self._stream()))
-                return
-            R, t, sym, Kx = xp
-            _check(lib().mi_grad_eri_xpairs(self._h, D.data_ptr(), M, float(hyb), *qs, R.data_ptr() if Kx > 0 else None,
-                                            t.ctypes.data_as(pd) if Kx > 0 else None,
-                                            sym.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if Kx > 0 else None, Kx,
-                                            grad.data_ptr(), int(rank), int(nranks), self._stream()))
-            return
-        _check(lib().mi_grad_eri_sharded(self._h, D.data_ptr(), M, float(hyb), grad.data_ptr(), int(rank), int(nranks), self._stream()))
+        pd, pi = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        _check(lib().mi_grad_eri_xpairs(self._h, D.data_ptr(), spin_density.data_ptr() if spin_density is not None else None, float(hyb),
+                                        Q.data_ptr() if K > 0 else None, s.ctypes.data_as(pd) if K > 0 else None, K,
+                                        R.data_ptr() if Kx > 0 else None, t.ctypes.data_as(pd) if Kx > 0 else None,
+                                        sym.ctypes.data_as(pi) if Kx > 0 else None, Kx,
+                                        grad.data_ptr(), int(rank), int(nranks), self._stream()))
 
     # --- C-PCM (pcm.py): surface-charge integrals and the two per-cycle passes over them -----------------------------------
     def pcm_pairs(self, ordered=False):

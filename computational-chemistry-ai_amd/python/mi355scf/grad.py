@@ -6,7 +6,12 @@
 derivatives + device contractions, no grid-weight response, as PySCF's default `grid_response=False` [MEM])
 + nuclear repulsion.  `FDGradients` (central finite differences of the SCF energy) is kept as the
 independent check used by the tests.
+
+The pieces every analytic gradient driver shares live here (`casscf_grad.py` and `tdscf_grad.py` use them too): `assemble` (1e +
+2e + nuclear + XC parts under their timers), `log_gradient`, `xc_force` (the grid-block loop of the XC term) and the scanner base `_GradScanner`.
 """
+import time
+
 import numpy as np
 import torch
 
@@ -47,6 +52,70 @@ def _add_xc_force(fmu, ao, dm, C, wv, gga):
             fmu[:, k] += -2.0 * (ao[1 + k] * T1).sum(dim=1)
 
 
+def xc_force(mf, body):
+    """XC gradient per atom: `body(fmu, ao, w)` adds one grid block's forces to fmu [nao, 3] (`_add_xc_force`), `ao` the AO values
+    with the derivatives the force needs and `w` the block's weights, over this rank's share of the SCF grid."""
+    eng = mf.engine
+    gga = mf._xc_functional()[2]
+    coords, weights = mf.grids.coords, mf.grids.weights
+    lo, hi = mf._grid_range(coords.shape[0])
+    fmu = torch.zeros(eng.nao, 3, dtype=torch.float64, device=eng.device)
+    B = max(4096, mf.grid_block // 4)
+    for p0 in range(lo, hi, B):
+        p1 = min(p0 + B, hi)
+        body(fmu, eng.eval_ao(coords[p0:p1], deriv=2 if gga else 1), weights[p0:p1])
+    if mf._nranks > 1:
+        from . import parallel
+        parallel.all_reduce_sum(fmu, mf._pg)
+    f = fmu.cpu().numpy()
+    sl = mf.mol.aoslice_by_atom()
+    return np.array([f[sl[ia, 2]:sl[ia, 3]].sum(axis=0) for ia in range(mf.mol.natm)])
+
+
+def assemble(eng, mol, D, W, two_electron, xc=None, timing=None, ranks=None):
+    """de [natm, 3] = `grad_1e` of (D, W) + the two-electron part + nuclear repulsion (+ the XC part `xc()`), each under its timer
+    (`timing`: grad_1e, grad_eri, grad_xc).  `two_electron(g2)` accumulates into the zeroed device array g2 or returns its own.
+    ranks = (nranks, process group) of a caller whose `two_electron` evaluates this rank's share only: g2 is summed over the ranks
+    and rank 0's result becomes everybody's."""
+    tm = {} if timing is None else timing
+    t0 = time.time()
+    g = torch.zeros(mol.natm, 3, dtype=torch.float64, device=eng.device)
+    eng.grad_1e(D, W, g)
+    torch.cuda.synchronize()
+    tm["grad_1e"] = time.time() - t0
+    t0 = time.time()
+    g2 = torch.zeros_like(g)
+    out = two_electron(g2)
+    g2 = g2 if out is None else out
+    torch.cuda.synchronize()
+    tm["grad_eri"] = time.time() - t0
+    nranks, pg = ranks if ranks is not None else (1, None)
+    if nranks > 1:   # derivative-quartet batches are dealt round-robin to ranks inside mi_grad_eri
+        from . import parallel
+        parallel.all_reduce_sum(g2, pg)
+    de = (g + g2).cpu().numpy() + grad_nuc(mol)
+    if xc is not None:
+        t0 = time.time()
+        de = de + xc()
+        torch.cuda.synchronize()
+        tm["grad_xc"] = time.time() - t0
+    if nranks > 1:
+        dt = torch.as_tensor(de, device=eng.device)
+        parallel.broadcast0(dt, pg)
+        de = dt.cpu().numpy()
+    return de
+
+
+def log_gradient(log, mol, de, table, timing=None, header="gradient", title="--------------- gradients ---------------"):
+    """The timing line and (table: the caller's verbosity asks for it) the per-atom table, through `log(level, text)`."""
+    if timing is not None:
+        log(4, f"{header} timings (s): " + ", ".join(f"{k} {v:.3f}" for k, v in timing.items()))
+    if table:
+        log(4, title)
+        for ia in range(mol.natm):
+            log(4, "%d %s  %16.10f %16.10f %16.10f" % (ia, mol.atom_pure_symbol(ia), *de[ia]))
+
+
 class Gradients:
     """Analytic RHF/RKS gradient on the MI355X engine."""
 
@@ -66,27 +135,16 @@ class Gradients:
         """XC gradient of one density (closed shell) or two (spin): per grid block the densities and the functional of the SCF's
         block body (`dft.KSMixin`), on AO values with second derivatives, then `_add_xc_force` of each (D_s, wv_s)."""
         mf = self.base
-        eng = mf.engine
         xcf = mf._xc_functional()
         gga = xcf[2]
-        coords, weights = mf.grids.coords, mf.grids.weights
-        lo, hi = mf._grid_range(coords.shape[0])
-        fmu = torch.zeros(eng.nao, 3, dtype=torch.float64, device=eng.device)
-        B = max(4096, mf.grid_block // 4)
-        for p0 in range(lo, hi, B):
-            p1 = min(p0 + B, hi)
-            ao = eng.eval_ao(coords[p0:p1], deriv=2 if gga else 1)
+
+        def body(fmu, ao, w):
             Cs = [dm @ ao[0] for dm in dms]
             dens = [mf._block_density(ao, dm, None, gga, C) for dm, C in zip(dms, Cs)]
-            _e, wvs = mf._block_functional(xcf, [d[0] for d in dens], [d[1] for d in dens], weights[p0:p1])
+            _e, wvs = mf._block_functional(xcf, [d[0] for d in dens], [d[1] for d in dens], w)
             for dm, C, wv in zip(dms, Cs, wvs):
                 _add_xc_force(fmu, ao, dm, C, wv, gga)
-        if mf._nranks > 1:
-            from . import parallel
-            parallel.all_reduce_sum(fmu, mf._pg)
-        f = fmu.cpu().numpy()
-        sl = mf.mol.aoslice_by_atom()
-        return np.array([f[sl[ia, 2]:sl[ia, 3]].sum(axis=0) for ia in range(mf.mol.natm)])
+        return xc_force(mf, body)
 
     def _densities(self):
         """What `kernel` contracts, from the converged SCF: (densities of the XC term, total density D, spin density M or None,
@@ -103,43 +161,17 @@ class Gradients:
         eng = mf.engine
         mol = mf.mol
         dms, D, M, W, dm_fit = self._densities()
-        import time
-        tm = {}
-        t0 = time.time()
-        g = torch.zeros(mol.natm, 3, dtype=torch.float64, device=eng.device)
-        eng.grad_1e(D, W, g)
-        torch.cuda.synchronize()
-        tm["grad_1e"] = time.time() - t0
         is_ks = getattr(mf, "xc", None) is not None and hasattr(mf, "grids")
         hyb = mf._xc_functional()[0] if is_ks else 1.0
-        t0 = time.time()
-        if getattr(mf, "with_df", None) is not None:
-            g2 = _fitted_tensor(mf).grad_jk(dm_fit, hyb, rank=mf._rank, nranks=mf._nranks)
-        else:
-            g2 = torch.zeros_like(g)
+
+        def two_electron(g2):
+            if getattr(mf, "with_df", None) is not None:
+                return _fitted_tensor(mf).grad_jk(dm_fit, hyb, rank=mf._rank, nranks=mf._nranks)
             eng.grad_eri(D, hyb, g2, spin_density=M, rank=mf._rank, nranks=mf._nranks)
-        tm["grad_eri"] = time.time() - t0
-        if mf._nranks > 1:   # derivative-quartet batches are dealt round-robin to ranks inside mi_grad_eri
-            from . import parallel
-            parallel.all_reduce_sum(g2, mf._pg)
-        de = (g + g2).cpu().numpy() + grad_nuc(mol)
-        if is_ks:
-            t0 = time.time()
-            de = de + self._grad_xc(dms)
-            torch.cuda.synchronize()
-            tm["grad_xc"] = time.time() - t0
-        if mf._nranks > 1:
-            from . import parallel
-            dt = torch.as_tensor(de, device=eng.device)
-            parallel.broadcast0(dt, mf._pg)
-            de = dt.cpu().numpy()
-        self.timing = tm
-        mf._log(4, "gradient timings (s): " + ", ".join(f"{k} {v:.3f}" for k, v in tm.items()))
-        self.de = de
-        if self.verbose >= 4:
-            mf._log(4, "--------------- gradients ---------------")
-            for ia in range(mol.natm):
-                mf._log(4, "%d %s  %16.10f %16.10f %16.10f" % (ia, mol.atom_pure_symbol(ia), *de[ia]))
+        self.timing = {}
+        self.de = de = assemble(eng, mol, D, W, two_electron, (lambda: self._grad_xc(dms)) if is_ks else None, self.timing,
+                                (mf._nranks, mf._pg))
+        log_gradient(mf._log, mol, de, self.verbose >= 4, self.timing)
         return de
 
     grad = kernel
@@ -220,10 +252,7 @@ class FDGradients:
                 Rm[ia, x] -= h
                 g[ia, x] = (self._energy_at(Rp, dm0) - self._energy_at(Rm, dm0)) / (2 * h)
         self.de = g
-        if self.verbose >= 5:
-            mf._log(4, "--------------- gradients (finite difference) ---------------")
-            for ia in range(mf.mol.natm):
-                mf._log(4, "%d %s  %16.10f %16.10f %16.10f" % (ia, mf.mol.atom_pure_symbol(ia), *g[ia]))
+        log_gradient(mf._log, mf.mol, g, self.verbose >= 5, title="--------------- gradients (finite difference) ---------------")
         return g
 
     grad = kernel
@@ -233,26 +262,42 @@ class FDGradients:
 
 
 class _GradScanner:
+    """(energy, de) at a new geometry.  `_energy` is what the methods differ in; the rest -- the geometry, the starting density,
+    the SCF with the gradient's prefetch, `grad_dtol` (set by `geomopt.optimize`), the gradient -- is here."""
+
     def __init__(self, g):
         self.g = g
         self.base = g.base
         self.mol = g.mol
         self.converged = True
 
+    @property
+    def _scf(self):
+        return getattr(self.base, "_scf", self.base)
+
+    def _run_scf(self, mol, dm0):
+        mf = self._scf
+        mf.reset(mol)
+        mf._grad_prefetch = True      # the gradient's host-side set-up overlaps this SCF (engine option `grad_prefetch`)
+        e = mf.kernel(dm0=dm0)
+        self.g.mol = self.mol = mol
+        return e
+
+    def _energy(self, mol, dm0):
+        """The energy at `mol` from the starting density dm0 (through `_run_scf`); sets `converged`."""
+        e = self._run_scf(mol, dm0)
+        self.converged = self._scf.converged
+        return e
+
     def __call__(self, mol_or_geom):
-        mf = self.g.base
+        mf = self._scf
         mol = mol_or_geom if isinstance(mol_or_geom, Mole) else mf.mol.set_geom_(mol_or_geom, unit="Bohr", inplace=False)
         # starting density: the converged AO matrix as it is (the basis functions follow their atoms).  Transporting it in the
         # Cholesky-orthonormal frame instead (D = L_new^-T (L_old^T D L_old) L_new^-1: idempotent and N-electron in the new
         # metric) was measured WORSE -- ibuprofen B3LYP/def2-TZVP optimisation 105 instead of 86 SCF cycles over 12 steps,
         # benzene 20 instead of 14 (tools/opt_variants.py): Gram-Schmidt in AO order drags every later atom's functions along
         dm0 = mf.make_rdm1() if mf.mo_coeff is not None else None
-        mf.reset(mol)
-        mf._grad_prefetch = True      # the gradient's host-side set-up overlaps this SCF (engine option `grad_prefetch`)
-        e = mf.kernel(dm0=dm0)
-        self.converged = mf.converged
-        self.g.mol = self.mol = mol
+        e = self._energy(mol, dm0)
         if getattr(self, "grad_dtol", None) is not None:
             mf.engine.set_option("grad_dtol", self.grad_dtol)   # density-weighted screening of the derivative quartets
-        de = self.g.kernel()
-        return e, de
+        return e, self.g.kernel()

@@ -39,7 +39,7 @@ import warnings
 import numpy as np
 import torch
 
-from .mole import Mole
+from .grad import _GradScanner, _add_xc_force, assemble, log_gradient, xc_force
 
 ALGORITHMS = ("onepass", "loop")
 FOLLOW_MIN_OVERLAP = 0.7   # the scanner warns when the followed state overlaps the previous one by less than this
@@ -283,7 +283,6 @@ class Gradients:
                 g2 += tmp
 
     def _grad_xc(self, D0, st):
-        from .grad import _add_xc_force
         td = self.base
         mf = td._scf
         eng = mf.engine
@@ -292,15 +291,9 @@ class Gradients:
         nc = 4 if gga else 1
         P, U = st["P"], st["U"]
         eps = self.xc3_step / max(float(U.abs().max()), 1e-300)
-        coords, weights = mf.grids.coords, mf.grids.weights
-        lo, hi = mf._grid_range(coords.shape[0])
-        fmu = torch.zeros(eng.nao, 3, dtype=torch.float64, device=eng.device)
-        B = max(4096, mf.grid_block // 4)
         DP = D0 + P
-        for p0 in range(lo, hi, B):
-            p1 = min(p0 + B, hi)
-            w = weights[p0:p1]
-            ao = eng.eval_ao(coords[p0:p1], deriv=2 if gga else 1)
+
+        def body(fmu, ao, w):
             C0, CP, CU = D0 @ ao[0], P @ ao[0], U @ ao[0]
             rho0, tau = mf._block_density(ao, D0, None, gga, C0)
             _e, (wv0,) = mf._block_functional(xcf, [rho0], [tau], w)
@@ -313,14 +306,11 @@ class Gradients:
             _add_xc_force(fmu, ao, DP, C0 + CP, wv0, gga)
             _add_xc_force(fmu, ao, D0, C0, wv1[0] + 4.0 * wv2, gga)
             _add_xc_force(fmu, ao, U, CU, 8.0 * wv1[1], gga)
-        f = fmu.cpu().numpy()
-        sl = mf.mol.aoslice_by_atom()
-        return np.array([f[sl[ia, 2]:sl[ia, 3]].sum(axis=0) for ia in range(mf.mol.natm)])
+        return xc_force(mf, body)
 
     def kernel(self, xy=None, state=None, atmlst=None):
         from .ao2mo import resident_engine
         from .dft import parse_xc
-        from .grad import grad_nuc
         td = self.base
         _refuse(td)
         if state is not None:
@@ -361,30 +351,11 @@ class Gradients:
         if not st["converged"]:
             raise RuntimeError(f"TDA/TDDFT gradients: the Z-vector equations did not converge in {self.max_cycle} iterations "
                                f"(|r| = {st['residual']:.2e}, conv_tol = {self.conv_tol:.1e})")
-        t0 = time.time()
-        g = torch.zeros(mol.natm, 3, **dev)
-        eng.grad_1e((D0 + st["P"]).contiguous(), st["W"], g)
-        torch.cuda.synchronize()
-        tm["grad_1e"] = time.time() - t0
-        t0 = time.time()
-        g2 = torch.zeros_like(g)
-        self._grad_eri(eng, D0, st, hyb, g2)
-        torch.cuda.synchronize()
-        tm["grad_eri"] = time.time() - t0
-        de = (g + g2).cpu().numpy() + grad_nuc(mol)
-        if semilocal:
-            t0 = time.time()
-            de = de + self._grad_xc(D0, st)
-            torch.cuda.synchronize()
-            tm["grad_xc"] = time.time() - t0
         self.timing = tm
-        td._log(4, f"TD gradient (state {state}, {self.algorithm}, Z-vector {st['niter']} iterations) timings (s): "
-                + ", ".join(f"{k} {v:.3f}" for k, v in tm.items()))
-        self.de = de
-        if self.verbose >= 4:
-            td._log(4, f"--------------- gradients of excited state {state} ---------------")
-            for ia in range(mol.natm):
-                td._log(4, "%d %s  %16.10f %16.10f %16.10f" % (ia, mol.atom_pure_symbol(ia), *de[ia]))
+        self.de = de = assemble(eng, mol, (D0 + st["P"]).contiguous(), st["W"], lambda g2: self._grad_eri(eng, D0, st, hyb, g2),
+                                (lambda: self._grad_xc(D0, st)) if semilocal else None, tm)
+        log_gradient(td._log, mol, de, self.verbose >= 4, tm, f"TD gradient (state {state}, {self.algorithm}, Z-vector {st['niter']} iterations)",
+                     f"--------------- gradients of excited state {state} ---------------")
         return de
 
     grad = kernel
@@ -395,36 +366,26 @@ class Gradients:
         return _TDGradScanner(self)
 
 
-class _TDGradScanner:
+class _TDGradScanner(_GradScanner):
     """(E_SCF + w_n, de) at a new geometry: the SCF from the previous density, the Davidson from the previous vectors (`x0`), the
     state followed by its overlap sum_ia X_ia X'_ia / (|X| |X'|) with the previous X.  Below FOLLOW_MIN_OVERLAP it warns and
     keeps the best match: the state is never switched silently."""
 
     def __init__(self, g):
-        self.g = g
-        self.base = g.base
-        self.mol = g.mol
-        self.converged = True
+        super().__init__(g)
         self.state = g.state
         self.overlap = None
 
-    def __call__(self, mol_or_geom):
+    def _energy(self, mol, dm0):
         g = self.g
         td = g.base
         mf = td._scf
-        mol = mol_or_geom if isinstance(mol_or_geom, Mole) else mf.mol.set_geom_(mol_or_geom, unit="Bohr", inplace=False)
-        dm0 = mf.make_rdm1() if mf.mo_coeff is not None else None
         prev = td.xy if (td.xy is not None and self.state > 0) else None
-        mf.reset(mol)
-        mf._grad_prefetch = True
-        e0 = mf.kernel(dm0=dm0)
-        g.mol = self.mol = mol
-        if getattr(self, "grad_dtol", None) is not None:
-            mf.engine.set_option("grad_dtol", self.grad_dtol)
+        e0 = self._run_scf(mol, dm0)
+        g.state = self.state          # what `g.kernel()` differentiates
+        self.converged = bool(mf.converged)
         if self.state == 0:
-            de = g.kernel(state=0)
-            self.converged = bool(mf.converged)
-            return e0, de
+            return e0
         td.kernel(x0=prev)
         n = self.state
         if prev is not None and self.state <= len(prev):
@@ -440,7 +401,11 @@ class _TDGradScanner:
                 elif n != self.state:
                     td._log(3, f"TD gradient scanner: following the state from root {self.state} to root {n} "
                                f"(overlap {self.overlap:.2f})")
-                self.state = n
-        de = g.kernel(state=n)
-        self.converged = bool(mf.converged and np.asarray(td.converged)[n - 1] and g.converged)
-        return e0 + float(td.e[n - 1]), de
+                g.state = self.state = n
+        self.converged = bool(mf.converged and np.asarray(td.converged)[n - 1])
+        return e0 + float(td.e[n - 1])
+
+    def __call__(self, mol_or_geom):
+        e, de = super().__call__(mol_or_geom)
+        self.converged = bool(self.converged and self.g.converged)   # the Z-vector solve of the gradient as well
+        return e, de

@@ -9,6 +9,7 @@ random symmetric O(1) matrices from fixed seeds, prepare_eri(1e-14), grad_dtol 1
 
 Driver (`mc.nuc_grad_method()`): the RHF limit, central finite differences of the CASSCF energy, and an optimisation.
 Each test prints its figures (pytest -rP shows them)."""
+import ctypes
 import functools
 import re
 
@@ -70,10 +71,16 @@ def _ref(key, mol, D, M, Qs, s, hyb, spin):
 
 
 def _grad_pairs(eng, mol, D, M, hyb, Qs, s, rank=0, nranks=1):
+    """`mi_grad_eri_pairs` itself (`Engine.grad_eri` reaches the pair term through `mi_grad_eri_xpairs`)."""
+    from mi355scf import engine
     g = torch.zeros(mol.natm, 3, dtype=torch.float64, device=eng.device)
+    Dd, Md = _dev(D, eng), (_dev(M, eng) if M is not None else None)
     Q = _dev(np.array(Qs), eng) if len(s) else None
-    eng.grad_eri(_dev(D, eng), hyb, g, spin_density=_dev(M, eng) if M is not None else None, rank=rank, nranks=nranks,
-                 pairs=(Q, np.asarray(s, dtype=np.float64)))
+    s = np.ascontiguousarray(np.asarray(s, dtype=np.float64))
+    engine._check(engine.lib().mi_grad_eri_pairs(eng._h, Dd.data_ptr(), Md.data_ptr() if Md is not None else None, float(hyb),
+                                                 Q.data_ptr() if Q is not None else None,
+                                                 s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if s.size else None, int(s.size),
+                                                 g.data_ptr(), rank, nranks, eng._stream()))
     return g.cpu().numpy()
 
 
@@ -106,8 +113,10 @@ def test_pair_kernel_matches_exact_oracle(system, spin):
             assert err3 < tol, (system, spin, "rank split", err3, tol)
     # K = 0 through the new entry is the plain entry (same kernels; the atomics' summation order is the only difference)
     g0 = _grad_pairs(eng, mol, D, Ms, 1.0, [], [])
+    from mi355scf import engine
     g1 = torch.zeros(mol.natm, 3, dtype=torch.float64, device=eng.device)
-    eng.grad_eri(_dev(D, eng), 1.0, g1, spin_density=_dev(Ms, eng) if spin else None)
+    Dd, Md = _dev(D, eng), (_dev(Ms, eng) if spin else None)
+    engine._check(engine.lib().mi_grad_eri_sharded(eng._h, Dd.data_ptr(), Md.data_ptr() if spin else None, 1.0, g1.data_ptr(), 0, 1, eng._stream()))
     g1 = g1.cpu().numpy()
     d0 = np.abs(g0 - g1).max()
     print(f"{system} spin={spin}: K = 0 against mi_grad_eri_sharded {d0:.2e}; worst relative error {worst:.2e}")

@@ -302,13 +302,14 @@ def test_no_exchange_pairs_reproduces_the_pair_entry_bit_for_bit(spin):
     eng = Engine(mol)
     eng.prepare_eri(QTOL)
     eng.set_option("grad_dtol", DTOL)
+    from test_gpu_casscf_grad import _grad_pairs   # calls mi_grad_eri_pairs itself
     for hyb in (0.2, 1.0):
-        old = _run(eng, mol, D, hyb, M=M, pairs=(Q, S2))
+        old = _grad_pairs(eng, mol, D, M, hyb, Q, S2)
         new = _run(eng, mol, D, hyb, M=M, pairs=(Q, S2), xpairs=([], (), ()))
         print(f"spin={spin} hyb={hyb}: max |new - old| = {np.abs(new - old).max():.1e}")
         assert np.array_equal(new, old), (spin, hyb, np.abs(new - old).max())
     plain = _run(eng, mol, D, 1.0, M=M)
-    assert np.array_equal(_run(eng, mol, D, 1.0, M=M, xpairs=([], (), ())), _run(eng, mol, D, 1.0, M=M, pairs=([], ())))
+    assert np.array_equal(_run(eng, mol, D, 1.0, M=M, xpairs=([], (), ())), _grad_pairs(eng, mol, D, M, 1.0, [], []))
     assert np.abs(plain - _run(eng, mol, D, 1.0, M=M, xpairs=([], (), ()))).max() <= 1e-13 * max(1.0, np.abs(plain).max())
 
 
