@@ -5396,6 +5396,7 @@ template <int N> __device__ inline DN<N> chain(DN<N> a, double f, double df) { D
     for (int i = 0; i < N; i++) r.d[i] = df * a.d[i]; return r; }
 template <int N> __device__ inline DN<N> dexp(DN<N> a) { double e = exp(a.v); return chain(a, e, e); }
 template <int N> __device__ inline DN<N> dlog(DN<N> a) { return chain(a, log(a.v), 1.0 / a.v); }
+template <int N> __device__ inline DN<N> dlog1p(DN<N> a) { return chain(a, log1p(a.v), 1.0 / (1.0 + a.v)); }
 template <int N> __device__ inline DN<N> dsqrt(DN<N> a) { double s = sqrt(a.v); return chain(a, s, 0.5 / s); }
 template <int N> __device__ inline DN<N> dpow(DN<N> a, double p) { double f = pow(a.v, p); return chain(a, f, p * f / a.v); }
 template <int N> __device__ inline DN<N> datan(DN<N> a) { return chain(a, atan(a.v), 1.0 / (1.0 + a.v * a.v)); }
@@ -5457,6 +5458,7 @@ template <int N> __device__ inline HD<N> chain2(HD<N> a, double f, double f1, do
 template <int N> __device__ inline HD<N> operator/(HD<N> a, HD<N> b) { double iv = 1.0 / b.v; return a * chain2(b, iv, -iv * iv, 2.0 * iv * iv * iv); }
 template <int N> __device__ inline HD<N> dexp(HD<N> a) { double e = exp(a.v); return chain2(a, e, e, e); }
 template <int N> __device__ inline HD<N> dlog(HD<N> a) { double iv = 1.0 / a.v; return chain2(a, log(a.v), iv, -iv * iv); }
+template <int N> __device__ inline HD<N> dlog1p(HD<N> a) { double iv = 1.0 / (1.0 + a.v); return chain2(a, log1p(a.v), iv, -iv * iv); }
 template <int N> __device__ inline HD<N> dsqrt(HD<N> a) { double s = sqrt(a.v); return chain2(a, s, 0.5 / s, -0.25 / (s * a.v)); }
 template <int N> __device__ inline HD<N> dpow(HD<N> a, double p) { double f = pow(a.v, p), iv = 1.0 / a.v;
     return chain2(a, f, p * f * iv, p * (p - 1.0) * f * iv * iv); }
@@ -5485,23 +5487,35 @@ template <class T> __device__ inline T f_b88(T rho, T sig)
 
 // ITYH attenuation (Iikura, Tsuneda, Yanai, Hirao, JCP 115, 3540 (2001)) of one spin channel's exchange by erfc(omega r12):
 //   F(a) = 1 - 8/3 a [sqrt(pi) erf(1/(2a)) + (2a - 4a^3) exp(-1/(4a^2)) - 3a + 4a^3],  a = omega / (2 k_sigma).
-// The bracket cancels catastrophically in FP64 for large a (relative error 4e-10 at a = 5, 3 % at a = 100; low-density grid
-// points reach a ~ 100), so from a = 4 on the asymptotic series 1/(36a^2) - 1/(960a^4) + 1/(26880a^6) - 1/(829440a^8) is used
-// (relative error 2e-11 at a = 4, 3e-12 at 5, ~1e-14 from 10 on; the closed form is good to ~1e-10 below the switch).
-#define ITYH_SERIES_A 4.0
-template <class T> __device__ inline T ityh_factor(T a)
+// The bracket cancels in FP64 as a grows (relative error of F ~1e-11 at a = 2..4, 4e-10 at 5, 3 % at 100; low-density grid
+// points reach a ~ 100 and beyond), so from a = 1 on the series in 1/a^2 is used.  It converges for every a (F is entire in
+// 1/a); twelve terms truncate below 1e-16 of F + a F'/2 at a = 1.  The energy density needs K F(a) with a^2 proportional to K,
+// and de/dsigma = K' (F + a F'/2), in which the leading 1/(36a^2) terms cancel and leave 1e-2 (a = 1) .. 1e-7 (a ~ 1000) of
+// F.  The series branch therefore returns P(u) = F(a)/u, u = 1/a^2, and the caller multiplies by K u = K/a^2, which it forms
+// without K: the leading term then has a derivative in sigma of exactly zero and nothing cancels.  Below the switch the
+// closed form keeps F + a F'/2 to ~1e-12 relative (bracket terms <= 4 against a result of 0.36 at a = 1).
+#define ITYH_SERIES_A 1.0
+template <class T> __device__ inline T ityh_closed(T a)
 {
-    if (a.v >= ITYH_SERIES_A) {
-        const T i2 = T(1.0) / (a * a);
-        return i2 * (T(1.0 / 36.0) - i2 * (T(1.0 / 960.0) - i2 * (T(1.0 / 26880.0) - i2 * T(1.0 / 829440.0))));
-    }
     const T a2 = a * a, a3 = a2 * a;
     return T(1.0) - T(8.0 / 3.0) * a * (T(1.7724538509055159) * derf(T(0.5) / a) + (T(2.0) * a - T(4.0) * a3) * dexp(T(-0.25) / a2)
                                         - T(3.0) * a + T(4.0) * a3);
 }
+// P(u) = F(a) a^2 at u = 1/a^2: 1/36 - u/960 + u^2/26880 - ...
+template <class T> __device__ inline T ityh_series_over_u(T u)
+{
+    const double c[12] = {1.0 / 36.0, 1.0 / 960.0, 1.0 / 26880.0, 1.0 / 829440.0, 1.0 / 28385280.0, 1.0 / 1073479680.0,
+                          1.0 / 44590694400.0, 1.0 / 2021444812800.0, 1.0 / 99407521382400.0, 1.0 / 5273830608076800.0,
+                          1.0 / 300357209869516800.0, 1.0 / 18282612774666240000.0};
+    T p(c[11]);
+#pragma unroll
+    for (int k = 10; k >= 0; k--) p = T(c[k]) - u * p;
+    return p;
+}
 
 // Short-range B88 of CAM-B3LYP, closed shell: per spin channel e_s^SR = e_s^B88 F(a_s) with e_s^B88 = -1/2 rho_s^(4/3) K_s (Slater
-// included, as f_b88), k_s = sqrt(9 pi / K_s) rho_s^(1/3), a_s = omega / (2 k_s).  omega > 0 (checked by the entry points).
+// included, as f_b88), k_s = sqrt(9 pi / K_s) rho_s^(1/3), a_s = omega / (2 k_s), i.e. a_s^2 = q K_s with q = omega^2 /
+// (36 pi rho_s^(2/3)).  omega > 0 (checked by the entry points).
 template <class T> __device__ inline T f_b88_sr(T rho, T sig, double omega)
 {
     const double beta = 0.0042;
@@ -5509,8 +5523,10 @@ template <class T> __device__ inline T f_b88_sr(T rho, T sig, double omega)
     T r13 = dpow(rs, 1.0 / 3.0), r43 = rs * r13;
     T x = dsqrt(sig * T(0.25) + T(1e-300)) / r43;
     T K = T(1.8610514726982001) /* 3/2 (6/pi)^(1/3) */ + T(2.0 * beta) * x * x / (T(1.0) + T(6.0 * beta) * x * dasinh(x));
-    T a = T(0.5 * omega) / (dsqrt(T(9.0 * M_PI) / K) * r13);
-    return -(r43 * K * ityh_factor(a));  // 2 e_s^SR
+    T q = T(omega * omega / (36.0 * M_PI)) / (r13 * r13);
+    T a2 = q * K;
+    if (a2.v >= ITYH_SERIES_A * ITYH_SERIES_A) return -(r43 / q * ityh_series_over_u(T(1.0) / a2));  // K F = (K u) P(u), K u = 1/q
+    return -(r43 * K * ityh_closed(dsqrt(a2)));  // 2 e_s^SR
 }
 
 // VWN fit: correlation energy per electron as a function of x = sqrt(rs)
@@ -5554,45 +5570,78 @@ template <class T> __device__ inline T f_pbe_x(T rho, T sig)
 template <class T> __device__ inline T pw92_g(T rs, double A, double a1, double b1, double b2, double b3, double b4)
 {
     T x = dsqrt(rs);
-    return T(-2 * A) * (T(1.0) + T(a1) * rs) * dlog(T(1.0) + T(1.0) / (T(2 * A) * (T(b1) * x + T(b2) * rs + T(b3) * rs * x + T(b4) * rs * rs)));
+    // log1p: the argument is 1e-5 in the density tail (rs ~ 1e3), where log(1 + .) keeps 11 digits only
+    return T(-2 * A) * (T(1.0) + T(a1) * rs) * dlog1p(T(1.0) / (T(2 * A) * (T(b1) * x + T(b2) * rs + T(b3) * rs * x + T(b4) * rs * rs)));
+}
+
+// eps_c + H of PBE correlation, H = g log(1 + (beta/gamma) t^2 (1 + y) / (1 + y + y^2)), g = gamma phi^3, y = A t^2,
+// A = (beta/gamma) / E1, E1 = exp(-eps_c / g) - 1.  At large reduced gradients y(1 + y)/(1 + y + y^2) -> 1 and H -> -eps_c:
+// the quotient rule then forms the derivative (1 + 2y)/(1 + y + y^2)^2 as a difference of two numbers y^2 times larger, and
+// eps_c + H cancels (y reaches 1e10 in density tails; de/dsigma and the second derivatives lost every digit there).  With
+// -eps_c = g log(1 + E1) the sum is g log(1 - E1/(1 + E1) / (1 + y + y^2)) exactly, in which nothing cancels; it is used
+// from y = 1 on, where the plain form is still well conditioned.
+template <class T> __device__ inline T pbe_c_eps_plus_h(T ec, T g, T t2)
+{
+    const double bg = 0.06672455060314922 / 0.031090690869654895;
+    T E1 = dexp(-ec / g) - T(1.0);
+    T y = T(bg) / E1 * t2;
+    T D = T(1.0) + y + y * y;
+    if (y.v > 1.0) return g * dlog1p(-(E1 / (T(1.0) + E1)) / D);
+    return ec + g * dlog(T(1.0) + T(bg) * t2 * (T(1.0) + y) / D);
 }
 
 template <class T> __device__ inline T f_pbe_c(T rho, T sig)
 {
-    const double beta = 0.06672455060314922, gamma = 0.031090690869654895;
+    const double gamma = 0.031090690869654895;
     T rs = dpow(T(0.75 / M_PI) / rho, 1.0 / 3.0);
     T ec = pw92_g(rs, 0.031090690869654895, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294);
     T kf = dpow(T(3.0 * M_PI * M_PI) * rho, 1.0 / 3.0);
     T ks2 = T(4.0 / M_PI) * kf;
     T t2 = sig / (T(4.0) * ks2 * rho * rho);
-    T Aa = T(beta / gamma) / (dexp(-ec / T(gamma)) - T(1.0));
-    T At2 = Aa * t2;
-    T H = T(gamma) * dlog(T(1.0) + T(beta / gamma) * t2 * (T(1.0) + At2) / (T(1.0) + At2 + At2 * At2));
-    return rho * (ec + H);
+    return rho * pbe_c_eps_plus_h(ec, T(gamma), t2);
 }
 
 // ---- spin-polarised forms e(rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb)
+// A spin channel is evaluated from XC_CHANNEL_FLOOR up.  The floor only keeps rho_s^(4/3) and the reduced gradient away from
+// underflow and 0/0.  What it drops is largest in M06-2X's opposite-spin correlation, which is linear in the minority density:
+// ~5 rho_s |eps_c| with eps_c ~ 1e-4 at rho = 1e-10, against 1e-11 of the LDA exchange 0.74 rho^(4/3) = 3e-14 of a point that
+// just passes the density cut-off of the kernels (rho_a + rho_b > 1e-10): rho_s < 6e-22.  Exchange drops (rho_s / rho)^(4/3).
+// (A floor of 1e-12 dropped 1e-4 of the LDA exchange at rho_a = 1e-9.)
+#define XC_CHANNEL_FLOOR 1e-24
 // exchange: spin scaling  E_x[ra, rb] = (E_x[2 ra] + E_x[2 rb]) / 2  with sigma -> 4 sigma_ss
 template <class T, class F> __device__ inline T spin_scaled_exchange(T ra, T rb, T saa, T sbb, F fx)
 {
     T e(0.0);
-    if (ra.v > 1e-12) e = e + T(0.5) * fx(T(2.0) * ra, T(4.0) * saa);
-    if (rb.v > 1e-12) e = e + T(0.5) * fx(T(2.0) * rb, T(4.0) * sbb);
+    if (ra.v > XC_CHANNEL_FLOOR) e = e + T(0.5) * fx(T(2.0) * ra, T(4.0) * saa);
+    if (rb.v > XC_CHANNEL_FLOOR) e = e + T(0.5) * fx(T(2.0) * rb, T(4.0) * sbb);
     return e;
 }
-// zeta = (ra - rb)/rho clipped away from +-1 (the derivatives of (1 +- zeta)^(4/3) etc. stay finite)
+// zeta = (ra - rb)/rho clipped away from +-1, for TPSS correlation's C(zeta, xi) alone: its (1 +- zeta)^(-4/3) stays finite
+// (1e20 at the clip) and multiplies xi^2, which vanishes with the minority gradient.  A clip at 1 - 1e-10 moved C(zeta, 0) of
+// every fully polarised point by 1e-9; the spin interpolations f(zeta) and phi(zeta) do not go through here (spin_pow_sum).
 template <class T> __device__ inline T spin_zeta(T ra, T rb)
 {
     T z = (ra - rb) / (ra + rb);
-    const double lim = 1.0 - 1e-10;
+    const double lim = 1.0 - 1e-15;
     if (z.v > lim) z = T(lim);
     if (z.v < -lim) z = T(-lim);
     return z;
 }
-template <class T> __device__ inline T spin_fzeta(T z) // ((1+z)^(4/3) + (1-z)^(4/3) - 2) / (2^(4/3) - 2)
+// (1 + zeta)^p + (1 - zeta)^p, p > 0, from 1 +- zeta = 2 rho_s / rho: the spin interpolations keep the digits of a nearly
+// empty channel, which zeta = (ra - rb)/rho rounds away and its clip replaces (phi of PBE correlation holds (1 - zeta)^(2/3):
+// a clip at 1 - d moves it by d^(2/3), 1e-10 even for d = 1e-15).  An empty channel contributes its limit, 0.
+template <class T> __device__ inline T spin_pow_sum(T ra, T rb, double p)
 {
-    return (dpow(T(1.0) + z, 4.0 / 3.0) + dpow(T(1.0) - z, 4.0 / 3.0) - T(2.0)) * T(1.0 / (2.5198420997897464 - 2.0));
+    T rho = ra + rb, s(0.0);
+    if (ra.v > 0.0) s = s + dpow(T(2.0) * ra / rho, p);
+    if (rb.v > 0.0) s = s + dpow(T(2.0) * rb / rho, p);
+    return s;
 }
+template <class T> __device__ inline T spin_fzeta(T ra, T rb) // ((1+z)^(4/3) + (1-z)^(4/3) - 2) / (2^(4/3) - 2)
+{
+    return (spin_pow_sum(ra, rb, 4.0 / 3.0) - T(2.0)) * T(1.0 / (2.5198420997897464 - 2.0));
+}
+template <class T> __device__ inline T spin_zeta4(T ra, T rb) { T z = (ra - rb) / (ra + rb), z2 = z * z; return z2 * z2; }
 // VWN-RPA (libxc LDA_C_VWN_RPA, the correlation of B3LYP): eps = eps_P + (eps_F - eps_P) f(zeta), RPA fits
 template <class T> __device__ inline T f_vwn_rpa_spin(T ra, T rb)
 {
@@ -5600,7 +5649,7 @@ template <class T> __device__ inline T f_vwn_rpa_spin(T ra, T rb)
     T x = dsqrt(dpow(T(0.75 / M_PI) / rho, 1.0 / 3.0));
     T eP = vwn_eps(x, 0.0310907, -0.409286, 13.0720, 42.7198);
     T eF = vwn_eps(x, 0.01554535, -0.743294, 20.1231, 101.578);
-    return rho * (eP + (eF - eP) * spin_fzeta(spin_zeta(ra, rb)));
+    return rho * (eP + (eF - eP) * spin_fzeta(ra, rb));
 }
 // VWN5: eps = eps_P + alpha_c f(z)/f''(0) (1 - z^4) + (eps_F - eps_P) f(z) z^4
 template <class T> __device__ inline T f_vwn5_spin(T ra, T rb)
@@ -5610,7 +5659,7 @@ template <class T> __device__ inline T f_vwn5_spin(T ra, T rb)
     T eP = vwn_eps(x, 0.0310907, -0.10498, 3.72744, 12.9352);
     T eF = vwn_eps(x, 0.01554535, -0.32500, 7.06042, 18.0578);
     T ac = vwn_eps(x, -1.0 / (6.0 * M_PI * M_PI), -0.0047584, 1.13107, 13.0045);
-    T z = spin_zeta(ra, rb), fz = spin_fzeta(z), z4 = z * z * z * z;
+    T fz = spin_fzeta(ra, rb), z4 = spin_zeta4(ra, rb);
     return rho * (eP + ac * fz * T(1.0 / 1.7099209341613657) * (T(1.0) - z4) + (eF - eP) * fz * z4);
 }
 // LYP, open-shell form of Miehlich, Savin, Stoll, Preuss, CPL 157, 200 (1989)
@@ -5636,24 +5685,21 @@ template <class T> __device__ inline T f_lyp_spin(T ra, T rb, T saa, T sab, T sb
 // PBE correlation with the PW92 spin interpolation and phi(zeta)
 template <class T> __device__ inline T f_pbe_c_spin(T ra, T rb, T saa, T sab, T sbb)
 {
-    const double beta = 0.06672455060314922, gamma = 0.031090690869654895;
+    const double gamma = 0.031090690869654895;
     T rho = ra + rb;
     T sig = saa + T(2.0) * sab + sbb;
     T rs = dpow(T(0.75 / M_PI) / rho, 1.0 / 3.0);
     T e0 = pw92_g(rs, 0.031090690869654895, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294);
     T e1 = pw92_g(rs, 0.015545345434827448, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517);
     T mac = pw92_g(rs, 0.016886863940389627, 0.11125, 10.357, 3.6231, 0.88026, 0.49671); // = -alpha_c
-    T z = spin_zeta(ra, rb), fz = spin_fzeta(z), z4 = z * z * z * z;
+    T fz = spin_fzeta(ra, rb), z4 = spin_zeta4(ra, rb);
     T ec = e0 - mac * fz * T(1.0 / 1.7099209341613657) * (T(1.0) - z4) + (e1 - e0) * fz * z4;
-    T phi = T(0.5) * (dpow(T(1.0) + z, 2.0 / 3.0) + dpow(T(1.0) - z, 2.0 / 3.0));
+    T phi = T(0.5) * spin_pow_sum(ra, rb, 2.0 / 3.0);
     T phi3 = phi * phi * phi;
     T kf = dpow(T(3.0 * M_PI * M_PI) * rho, 1.0 / 3.0);
     T ks2 = T(4.0 / M_PI) * kf;
     T t2 = sig / (T(4.0) * phi * phi * ks2 * rho * rho);
-    T Aa = T(beta / gamma) / (dexp(-ec / (T(gamma) * phi3)) - T(1.0));
-    T At2 = Aa * t2;
-    T H = T(gamma) * phi3 * dlog(T(1.0) + T(beta / gamma) * t2 * (T(1.0) + At2) / (T(1.0) + At2 + At2 * At2));
-    return rho * (ec + H);
+    return rho * pbe_c_eps_plus_h(ec, T(gamma) * phi3, t2);
 }
 
 // =================================================================================================
@@ -5678,7 +5724,7 @@ template <class T> __device__ inline T pw92_eps_spin(T ra, T rb)
     T e0 = pw92_g(rs, 0.031090690869654895, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294);
     T e1 = pw92_g(rs, 0.015545345434827448, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517);
     T mac = pw92_g(rs, 0.016886863940389627, 0.11125, 10.357, 3.6231, 0.88026, 0.49671);
-    T z = spin_zeta(ra, rb), fz = spin_fzeta(z), z4 = z * z * z * z;
+    T fz = spin_fzeta(ra, rb), z4 = spin_zeta4(ra, rb);
     return e0 - mac * fz * T(1.0 / 1.7099209341613657) * (T(1.0) - z4) + (e1 - e0) * fz * z4;
 }
 
@@ -5709,8 +5755,10 @@ template <class T> __device__ inline T f_tpss_x_unpol(T rho, T sig, T tau)
 template <class T> __device__ inline T f_tpss_x_spin(T ra, T rb, T saa, T sbb, T ta, T tb)
 {
     T e(0.0);
-    if (ra.v > 1e-12 && ta.v > 1e-14) e = e + T(0.5) * f_tpss_x_unpol(T(2.0) * ra, T(4.0) * saa, T(2.0) * ta);
-    if (rb.v > 1e-12 && tb.v > 1e-14) e = e + T(0.5) * f_tpss_x_unpol(T(2.0) * rb, T(4.0) * sbb, T(2.0) * tb);
+    // tau_s > 0 is all the formula needs (z = tau_W / tau may overflow to inf, which the clip z <= 1 takes); the uniform-gas
+    // tau of a tail point is far below any fixed threshold (2.9 rho^(5/3) = 3e-15 at rho = 1e-9)
+    if (ra.v > XC_CHANNEL_FLOOR && ta.v > 0.0) e = e + T(0.5) * f_tpss_x_unpol(T(2.0) * ra, T(4.0) * saa, T(2.0) * ta);
+    if (rb.v > XC_CHANNEL_FLOOR && tb.v > 0.0) e = e + T(0.5) * f_tpss_x_unpol(T(2.0) * rb, T(4.0) * sbb, T(2.0) * tb);
     return e;
 }
 // ---- TPSS correlation (revPKZB)
@@ -5718,7 +5766,7 @@ template <class T> __device__ inline T f_tpss_c_spin(T ra, T rb, T saa, T sab, T
 {
     const double d = 2.8;
     T rho = ra + rb, sig = saa + T(2.0) * sab + sbb, tau = ta + tb;
-    if (tau.v < 1e-14) return T(0.0);
+    if (!(tau.v > 0.0)) return T(0.0);
     T tw = sig / (T(8.0) * rho);
     T z = tw / tau;
     if (z.v > 1.0) z = T(1.0);
@@ -5734,8 +5782,8 @@ template <class T> __device__ inline T f_tpss_c_spin(T ra, T rb, T saa, T sab, T
     T C = C0 / (den2 * den2);
     T epbe = f_pbe_c_spin(ra, rb, saa, sab, sbb) / rho;
     T ea = epbe, eb = epbe;
-    if (ra.v > 1e-12) ea = dmaxv(f_pbe_c_spin(ra, T(0.0), saa, T(0.0), T(0.0)) / ra, epbe);
-    if (rb.v > 1e-12) eb = dmaxv(f_pbe_c_spin(rb, T(0.0), sbb, T(0.0), T(0.0)) / rb, epbe);
+    if (ra.v > XC_CHANNEL_FLOOR) ea = dmaxv(f_pbe_c_spin(ra, T(0.0), saa, T(0.0), T(0.0)) / ra, epbe);
+    if (rb.v > XC_CHANNEL_FLOOR) eb = dmaxv(f_pbe_c_spin(rb, T(0.0), sbb, T(0.0), T(0.0)) / rb, epbe);
     T zz = z * z;
     T erev = epbe * (T(1.0) + C * zz) - (T(1.0) + C) * zz * (ra / rho * ea + rb / rho * eb);
     return rho * erev * (T(1.0) + T(d) * erev * zz * z);
@@ -5753,8 +5801,7 @@ __device__ __constant__ double M062X_DAB[6] = {1.166404e-01, -9.120847e-02, -6.7
 template <class T> __device__ inline T f_m06_x_channel(T r, T s, T tau, const double *a) // one spin channel: r = rho_s
 {
     T tl = T(0.3 * 15.192666241151989 /* (6 pi^2)^(2/3) */) * dpow(r, 5.0 / 3.0);
-    T t = tl / tau;
-    T w = (t - T(1.0)) / (t + T(1.0));
+    T w = (tl - tau) / (tl + tau);          // (t - 1)/(t + 1) with t = tau_LDA / tau, without the quotient that overflows
     T fw(a[11]);
 #pragma unroll
     for (int i = 10; i >= 0; i--) fw = fw * w + T(a[i]);
@@ -5763,8 +5810,8 @@ template <class T> __device__ inline T f_m06_x_channel(T r, T s, T tau, const do
 template <class T> __device__ inline T f_m062x_x_spin(T ra, T rb, T saa, T sbb, T ta, T tb)
 {
     T e(0.0);
-    if (ra.v > 1e-12 && ta.v > 1e-14) e = e + f_m06_x_channel(ra, saa, ta, M062X_A);
-    if (rb.v > 1e-12 && tb.v > 1e-14) e = e + f_m06_x_channel(rb, sbb, tb, M062X_A);
+    if (ra.v > XC_CHANNEL_FLOOR && ta.v > 0.0) e = e + f_m06_x_channel(ra, saa, ta, M062X_A);
+    if (rb.v > XC_CHANNEL_FLOOR && tb.v > 0.0) e = e + f_m06_x_channel(rb, sbb, tb, M062X_A);
     return e;
 }
 template <class T> __device__ inline T m06_h(T x2, T z, const double *dc, double alpha)
@@ -5782,13 +5829,13 @@ template <class T> __device__ inline T m06_g(T x2, const double *cc, double gamm
 }
 template <class T> __device__ inline T f_m062x_c_spin(T ra, T rb, T saa, T sbb, T ta, T tb)
 {
-    const bool ha = ra.v > 1e-12 && ta.v > 1e-14, hb = rb.v > 1e-12 && tb.v > 1e-14;
+    const bool ha = ra.v > XC_CHANNEL_FLOOR && ta.v > 0.0, hb = rb.v > XC_CHANNEL_FLOOR && tb.v > 0.0;
     T e(0.0), ess_a(0.0), ess_b(0.0), x2a(0.0), x2b(0.0), za(0.0), zb(0.0);
     if (ha) {
         x2a = saa / dpow(ra, 8.0 / 3.0);
         za = T(2.0) * ta / dpow(ra, 5.0 / 3.0) - T(M06_CF);
         ess_a = ra * pw92_eps_spin(ra, T(0.0));
-        T Dsic = T(1.0) - x2a / (T(4.0) * (za + T(M06_CF)));
+        T Dsic = T(1.0) - saa / (T(8.0) * ra * ta);   // 1 - x^2 / (4 (z + C_F)) = 1 - tau_W / tau, without the detour (z - C_F) + C_F
         if (Dsic.v < 0.0) Dsic = T(0.0);
         e = e + ess_a * (m06_g(x2a, M062X_CSS, 0.06) + m06_h(x2a, za, M062X_DSS, 0.00515088)) * Dsic;
     }
@@ -5796,7 +5843,7 @@ template <class T> __device__ inline T f_m062x_c_spin(T ra, T rb, T saa, T sbb, 
         x2b = sbb / dpow(rb, 8.0 / 3.0);
         zb = T(2.0) * tb / dpow(rb, 5.0 / 3.0) - T(M06_CF);
         ess_b = rb * pw92_eps_spin(rb, T(0.0));
-        T Dsic = T(1.0) - x2b / (T(4.0) * (zb + T(M06_CF)));
+        T Dsic = T(1.0) - sbb / (T(8.0) * rb * tb);
         if (Dsic.v < 0.0) Dsic = T(0.0);
         e = e + ess_b * (m06_g(x2b, M062X_CSS, 0.06) + m06_h(x2b, zb, M062X_DSS, 0.00515088)) * Dsic;
     }

@@ -370,17 +370,33 @@ def _vwn_eps(x, A, x0, b, c):
     return A * (np.log(x * x / X) + 2 * b / Q * at - b * x0 / X0 * (np.log((x - x0) ** 2 / X) + 2 * (b + 2 * x0) / Q * at))
 
 
-def _fzeta(z):
-    return ((1 + z) ** (4.0 / 3) + (1 - z) ** (4.0 / 3) - 2) / (2 ** (4.0 / 3) - 2)
-
-
 _FPP0 = 4.0 / (9.0 * (2 ** (1.0 / 3) - 1))   # f''(0)
 
 
 def _zeta(ra, rb):
+    """zeta clipped away from +-1, for TPSS correlation's C(zeta, xi) alone (its (1 +- zeta)^(-4/3) stays finite)."""
     z = (ra - rb) / (ra + rb)
-    lim = 1.0 - 1e-10
+    lim = 1.0 - 1e-15
     return np.where(np.real(z) > lim, lim, np.where(np.real(z) < -lim, -lim, z))
+
+
+def _pow_sum(ra, rb, p):
+    """(1 + zeta)^p + (1 - zeta)^p, p > 0, from 1 +- zeta = 2 rho_s / rho: no clip, and a nearly empty channel keeps its
+    digits ((1 - zeta)^(2/3) of PBE's phi moves by d^(2/3) under a clip at 1 - d).  An empty channel contributes 0."""
+    r = ra + rb
+    out = 0.0
+    for r_ in (ra, rb):
+        ok = np.real(r_) > 0
+        out = out + np.where(ok, (2 * np.where(ok, r_, 1.0) / r) ** p, 0.0)
+    return out
+
+
+def _fzeta_ab(ra, rb):
+    return (_pow_sum(ra, rb, 4.0 / 3) - 2) / (2 ** (4.0 / 3) - 2)
+
+
+def _zeta4(ra, rb):
+    return ((ra - rb) / (ra + rb)) ** 4
 
 
 def _vwn_rpa_spin(ra, rb):
@@ -389,7 +405,7 @@ def _vwn_rpa_spin(ra, rb):
     x = np.sqrt((3.0 / (4 * np.pi * r)) ** (1.0 / 3))
     eP = _vwn_eps(x, 0.0310907, -0.409286, 13.0720, 42.7198)
     eF = _vwn_eps(x, 0.01554535, -0.743294, 20.1231, 101.578)
-    return r * (eP + (eF - eP) * _fzeta(_zeta(ra, rb)))
+    return r * (eP + (eF - eP) * _fzeta_ab(ra, rb))
 
 
 def _vwn5_spin(ra, rb):
@@ -399,8 +415,7 @@ def _vwn5_spin(ra, rb):
     eP = _vwn_eps(x, 0.0310907, -0.10498, 3.72744, 12.9352)
     eF = _vwn_eps(x, 0.01554535, -0.32500, 7.06042, 18.0578)
     ac = _vwn_eps(x, -1.0 / (6 * np.pi ** 2), -0.0047584, 1.13107, 13.0045)
-    z = _zeta(ra, rb)
-    fz, z4 = _fzeta(z), z ** 4
+    fz, z4 = _fzeta_ab(ra, rb), _zeta4(ra, rb)
     return r * (eP + ac * fz / _FPP0 * (1 - z4) + (eF - eP) * fz * z4)
 
 
@@ -418,10 +433,9 @@ def _pbe_c_spin(ra, rb, saa, sab, sbb):
     e0 = _pw92_g(rs, 0.031090690869654895, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294)
     e1 = _pw92_g(rs, 0.015545345434827448, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517)
     mac = _pw92_g(rs, 0.016886863940389627, 0.11125, 10.357, 3.6231, 0.88026, 0.49671)
-    z = _zeta(ra, rb)
-    fz, z4 = _fzeta(z), z ** 4
+    fz, z4 = _fzeta_ab(ra, rb), _zeta4(ra, rb)
     ec = e0 - mac * fz / _FPP0 * (1 - z4) + (e1 - e0) * fz * z4
-    phi = 0.5 * ((1 + z) ** (2.0 / 3) + (1 - z) ** (2.0 / 3))
+    phi = 0.5 * _pow_sum(ra, rb, 2.0 / 3)
     kf = (3 * np.pi ** 2 * r) ** (1.0 / 3)
     ks2 = 4 * kf / np.pi
     t2 = s / (4 * phi ** 2 * ks2 * r * r)
@@ -575,6 +589,7 @@ M062X_DSS = (6.902145e-01, 9.847204e-02, 2.214797e-01, -1.968264e-03, -6.775479e
 M062X_DAB = (1.166404e-01, -9.120847e-02, -6.726189e-02, 6.720580e-05, 8.448011e-04, 0.0)
 M062X_HYB = 0.54
 _CF6 = 0.6 * (6 * np.pi ** 2) ** (2.0 / 3)
+CHANNEL_FLOOR = 1e-24   # a spin channel is evaluated from here up, as in the kernels (XC_CHANNEL_FLOOR); tau_s only has to be > 0
 
 
 def _pw92_eps_spin(ra, rb):
@@ -583,8 +598,7 @@ def _pw92_eps_spin(ra, rb):
     e0 = _pw92_g(rs, 0.031090690869654895, 0.21370, 7.5957, 3.5876, 1.6382, 0.49294)
     e1 = _pw92_g(rs, 0.015545345434827448, 0.20548, 14.1189, 6.1977, 3.3662, 0.62517)
     mac = _pw92_g(rs, 0.016886863940389627, 0.11125, 10.357, 3.6231, 0.88026, 0.49671)
-    z = _zeta(ra, rb)
-    fz, z4 = _fzeta(z), z ** 4
+    fz, z4 = _fzeta_ab(ra, rb), _zeta4(ra, rb)
     return e0 - mac * fz / _FPP0 * (1 - z4) + (e1 - e0) * fz * z4
 
 
@@ -620,7 +634,7 @@ def _channel(ok, fn, *args):
 def _tpss_x_spin(ra, rb, saa, sbb, ta, tb):
     e = 0.0
     for r_, s_, t_ in ((ra, saa, ta), (rb, sbb, tb)):
-        ok = (np.real(r_) > 1e-12) & (np.real(t_) > 1e-14)
+        ok = (np.real(r_) > CHANNEL_FLOOR) & (np.real(t_) > 0.0)
         e = e + _channel(ok, lambda r, s, t: 0.5 * _tpss_x_unpol(2 * r, 4 * s, 2 * t), r_, s_, t_)
     return e
 
@@ -637,7 +651,7 @@ def _tpss_c_spin(ra, rb, saa, sab, sbb, ta, tb):
     epbe = _pbe_c_spin(ra, rb, saa, sab, sbb) / r
     ets = []
     for r_, s_ in ((ra, saa), (rb, sbb)):
-        ok = np.real(r_) > 1e-12
+        ok = np.real(r_) > CHANNEL_FLOOR
         one = _channel(ok, lambda rr, ss: _pbe_c_spin(rr, 0 * rr, ss, 0 * ss, 0 * ss) / rr, r_, s_)
         ets.append(np.where(ok & (np.real(one) >= np.real(epbe)), one, epbe))
     erev = epbe * (1 + C * z * z) - (1 + C) * z * z * (ra / r * ets[0] + rb / r * ets[1])
@@ -661,14 +675,14 @@ def _m062x_x_spin(ra, rb, saa, sbb, ta, tb):
         return 0.5 * _pbe_x(2 * r, 4 * s) * sum(a * w ** i for i, a in enumerate(M062X_A))
     e = 0.0
     for r_, s_, t_ in ((ra, saa, ta), (rb, sbb, tb)):
-        ok = (np.real(r_) > 1e-12) & (np.real(t_) > 1e-14)
+        ok = (np.real(r_) > CHANNEL_FLOOR) & (np.real(t_) > 0.0)
         e = e + _channel(ok, chan, r_, s_, t_)
     return e
 
 
 def _m062x_c_spin(ra, rb, saa, sbb, ta, tb):
-    oka = (np.real(ra) > 1e-12) & (np.real(ta) > 1e-14)
-    okb = (np.real(rb) > 1e-12) & (np.real(tb) > 1e-14)
+    oka = (np.real(ra) > CHANNEL_FLOOR) & (np.real(ta) > 0.0)
+    okb = (np.real(rb) > CHANNEL_FLOOR) & (np.real(tb) > 0.0)
     sa = [np.where(oka, a, 1.0 + 0 * a) for a in (ra, saa, ta)]
     sb = [np.where(okb, a, 1.0 + 0 * a) for a in (rb, sbb, tb)]
     out = 0.0
@@ -677,7 +691,7 @@ def _m062x_c_spin(ra, rb, saa, sbb, ta, tb):
         x2 = s / r ** (8.0 / 3)
         z = 2 * t / r ** (5.0 / 3) - _CF6
         e_ss = r * _pw92_eps_spin(r, 0 * r)
-        D = _clip_lo(1 - x2 / (4 * (z + _CF6)), 0.0)
+        D = _clip_lo(1 - s / (8 * r * t), 0.0)      # 1 - x2 / (4 (z + C_F)) = 1 - tau_W / tau, exactly 0 at tau = tau_W
         out = out + np.where(ok, e_ss * (_m06_g(x2, M062X_CSS, 0.06) + _m06_h(x2, z, M062X_DSS, 0.00515088)) * D, 0.0)
         xs.append(x2); zs.append(z); ess.append(e_ss)
     both = oka & okb

@@ -9,7 +9,11 @@ import pytest
 from scipy import integrate, special
 
 CAM_OMEGA = 0.33
-ITYH_SERIES_A = 4.0   # the kernel's switch from the closed form of F(a) to its asymptotic series
+ITYH_SERIES_A = 1.0   # the kernel's switch from the closed form of F(a) to its series in 1/a^2
+# F(a) = u (c0 - c1 u + c2 u^2 - ...), u = 1/a^2: the kernel's twelve terms
+ITYH_COEF = (1.0 / 36.0, 1.0 / 960.0, 1.0 / 26880.0, 1.0 / 829440.0, 1.0 / 28385280.0, 1.0 / 1073479680.0, 1.0 / 44590694400.0,
+             1.0 / 2021444812800.0, 1.0 / 99407521382400.0, 1.0 / 5273830608076800.0, 1.0 / 300357209869516800.0,
+             1.0 / 18282612774666240000.0)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -178,9 +182,17 @@ def ityh_closed(a):
                                   - 3 * a + 4 * a ** 3)
 
 
+def ityh_series_over_u(u):
+    """P(u) = F(a) a^2 at u = 1/a^2 (Horner, as the kernel)."""
+    p = ITYH_COEF[-1]
+    for c in ITYH_COEF[-2::-1]:
+        p = c - u * p
+    return p
+
+
 def ityh_series(a):
-    i2 = 1.0 / (a * a)
-    return i2 * (1.0 / 36 - i2 * (1.0 / 960 - i2 * (1.0 / 26880 - i2 / 829440)))
+    u = 1.0 / (a * a)
+    return u * ityh_series_over_u(u)
 
 
 def ityh(a):
@@ -198,8 +210,14 @@ def b88_sr_channel(r, s, omega):
     x = np.sqrt(s) / r43
     asinh = np.log(x + np.sqrt(x * x + 1))
     K = 1.5 * (6 / np.pi) ** (1.0 / 3) + 2 * beta * x * x / (1 + 6 * beta * x * asinh)
-    a = omega / (2 * np.sqrt(9 * np.pi / K) * r13)
-    return -0.5 * r43 * K * ityh(a)
+    # a^2 = q K.  On the series K F(a) = P(1/a^2) / q, formed without K as in the kernel: de/dsigma = K' (F + a F'/2), whose
+    # leading 1/(36 a^2) terms cancel, then comes out of P alone (also under the complex step)
+    q = omega * omega / (36 * np.pi * r13 * r13)
+    a2 = q * K
+    big = np.real(a2) >= ITYH_SERIES_A ** 2
+    series = ityh_series_over_u(1.0 / np.where(big, a2, 4.0)) / q
+    closed = K * ityh_closed(np.sqrt(np.where(big, 0.25, a2)))
+    return -0.5 * r43 * np.where(big, series, closed)
 
 
 def b88_channel(r, s):
