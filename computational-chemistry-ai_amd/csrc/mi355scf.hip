@@ -4944,6 +4944,169 @@ extern "C" int mi_grid_becke(mi_ctx *c, const double *d_coords, const int32_t *d
     return 0;
 }
 
+// ---- grid-weight response: out_C += sum_g e_g vol_g d[P_o / sum_B P_B](r_g; R) / dR_C, the point moving with its parent o ----
+struct BeckeGradArgs {
+    const double *coords; // [ng][3] of this chunk of points
+    const int32_t *atom_of;
+    const double *vol;
+    const double *e;        // unweighted energy density per point
+    const double *atom_xyz; // [natm][3]
+    const double *adj;      // [natm][natm]
+    int natm;
+    int64_t ng;
+    double *cell;           // [natm][ldc]: the cell functions P_i of every point of the chunk (each lane reads back its own column)
+    int64_t ldc;
+    double *part;           // [waves][natm][3]: one private row per wave, summed in a fixed order by becke_grad_reduce_kernel
+};
+
+// One lane per grid point.  With s_ij = s(nu_ij), s_ji = 1 - s_ij (mu, a and the polynomial are odd under i <-> j) and
+// q_i = e vol (delta_io - P_o/Z) P_i / Z, the pair {C, j} moves atom C by
+//     (q_C / s_Cj - q_j / s_jC) s'(nu_Cj) (1 - 2 a_Cj mu_Cj) dmu_Cj/dR_C,     dmu_Cj/dR_C = -(u_C + mu_Cj e_Cj) / R_Cj,
+// u_C the unit vector from atom C to the point (zero for a point on the nucleus) and e_Cj the one from j to C.  The point's
+// own derivative is minus the sum of the two atom derivatives of every pair, so the parent atom gets -sum_C (all of the above).
+// Pass 1 is the pair loop of becke_weights_kernel (same arithmetic, so the same P_i to the bit) and leaves P_i in `cell`;
+// pass 2 loops over the target atom C with three register accumulators and one wave reduction per C; pass 3 books the
+// accumulated point derivative to the parent atoms present in the wave.
+// q_i / s_ij stands for q_i's product without the factor s_ij and is formed only where s_ij > 0 (then s_ij >= 2^-54 and the
+// quotient is exact to rounding).  1 - f3 rounds to exactly zero within 7e-3 of nu = 1; there P_i is exactly zero too, and the
+// pair contributes exactly zero, never 0/0.  What that drops is s' times the other factors, below 6e-14 per unit of e vol --
+// the size of the rounding of 1 - f3 itself, which the weights carry as well.
+__global__ __launch_bounds__(256) void becke_grad_kernel(BeckeGradArgs A)
+{
+    extern __shared__ double sh[]; // atom coordinates
+    for (int i = threadIdx.x; i < A.natm * 3; i += blockDim.x) sh[i] = A.atom_xyz[i];
+    __syncthreads();
+    const int natm = A.natm;
+    const int lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = g < A.ng;
+    const int64_t gl = live ? g : A.ng - 1;   // lanes past the end stay in the wave reductions with a zero coefficient
+    const double x = A.coords[3 * gl], y = A.coords[3 * gl + 1], z = A.coords[3 * gl + 2];
+    const int own = A.atom_of[gl];
+    const double ev = live ? A.e[gl] * A.vol[gl] : 0.0;
+    double *cell = A.cell + gl;
+    double psum = 0.0, pown = 0.0;
+    for (int i = 0; i < natm; i++) {
+        double dxi = x - sh[3 * i], dyi = y - sh[3 * i + 1], dzi = z - sh[3 * i + 2];
+        double ri = sqrt(dxi * dxi + dyi * dyi + dzi * dzi);
+        double p = 1.0;
+        for (int j = 0; j < natm; j++) {
+            if (j == i) continue;
+            double dxj = x - sh[3 * j], dyj = y - sh[3 * j + 1], dzj = z - sh[3 * j + 2];
+            double rj = sqrt(dxj * dxj + dyj * dyj + dzj * dzj);
+            double ax = sh[3 * i] - sh[3 * j], ay = sh[3 * i + 1] - sh[3 * j + 1], az = sh[3 * i + 2] - sh[3 * j + 2];
+            double mu = (ri - rj) * rsqrt(ax * ax + ay * ay + az * az);
+            mu = mu + A.adj[i * natm + j] * (1.0 - mu * mu);
+            mu = (3.0 - mu * mu) * mu * 0.5;
+            mu = (3.0 - mu * mu) * mu * 0.5;
+            mu = (3.0 - mu * mu) * mu * 0.5;
+            p *= 0.5 * (1.0 - mu);
+        }
+        psum += p;
+        if (i == own) pown = p;
+        if (live) cell[(int64_t)i * A.ldc] = p;
+    }
+    const double zinv = 1.0 / psum;
+    const double qo = ev * zinv, qz = ev * pown * zinv * zinv;   // q_i = (delta_io qo - qz) P_i
+    double *row = A.part + ((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * (size_t)(natm * 3);
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int C = 0; C < natm; C++) {
+        const double cx = sh[3 * C], cy = sh[3 * C + 1], cz = sh[3 * C + 2];
+        const double dxc = x - cx, dyc = y - cy, dzc = z - cz;
+        const double rc = sqrt(dxc * dxc + dyc * dyc + dzc * dzc);
+        const double rci = rc > 0.0 ? 1.0 / rc : 0.0;
+        const double ucx = dxc * rci, ucy = dyc * rci, ucz = dzc * rci;
+        const double qC = ((C == own ? qo : 0.0) - qz) * (live ? cell[(int64_t)C * A.ldc] : 0.0);
+        double gx = 0.0, gy = 0.0, gz = 0.0;
+        for (int j = 0; j < natm; j++) {
+            if (j == C) continue;
+            const double dxj = x - sh[3 * j], dyj = y - sh[3 * j + 1], dzj = z - sh[3 * j + 2];
+            const double rj = sqrt(dxj * dxj + dyj * dyj + dzj * dzj);
+            const double ex = cx - sh[3 * j], ey = cy - sh[3 * j + 1], ez = cz - sh[3 * j + 2];
+            const double rinv = rsqrt(ex * ex + ey * ey + ez * ez);
+            const double mu = (rc - rj) * rinv;
+            const double a = A.adj[C * natm + j];
+            const double nu = mu + a * (1.0 - mu * mu);
+            const double f1 = (3.0 - nu * nu) * nu * 0.5;
+            const double f2 = (3.0 - f1 * f1) * f1 * 0.5;
+            const double f3 = (3.0 - f2 * f2) * f2 * 0.5;
+            const double sp = -1.6875 * (1.0 - f2 * f2) * (1.0 - f1 * f1) * (1.0 - nu * nu);   // s'(nu) = -1/2 (3/2)^3 prod (1 - f_k^2)
+            const double sCj = 0.5 * (1.0 - f3), sjC = 0.5 * (1.0 + f3);
+            const double qj = ((j == own ? qo : 0.0) - qz) * (live ? cell[(int64_t)j * A.ldc] : 0.0);
+            const double t = (sCj > 0.0 ? qC / sCj : 0.0) - (sjC > 0.0 ? qj / sjC : 0.0);
+            const double k = -t * sp * (1.0 - 2.0 * a * mu) * rinv;
+            const double me = mu * rinv;
+            gx += k * (ucx + me * ex);
+            gy += k * (ucy + me * ey);
+            gz += k * (ucz + me * ez);
+        }
+        sx += gx; sy += gy; sz += gz;
+        for (int o = 32; o > 0; o >>= 1) { gx += __shfl_xor(gx, o); gy += __shfl_xor(gy, o); gz += __shfl_xor(gz, o); }
+        if (lane == 0) { row[3 * C] = gx; row[3 * C + 1] = gy; row[3 * C + 2] = gz; }
+    }
+    unsigned long long pending = __ballot(live);
+    while (pending) {   // wave-uniform: one round per parent atom present in the wave
+        const int oc = __shfl(own, __ffsll((long long)pending) - 1);
+        const bool mine = live && own == oc;
+        double gx = mine ? sx : 0.0, gy = mine ? sy : 0.0, gz = mine ? sz : 0.0;
+        for (int o = 32; o > 0; o >>= 1) { gx += __shfl_xor(gx, o); gy += __shfl_xor(gy, o); gz += __shfl_xor(gz, o); }
+        if (lane == 0 && oc >= 0 && oc < natm) { row[3 * oc] -= gx; row[3 * oc + 1] -= gy; row[3 * oc + 2] -= gz; }   // the lane that wrote the row
+        pending &= ~__ballot(mine);
+    }
+}
+
+// out[c] += sum_w part[w][c]: one workgroup per component, a strided partial sum per thread and an LDS tree -- the order
+// depends on the number of waves only, so the result is reproducible to the bit.
+__global__ __launch_bounds__(256) void becke_grad_reduce_kernel(const double *part, int64_t nw, int n3, double *out)
+{
+    __shared__ double red[256];
+    const int c = blockIdx.x;
+    double s = 0.0;
+    for (int64_t w = threadIdx.x; w < nw; w += 256) s += part[(size_t)w * n3 + c];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[c] += red[0];
+}
+
+#define BECKE_GRAD_CELL_DOUBLES ((int64_t)1 << 25)   // cap of the cell-function workspace (256 MB): larger grids go in chunks of points
+
+extern "C" int mi_grid_becke_grad(mi_ctx *c, const double *d_coords, const int32_t *d_atom_of, const double *d_vol, const double *d_e,
+                                  int64_t ng, const double *d_adjust, double *d_out, void *stream)
+{
+    if (!c || !d_coords || !d_atom_of || !d_vol || !d_e || !d_adjust || !d_out) return fail("mi_grid_becke_grad: null argument");
+    if (c->natm > MAXATM_LDS) return fail("mi_grid_becke_grad: too many atoms");
+    if (ng < 0) return fail("mi_grid_becke_grad: negative number of grid points");
+    if (ng == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int natm = c->natm;
+    std::vector<double> xyz(natm * 3);
+    for (int i = 0; i < natm; i++)
+        for (int d = 0; d < 3; d++) xyz[3 * i + d] = c->env[c->atm[i * ATM_SLOTS + 1] + d];
+    DevBuf<double> d_xyz, d_cell, d_part;
+    HIPCHK(d_xyz.alloc(xyz.size()));
+    HIPCHK(hipMemcpy(d_xyz, xyz.data(), sizeof(double) * xyz.size(), hipMemcpyHostToDevice));
+    const int64_t chunk = std::min<int64_t>((ng + 255) / 256 * 256, std::max<int64_t>(256, BECKE_GRAD_CELL_DOUBLES / natm / 256 * 256));
+    const int64_t waves = chunk / 64;
+    HIPCHK(d_cell.alloc((size_t)natm * chunk));
+    HIPCHK(d_part.alloc((size_t)waves * natm * 3));
+    for (int64_t p0 = 0; p0 < ng; p0 += chunk) {
+        const int64_t n = std::min(chunk, ng - p0);
+        const int64_t nblk = (n + 255) / 256;
+        BeckeGradArgs A{d_coords + 3 * p0, d_atom_of + p0, d_vol + p0, d_e + p0, d_xyz, d_adjust, natm, n, d_cell, chunk, d_part};
+        hipLaunchKernelGGL(becke_grad_kernel, dim3((unsigned)nblk), dim3(256), sizeof(double) * 3 * natm, st, A);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(becke_grad_reduce_kernel, dim3(natm * 3), dim3(256), 0, st, d_part.get(), nblk * 4, natm * 3, d_out);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(st));   // the workspaces are freed on return
+    return 0;
+}
+
 struct AoArgs {
     const int32_t *atm, *bas;
     const double *env;

@@ -418,6 +418,9 @@ class RKS(KSMixin, RHF):
             self.grids.generation = next(_grid_generation)
             if self.grids.atom_of is not None:
                 self.grids.atom_of = self.grids.atom_of[keep.cpu().numpy()]
+                # the weight response of the gradient is that of the kept points: the quadrature the SCF energy is made of
+                self.grids.atom_of_dev = self.grids.atom_of_dev[keep].contiguous()
+                self.grids.vol = self.grids.vol[keep].contiguous()
 
     def _fock_energy(self, dm, part):
         """Kohn-Sham Fock matrix with ONE collective per build: this rank's partial J, K (tile-run

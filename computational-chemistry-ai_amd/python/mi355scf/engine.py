@@ -86,6 +86,7 @@ def lib():
         L.mi_diis_combine_dev.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp]
         i64 = ctypes.c_int64
         L.mi_grid_becke.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
+        L.mi_grid_becke_grad.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp]
         L.mi_eval_ao.argtypes = [vp, vp, i64, ctypes.c_int, vp, vp]
         L.mi_xc_rho.argtypes = [vp, vp, vp, i64, ctypes.c_int, vp, vp]
         L.mi_xc_eval.argtypes = [ip, dp, ctypes.c_int, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp, vp]
@@ -479,6 +480,19 @@ class Engine:
         _check(lib().mi_grid_becke(self._h, coords.data_ptr(), atom_of.data_ptr(), vol.data_ptr(), vol.numel(),
                                    adjust.data_ptr(), w.data_ptr(), self._stream()))
         return w
+
+    def becke_weights_grad(self, coords, atom_of, vol, adjust, e, out=None):
+        """out[natm, 3] += sum_g e_g vol_g d(P_o / sum_B P_B)/dR_C (mi_grid_becke_grad): the weight derivative of the
+        quadrature sum_g w_g e_g with the points riding on their parent atoms; `e` is the unweighted energy density."""
+        ng = vol.numel()
+        if out is None:
+            out = torch.zeros(self.mol.natm, 3, dtype=torch.float64, device=self.device)
+        assert coords.is_contiguous() and coords.shape == (ng, 3) and atom_of.dtype == torch.int32 and atom_of.numel() == ng
+        assert vol.is_contiguous() and e.is_contiguous() and e.numel() == ng and adjust.is_contiguous()
+        assert out.is_contiguous() and out.shape == (self.mol.natm, 3) and out.dtype == torch.float64
+        _check(lib().mi_grid_becke_grad(self._h, coords.data_ptr(), atom_of.data_ptr(), vol.data_ptr(), e.data_ptr(), ng,
+                                        adjust.data_ptr(), out.data_ptr(), self._stream()))
+        return out
 
     def eval_ao(self, coords, deriv=1, out=None):
         ng = coords.shape[0]

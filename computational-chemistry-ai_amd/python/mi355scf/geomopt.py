@@ -222,6 +222,11 @@ def optimize(mf, maxsteps=100, callback=None, coordsys="internal", **kw):
     # 1e-10 0.87 s, 1.3e-6 (0.3 % of geomeTRIC's 4.5e-4 max-gradient criterion); 1e-9 0.72 s, 1.5e-5 (too close to it).
     # `optimize(mf, grad_dtol=...)` overrides; single gradients (`mf.nuc_grad_method().kernel()`) keep 1e-13.
     gs.grad_dtol = kw.pop("grad_dtol", 1e-10)
+    # `optimize(mf, grid_response=True)`: forces with the grid-weight response of the XC quadrature (`grad.Gradients.grid_response`)
+    if "grid_response" in kw:
+        if not hasattr(gs.g, "grid_response"):
+            raise NotImplementedError(f"grid_response is not available for {type(gs.g).__module__}.{type(gs.g).__name__}")
+        gs.g.grid_response = bool(kw.pop("grid_response"))
     mol = mf.mol
     log = lambda msg: mf._log(3, msg)
     log("Step    Energy (Ha)        dE         RMS grad    max grad    RMS disp(A)  max disp(A)")

@@ -33,10 +33,11 @@ def grad_nuc(mol):
 _D2 = {(0, 0): 4, (0, 1): 5, (0, 2): 6, (1, 1): 7, (1, 2): 8, (2, 2): 9}   # component of eval_ao(deriv=2) holding d_j d_k phi, j <= k
 
 
-def _add_xc_force(fmu, ao, dm, C, wv, gga):
+def _add_xc_force(fmu, ao, dm, C, wv, gga, pt=None):
     """fmu[mu] += -2 D_mu,nu int [v_rho dphi_mu phi_nu + 2 v_sigma grad rho . grad(dphi_mu phi_nu)] (+ the tau term) over one
     grid block, for one density `dm` (closed shell, or one spin) with C = dm.ao0 and the weighted derivatives `wv` of the
-    functional that belong to it."""
+    functional that belong to it.  pt [3, points of the block] (grid response): += the same integrand summed over the AOs at
+    each point, i.e. -w grad_r e of this density's part."""
     T1 = 2.0 * wv[0] * C
     if gga:
         Ck = [dm @ ao[1 + j] for j in range(3)]
@@ -44,32 +45,58 @@ def _add_xc_force(fmu, ao, dm, C, wv, gga):
             T1 += wv[1 + j] * Ck[j]
         for k in range(3):
             t2 = sum(wv[1 + j] * ao[_D2[(min(j, k), max(j, k))]] for j in range(3))
-            fmu[:, k] += -2.0 * ((ao[1 + k] * T1).sum(dim=1) + (t2 * C).sum(dim=1))
+            p1, p2 = ao[1 + k] * T1, t2 * C
+            fmu[:, k] += -2.0 * (p1.sum(dim=1) + p2.sum(dim=1))
+            if pt is not None:
+                pt[k] += -2.0 * (p1.sum(dim=0) + p2.sum(dim=0))
             if gga == 2:   # d tau / d A_x = - sum_k (d_x d_k phi_mu) (D d_k phi)_mu ; wv[4] = w/4 de/dtau
-                fmu[:, k] += -4.0 * sum((ao[_D2[(min(j, k), max(j, k))]] * (wv[4] * Ck[j])).sum(dim=1) for j in range(3))
+                p3 = [ao[_D2[(min(j, k), max(j, k))]] * (wv[4] * Ck[j]) for j in range(3)]
+                fmu[:, k] += -4.0 * sum(p.sum(dim=1) for p in p3)
+                if pt is not None:
+                    pt[k] += -4.0 * sum(p.sum(dim=0) for p in p3)
     else:
         for k in range(3):
-            fmu[:, k] += -2.0 * (ao[1 + k] * T1).sum(dim=1)
+            p1 = ao[1 + k] * T1
+            fmu[:, k] += -2.0 * p1.sum(dim=1)
+            if pt is not None:
+                pt[k] += -2.0 * p1.sum(dim=0)
 
 
-def xc_force(mf, body):
+def xc_force(mf, body, grid_response=False):
     """XC gradient per atom: `body(fmu, ao, w)` adds one grid block's forces to fmu [nao, 3] (`_add_xc_force`), `ao` the AO values
-    with the derivatives the force needs and `w` the block's weights, over this rank's share of the SCF grid."""
+    with the derivatives the force needs and `w` the block's weights, over this rank's share of the SCF grid.
+
+    grid_response: the quadrature E_xc = sum_g w_g(R) e(r_g(R)) is differentiated as well.  `body(fmu, ao, w, pt)` then also adds
+    the per-point AO sums of its integrand to pt [3, points] and returns the block's unweighted energy density e.  Because e at
+    a point depends on r - R_B only, -pt is w grad_r e: booked to the point's parent atom it is the moving-point term, and
+    `engine.becke_weights_grad` adds sum_g e_g dw_g/dR.  Both are O(1) Ha/Bohr and cancel to three or four digits, so both take
+    the SAME e (the evaluator's own density floor) and are summed in FP64.  They sit behind fmu in one buffer: one all-reduce."""
     eng = mf.engine
     gga = mf._xc_functional()[2]
-    coords, weights = mf.grids.coords, mf.grids.weights
+    grids = mf.grids
+    coords, weights = grids.coords, grids.weights
     lo, hi = mf._grid_range(coords.shape[0])
-    fmu = torch.zeros(eng.nao, 3, dtype=torch.float64, device=eng.device)
+    nao, natm = eng.nao, mf.mol.natm
+    fmu = torch.zeros(nao + (natm if grid_response else 0), 3, dtype=torch.float64, device=eng.device)
     B = max(4096, mf.grid_block // 4)
     for p0 in range(lo, hi, B):
         p1 = min(p0 + B, hi)
-        body(fmu, eng.eval_ao(coords[p0:p1], deriv=2 if gga else 1), weights[p0:p1])
+        ao = eng.eval_ao(coords[p0:p1], deriv=2 if gga else 1)
+        if not grid_response:
+            body(fmu, ao, weights[p0:p1])
+            continue
+        pt = torch.zeros(3, p1 - p0, dtype=torch.float64, device=eng.device)
+        e = body(fmu[:nao], ao, weights[p0:p1], pt)
+        resp = fmu[nao:]
+        resp.index_add_(0, grids.atom_of_dev[p0:p1].long(), pt.T, alpha=-1.0)
+        eng.becke_weights_grad(coords[p0:p1], grids.atom_of_dev[p0:p1], grids.vol[p0:p1], grids.adjust, e.contiguous(), out=resp)
     if mf._nranks > 1:
         from . import parallel
         parallel.all_reduce_sum(fmu, mf._pg)
     f = fmu.cpu().numpy()
     sl = mf.mol.aoslice_by_atom()
-    return np.array([f[sl[ia, 2]:sl[ia, 3]].sum(axis=0) for ia in range(mf.mol.natm)])
+    de = np.array([f[sl[ia, 2]:sl[ia, 3]].sum(axis=0) for ia in range(natm)])
+    return de + f[nao:] if grid_response else de
 
 
 def assemble(eng, mol, D, W, two_electron, xc=None, timing=None, ranks=None):
@@ -118,6 +145,9 @@ def log_gradient(log, mol, de, table, timing=None, header="gradient", title="---
 
 class Gradients:
     """Analytic RHF/RKS gradient on the MI355X engine."""
+    # True (PySCF's switch): the XC term is the derivative of the quadrature the SCF energy is made of -- the points move with
+    # their atoms and the Becke weights are differentiated (`xc_force`); the scanner carries it with this object
+    grid_response = False
 
     def __init__(self, mf):
         from .dft import require_no_rsh
@@ -138,13 +168,14 @@ class Gradients:
         xcf = mf._xc_functional()
         gga = xcf[2]
 
-        def body(fmu, ao, w):
+        def body(fmu, ao, w, pt=None):
             Cs = [dm @ ao[0] for dm in dms]
             dens = [mf._block_density(ao, dm, None, gga, C) for dm, C in zip(dms, Cs)]
-            _e, wvs = mf._block_functional(xcf, [d[0] for d in dens], [d[1] for d in dens], w)
+            e, wvs = mf._block_functional(xcf, [d[0] for d in dens], [d[1] for d in dens], w)
             for dm, C, wv in zip(dms, Cs, wvs):
-                _add_xc_force(fmu, ao, dm, C, wv, gga)
-        return xc_force(mf, body)
+                _add_xc_force(fmu, ao, dm, C, wv, gga, pt)
+            return e
+        return xc_force(mf, body, bool(self.grid_response))
 
     def _densities(self):
         """What `kernel` contracts, from the converged SCF: (densities of the XC term, total density D, spin density M or None,

@@ -19,6 +19,10 @@ import numpy as np
 
 class Hessian:
     step = 5.0e-3   # Bohr
+    # True: the differenced Kohn-Sham gradients carry the grid-weight response (`grad.Gradients.grid_response`), i.e. they are the
+    # derivative of the energy the displaced SCFs report -- the Hessian is then symmetric and translationally invariant to the
+    # accuracy of the differences instead of to the 1e-4 Ha/Bohr inconsistency of the gradient
+    grid_response = False
 
     def __init__(self, mf):
         from .dft import require_no_rsh
@@ -95,6 +99,7 @@ class Hessian:
             work.shard(0, 1)
         work.kernel(dm0=dm0)
         scan = work.nuc_grad_method().as_scanner()
+        scan.g.grid_response = bool(self.grid_response)   # every displaced gradient of this rank's share, replica mode included
         for ia in range(n):
             for x in range(3):
                 if (3 * ia + x) % nranks != rank:
@@ -120,6 +125,7 @@ class Hessian:
             buf = buf.cpu().numpy()
             H, dmu = buf[:H.size].reshape(H.shape), buf[H.size:].reshape(dmu.shape)
         Hm = H.reshape(3 * n, 3 * n)
+        self.hess_raw = Hm.copy()    # row ix = d(gradient)/dR_ix as differenced: its asymmetry measures the gradients' consistency
         Hm = 0.5 * (Hm + Hm.T)
         self.de = Hm.reshape(n, 3, n, 3).transpose(0, 2, 1, 3).copy()
         self.dipole_deriv = dmu

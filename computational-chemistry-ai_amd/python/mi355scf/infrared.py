@@ -12,6 +12,8 @@ KM_PER_MOL = 974.8801   # (e^2/amu) -> km/mol  [= 42.2561 km/mol per (D/A)^2/amu
 
 
 class Infrared:
+    grid_response = False   # forwarded to the Hessian's displaced gradients (`hessian.Hessian.grid_response`)
+
     def __init__(self, mf):
         from .dft import require_no_rsh
         require_no_rsh(mf, "infrared spectrum")
@@ -25,6 +27,7 @@ class Infrared:
 
     def kernel(self):
         h = Hessian(self.base)
+        h.grid_response = self.grid_response
         hess = h.kernel()
         if self.hessian is None:
             self.hessian = hess

@@ -285,6 +285,14 @@ int mi_commutator_norm(mi_ctx *ctx, const double *d_M, double *d_E, double *d_pa
 int mi_grid_becke(mi_ctx *ctx, const double *d_coords, const int32_t *d_atom_of, const double *d_vol,
                   int64_t ng, const double *d_adjust, double *d_weights, void *stream);
 
+/* Grid-weight response of a quadrature sum_g w_g e_g: d_out[natm][3] += sum_g d_e[g] d_vol[g] d(P_o / sum_B P_B)(r_g; R)/dR_C,
+ * the total derivative of the Becke partition of mi_grid_becke (same inputs) with every point moving rigidly with its parent
+ * atom; d_e[ng] is the UNWEIGHTED energy density per point.  FP64, O(natm^2) per point, reproducible to the bit.  The three
+ * derivatives of every pair sum to zero, so sum_C d_out[C] keeps its value.  A point on a nucleus takes a zero unit vector.
+ * ng == 0: d_out is left untouched; ng < 0 is an error.  PySCF: grad.rks.get_vxc_full / grids_response_cc [MEM]. */
+int mi_grid_becke_grad(mi_ctx *ctx, const double *d_coords, const int32_t *d_atom_of, const double *d_vol, const double *d_e,
+                       int64_t ng, const double *d_adjust, double *d_out, void *stream);
+
 /* AO values (deriv=0), +gradient (deriv=1), +second derivatives xx,xy,xz,yy,yz,zz (deriv=2, for the XC
  * nuclear gradient) on grid points: d_ao[(1|4|10)][nao][ng].
  * Replaces libdft GTOval_sph_deriv1 / gpu4pyscf GDFTeval_gto [MEM] (numint.eval_ao). */
