@@ -360,6 +360,9 @@ struct mi_ctx {
     int c2s_off[LMAX + 2];
     RysDev rys;                          // device pointers inside
     double *d_rys_cheb = nullptr, *d_herm_r = nullptr, *d_herm_w = nullptr;
+    // shell pairs grouped by angular class for the one-electron and PCM launches (shell_pair_classes): [0] i >= j with the
+    // higher l first, [1] all ordered (i, j); class k = la * 4 + lb is rows start[k] .. start[k + 1] of pairs [n][2]
+    struct PairClasses { std::vector<int> pairs; int start[17] = {}; int *d_pairs = nullptr; } pair_classes[2];
     // pairs
     PairClass pc[NPC];
     double *d_prim = nullptr;            // all primitive-pair records
@@ -493,6 +496,32 @@ struct HostStash {
 };
 static HostStash g_stash[16];
 
+// Shell pairs grouped by angular class, built and uploaded once per context: ordered = 0: i >= j, stored with the higher l
+// first (S/T/V/dipole, B), 1: all (i, j) (gradients, derivative on i).  A context with shells beyond f (auxiliary basis) keeps
+// empty lists: every reader refuses it first (check_orbital_lmax).
+static int shell_pair_classes(mi_ctx *c, int ordered)
+{
+    mi_ctx::PairClasses &pc = c->pair_classes[ordered];
+    std::vector<std::vector<int>> by(16);
+    bool orbital = true;
+    for (const ShellH &s : c->shells) orbital = orbital && s.l <= LMAX_1E;
+    for (int i = 0; orbital && i < c->nbas; i++)
+        for (int j = 0; j < (ordered ? c->nbas : i + 1); j++) {
+            int a = i, b = j;
+            if (!ordered && c->shells[a].l < c->shells[b].l) std::swap(a, b);
+            by[c->shells[a].l * 4 + c->shells[b].l].push_back(a);
+            by[c->shells[a].l * 4 + c->shells[b].l].push_back(b);
+        }
+    for (int k = 0; k < 16; k++) {
+        pc.start[k] = (int)pc.pairs.size() / 2;
+        pc.pairs.insert(pc.pairs.end(), by[k].begin(), by[k].end());
+    }
+    pc.start[16] = (int)pc.pairs.size() / 2;
+    HIPCHK(dev_malloc(&pc.d_pairs, sizeof(int) * std::max<size_t>(pc.pairs.size(), 2)));
+    HIPCHK(hipMemcpy(pc.d_pairs, pc.pairs.data(), sizeof(int) * pc.pairs.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
 extern "C" int mi_ctx_create(const int32_t *atm, int natm, const int32_t *bas, int nbas, const double *env,
                              int nenv, int device_id, mi_ctx **out)
 {
@@ -555,6 +584,7 @@ extern "C" int mi_ctx_create(const int32_t *atm, int natm, const int32_t *bas, i
     c->c2s_off[LMAX + 1] = (int)all.size();
     HIPCHK(dev_malloc(&c->d_c2s, sizeof(double) * all.size()));
     HIPCHK(hipMemcpy(c->d_c2s, all.data(), sizeof(double) * all.size(), hipMemcpyHostToDevice));
+    if (shell_pair_classes(c, 0) || shell_pair_classes(c, 1)) return -1;
     // Rys tables
     HIPCHK(dev_malloc(&c->d_rys_cheb, sizeof(double) * RYS_CHEB_SIZE));
     HIPCHK(hipMemcpy(c->d_rys_cheb, RYS_CHEB_H, sizeof(double) * RYS_CHEB_SIZE, hipMemcpyHostToDevice));
@@ -765,6 +795,7 @@ extern "C" void mi_ctx_destroy(mi_ctx *c)
     hipSetDevice(c->device);
     free_eri(c);
     void *ptrs[] = {c->d_env, c->d_bas, c->d_atm, c->d_shell_ao, c->d_c2s, c->d_rys_cheb, c->d_herm_r, c->d_herm_w,
+                    c->pair_classes[0].d_pairs, c->pair_classes[1].d_pairs,
                     c->d_Dpad, c->d_Jacc, c->d_Kacc, c->d_red, c->d_shell_xyz, c->d_xt_scratch, c->d_perm, c->d_iperm,
                     c->d_mDpad, c->d_mJacc, c->d_mKacc};
     for (void *p : ptrs) if (p) dev_free(p);
@@ -837,10 +868,14 @@ extern "C" int mi_set_option(mi_ctx *c, const char *key, double value)
 }
 
 // =================================================================================================
-// One-electron integrals: one thread per shell pair (i >= j)
+// One-electron integrals.
+//
+// The pieces below are the one body of the four kernel families that evaluate <m|1/r_C|n> or its attenuated twin
+// <m|erf(zeta r_C)/r_C|n>: int1e_kernel (S, T, V, dipole), int1e_grad_kernel (section "Analytic nuclear gradient, one-electron
+// part"), pcm_int_kernel and pcm_grad_kernel (section "C-PCM").  All are templates on the angular class <LA, LB>: every table is a
+// fixed-size array indexed inside fully unrolled loops (registers, no per-thread blocks sized for the largest class), and a
+// launch holds the shell pairs of ONE class from the context's class-sorted lists (mi_ctx::pair_classes).
 // =================================================================================================
-#define NC1 10 /* ncart(LMAX_1E) */
-
 __device__ inline void cart_pow(int l, int idx, int &x, int &y, int &z)
 {
     int n = 0;
@@ -852,7 +887,15 @@ __device__ inline void cart_pow(int l, int idx, int &x, int &y, int &z)
     x = y = z = 0;
 }
 
-struct Int1eArgs {
+__device__ inline int cart_exp(int l, int idx, int d)   // exponent of direction d of cartesian component idx of shell l
+{
+    int x = 0, y = 0, z = 0;
+    cart_pow(l, idx, x, y, z);
+    return d == 0 ? x : (d == 1 ? y : z);
+}
+
+// The basis as the one-electron, PCM and AO-value kernels read it: base of their argument structs.
+struct BasisDev {
     const int32_t *atm, *bas;
     const double *env;
     const int *shell_ao;
@@ -860,132 +903,285 @@ struct Int1eArgs {
     int c2s_off[LMAX + 2];
     RysDev rys;
     int natm, nbas, nao;
+};
+
+static BasisDev basis_dev(const mi_ctx *c)
+{
+    BasisDev B;
+    B.atm = c->d_atm; B.bas = c->d_bas; B.env = c->d_env; B.shell_ao = c->d_shell_ao; B.c2s = c->d_c2s;
+    for (int i = 0; i <= LMAX + 1; i++) B.c2s_off[i] = c->c2s_off[i];
+    B.rys = c->rys; B.natm = c->natm; B.nbas = c->nbas; B.nao = c->nao;
+    return B;
+}
+
+// One primitive pair of the shells with `bas` rows bi, bj on centres ra, rb (AB = ra - rb).
+struct PrimPair {
+    double a, b, cc;   // exponents, product of the contraction coefficients (times whatever the caller folds in)
+    double p, h, ex;   // a + b, 1 / 2p, exp(-a b / p |AB|^2)
+    double PA[3], PB[3], P[3];
+};
+
+__device__ __forceinline__ PrimPair prim_pair(const double *env, const int32_t *bi, const int32_t *bj, int ip, int jp, const double *ra,
+                                              const double *rb, const double (&AB)[3])
+{
+    PrimPair q;
+    q.a = env[bi[5] + ip]; q.b = env[bj[5] + jp];
+    q.cc = env[bi[6] + ip] * env[bj[6] + jp];
+    q.p = q.a + q.b; q.h = 0.5 / q.p;
+    q.ex = exp(-q.a * q.b / q.p * (AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2]));
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        q.P[d] = (q.a * ra[d] + q.b * rb[d]) / q.p;
+        q.PA[d] = q.P[d] - ra[d];
+        q.PB[d] = q.P[d] - rb[d];
+    }
+    return q;
+}
+
+// 1-D attraction table gt[d][i][j], i + j < NI, of Rys root r of nr for the operator centred at C: vertical recurrence on the
+// first shell, then the horizontal transfer with AB.  Returns prefactor x weight of the root.  ATTENUATED: erf(sqrt(eta) r)/r
+// -- with theta = eta / (p + eta) the Boys argument and the root are scaled by theta and the prefactor by sqrt(theta);
+// otherwise the plain nuclear formula (eta unused).
+template <int LB, int NI, bool ATTENUATED>
+__device__ __forceinline__ double attraction_table(double (&gt)[3][NI][LB + 1], const PrimPair &q, const double *C, double eta,
+                                                   const double (&AB)[3], int nr, int r, const RysDev &rys)
+{
+    const double PC[3] = {q.P[0] - C[0], q.P[1] - C[1], q.P[2] - C[2]};
+    const double r2 = PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2];
+    double x, pv, u;
+    if constexpr (ATTENUATED) {
+        const double theta = eta / (q.p + eta);
+        x = q.p * theta * r2;
+        pv = q.cc * q.ex * 2.0 * M_PI / q.p * sqrt(theta);
+        u = rys_eval(rys, nr, r, x) * theta;
+    } else {
+        x = q.p * r2;
+        pv = q.cc * q.ex * 2.0 * M_PI / q.p;
+        u = rys_eval(rys, nr, r, x);
+    }
+    const double w = rys_eval(rys, nr, nr + r, x);
+    const double b10 = (1.0 - u) * q.h;
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        const double c00 = q.PA[d] - u * PC[d];
+        gt[d][0][0] = 1.0;
+#pragma unroll
+        for (int i = 0; i + 1 < NI; i++) gt[d][i + 1][0] = c00 * gt[d][i][0] + (i > 0 ? i * b10 * gt[d][i > 0 ? i - 1 : 0][0] : 0.0);
+#pragma unroll
+        for (int j = 0; j < LB; j++)
+#pragma unroll
+            for (int i = 0; i < NI - j - 1; i++) gt[d][i][j + 1] = gt[d][i + 1][j] + AB[d] * gt[d][i][j];
+    }
+    return pv * w;
+}
+
+// acc[ia][ib] += f g_x g_y g_z: the cartesian block of one root
+template <int LA, int LB, int NI>
+__device__ __forceinline__ void attraction_accumulate(double *acc, const double (&gt)[3][NI][LB + 1], double f)
+{
+    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2;
+#pragma unroll
+    for (int ia = 0; ia < NCA; ia++)
+#pragma unroll
+        for (int ib = 0; ib < NCB; ib++)
+            acc[ia * NCB + ib] += f * gt[0][cart_exp(LA, ia, 0)][cart_exp(LB, ib, 0)] * gt[1][cart_exp(LA, ia, 1)][cart_exp(LB, ib, 1)] *
+                                  gt[2][cart_exp(LA, ia, 2)][cart_exp(LB, ib, 2)];
+}
+
+// gc[x] += f sum_{ia,ib} Dc[ia][ib] d/dA_x of the block of one root: d/dA_x acts on the 1-D factor as 2a g[i+1][j] - i g[i-1][j]
+template <int LA, int LB, int NI>
+__device__ __forceinline__ void attraction_bra_gradient(double (&gc)[3], const double (&gt)[3][NI][LB + 1], double f, double a, const double *Dc)
+{
+    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2;
+#pragma unroll
+    for (int ia = 0; ia < NCA; ia++)
+#pragma unroll
+        for (int ib = 0; ib < NCB; ib++) {
+            double v0[3], vd[3];
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                const int i = cart_exp(LA, ia, d), j = cart_exp(LB, ib, d);
+                v0[d] = gt[d][i][j];
+                vd[d] = 2.0 * a * gt[d][i + 1][j] - (i > 0 ? i * gt[d][i > 0 ? i - 1 : 0][j] : 0.0);
+            }
+            const double dc = f * Dc[ia * NCB + ib];
+            gc[0] += dc * vd[0] * v0[1] * v0[2];
+            gc[1] += dc * v0[0] * vd[1] * v0[2];
+            gc[2] += dc * v0[0] * v0[1] * vd[2];
+        }
+}
+
+// Obara-Saika 1-D overlaps s[d][i][j], i <= LA + 1 (dipole, bra derivative), j <= LB + 2 (kinetic), without the prefactor
+template <int LA, int LB>
+__device__ __forceinline__ void overlap_table(double (&s)[3][LA + 2][LB + 3], const PrimPair &q)
+{
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        s[d][0][0] = 1.0;
+#pragma unroll
+        for (int i = 0; i <= LA; i++) s[d][i + 1][0] = q.PA[d] * s[d][i][0] + (i > 0 ? i * q.h * s[d][i > 0 ? i - 1 : 0][0] : 0.0);
+#pragma unroll
+        for (int j = 0; j <= LB + 1; j++)
+#pragma unroll
+            for (int i = 0; i <= LA + 1; i++)
+                s[d][i][j + 1] = q.PB[d] * s[d][i][j] + (i > 0 ? i * q.h * s[d][i > 0 ? i - 1 : 0][j] : 0.0) +
+                                 (j > 0 ? j * q.h * s[d][i][j > 0 ? j - 1 : 0] : 0.0);
+    }
+}
+
+// kinetic 1-D factor T(i, j) = -1/2 <i| d^2/dx^2 |j> from one direction's overlaps (b: exponent of the second shell)
+template <int NA, int NB>
+__device__ __forceinline__ double kinetic_1d(const double (&s)[NA][NB], int i, int j, double b)
+{
+    double t = -2.0 * b * (2 * j + 1) * s[i][j] + 4.0 * b * b * s[i][j + 2];
+    if (j >= 2) t += j * (j - 1) * s[i][j >= 2 ? j - 2 : 0];
+    return -0.5 * t;
+}
+
+// element (i, j) of the spherical block ca^T acc cb (ca, cb: cart -> sph tables of LA, LB)
+template <int LA, int LB>
+__device__ __forceinline__ double block_to_spherical(const double *acc, const double *ca, const double *cb, int i, int j)
+{
+    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2, NSA = 2 * LA + 1, NSB = 2 * LB + 1;
+    double v = 0.0;
+#pragma unroll
+    for (int ia = 0; ia < NCA; ia++) {
+        double t = 0.0;
+#pragma unroll
+        for (int ib = 0; ib < NCB; ib++) t += acc[ia * NCB + ib] * cb[ib * NSB + j];
+        v += ca[ia * NSA + i] * t;
+    }
+    return v;
+}
+
+// element (ia, ib) of ca D_block cb^T: the spherical density block at AOs (ao_i.., ao_j..) back-transformed to cartesian components
+template <int LA, int LB>
+__device__ __forceinline__ double density_block_to_cartesian(const double *D, int nao, int ao_i, int ao_j, const double *ca, const double *cb,
+                                                             int ia, int ib)
+{
+    constexpr int NSA = 2 * LA + 1, NSB = 2 * LB + 1;
+    double s = 0.0;
+    for (int i = 0; i < NSA; i++) {
+        double t = 0.0;
+        for (int j = 0; j < NSB; j++) t += D[(size_t)(ao_i + i) * nao + ao_j + j] * cb[ib * NSB + j];
+        s += ca[ia * NSA + i] * t;
+    }
+    return s;
+}
+
+// One launch of KERNEL<la, lb> per non-empty angular class of the context's pair list: launch(la, lb, first, count) gets the
+// class as two std::integral_constant and its rows of the list.  blocks_per_pair: workgroups a launch spends per pair in grid.x.
+template <bool ORDERED, class F>
+static int launch_pair_classes(const mi_ctx *c, int64_t blocks_per_pair, const char *who, F launch)
+{
+    const mi_ctx::PairClasses &pc = c->pair_classes[ORDERED];
+    if ((int64_t)pc.start[16] * blocks_per_pair >= (int64_t)1 << 31)
+        return fail("%s: %d shell pairs x %lld point blocks exceed one launch", who, pc.start[16], (long long)blocks_per_pair);
+#define PAIR_CLASS(a, b)                                                                                                \
+    if constexpr (ORDERED || (a) >= (b)) {                                                                              \
+        const int first = pc.start[(a) * 4 + (b)], count = pc.start[(a) * 4 + (b) + 1] - first;                         \
+        if (count > 0) launch(std::integral_constant<int, a>{}, std::integral_constant<int, b>{}, first, count);        \
+    }
+    PAIR_CLASS(0, 0) PAIR_CLASS(0, 1) PAIR_CLASS(0, 2) PAIR_CLASS(0, 3) PAIR_CLASS(1, 0) PAIR_CLASS(1, 1) PAIR_CLASS(1, 2) PAIR_CLASS(1, 3)
+    PAIR_CLASS(2, 0) PAIR_CLASS(2, 1) PAIR_CLASS(2, 2) PAIR_CLASS(2, 3) PAIR_CLASS(3, 0) PAIR_CLASS(3, 1) PAIR_CLASS(3, 2) PAIR_CLASS(3, 3)
+#undef PAIR_CLASS
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("%s: launch failed: %s", who, hipGetErrorString(e));
+    return 0;
+}
+
+struct Int1eArgs : BasisDev {
+    const int *pairs;   // [npair][2] shell pairs of the launch's class, l of the first >= l of the second
+    int npair;
     double *S, *T, *V, *dip;
     double org[3];
 };
 
-// grid.y = natm + 1: slice y < natm adds the nuclear-attraction contribution of nucleus y (FP64 atomics into a zeroed
-// V: natm-fold more parallelism for the only part that scales with the number of atoms), slice y == natm writes S, T
-// and the dipole blocks.
+// One thread per shell pair.  grid.y = natm + 1: slice y < natm adds the nuclear-attraction contribution of nucleus y (FP64
+// atomics into a zeroed V: natm-fold more parallelism for the only part that scales with the number of atoms), slice y == natm
+// writes S, T and the dipole blocks.  The pair's first shell has the higher l, not necessarily the higher index: block (i, j) and
+// its transpose are stored, and the dipole operator is raised on the first shell's centre.
+template <int LA, int LB>
 __global__ __launch_bounds__(64) void int1e_kernel(Int1eArgs A)
 {
-    int pid = blockIdx.x * blockDim.x + threadIdx.x;
-    int npair = A.nbas * (A.nbas + 1) / 2;
-    if (pid >= npair) return;
+    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2, NSA = 2 * LA + 1, NSB = 2 * LB + 1;
+    constexpr int NR = (LA + LB) / 2 + 1, NI = LA + LB + 1;
+    const int pid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pid >= A.npair) return;
     const int vatom = (int)blockIdx.y < A.natm ? (int)blockIdx.y : -1; // -1: the S/T/dipole slice
     if (vatom >= 0 && (A.V == nullptr || A.atm[vatom * ATM_SLOTS + 0] == 0)) return;
-    int ish = (int)((sqrt(8.0 * pid + 1.0) - 1.0) * 0.5);
-    while ((ish + 1) * (ish + 2) / 2 <= pid) ish++;
-    while (ish * (ish + 1) / 2 > pid) ish--;
-    int jsh = pid - ish * (ish + 1) / 2;
+    const int ish = A.pairs[2 * pid], jsh = A.pairs[2 * pid + 1];
     const int32_t *bi = A.bas + ish * BAS_SLOTS, *bj = A.bas + jsh * BAS_SLOTS;
-    int la = bi[1], lb = bj[1];
     const double *ra = A.env + A.atm[bi[0] * ATM_SLOTS + 1], *rb = A.env + A.atm[bj[0] * ATM_SLOTS + 1];
-    int nca = (la + 1) * (la + 2) / 2, ncb = (lb + 1) * (lb + 2) / 2;
-    // 6 cartesian blocks: S, T, V, x, y, z
-    double blk[6][NC1 * NC1];
-    for (int m = 0; m < 6; m++)
-        for (int k = 0; k < nca * ncb; k++) blk[m][k] = 0.0;
-    double AB[3] = {ra[0] - rb[0], ra[1] - rb[1], ra[2] - rb[2]};
+    const double AB[3] = {ra[0] - rb[0], ra[1] - rb[1], ra[2] - rb[2]};
+    const double *ca = A.c2s + A.c2s_off[LA], *cb = A.c2s + A.c2s_off[LB];
+    const int ao_i = A.shell_ao[ish], ao_j = A.shell_ao[jsh];
+    if (vatom >= 0) {
+        const double Z = A.atm[vatom * ATM_SLOTS + 0];
+        const double *C = A.env + A.atm[vatom * ATM_SLOTS + 1];
+        double acc[NCA * NCB];
+#pragma unroll
+        for (int k = 0; k < NCA * NCB; k++) acc[k] = 0.0;
+        for (int ip = 0; ip < bi[2]; ip++)
+            for (int jp = 0; jp < bj[2]; jp++) {
+                const PrimPair q = prim_pair(A.env, bi, bj, ip, jp, ra, rb, AB);
+#pragma unroll
+                for (int r = 0; r < NR; r++) {
+                    double gt[3][NI][LB + 1];
+                    const double f = attraction_table<LB, NI, false>(gt, q, C, 0.0, AB, NR, r, A.rys);
+                    attraction_accumulate<LA, LB>(acc, gt, -Z * f);
+                }
+            }
+        // one nucleus' share: accumulate (the diagonal shell pair visits (i,j) and (j,i) itself)
+        for (int i = 0; i < NSA; i++)
+            for (int j = 0; j < NSB; j++) {
+                const double v = block_to_spherical<LA, LB>(acc, ca, cb, i, j);
+                atomicAdd(&A.V[(size_t)(ao_i + i) * A.nao + ao_j + j], v);
+                if (ish != jsh) atomicAdd(&A.V[(size_t)(ao_j + j) * A.nao + ao_i + i], v);
+            }
+        return;
+    }
+    double blk[5][NCA * NCB];   // cartesian blocks of S, T, x, y, z
+#pragma unroll
+    for (int m = 0; m < 5; m++)
+#pragma unroll
+        for (int k = 0; k < NCA * NCB; k++) blk[m][k] = 0.0;
     for (int ip = 0; ip < bi[2]; ip++)
         for (int jp = 0; jp < bj[2]; jp++) {
-            double a = A.env[bi[5] + ip], b = A.env[bj[5] + jp];
-            double cc = A.env[bi[6] + ip] * A.env[bj[6] + jp];
-            double p = a + b, mu = a * b / p, h = 0.5 / p;
-            double ex = exp(-mu * (AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2]));
-            double P[3], PA[3], PB[3];
-            for (int d = 0; d < 3; d++) { P[d] = (a * ra[d] + b * rb[d]) / p; PA[d] = P[d] - ra[d]; PB[d] = P[d] - rb[d]; }
-            // 1-D overlaps s[d][i][j], i <= la+1, j <= lb+2
-            double s[3][LMAX_1E + 2][LMAX_1E + 3];
-            for (int d = 0; d < 3; d++) {
-                s[d][0][0] = 1.0;
-                for (int i = 0; i <= la; i++)
-                    s[d][i + 1][0] = PA[d] * s[d][i][0] + (i > 0 ? i * h * s[d][i - 1][0] : 0.0);
-                for (int j = 0; j <= lb + 1; j++)
-                    for (int i = 0; i <= la + 1; i++)
-                        s[d][i][j + 1] = PB[d] * s[d][i][j] + (i > 0 ? i * h * s[d][i - 1][j] : 0.0) + (j > 0 ? j * h * s[d][i][j - 1] : 0.0);
-            }
-            double pref = cc * ex * pow(M_PI / p, 1.5);
-            for (int ia = 0; ia < (vatom < 0 ? nca : 0); ia++) {
-                int pa[3];
-                cart_pow(la, ia, pa[0], pa[1], pa[2]);
-                for (int ib = 0; ib < ncb; ib++) {
-                    int pb[3];
-                    cart_pow(lb, ib, pb[0], pb[1], pb[2]);
+            const PrimPair q = prim_pair(A.env, bi, bj, ip, jp, ra, rb, AB);
+            double s[3][LA + 2][LB + 3];
+            overlap_table<LA, LB>(s, q);
+            const double pref = q.cc * q.ex * pow(M_PI / q.p, 1.5);
+#pragma unroll
+            for (int ia = 0; ia < NCA; ia++)
+#pragma unroll
+                for (int ib = 0; ib < NCB; ib++) {
                     double s1[3], t1[3], x1[3];
+#pragma unroll
                     for (int d = 0; d < 3; d++) {
-                        int i = pa[d], j = pb[d];
-                        double sij = s[d][i][j];
-                        double tij = -2.0 * b * (2 * j + 1) * sij + 4.0 * b * b * s[d][i][j + 2];
-                        if (j >= 2) tij += j * (j - 1) * s[d][i][j - 2];
-                        s1[d] = sij; t1[d] = -0.5 * tij;
-                        x1[d] = s[d][i + 1][j] + (ra[d] - A.org[d]) * sij;
+                        const int i = cart_exp(LA, ia, d), j = cart_exp(LB, ib, d);
+                        s1[d] = s[d][i][j];
+                        t1[d] = kinetic_1d(s[d], i, j, q.b);
+                        x1[d] = s[d][i + 1][j] + (ra[d] - A.org[d]) * s1[d];
                     }
-                    int k = ia * ncb + ib;
+                    const int k = ia * NCB + ib;
                     blk[0][k] += pref * s1[0] * s1[1] * s1[2];
                     blk[1][k] += pref * (t1[0] * s1[1] * s1[2] + s1[0] * t1[1] * s1[2] + s1[0] * s1[1] * t1[2]);
-                    blk[3][k] += pref * x1[0] * s1[1] * s1[2];
-                    blk[4][k] += pref * s1[0] * x1[1] * s1[2];
-                    blk[5][k] += pref * s1[0] * s1[1] * x1[2];
+                    blk[2][k] += pref * x1[0] * s1[1] * s1[2];
+                    blk[3][k] += pref * s1[0] * x1[1] * s1[2];
+                    blk[4][k] += pref * s1[0] * s1[1] * x1[2];
                 }
-            }
-            // nuclear attraction by Rys quadrature, nroots = (la+lb)/2 + 1
-            int nr = (la + lb) / 2 + 1;
-            double pv = cc * ex * 2.0 * M_PI / p;
-            for (int ic = (vatom < 0 ? A.natm : vatom); ic < (vatom < 0 ? A.natm : vatom + 1); ic++) {
-                double Z = A.atm[ic * ATM_SLOTS + 0];
-                if (Z == 0.0) continue;
-                const double *C = A.env + A.atm[ic * ATM_SLOTS + 1];
-                double PC[3] = {P[0] - C[0], P[1] - C[1], P[2] - C[2]};
-                double x = p * (PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2]);
-                for (int r = 0; r < nr; r++) {
-                    double u = rys_eval(A.rys, nr, r, x), w = rys_eval(A.rys, nr, nr + r, x);
-                    double g[3][2 * LMAX_1E + 1][LMAX_1E + 1]; // g[d][i][j]
-                    double b10 = (1.0 - u) * h;
-                    for (int d = 0; d < 3; d++) {
-                        double c00 = PA[d] - u * PC[d];
-                        g[d][0][0] = 1.0;
-                        for (int i = 0; i < la + lb; i++)
-                            g[d][i + 1][0] = c00 * g[d][i][0] + (i > 0 ? i * b10 * g[d][i - 1][0] : 0.0);
-                        for (int j = 0; j < lb; j++)
-                            for (int i = 0; i <= la + lb - j - 1; i++) g[d][i][j + 1] = g[d][i + 1][j] + AB[d] * g[d][i][j];
-                    }
-                    double f = -Z * pv * w;
-                    for (int ia = 0; ia < nca; ia++) {
-                        int pa[3];
-                        cart_pow(la, ia, pa[0], pa[1], pa[2]);
-                        for (int ib = 0; ib < ncb; ib++) {
-                            int pb[3];
-                            cart_pow(lb, ib, pb[0], pb[1], pb[2]);
-                            blk[2][ia * ncb + ib] += f * g[0][pa[0]][pb[0]] * g[1][pa[1]][pb[1]] * g[2][pa[2]][pb[2]];
-                        }
-                    }
-                }
-            }
         }
     // cart -> sph and store both triangles
-    const double *ca = A.c2s + A.c2s_off[la], *cb = A.c2s + A.c2s_off[lb];
-    int nsa = 2 * la + 1, nsb = 2 * lb + 1;
-    int ao_i = A.shell_ao[ish], ao_j = A.shell_ao[jsh];
-    double *outs[6] = {A.S, A.T, A.V, A.dip, A.dip ? A.dip + (size_t)A.nao * A.nao : nullptr,
-                       A.dip ? A.dip + 2 * (size_t)A.nao * A.nao : nullptr};
-    for (int m = 0; m < 6; m++) {
-        if (!outs[m] || (vatom >= 0) != (m == 2)) continue;
-        for (int i = 0; i < nsa; i++)
-            for (int j = 0; j < nsb; j++) {
-                double v = 0.0;
-                for (int a = 0; a < nca; a++) {
-                    double t = 0.0;
-                    for (int b = 0; b < ncb; b++) t += blk[m][a * ncb + b] * cb[b * nsb + j];
-                    v += ca[a * nsa + i] * t;
-                }
-                if (m == 2) {   // one nucleus' share: accumulate (the diagonal shell pair visits (i,j) and (j,i) itself)
-                    atomicAdd(&outs[m][(size_t)(ao_i + i) * A.nao + ao_j + j], v);
-                    if (ish != jsh) atomicAdd(&outs[m][(size_t)(ao_j + j) * A.nao + ao_i + i], v);
-                } else {
-                    outs[m][(size_t)(ao_i + i) * A.nao + ao_j + j] = v;
-                    outs[m][(size_t)(ao_j + j) * A.nao + ao_i + i] = v;
-                }
+    double *outs[5] = {A.S, A.T, A.dip, A.dip ? A.dip + (size_t)A.nao * A.nao : nullptr, A.dip ? A.dip + 2 * (size_t)A.nao * A.nao : nullptr};
+#pragma unroll
+    for (int m = 0; m < 5; m++) {
+        if (!outs[m]) continue;
+        for (int i = 0; i < NSA; i++)
+            for (int j = 0; j < NSB; j++) {
+                const double v = block_to_spherical<LA, LB>(blk[m], ca, cb, i, j);
+                outs[m][(size_t)(ao_i + i) * A.nao + ao_j + j] = v;
+                outs[m][(size_t)(ao_j + j) * A.nao + ao_i + i] = v;
             }
     }
 }
@@ -1003,17 +1199,16 @@ extern "C" int mi_int1e(mi_ctx *c, double *d_S, double *d_T, double *d_V, double
     if (c && check_orbital_lmax(c, "mi_int1e")) return -1;
     if (!c) return fail("mi_int1e: null context");
     HIPCHK(hipSetDevice(c->device));
-    Int1eArgs A;
-    A.atm = c->d_atm; A.bas = c->d_bas; A.env = c->d_env; A.shell_ao = c->d_shell_ao; A.c2s = c->d_c2s;
-    for (int i = 0; i <= LMAX + 1; i++) A.c2s_off[i] = c->c2s_off[i];
-    A.rys = c->rys; A.natm = c->natm; A.nbas = c->nbas; A.nao = c->nao;
+    Int1eArgs A{basis_dev(c)};
     A.S = d_S; A.T = d_T; A.V = d_V; A.dip = d_dip;
     for (int d = 0; d < 3; d++) A.org[d] = origin ? origin[d] : 0.0;
-    int npair = c->nbas * (c->nbas + 1) / 2;
     if (d_V) HIPCHK(hipMemsetAsync(d_V, 0, sizeof(double) * (size_t)c->nao * c->nao, (hipStream_t)stream));
-    hipLaunchKernelGGL(int1e_kernel, dim3((npair + 63) / 64, c->natm + 1), dim3(64), 0, (hipStream_t)stream, A);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_pair_classes<false>(c, 1, "mi_int1e", [&](auto la, auto lb, int first, int count) {
+        A.pairs = c->pair_classes[0].d_pairs + 2 * first;
+        A.npair = count;
+        hipLaunchKernelGGL((int1e_kernel<decltype(la)::value, decltype(lb)::value>), dim3((count + 63) / 64, c->natm + 1), dim3(64), 0,
+                           (hipStream_t)stream, A);
+    });
 }
 
 // Upper bound of |G| = |D_ab D_cd - hyb/4 (D_ac D_bd + D_ad D_bc)| over the AO quadruples of a shell quartet.
@@ -5107,13 +5302,8 @@ extern "C" int mi_grid_becke_grad(mi_ctx *c, const double *d_coords, const int32
     return 0;
 }
 
-struct AoArgs {
-    const int32_t *atm, *bas;
-    const double *env;
-    const int *shell_ao;
-    const double *c2s;
-    int c2s_off[LMAX + 2];
-    int nbas, nao, deriv;
+struct AoArgs : BasisDev {
+    int deriv;
     const double *coords; // [ng][3]
     int64_t ng;
     double *ao;           // [1 | 4 | 10][nao][ng]: value; +gradient; +second derivatives xx,xy,xz,yy,yz,zz
@@ -5231,10 +5421,8 @@ extern "C" int mi_eval_ao(mi_ctx *c, const double *d_coords, int64_t ng, int der
     if (c && check_orbital_lmax(c, "mi_eval_ao")) return -1;
     if (!c || !d_coords || !d_ao) return fail("mi_eval_ao: null argument");
     HIPCHK(hipSetDevice(c->device));
-    AoArgs A;
-    A.atm = c->d_atm; A.bas = c->d_bas; A.env = c->d_env; A.shell_ao = c->d_shell_ao; A.c2s = c->d_c2s;
-    for (int i = 0; i <= LMAX + 1; i++) A.c2s_off[i] = c->c2s_off[i];
-    A.nbas = c->nbas; A.nao = c->nao; A.deriv = deriv; A.coords = d_coords; A.ng = ng; A.ao = d_ao;
+    AoArgs A{basis_dev(c)};
+    A.deriv = deriv; A.coords = d_coords; A.ng = ng; A.ao = d_ao;
     const dim3 grid((unsigned)((ng + 255) / 256)), block(256);
     if (deriv <= 0) hipLaunchKernelGGL(eval_ao_kernel<0>, grid, block, 0, (hipStream_t)stream, A);
     else if (deriv == 1) hipLaunchKernelGGL(eval_ao_kernel<1>, grid, block, 0, (hipStream_t)stream, A);
@@ -6483,145 +6671,87 @@ extern "C" int mi_sp2_update(mi_ctx *c, double *d_X, const double *d_X2, double 
 //   g[C] -= 2 sum_{mu,nu} D_mu,nu <d mu|v_C|nu>                               (Hellmann-Feynman, via
 //                                                                               translational invariance)
 // One thread per ORDERED shell pair (ish, jsh); the derivative acts on the first shell.  d/dA_x of a
-// primitive cartesian Gaussian = 2a (a+1_x) - a_x (a-1_x), applied inside the primitive loop.
+// primitive cartesian Gaussian = 2a (a+1_x) - a_x (a-1_x), applied inside the primitive loop.  One launch per angular class
+// from the context's ordered pair list; the integral pieces are the one-electron section's (attraction_table, overlap_table, ...).
 // =================================================================================================
-struct Grad1eArgs {
-    const int32_t *atm, *bas;
-    const double *env;
-    const int *shell_ao;
-    const double *c2s;
-    int c2s_off[LMAX + 2];
-    RysDev rys;
-    int natm, nbas, nao;
+struct Grad1eArgs : BasisDev {
+    const int *pairs;    // [npair][2] ordered shell pairs of the launch's class
+    int npair;
     const double *D, *W; // [nao][nao]
     double *grad;        // [natm][3]
 };
 
+template <int LA, int LB>
 __global__ __launch_bounds__(64) void int1e_grad_kernel(Grad1eArgs A)
 {
-    int pid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pid >= A.nbas * A.nbas) return;
+    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2;
+    constexpr int NR = (LA + LB + 1) / 2 + 1, NI = LA + LB + 2;   // the differentiated bra reaches LA + 1
+    const int pid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pid >= A.npair) return;
     // grid.y = natm + 1 slices, as in int1e_kernel: y < natm: nuclear attraction of nucleus y; y == natm: overlap + kinetic
     const int vatom = (int)blockIdx.y < A.natm ? (int)blockIdx.y : -1;
     if (vatom >= 0 && A.atm[vatom * ATM_SLOTS + 0] == 0) return;
-    int ish = pid / A.nbas, jsh = pid - ish * A.nbas;
+    const int ish = A.pairs[2 * pid], jsh = A.pairs[2 * pid + 1];
     const int32_t *bi = A.bas + ish * BAS_SLOTS, *bj = A.bas + jsh * BAS_SLOTS;
-    int la = bi[1], lb = bj[1];
     const double *ra = A.env + A.atm[bi[0] * ATM_SLOTS + 1], *rb = A.env + A.atm[bj[0] * ATM_SLOTS + 1];
-    int nca = (la + 1) * (la + 2) / 2, ncb = (lb + 1) * (lb + 2) / 2;
-    int nsa = 2 * la + 1, nsb = 2 * lb + 1;
-    int ao_i = A.shell_ao[ish], ao_j = A.shell_ao[jsh];
-    const double *ca = A.c2s + A.c2s_off[la], *cb = A.c2s + A.c2s_off[lb];
-    // back-transform the density blocks to cartesian components
-    double Dc[NC1 * NC1], Wc[NC1 * NC1];
-    for (int a = 0; a < nca; a++)
-        for (int b = 0; b < ncb; b++) {
-            double sd = 0.0, sw = 0.0;
-            for (int i = 0; i < nsa; i++) {
-                double t = 0.0, u = 0.0;
-                for (int j = 0; j < nsb; j++) {
-                    t += A.D[(size_t)(ao_i + i) * A.nao + ao_j + j] * cb[b * nsb + j];
-                    u += A.W[(size_t)(ao_i + i) * A.nao + ao_j + j] * cb[b * nsb + j];
-                }
-                sd += ca[a * nsa + i] * t; sw += ca[a * nsa + i] * u;
-            }
-            Dc[a * ncb + b] = sd; Wc[a * ncb + b] = sw;
-        }
+    const double AB[3] = {ra[0] - rb[0], ra[1] - rb[1], ra[2] - rb[2]};
+    const double *ca = A.c2s + A.c2s_off[LA], *cb = A.c2s + A.c2s_off[LB];
+    const int ao_i = A.shell_ao[ish], ao_j = A.shell_ao[jsh];
+    double Dc[NCA * NCB];
+#pragma unroll
+    for (int ia = 0; ia < NCA; ia++)
+#pragma unroll
+        for (int ib = 0; ib < NCB; ib++) Dc[ia * NCB + ib] = density_block_to_cartesian<LA, LB>(A.D, A.nao, ao_i, ao_j, ca, cb, ia, ib);
     double gA[3] = {0.0, 0.0, 0.0};
-    double AB[3] = {ra[0] - rb[0], ra[1] - rb[1], ra[2] - rb[2]};
-    for (int ip = 0; ip < bi[2]; ip++)
-        for (int jp = 0; jp < bj[2]; jp++) {
-            double a = A.env[bi[5] + ip], b = A.env[bj[5] + jp];
-            double cc = A.env[bi[6] + ip] * A.env[bj[6] + jp];
-            double p = a + b, mu = a * b / p, h = 0.5 / p;
-            double ex = exp(-mu * (AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2]));
-            double P[3], PA[3], PB[3];
-            for (int d = 0; d < 3; d++) { P[d] = (a * ra[d] + b * rb[d]) / p; PA[d] = P[d] - ra[d]; PB[d] = P[d] - rb[d]; }
-            double s[3][LMAX_1E + 3][LMAX_1E + 3]; // s[d][i][j], i <= la+1, j <= lb+2
-            for (int d = 0; d < 3; d++) {
-                s[d][0][0] = 1.0;
-                for (int i = 0; i <= la; i++) s[d][i + 1][0] = PA[d] * s[d][i][0] + (i > 0 ? i * h * s[d][i - 1][0] : 0.0);
-                for (int j = 0; j <= lb + 1; j++)
-                    for (int i = 0; i <= la + 1; i++)
-                        s[d][i][j + 1] = PB[d] * s[d][i][j] + (i > 0 ? i * h * s[d][i - 1][j] : 0.0) + (j > 0 ? j * h * s[d][i][j - 1] : 0.0);
-            }
-            double pref = cc * ex * pow(M_PI / p, 1.5);
-            // overlap and kinetic: 1-D factors S(i,j), T(i,j) for i in {a-1, a, a+1}  (only in the y == natm slice)
-            for (int ia = 0; ia < (vatom < 0 ? nca : 0); ia++) {
-                int pa[3];
-                cart_pow(la, ia, pa[0], pa[1], pa[2]);
-                for (int ib = 0; ib < ncb; ib++) {
-                    int pb[3];
-                    cart_pow(lb, ib, pb[0], pb[1], pb[2]);
-                    double s0[3], t0[3], sd[3], td[3]; // plain and differentiated 1-D factors
-                    for (int d = 0; d < 3; d++) {
-                        int i = pa[d], j = pb[d];
-                        auto S1 = [&](int ii) { return s[d][ii][j]; };
-                        auto T1 = [&](int ii) {
-                            double t = -2.0 * b * (2 * j + 1) * s[d][ii][j] + 4.0 * b * b * s[d][ii][j + 2];
-                            if (j >= 2) t += j * (j - 1) * s[d][ii][j - 2];
-                            return -0.5 * t;
-                        };
-                        s0[d] = S1(i); t0[d] = T1(i);
-                        sd[d] = 2.0 * a * S1(i + 1) - (i > 0 ? i * S1(i - 1) : 0.0);
-                        td[d] = 2.0 * a * T1(i + 1) - (i > 0 ? i * T1(i - 1) : 0.0);
-                    }
-                    double dc = Dc[ia * ncb + ib], wc = Wc[ia * ncb + ib];
-                    for (int x = 0; x < 3; x++) {
-                        int y = (x + 1) % 3, z = (x + 2) % 3;
-                        double dS = sd[x] * s0[y] * s0[z];
-                        double dT = td[x] * s0[y] * s0[z] + sd[x] * t0[y] * s0[z] + sd[x] * s0[y] * t0[z];
-                        gA[x] += 2.0 * pref * (dc * dT - wc * dS);
-                    }
+    if (vatom >= 0) {   // nuclear attraction with the differentiated bra; the operator's own derivative by translational invariance
+        const double Z = A.atm[vatom * ATM_SLOTS + 0];
+        const double *C = A.env + A.atm[vatom * ATM_SLOTS + 1];
+        for (int ip = 0; ip < bi[2]; ip++)
+            for (int jp = 0; jp < bj[2]; jp++) {
+                const PrimPair q = prim_pair(A.env, bi, bj, ip, jp, ra, rb, AB);
+#pragma unroll
+                for (int r = 0; r < NR; r++) {
+                    double gt[3][NI][LB + 1];
+                    const double f = attraction_table<LB, NI, false>(gt, q, C, 0.0, AB, NR, r, A.rys);
+                    attraction_bra_gradient<LA, LB>(gA, gt, -2.0 * Z * f, q.a, Dc);
                 }
             }
-            // nuclear attraction with the differentiated bra: Rys, nroots = (la+lb+1)/2 + 1
-            int nr = (la + lb + 1) / 2 + 1;
-            double pv = cc * ex * 2.0 * M_PI / p;
-            for (int ic = (vatom < 0 ? A.natm : vatom); ic < (vatom < 0 ? A.natm : vatom + 1); ic++) {
-                double Z = A.atm[ic * ATM_SLOTS + 0];
-                if (Z == 0.0) continue;
-                const double *C = A.env + A.atm[ic * ATM_SLOTS + 1];
-                double PC[3] = {P[0] - C[0], P[1] - C[1], P[2] - C[2]};
-                double xarg = p * (PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2]);
-                double gc[3] = {0.0, 0.0, 0.0};
-                for (int r = 0; r < nr; r++) {
-                    double u = rys_eval(A.rys, nr, r, xarg), w = rys_eval(A.rys, nr, nr + r, xarg);
-                    double g[3][2 * LMAX_1E + 2][LMAX_1E + 1];
-                    double b10 = (1.0 - u) * h;
-                    for (int d = 0; d < 3; d++) {
-                        double c00 = PA[d] - u * PC[d];
-                        g[d][0][0] = 1.0;
-                        for (int i = 0; i < la + lb + 1; i++) g[d][i + 1][0] = c00 * g[d][i][0] + (i > 0 ? i * b10 * g[d][i - 1][0] : 0.0);
-                        for (int j = 0; j < lb; j++)
-                            for (int i = 0; i <= la + lb - j; i++) g[d][i][j + 1] = g[d][i + 1][j] + AB[d] * g[d][i][j];
-                    }
-                    double f = -Z * pv * w;
-                    for (int ia = 0; ia < nca; ia++) {
-                        int pa[3];
-                        cart_pow(la, ia, pa[0], pa[1], pa[2]);
-                        for (int ib = 0; ib < ncb; ib++) {
-                            int pb[3];
-                            cart_pow(lb, ib, pb[0], pb[1], pb[2]);
-                            double v0[3], vd[3];
-                            for (int d = 0; d < 3; d++) {
-                                int i = pa[d], j = pb[d];
-                                v0[d] = g[d][i][j];
-                                vd[d] = 2.0 * a * g[d][i + 1][j] - (i > 0 ? i * g[d][i - 1][j] : 0.0);
-                            }
-                            double dc = f * Dc[ia * ncb + ib];
-                            gc[0] += dc * vd[0] * v0[1] * v0[2];
-                            gc[1] += dc * v0[0] * vd[1] * v0[2];
-                            gc[2] += dc * v0[0] * v0[1] * vd[2];
+        for (int x = 0; x < 3; x++) atomicAdd(&A.grad[vatom * 3 + x], -gA[x]);
+    } else {            // overlap and kinetic: 1-D factors S(i,j), T(i,j) for i in {a-1, a, a+1}
+        double Wc[NCA * NCB];
+#pragma unroll
+        for (int ia = 0; ia < NCA; ia++)
+#pragma unroll
+            for (int ib = 0; ib < NCB; ib++) Wc[ia * NCB + ib] = density_block_to_cartesian<LA, LB>(A.W, A.nao, ao_i, ao_j, ca, cb, ia, ib);
+        for (int ip = 0; ip < bi[2]; ip++)
+            for (int jp = 0; jp < bj[2]; jp++) {
+                const PrimPair q = prim_pair(A.env, bi, bj, ip, jp, ra, rb, AB);
+                double s[3][LA + 2][LB + 3];
+                overlap_table<LA, LB>(s, q);
+                const double pref = q.cc * q.ex * pow(M_PI / q.p, 1.5);
+#pragma unroll
+                for (int ia = 0; ia < NCA; ia++)
+#pragma unroll
+                    for (int ib = 0; ib < NCB; ib++) {
+                        double s0[3], t0[3], sd[3], td[3]; // plain and differentiated 1-D factors
+#pragma unroll
+                        for (int d = 0; d < 3; d++) {
+                            const int i = cart_exp(LA, ia, d), j = cart_exp(LB, ib, d), im = i > 0 ? i - 1 : 0;
+                            s0[d] = s[d][i][j]; t0[d] = kinetic_1d(s[d], i, j, q.b);
+                            sd[d] = 2.0 * q.a * s[d][i + 1][j] - (i > 0 ? i * s[d][im][j] : 0.0);
+                            td[d] = 2.0 * q.a * kinetic_1d(s[d], i + 1, j, q.b) - (i > 0 ? i * kinetic_1d(s[d], im, j, q.b) : 0.0);
+                        }
+                        const double dc = Dc[ia * NCB + ib], wc = Wc[ia * NCB + ib];
+#pragma unroll
+                        for (int x = 0; x < 3; x++) {
+                            const int y = (x + 1) % 3, z = (x + 2) % 3;
+                            const double dS = sd[x] * s0[y] * s0[z];
+                            const double dT = td[x] * s0[y] * s0[z] + sd[x] * t0[y] * s0[z] + sd[x] * s0[y] * t0[z];
+                            gA[x] += 2.0 * pref * (dc * dT - wc * dS);
                         }
                     }
-                }
-                for (int x = 0; x < 3; x++) {
-                    gA[x] += 2.0 * gc[x];
-                    atomicAdd(&A.grad[ic * 3 + x], -2.0 * gc[x]);
-                }
             }
-        }
+    }
     for (int x = 0; x < 3; x++) atomicAdd(&A.grad[bi[0] * 3 + x], gA[x]);
 }
 
@@ -6630,15 +6760,14 @@ extern "C" int mi_grad_1e(mi_ctx *c, const double *d_D, const double *d_W, doubl
     if (c && check_orbital_lmax(c, "mi_grad_1e")) return -1;
     if (!c || !d_D || !d_W || !d_grad) return fail("mi_grad_1e: null argument");
     HIPCHK(hipSetDevice(c->device));
-    Grad1eArgs A;
-    A.atm = c->d_atm; A.bas = c->d_bas; A.env = c->d_env; A.shell_ao = c->d_shell_ao; A.c2s = c->d_c2s;
-    for (int i = 0; i <= LMAX + 1; i++) A.c2s_off[i] = c->c2s_off[i];
-    A.rys = c->rys; A.natm = c->natm; A.nbas = c->nbas; A.nao = c->nao;
+    Grad1eArgs A{basis_dev(c)};
     A.D = d_D; A.W = d_W; A.grad = d_grad;
-    int n = c->nbas * c->nbas;
-    hipLaunchKernelGGL(int1e_grad_kernel, dim3((n + 63) / 64, c->natm + 1), dim3(64), 0, (hipStream_t)stream, A);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_pair_classes<true>(c, 1, "mi_grad_1e", [&](auto la, auto lb, int first, int count) {
+        A.pairs = c->pair_classes[1].d_pairs + 2 * first;
+        A.npair = count;
+        hipLaunchKernelGGL((int1e_grad_kernel<decltype(la)::value, decltype(lb)::value>), dim3((count + 63) / 64, c->natm + 1), dim3(64), 0,
+                           (hipStream_t)stream, A);
+    });
 }
 
 // =================================================================================================
@@ -9084,14 +9213,7 @@ extern "C" int mi_xc_vmat_fold(mi_ctx *c, const double *d_ao, const double *d_wv
 //   pcm_fock_finalize_kernel    V[m,n] (+)= scale sum_k part[k][c(m,n)]        (chunks added in index order)
 //   pcm_grad_kernel<LA,LB>      -2 sum_g q_g sum_{m in A, n} D_mn <d_A m|erf/r|n> per (ordered pair, point block)
 // =================================================================================================
-struct PcmArgs {
-    const int32_t *atm, *bas;
-    const double *env;
-    const int *shell_ao;
-    const double *c2s;
-    int c2s_off[LMAX + 2];
-    RysDev rys;
-    int nao;
+struct PcmArgs : BasisDev {
     const int *pairs;     // [n][2] shell pairs of one class (la, lb) = template arguments
     const double *pts;    // [npts][4]: x, y, z, zeta
     const int *blk;       // [nblk][3]: first point, count (1..64), owning atom
@@ -9101,13 +9223,6 @@ struct PcmArgs {
     const double *D, *q;  // gradient: density [nao][nao], surface charges [npts]
     double *part;         // gradient: [n][nblk][3] (rows of the launch's class at its offset)
 };
-
-__device__ inline int pcm_cart(int l, int idx, int d)   // exponent of direction d of cartesian component idx of shell l
-{
-    int x = 0, y = 0, z = 0;
-    cart_pow(l, idx, x, y, z);
-    return d == 0 ? x : (d == 1 ? y : z);
-}
 
 template <int LA, int LB>
 __global__ __launch_bounds__(64) void pcm_int_kernel(PcmArgs A)
@@ -9129,44 +9244,12 @@ __global__ __launch_bounds__(64) void pcm_int_kernel(PcmArgs A)
     for (int k = 0; k < NCA * NCB; k++) acc[k] = 0.0;
     for (int ip = 0; ip < bi[2]; ip++)
         for (int jp = 0; jp < bj[2]; jp++) {
-            const double a = A.env[bi[5] + ip], bb = A.env[bj[5] + jp];
-            const double cc = A.env[bi[6] + ip] * A.env[bj[6] + jp];
-            const double p = a + bb, h = 0.5 / p;
-            const double ex = exp(-a * bb / p * (AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2]));
-            const double theta = eta / (p + eta);          // rho / p
-            double PA[3], PC[3];
-#pragma unroll
-            for (int d = 0; d < 3; d++) {
-                const double P = (a * ra[d] + bb * rb[d]) / p;
-                PA[d] = P - ra[d];
-                PC[d] = P - C[d];
-            }
-            const double x = p * theta * (PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2]);
-            const double pv = cc * ex * 2.0 * M_PI / p * sqrt(theta);
+            const PrimPair q = prim_pair(A.env, bi, bj, ip, jp, ra, rb, AB);
 #pragma unroll
             for (int r = 0; r < NR; r++) {
-                const double u = rys_eval(A.rys, NR, r, x) * theta, w = rys_eval(A.rys, NR, NR + r, x);
-                const double b10 = (1.0 - u) * h;
                 double gt[3][NI][LB + 1];
-#pragma unroll
-                for (int d = 0; d < 3; d++) {
-                    const double c00 = PA[d] - u * PC[d];
-                    gt[d][0][0] = 1.0;
-#pragma unroll
-                    for (int i = 0; i + 1 < NI; i++) gt[d][i + 1][0] = c00 * gt[d][i][0] + (i > 0 ? i * b10 * gt[d][i - 1][0] : 0.0);
-#pragma unroll
-                    for (int j = 0; j < LB; j++)
-#pragma unroll
-                        for (int i = 0; i < NI - j - 1; i++) gt[d][i][j + 1] = gt[d][i + 1][j] + AB[d] * gt[d][i][j];
-                }
-                const double f = pv * w;
-#pragma unroll
-                for (int ia = 0; ia < NCA; ia++)
-#pragma unroll
-                    for (int ib = 0; ib < NCB; ib++)
-                        acc[ia * NCB + ib] += f * gt[0][pcm_cart(LA, ia, 0)][pcm_cart(LB, ib, 0)] *
-                                              gt[1][pcm_cart(LA, ia, 1)][pcm_cart(LB, ib, 1)] *
-                                              gt[2][pcm_cart(LA, ia, 2)][pcm_cart(LB, ib, 2)];
+                const double f = attraction_table<LB, NI, true>(gt, q, C, eta, AB, NR, r, A.rys);
+                attraction_accumulate<LA, LB>(acc, gt, f);
             }
         }
     const double *ca = A.c2s + A.c2s_off[LA], *cb = A.c2s + A.c2s_off[LB];
@@ -9176,14 +9259,7 @@ __global__ __launch_bounds__(64) void pcm_int_kernel(PcmArgs A)
         for (int j = 0; j < NSB; j++) {
             int m = ao_i + i, n = ao_j + j;
             if (ish == jsh && n > m) continue;
-            double v = 0.0;
-#pragma unroll
-            for (int ia = 0; ia < NCA; ia++) {
-                double t = 0.0;
-#pragma unroll
-                for (int ib = 0; ib < NCB; ib++) t += acc[ia * NCB + ib] * cb[ib * NSB + j];
-                v += ca[ia * NSA + i] * t;
-            }
+            const double v = block_to_spherical<LA, LB>(acc, ca, cb, i, j);
             if (m < n) { const int s_ = m; m = n; n = s_; }
             row[(size_t)m * (m + 1) / 2 + n] = v;
         }
@@ -9192,7 +9268,7 @@ __global__ __launch_bounds__(64) void pcm_int_kernel(PcmArgs A)
 template <int LA, int LB>
 __global__ __launch_bounds__(64) void pcm_grad_kernel(PcmArgs A)
 {
-    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2, NSA = 2 * LA + 1, NSB = 2 * LB + 1;
+    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2;
     constexpr int NR = (LA + LB + 1) / 2 + 1, NI = LA + LB + 2;
     __shared__ double Dc[NCA * NCB];
     const int pidx = blockIdx.x / A.nblk, b = blockIdx.x - pidx * A.nblk;
@@ -9201,16 +9277,8 @@ __global__ __launch_bounds__(64) void pcm_grad_kernel(PcmArgs A)
     const int32_t *bi = A.bas + ish * BAS_SLOTS, *bj = A.bas + jsh * BAS_SLOTS;
     const int ao_i = A.shell_ao[ish], ao_j = A.shell_ao[jsh];
     const double *ca = A.c2s + A.c2s_off[LA], *cb = A.c2s + A.c2s_off[LB];
-    for (int k = threadIdx.x; k < NCA * NCB; k += 64) {   // density block back-transformed to cartesian components, once per workgroup
-        const int ia = k / NCB, ib = k - ia * NCB;
-        double s = 0.0;
-        for (int i = 0; i < NSA; i++) {
-            double t = 0.0;
-            for (int j = 0; j < NSB; j++) t += A.D[(size_t)(ao_i + i) * A.nao + ao_j + j] * cb[ib * NSB + j];
-            s += ca[ia * NSA + i] * t;
-        }
-        Dc[k] = s;
-    }
+    for (int k = threadIdx.x; k < NCA * NCB; k += 64)   // density block back-transformed to cartesian components, once per workgroup
+        Dc[k] = density_block_to_cartesian<LA, LB>(A.D, A.nao, ao_i, ao_j, ca, cb, k / NCB, k % NCB);
     __syncthreads();
     double gc[3] = {0.0, 0.0, 0.0};
     if ((int)threadIdx.x < bk[1]) {
@@ -9222,53 +9290,13 @@ __global__ __launch_bounds__(64) void pcm_grad_kernel(PcmArgs A)
         const double AB[3] = {ra[0] - rb[0], ra[1] - rb[1], ra[2] - rb[2]};
         for (int ip = 0; ip < bi[2]; ip++)
             for (int jp = 0; jp < bj[2]; jp++) {
-                const double a = A.env[bi[5] + ip], bb = A.env[bj[5] + jp];
-                const double cc = A.env[bi[6] + ip] * A.env[bj[6] + jp];
-                const double p = a + bb, h = 0.5 / p;
-                const double ex = exp(-a * bb / p * (AB[0] * AB[0] + AB[1] * AB[1] + AB[2] * AB[2]));
-                const double theta = eta / (p + eta);
-                double PA[3], PC[3];
-#pragma unroll
-                for (int d = 0; d < 3; d++) {
-                    const double P = (a * ra[d] + bb * rb[d]) / p;
-                    PA[d] = P - ra[d];
-                    PC[d] = P - C[d];
-                }
-                const double x = p * theta * (PC[0] * PC[0] + PC[1] * PC[1] + PC[2] * PC[2]);
-                const double pv = qg * cc * ex * 2.0 * M_PI / p * sqrt(theta);
+                PrimPair q = prim_pair(A.env, bi, bj, ip, jp, ra, rb, AB);
+                q.cc = qg * q.cc;   // the point's charge rides on the prefactor
 #pragma unroll
                 for (int r = 0; r < NR; r++) {
-                    const double u = rys_eval(A.rys, NR, r, x) * theta, w = rys_eval(A.rys, NR, NR + r, x);
-                    const double b10 = (1.0 - u) * h;
                     double gt[3][NI][LB + 1];
-#pragma unroll
-                    for (int d = 0; d < 3; d++) {
-                        const double c00 = PA[d] - u * PC[d];
-                        gt[d][0][0] = 1.0;
-#pragma unroll
-                        for (int i = 0; i + 1 < NI; i++) gt[d][i + 1][0] = c00 * gt[d][i][0] + (i > 0 ? i * b10 * gt[d][i - 1][0] : 0.0);
-#pragma unroll
-                        for (int j = 0; j < LB; j++)
-#pragma unroll
-                            for (int i = 0; i < NI - j - 1; i++) gt[d][i][j + 1] = gt[d][i + 1][j] + AB[d] * gt[d][i][j];
-                    }
-                    const double f = pv * w;
-#pragma unroll
-                    for (int ia = 0; ia < NCA; ia++)
-#pragma unroll
-                        for (int ib = 0; ib < NCB; ib++) {
-                            double v0[3], vd[3];
-#pragma unroll
-                            for (int d = 0; d < 3; d++) {
-                                const int i = pcm_cart(LA, ia, d), j = pcm_cart(LB, ib, d);
-                                v0[d] = gt[d][i][j];
-                                vd[d] = 2.0 * a * gt[d][i + 1][j] - (i > 0 ? i * gt[d][i > 0 ? i - 1 : 0][j] : 0.0);
-                            }
-                            const double dc = f * Dc[ia * NCB + ib];
-                            gc[0] += dc * vd[0] * v0[1] * v0[2];
-                            gc[1] += dc * v0[0] * vd[1] * v0[2];
-                            gc[2] += dc * v0[0] * v0[1] * vd[2];
-                        }
+                    const double f = attraction_table<LB, NI, true>(gt, q, C, eta, AB, NR, r, A.rys);
+                    attraction_bra_gradient<LA, LB>(gc, gt, f, q.a, Dc);
                 }
             }
     }
@@ -9354,70 +9382,30 @@ __global__ __launch_bounds__(256) void pcm_fock_finalize_kernel(const double *pa
     V[idx] = (accumulate ? V[idx] : 0.0) + scale * s;
 }
 
-// Shell pairs of the PCM launches, grouped by angular class: ordered = 0: i >= j with l_i >= l_j (B), 1: all (i, j) (gradient,
-// derivative on i).  class_start[k] .. class_start[k + 1] is class k = la * 4 + lb.
-static void pcm_pair_list(const mi_ctx *c, int ordered, std::vector<int> &pairs, std::vector<int> &class_start)
-{
-    std::vector<std::vector<int>> by(16);
-    for (int i = 0; i < c->nbas; i++)
-        for (int j = 0; j < (ordered ? c->nbas : i + 1); j++) {
-            int a = i, b = j;
-            if (!ordered && c->shells[a].l < c->shells[b].l) std::swap(a, b);
-            by[c->shells[a].l * 4 + c->shells[b].l].push_back(a);
-            by[c->shells[a].l * 4 + c->shells[b].l].push_back(b);
-        }
-    pairs.clear();
-    class_start.assign(17, 0);
-    for (int k = 0; k < 16; k++) {
-        class_start[k] = (int)pairs.size() / 2;
-        pairs.insert(pairs.end(), by[k].begin(), by[k].end());
-    }
-    class_start[16] = (int)pairs.size() / 2;
-}
-
+// rows of the context's class-sorted pair list (shell_pair_classes): the order of B's launches and of `part`'s rows
 extern "C" int mi_pcm_pairs(mi_ctx *c, int ordered, int32_t *out)
 {
     if (!c) return fail("mi_pcm_pairs: null context");
-    std::vector<int> pairs, cs;
-    pcm_pair_list(c, ordered, pairs, cs);
+    const std::vector<int> &pairs = c->pair_classes[ordered ? 1 : 0].pairs;
     if (out) std::copy(pairs.begin(), pairs.end(), out);
     return (int)(pairs.size() / 2);
 }
 
-template <int LA, int LB>
-static void pcm_launch(bool grad, const PcmArgs &A0, const int *d_pairs, int first, int count, hipStream_t st)
+template <bool GRAD>
+static int pcm_dispatch(mi_ctx *c, PcmArgs &A, hipStream_t st)
 {
-    if (count <= 0) return;
-    PcmArgs A = A0;
-    A.pairs = d_pairs + 2 * first;
-    if (grad) A.part = A0.part + (size_t)first * A0.nblk * 3;
-    const dim3 grid((unsigned)((int64_t)count * A.nblk));
-    if (grad) hipLaunchKernelGGL((pcm_grad_kernel<LA, LB>), grid, dim3(64), 0, st, A);
-    else hipLaunchKernelGGL((pcm_int_kernel<LA, LB>), grid, dim3(64), 0, st, A);
-}
-
-static int pcm_dispatch(mi_ctx *c, bool grad, PcmArgs &A, int npts, hipStream_t st)
-{
-    std::vector<int> pairs, cs;
-    pcm_pair_list(c, grad ? 1 : 0, pairs, cs);
-    const int n = cs[16];
-    if ((int64_t)n * A.nblk >= (int64_t)1 << 31) return fail("mi_pcm: %d shell pairs x %d point blocks exceed one launch", n, A.nblk);
-    DevBuf<int> d_pairs;
-    HIPCHK(d_pairs.alloc(std::max<size_t>(pairs.size(), 2)));
-    HIPCHK(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(int) * pairs.size(), hipMemcpyHostToDevice, st));
-    A.atm = c->d_atm; A.bas = c->d_bas; A.env = c->d_env; A.shell_ao = c->d_shell_ao; A.c2s = c->d_c2s;
-    for (int i = 0; i <= LMAX + 1; i++) A.c2s_off[i] = c->c2s_off[i];
-    A.rys = c->rys; A.nao = c->nao;
-#define PCM_CASE(a, b) pcm_launch<a, b>(grad, A, d_pairs, cs[(a) * 4 + (b)], cs[(a) * 4 + (b) + 1] - cs[(a) * 4 + (b)], st)
-    PCM_CASE(0, 0); PCM_CASE(1, 0); PCM_CASE(1, 1); PCM_CASE(2, 0); PCM_CASE(2, 1); PCM_CASE(2, 2);
-    PCM_CASE(3, 0); PCM_CASE(3, 1); PCM_CASE(3, 2); PCM_CASE(3, 3);
-    if (grad) { PCM_CASE(0, 1); PCM_CASE(0, 2); PCM_CASE(0, 3); PCM_CASE(1, 2); PCM_CASE(1, 3); PCM_CASE(2, 3); }
-#undef PCM_CASE
-    hipError_t e = hipGetLastError();
-    // the pair list is read by the launches above: the pool's dev_free synchronises the device before parking the block
-    HIPCHK(hipStreamSynchronize(st));
-    if (e != hipSuccess) return fail("mi_pcm: launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_pair_classes<GRAD>(c, A.nblk, "mi_pcm", [&](auto la, auto lb, int first, int count) {
+        constexpr int LA = decltype(la)::value, LB = decltype(lb)::value;
+        PcmArgs B = A;
+        B.pairs = c->pair_classes[GRAD].d_pairs + 2 * first;
+        const dim3 grid((unsigned)((int64_t)count * A.nblk));
+        if constexpr (GRAD) {
+            B.part = A.part + (size_t)first * A.nblk * 3;
+            hipLaunchKernelGGL((pcm_grad_kernel<LA, LB>), grid, dim3(64), 0, st, B);
+        } else {
+            hipLaunchKernelGGL((pcm_int_kernel<LA, LB>), grid, dim3(64), 0, st, B);
+        }
+    });
 }
 
 static int pcm_check_points(const mi_ctx *c, const char *who, const double *d_pts, int npts, const int32_t *d_blk, int nblk)
@@ -9436,9 +9424,9 @@ extern "C" int mi_pcm_eval(mi_ctx *c, const double *d_pts, int npts, const int32
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(d_B, 0, sizeof(double) * (size_t)npts * ld, st));
-    PcmArgs A{};
+    PcmArgs A{basis_dev(c)};
     A.pts = d_pts; A.blk = d_blk; A.nblk = nblk; A.ld = ld; A.B = d_B;
-    return pcm_dispatch(c, false, A, npts, st);
+    return pcm_dispatch<false>(c, A, st);
 }
 
 extern "C" int mi_pcm_grad(mi_ctx *c, const double *d_pts, int npts, const int32_t *d_blk, int nblk, const double *d_D, const double *d_q,
@@ -9447,9 +9435,9 @@ extern "C" int mi_pcm_grad(mi_ctx *c, const double *d_pts, int npts, const int32
     if (pcm_check_points(c, "mi_pcm_grad", d_pts, npts, d_blk, nblk)) return -1;
     if (!d_D || !d_q || !d_part) return fail("mi_pcm_grad: null argument");
     HIPCHK(hipSetDevice(c->device));
-    PcmArgs A{};
+    PcmArgs A{basis_dev(c)};
     A.pts = d_pts; A.blk = d_blk; A.nblk = nblk; A.D = d_D; A.q = d_q; A.part = d_part;
-    return pcm_dispatch(c, true, A, npts, (hipStream_t)stream);
+    return pcm_dispatch<true>(c, A, (hipStream_t)stream);
 }
 
 extern "C" int mi_pcm_potential(mi_ctx *c, const double *d_B, int npts, int64_t ld, const double *d_D, double *d_dpack, const double *d_vn,

@@ -84,7 +84,8 @@ void mi_release_cache(void);
 int mi_set_option(mi_ctx *ctx, const char *key, double value);
 
 /* One-electron integrals into device buffers (any of them may be NULL): overlap S, kinetic T, nuclear
- * attraction V, dipole d_dip[3][nao][nao] about `origin` (host double[3], NULL = zero).
+ * attraction V, dipole d_dip[3][nao][nao] about `origin` (host double[3], NULL = zero).  One launch per angular
+ * class of shell pairs; V is summed over the nuclei by FP64 atomics (last-bit run-to-run differences).
  * Replaces: libcint int1e_ovlp_sph / int1e_kin_sph / int1e_nuc_sph / int1e_r_sph [MEM], reached from
  * mf.kernel() -> get_ovlp/get_hcore (templates/calculate_energy.py:155,205) and mf.dip_moment
  * (templates/calculate_energy.py:253). */
@@ -375,7 +376,7 @@ int mi_xc_aow(mi_ctx *ctx, const double *d_ao, const double *d_wv, int64_t ng, i
 
 /* ---- analytic nuclear gradient ---------------------------------------------- */
 /* d_grad[natm][3] += 2 sum D <d mu|T+V|nu> - 2 sum W <d mu|nu> + Hellmann-Feynman terms.  d_W is the
- * energy-weighted density (D F D / 2).  Replaces libcint int1e_ipovlp/ipkin/ipnuc/iprinv [MEM], reached
+ * energy-weighted density (D F D / 2).  One launch per angular class of ordered shell pairs.  Replaces libcint int1e_ipovlp/ipkin/ipnuc/iprinv [MEM], reached
  * through optimize(mf) -> mf.nuc_grad_method() (templates/optimize_geometry.py:99). */
 int mi_grad_1e(mi_ctx *ctx, const double *d_D, const double *d_W, double *d_grad, void *stream);
 

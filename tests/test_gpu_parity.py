@@ -37,6 +37,65 @@ def test_int1e_matches_oracle(name, basis):
     assert np.abs(dip - dipo).max() < 1e-11
 
 
+def test_int1e_matches_oracle_every_class():
+    """int1e_kernel<LA,LB> at each of its 10 angular classes on the synthetic s..f molecule with a ghost centre (16 shells, one
+    of every l per centre): S, T, V and the dipole per shell-pair block against the oracle with test_int1e_matches_oracle's
+    bounds.  Every class occurs on one centre and across two, with the higher l on the higher and on the lower shell index (the
+    kernel always takes the higher l first, so the second case stores the transposed block and raises the dipole on the other
+    centre), and next to the ghost centre.  Calls with null outputs (V alone; S and T alone) give the full call's S and T
+    exactly and its V within 1e-13 max|V| (FP64 atomics in no fixed order).
+
+    Observed on the MI355X, worst block per class: S 1e-16 .. 7e-16, T 2e-16 .. 2e-15, V 3e-15 .. 3e-14 (max|V| 13.9),
+    dipole 2e-16 .. 9e-16; V alone against the full call 1.8e-15."""
+    import ctypes
+    import torch
+    from mi355scf.engine import Engine, lib
+    from oracle import oracle as orc
+    from test_gpu_pcm_kernels import _synthetic_with_ghost
+    mol = _synthetic_with_ghost()
+    origin = np.array([0.1, -0.2, 0.3])
+    eng = Engine(mol)
+    got = [x.cpu().numpy() for x in eng.int1e(with_dipole=True, origin=origin)]
+    ref = orc.Oracle(mol).int1e(origin=origin)
+    bounds = {"S": 1e-12, "T": 1e-11, "V": 1e-10, "dipole": 1e-11}
+    l, at, loc = mol._bas[:, 1], mol._bas[:, 0], mol.ao_loc_nr()
+    nb = mol._bas.shape[0]
+    seen, worst, bad = {}, {}, []
+    for i in range(nb):
+        for j in range(nb):
+            cls = (int(max(l[i], l[j])), int(min(l[i], l[j])))
+            si, sj = slice(loc[i], loc[i + 1]), slice(loc[j], loc[j + 1])
+            if i >= j:
+                kinds = seen.setdefault(cls, set())
+                kinds.add("one-centre" if at[i] == at[j] else "two-centre")
+                kinds.add("higher l first" if l[i] > l[j] else "lower l first" if l[i] < l[j] else "equal l")
+                if 3 in (at[i], at[j]):
+                    kinds.add("ghost")
+            for (name, tol), g, r in zip(bounds.items(), got, ref):
+                err = np.abs(g[..., si, sj] - r[..., si, sj]).max()
+                worst[cls, name] = max(worst.get((cls, name), 0.0), err)
+                if not err < tol:
+                    bad.append(f"{name} block ({i},{j}) class {cls} atoms ({at[i]},{at[j]}): |err| = {err:.2e} (bound {tol:.0e})")
+    assert sorted(seen) == [(a, b) for a in range(4) for b in range(a + 1)]
+    for cls, kinds in seen.items():
+        want = {"one-centre", "two-centre", "ghost"} | ({"equal l"} if cls[0] == cls[1] else {"higher l first", "lower l first"})
+        assert kinds == want, (cls, kinds)
+    for cls in sorted(seen):
+        print(f"int1e<{cls[0]},{cls[1]}>: " + ", ".join(f"{name} {worst[cls, name]:.1e}" for name in bounds))
+    assert not bad, "blocks over their bound:\n" + "\n".join(bad)
+
+    n = mol.nao
+    vp, org = ctypes.c_void_p, origin.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    V2, S2, T2 = (torch.full((n, n), float("nan"), dtype=torch.float64, device=eng.device) for _ in range(3))
+    with torch.cuda.device(eng.device):
+        assert lib().mi_int1e(eng._h, None, None, vp(V2.data_ptr()), None, org, eng._stream()) == 0
+        assert lib().mi_int1e(eng._h, vp(S2.data_ptr()), vp(T2.data_ptr()), None, None, org, eng._stream()) == 0
+    assert np.array_equal(S2.cpu().numpy(), got[0]) and np.array_equal(T2.cpu().numpy(), got[1])
+    dv = np.abs(V2.cpu().numpy() - got[2]).max()
+    print(f"V alone against the full call: {dv:.1e} of max|V| {np.abs(got[2]).max():.1f}")
+    assert dv <= 1e-13 * np.abs(got[2]).max()
+
+
 @pytest.mark.parametrize("name,basis", CASES)
 def test_jk_matches_oracle(name, basis):
     from mi355scf.engine import Engine

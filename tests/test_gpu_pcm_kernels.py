@@ -35,12 +35,27 @@ def _synthetic():
     """Three atoms, each carrying one two-primitive shell of every l = 0..3 (exponents differ per atom): 12 shells, 48 AOs,
     shell index of (atom a, l) = 4 a + l."""
     if "mol" not in _CACHE:
-        basis = {el: [[l, [1.3 + 0.2 * a + 0.1 * l, 0.6], [0.45 + 0.05 * a, 0.5]] for l in range(4)]
-                 for a, el in enumerate(("He", "Be", "C"))}
-        mol = _mol(SYNTH_ATOMS, basis, unit="Bohr")
+        mol = _mol(SYNTH_ATOMS, _synthetic_basis(), unit="Bohr")
         assert mol._bas.shape[0] == 12 and mol.nao == 48
         _CACHE["mol"] = mol
     return _CACHE["mol"]
+
+
+def _synthetic_basis():
+    return {el: [[l, [1.3 + 0.2 * a + 0.1 * l, 0.6], [0.45 + 0.05 * a, 0.5]] for l in range(4)]
+            for a, el in enumerate(("He", "Be", "C"))}
+
+
+def _synthetic_with_ghost():
+    """`_synthetic` plus a fourth centre, a ghost carrying C's four shells (the one-electron kernels' every-class tests): 16
+    shells, 64 AOs, nuclear charges 2, 4, 6, 0."""
+    if "ghost" not in _CACHE:
+        basis = _synthetic_basis()
+        basis["Ghost:C"] = basis["C"]
+        mol = _mol(SYNTH_ATOMS + "; Ghost:C 1.4 -0.8 0.5", basis, unit="Bohr")
+        assert mol._bas.shape[0] == 16 and mol.nao == 64 and list(mol._atm[:, 0]) == [2, 4, 6, 0]
+        _CACHE["ghost"] = mol
+    return _CACHE["ghost"]
 
 
 def _points():
