@@ -210,23 +210,36 @@ struct RysDev {
     int nint[RYS_NMAX + 1];
 };
 
+// Chebyshev series of degree RYS_DEG at s in [-1, 1] (Clenshaw): every evaluation of a root / weight function, host and device
+__host__ __device__ inline double rys_clenshaw(const double *c, double s)
+{
+    double b1 = 0.0, b2 = 0.0;
+    const double s2 = 2.0 * s;
+#pragma unroll
+    for (int k = RYS_DEG; k >= 1; k--) {
+        const double t = s2 * b1 - b2 + c[k];
+        b2 = b1;
+        b1 = t;
+    }
+    return s * b1 - b2 + c[0];
+}
+// interval of x in a table of `nint` intervals of width RYS_H, and the series argument inside it
+__host__ __device__ inline int rys_interval(double x, int nint, double &s)
+{
+    int iv = (int)(x * (1.0 / RYS_H));
+    if (iv >= nint) iv = nint - 1;
+    s = (x - (iv * RYS_H + 0.5 * RYS_H)) * (2.0 / RYS_H);
+    return iv;
+}
+
 template <class T>
 __device__ inline double rys_eval_impl(const T &R, int n, int f, double x)
 {
     int ni = R.nint[n];
     if (x < ni * RYS_H) {
-        int iv = (int)(x * (1.0 / RYS_H));
-        if (iv >= ni) iv = ni - 1;
-        double s = (x - (iv * RYS_H + 0.5 * RYS_H)) * (2.0 / RYS_H);
-        const double *c = R.cheb + R.off[n] + (size_t)(iv * 2 * n + f) * (RYS_DEG + 1);
-        double b1 = 0.0, b2 = 0.0, s2 = 2.0 * s;
-#pragma unroll
-        for (int k = RYS_DEG; k >= 1; k--) {
-            double t = s2 * b1 - b2 + c[k];
-            b2 = b1;
-            b1 = t;
-        }
-        return s * b1 - b2 + c[0];
+        double s;
+        const int iv = rys_interval(x, ni, s);
+        return rys_clenshaw(R.cheb + R.off[n] + (size_t)(iv * 2 * n + f) * (RYS_DEG + 1), s);
     }
     if (f < n) return R.herm_r[n * RYS_NMAX + f] / x;
     return R.herm_w[n * RYS_NMAX + (f - n)] * rsqrt(x);
@@ -240,19 +253,15 @@ extern "C" int mi_rys_roots_host(int n, double x, double *roots, double *weights
     R.cheb = RYS_CHEB_H; R.herm_r = &RYS_HERM_R_H[0][0]; R.herm_w = &RYS_HERM_W_H[0][0];
     for (int i = 0; i <= RYS_NMAX; i++) { R.off[i] = i == 0 ? 0 : RYS_OFFSET_H[i]; R.nint[i] = RYS_NINT_H[i]; }
     for (int f = 0; f < n; f++) {
-        // host path mirrors rys_eval_impl but with std:: functions
+        // host path: rys_eval_impl's branches with std:: functions
         int ni = R.nint[n];
         for (int pass = 0; pass < 2; pass++) {
             int ff = f + pass * n;
             double val;
             if (x < ni * RYS_H) {
-                int iv = (int)(x / RYS_H);
-                if (iv >= ni) iv = ni - 1;
-                double s = (x - (iv * RYS_H + 0.5 * RYS_H)) * (2.0 / RYS_H);
-                const double *c = R.cheb + R.off[n] + (size_t)(iv * 2 * n + ff) * (RYS_DEG + 1);
-                double b1 = 0, b2 = 0;
-                for (int k = RYS_DEG; k >= 1; k--) { double t = 2 * s * b1 - b2 + c[k]; b2 = b1; b1 = t; }
-                val = s * b1 - b2 + c[0];
+                double s;
+                const int iv = rys_interval(x, ni, s);
+                val = rys_clenshaw(R.cheb + R.off[n] + (size_t)(iv * 2 * n + ff) * (RYS_DEG + 1), s);
             } else if (pass == 0) val = R.herm_r[n * RYS_NMAX + f] / x;
             else val = R.herm_w[n * RYS_NMAX + f] / std::sqrt(x);
             (pass == 0 ? roots : weights)[f] = val;
@@ -414,6 +423,7 @@ struct mi_ctx {
     double opt_grad_dtol = 1e-13; // gradient: skip quartets with q_ab q_cd max|G| below this (0: Schwarz only)
     int opt_xf_mfma_min = 300; // transform kernel: MFMA tiles only when the spherical block has at least this many elements
     double opt_tpq_maxprim = 32.0; // thread-per-quartet kernels only when the mean primitive quartets per shell quartet stay below this
+    int64_t opt_tpq_min_tasks = 32768; // ... and the class pair has at least this many quartets (a smaller launch leaves the device idle)
     int opt_eri_tpq = 1;     // thread-per-quartet fused ERI kernels for the low angular classes (0: wave-per-quartet pair everywhere)
     int opt_jk_multi_batch = 8;  // mi_build_jk_multi: densities per launch (1..JKM_BATCH); 8 measured faster per density than 16
     int opt_jk_pair = -1;    // n_dm = 2: one pass with two waves per work item (-1: for stores > 16 GB, 0: one pass per density, 1: always)
@@ -860,6 +870,7 @@ extern "C" int mi_set_option(mi_ctx *c, const char *key, double value)
     else if (k == "xf_mlds") c->opt_xf_mlds = (int)value;
     else if (k == "eri_tpq") c->opt_eri_tpq = (int)value;
     else if (k == "tpq_maxprim") c->opt_tpq_maxprim = value;
+    else if (k == "tpq_min_tasks") c->opt_tpq_min_tasks = (int64_t)value;
     else if (k == "xf_mfma_min") c->opt_xf_mfma_min = (int)value;   // takes effect at the next mi_eri_prepare
     else if (k == "grad_dtol") c->opt_grad_dtol = value;
     else if (k == "grad_prefetch") c->opt_grad_prefetch = (int)value;   // takes effect at the next mi_eri_prepare
@@ -1463,26 +1474,149 @@ __global__ __launch_bounds__(256) void live_fill_kernel(LiveArgs A, const int64_
 }
 
 // Does any AO quadruple of the shell quartet land in a tile that is resident on this rank?  (<= 16 block
-// combinations; every symmetry image of a quadruple maps to the same canonical tile.)
+// combinations; every symmetry image of a quadruple maps to the same canonical tile.)  Corner c of the quartet's block ranges:
+// bit 0 .. 3 picks the last instead of the first block of shell i, j, k, l.
+__device__ inline bool block_corner_resident(const int32_t *table, int corner, int ao_i, int ni, int ao_j, int nj, int ao_k, int nk,
+                                             int ao_l, int nl)
+{
+    int I = (corner & 1) ? (ao_i + ni - 1) >> 3 : ao_i >> 3;
+    int J = (corner & 2) ? (ao_j + nj - 1) >> 3 : ao_j >> 3;
+    int K = (corner & 4) ? (ao_k + nk - 1) >> 3 : ao_k >> 3;
+    int L = (corner & 8) ? (ao_l + nl - 1) >> 3 : ao_l >> 3;
+    int hi = max(I, J), lo = min(I, J), bij = hi * (hi + 1) / 2 + lo;
+    hi = max(K, L); lo = min(K, L);
+    int bkl = hi * (hi + 1) / 2 + lo;
+    int bmax = max(bij, bkl), bmin = min(bij, bkl);
+    return table[(size_t)bmax * (bmax + 1) / 2 + bmin] >= 0;
+}
+// one thread looks at all 16 corners (thread-per-quartet kernels) ...
+__device__ inline bool quartet_has_resident_tile_thread(const int32_t *table, int ao_i, int ni, int ao_j, int nj, int ao_k, int nk, int ao_l, int nl)
+{
+    bool hit = false;
+    for (int q = 0; q < 16; q++) hit = hit || block_corner_resident(table, q, ao_i, ni, ao_j, nj, ao_k, nk, ao_l, nl);
+    return hit;
+}
+// ... or 16 lanes one each (wave-per-quartet kernels)
 __device__ inline bool quartet_has_resident_tile(const int32_t *table, int ao_i, int ni, int ao_j, int nj, int ao_k, int nk,
                                                  int ao_l, int nl, int lane, int gsz = 64, int grp = 0)
 {
     // `lane` is the lane inside a group of `gsz` (>= 16) lanes working on this quartet; groups vote separately
-    bool hit = false;
-    if (lane < 16) {
-        int I = (lane & 1) ? (ao_i + ni - 1) >> 3 : ao_i >> 3;
-        int J = (lane & 2) ? (ao_j + nj - 1) >> 3 : ao_j >> 3;
-        int K = (lane & 4) ? (ao_k + nk - 1) >> 3 : ao_k >> 3;
-        int L = (lane & 8) ? (ao_l + nl - 1) >> 3 : ao_l >> 3;
-        int hi = max(I, J), lo = min(I, J), bij = hi * (hi + 1) / 2 + lo;
-        hi = max(K, L); lo = min(K, L);
-        int bkl = hi * (hi + 1) / 2 + lo;
-        int bmax = max(bij, bkl), bmin = min(bij, bkl);
-        hit = table[(size_t)bmax * (bmax + 1) / 2 + bmin] >= 0;
-    }
+    const bool hit = lane < 16 && block_corner_resident(table, lane, ao_i, ni, ao_j, nj, ao_k, nk, ao_l, nl);
     const unsigned long long votes = __ballot(hit);
     const unsigned long long gmask = (gsz >= 64 ? ~0ull : ((1ull << gsz) - 1ull) << (gsz * grp));
     return (votes & gmask) != 0ull;
+}
+
+// ---- the Rys phases of the wave-per-quartet kernels (eri_rys_kernel, the fused kernel's first half, eri_grad_rows_kernel) ----
+// LDS of one quartet's Rys phases: T0 [PB n][3][tsz] recurrence tables, then rw [PB][2 n] roots and weights; what a kernel keeps
+// behind them (staged primitive records, the row kernel's matrices) starts at doubles().  Kernels and host launches size from it.
+struct RysLds {
+    int PB, n, tsz;
+    __host__ __device__ size_t rw() const { return (size_t)PB * n * 3 * tsz; }
+    __host__ __device__ size_t doubles() const { return rw() + (size_t)PB * 2 * n; }
+};
+
+// prim_b / prim_k: the primitive-pair records of the two pairs; primitive quartet pq = ip * ncd + jp.
+// ONE_TRIP: the caller's batch fits the group (npq * 3 n <= GSZ, as PB = GSZ / (3 n) guarantees), so a lane has at most one item and
+// the loop is a guard; the 16-lane groups of eri_rys_kernel would otherwise diverge on the trip count (measured 5-12 % on their
+// classes).  The row kernel keeps its strided loop.
+// phase R: roots and weights of the primitive quartets pq0 .. pq0 + npq - 1, one (primitive quartet, function) per lane of the group
+template <int GSZ, bool ONE_TRIP>
+__device__ __forceinline__ void rys_phase_roots(const RysDev &rys, double omega, int n, const double *prim_b, const double *prim_k, int ncd, int pq0,
+                                                int npq, int lane, double *rw)
+{
+    for (int idx = lane; idx < npq * 2 * n; idx += GSZ) {
+        const int pql = idx / (2 * n), f = idx - pql * 2 * n;
+        const int pq = pq0 + pql, ip = pq / ncd, jp = pq - ip * ncd;
+        const double *b = prim_b + (size_t)ip * 8, *k = prim_k + (size_t)jp * 8;
+        const double p = b[0], q = k[0];
+        const double dx = b[1] - k[1], dy = b[2] - k[2], dz = b[3] - k[3];
+        const double rho = p * q / (p + q), x = rho * (dx * dx + dy * dy + dz * dz);
+        if (omega > 0.0) rw[idx] = rys_attenuate(rys, n, f, rho, x, omega);
+        else rw[idx] = rys_eval(rys, n, f, x);
+        if (ONE_TRIP) break;
+    }
+}
+// phase A: the 2-D vertical recurrence tables T[i][m], i <= nmax, m <= mmax, one (primitive quartet, root, direction) per lane;
+// the z table carries the weight and the prefactor 2 pi^(5/2) K_ab K_cd / (p q sqrt(p + q))
+template <int GSZ, bool ONE_TRIP>
+__device__ __forceinline__ void rys_phase_tables(int n, int nmax, int mmax, int tsz, const double *prim_b, const double *prim_k, int ncd, int pq0,
+                                                 int npq, int lane, const double *rw, double *T0)
+{
+    const int M1 = mmax + 1;
+    for (int idx = lane; idx < npq * n * 3; idx += GSZ) {
+        const int pql = idx / (3 * n), rem = idx - pql * 3 * n, r = rem / 3, d = rem - r * 3;
+        const int pq = pq0 + pql, ip = pq / ncd, jp = pq - ip * ncd;
+        const double *b = prim_b + (size_t)ip * 8, *k = prim_k + (size_t)jp * 8;
+        const double p = b[0], q = k[0], pq1 = 1.0 / (p + q);
+        const double u = rw[pql * 2 * n + r];
+        const double PQd = b[1 + d] - k[1 + d];
+        const double b00 = 0.5 * u * pq1, b10 = 0.5 / p * (1.0 - u * q * pq1), b01 = 0.5 / q * (1.0 - u * p * pq1);
+        const double c00 = b[4 + d] - u * q * pq1 * PQd, c01 = k[4 + d] + u * p * pq1 * PQd;
+        double *T = T0 + (size_t)idx * tsz;
+        double t00 = 1.0;
+        if (d == 2) t00 = rw[pql * 2 * n + n + r] * b[7] * k[7] * 34.986836655249725 /* 2 pi^2.5 */ * pq1 * sqrt(p + q) / (p * q);
+        T[0] = t00;
+        double tm = 0.0, tc = t00;
+        for (int i = 0; i < nmax; i++) {
+            const double tn = c00 * tc + i * b10 * tm;
+            T[(i + 1) * M1] = tn;
+            tm = tc; tc = tn;
+        }
+        for (int m = 0; m < mmax; m++)
+            for (int i = 0; i <= nmax; i++) {
+                double v = c01 * T[i * M1 + m];
+                if (m > 0) v += m * b01 * T[i * M1 + m - 1];
+                if (i > 0) v += i * b00 * T[(i - 1) * M1 + m];
+                T[i * M1 + m + 1] = v;
+            }
+        if (ONE_TRIP) break;
+    }
+}
+
+// The Rys phases of ONE quartet on a group of GSZ lanes: per batch of PB primitive quartets phase R, phase A, then phase C, the
+// component products through the packed `comp` words, MAXC components per lane in registers.  nPQ: primitive quartets of this
+// group's quartet (0: the group has none and only keeps the barriers); nPQ_all: the largest nPQ of the wave, the uniform trip
+// count.  lds: the group's RysLds block.  store(c, v) receives component c of the contracted [e0|f0] block.
+template <int MAXC, int GSZ, class Store>
+__device__ __forceinline__ void rys_quartet_body(const EriArgs &A, const double *prim_b, const double *prim_k, int ncd, int nPQ, int nPQ_all, int lane, double *lds, Store store)
+{
+    const int n = A.nroots, tsz = A.tsz, PB = A.PB;
+    double *T0 = lds, *rw = lds + RysLds{PB, n, tsz}.rw();
+    for (int c0 = 0; c0 < A.ncomp; c0 += GSZ * MAXC) {
+        double acc[MAXC];
+        uint32_t idx[MAXC];
+#pragma unroll
+        for (int ci = 0; ci < MAXC; ci++) {
+            acc[ci] = 0.0;
+            const int c = c0 + ci * GSZ + lane;
+            idx[ci] = (c < A.ncomp) ? A.comp[c] : 0xFFFFFFFFu;
+        }
+        for (int pq0 = 0; pq0 < nPQ_all; pq0 += PB) {
+            const int npq = GSZ == 64 ? min(PB, nPQ - pq0) : max(0, min(PB, nPQ - pq0));
+            rys_phase_roots<GSZ, true>(A.rys, A.omega, n, prim_b, prim_k, ncd, pq0, npq, lane, rw);
+            __syncthreads();
+            rys_phase_tables<GSZ, true>(n, A.nmax, A.mmax, tsz, prim_b, prim_k, ncd, pq0, npq, lane, rw, T0);
+            __syncthreads();
+            const int nslot = npq * n;
+            for (int s = 0; s < nslot; s++) {
+                const double *Tx = T0 + (size_t)s * 3 * tsz, *Ty = Tx + tsz, *Tz = Ty + tsz;
+#pragma unroll
+                for (int ci = 0; ci < MAXC; ci++) {
+                    const uint32_t w = idx[ci];
+                    if (w != 0xFFFFFFFFu) acc[ci] += Tx[w & 1023u] * Ty[(w >> 10) & 1023u] * Tz[(w >> 20) & 1023u];
+                }
+            }
+            __syncthreads();
+        }
+        if (nPQ > 0) {
+#pragma unroll
+            for (int ci = 0; ci < MAXC; ci++) {
+                const int c = c0 + ci * GSZ + lane;
+                if (c < A.ncomp) store(c, acc[ci]);
+            }
+        }
+    }
 }
 
 // GSZ = lanes per shell quartet: 64, or 16 (four quartets per wave) for the low angular classes, whose handful of
@@ -1511,191 +1645,27 @@ __global__ __launch_bounds__(64) void eri_rys_kernel(EriArgs A)
             live = quartet_has_resident_tile(A.own_table, ab.ao_i, A.ni, ab.ao_j, A.nj, cd.ao_i, A.nk, cd.ao_j, A.nl, lane, GSZ, grp) && live;
         if (A.scr.negligible(ib, ik, ab.sh_i, ab.sh_j, cd.sh_i, cd.sh_j)) live = false;
     }
-    const int n = A.nroots, tsz = A.tsz, M1 = A.mmax + 1;
-    const int ncd = cd.nprim, nPQ = live ? ab.nprim * ncd : 0;
-    const int PB = A.PB;
-    const size_t lds_per = (size_t)PB * n * 3 * tsz + (size_t)PB * 2 * n + (size_t)A.prim_lds * 8;
-    double *lds = QPW == 1 ? lds_all : lds_all + (size_t)grp * lds_per;
-    double *T0 = lds;                       // [PB*n][3][tsz]
-    double *rw = lds + (size_t)PB * n * 3 * tsz; // [PB][2n]
+    const RysLds L{A.PB, A.nroots, A.tsz};
+    double *lds = lds_all + (size_t)grp * (L.doubles() + (size_t)A.prim_lds * 8);
     // primitive-pair records {p, P, P-A, K} of the bra and the ket pair: staged once per quartet in LDS (coalesced 64-byte
     // records) so that the R and A phases of every batch read them on-chip instead of paying a global round trip each
     const double *prim_b = A.prim + (size_t)ab.prim_off * 8, *prim_k = A.prim + (size_t)cd.prim_off * 8;
     if (A.prim_lds > 0) {
-        double *pl = rw + (size_t)PB * 2 * n;
-        const int nb8 = ab.nprim * 8, nk8 = ncd * 8;
-        if (live && ab.nprim + ncd <= A.prim_lds) {
+        double *pl = lds + L.doubles();
+        const int nb8 = ab.nprim * 8, nk8 = cd.nprim * 8;
+        if (live && ab.nprim + cd.nprim <= A.prim_lds) {
             for (int x = lane; x < nb8; x += GSZ) pl[x] = prim_b[x];
             for (int x = lane; x < nk8; x += GSZ) pl[nb8 + x] = prim_k[x];
             prim_b = pl; prim_k = pl + nb8;
         }
         __syncthreads();
     }
-    double *wout = A.work + (size_t)tl * A.ncomp;
-    int nPQ_all = nPQ; // uniform trip count over the quartets sharing this wave (the barriers below sit in the loop)
+    const int nPQ = live ? ab.nprim * cd.nprim : 0;
+    int nPQ_all = nPQ; // uniform trip count over the quartets sharing this wave (the barriers sit in the batch loop)
     if (QPW > 1)
         for (int o = GSZ; o < 64; o <<= 1) nPQ_all = max(nPQ_all, __shfl_xor(nPQ_all, o));
-
-    for (int c0 = 0; c0 < A.ncomp; c0 += GSZ * MAXC) {
-        double acc[MAXC];
-        uint32_t idx[MAXC];
-#pragma unroll
-        for (int ci = 0; ci < MAXC; ci++) {
-            acc[ci] = 0.0;
-            int c = c0 + ci * GSZ + lane;
-            idx[ci] = (c < A.ncomp) ? A.comp[c] : 0xFFFFFFFFu;
-        }
-        for (int pq0 = 0; pq0 < nPQ_all; pq0 += PB) {
-            const int npq = QPW == 1 ? min(PB, nPQ - pq0) : max(0, min(PB, nPQ - pq0));
-            // ---- phase R
-            if (lane < npq * 2 * n) {
-                int pql = lane / (2 * n), f = lane - pql * 2 * n;
-                int pq = pq0 + pql, ip = pq / ncd, jp = pq - ip * ncd;
-                const double *b = prim_b + (size_t)ip * 8, *k = prim_k + (size_t)jp * 8;
-                double p = b[0], q = k[0];
-                double dx = b[1] - k[1], dy = b[2] - k[2], dz = b[3] - k[3];
-                double x = p * q / (p + q) * (dx * dx + dy * dy + dz * dz);
-                if (A.omega > 0.0) rw[pql * 2 * n + f] = rys_attenuate(A.rys, n, f, p * q / (p + q), x, A.omega);
-                else rw[pql * 2 * n + f] = rys_eval(A.rys, n, f, x);
-            }
-            __syncthreads();
-            // ---- phase A
-            if (lane < npq * n * 3) {
-                int pql = lane / (3 * n), rem = lane - pql * 3 * n, r = rem / 3, d = rem - r * 3;
-                int pq = pq0 + pql, ip = pq / ncd, jp = pq - ip * ncd;
-                const double *b = prim_b + (size_t)ip * 8, *k = prim_k + (size_t)jp * 8;
-                double p = b[0], q = k[0], pq1 = 1.0 / (p + q);
-                double u = rw[pql * 2 * n + r];
-                double PQd = b[1 + d] - k[1 + d];
-                double b00 = 0.5 * u * pq1;
-                double b10 = 0.5 / p * (1.0 - u * q * pq1);
-                double b01 = 0.5 / q * (1.0 - u * p * pq1);
-                double c00 = b[4 + d] - u * q * pq1 * PQd;
-                double c01 = k[4 + d] + u * p * pq1 * PQd;
-                double *T = T0 + ((size_t)(pql * n + r) * 3 + d) * tsz;
-                double t00 = 1.0;
-                if (d == 2) {
-                    double w = rw[pql * 2 * n + n + r];
-                    t00 = w * b[7] * k[7] * 34.986836655249725 /* 2 pi^2.5 */ * pq1 * sqrt(p + q) / (p * q) ;
-                    // 2 pi^(5/2) / (p q sqrt(p+q)) = 2 pi^2.5 * sqrt(p+q)/(p q (p+q))
-                }
-                T[0] = t00;
-                double tm = 0.0, tc = t00;
-                for (int i = 0; i < A.nmax; i++) {
-                    double tn = c00 * tc + i * b10 * tm;
-                    T[(i + 1) * M1] = tn;
-                    tm = tc; tc = tn;
-                }
-                for (int m = 0; m < A.mmax; m++)
-                    for (int i = 0; i <= A.nmax; i++) {
-                        double v = c01 * T[i * M1 + m];
-                        if (m > 0) v += m * b01 * T[i * M1 + m - 1];
-                        if (i > 0) v += i * b00 * T[(i - 1) * M1 + m];
-                        T[i * M1 + m + 1] = v;
-                    }
-            }
-            __syncthreads();
-            // ---- phase C
-            const int nslot = npq * n;
-            for (int s = 0; s < nslot; s++) {
-                const double *Tx = T0 + (size_t)s * 3 * tsz, *Ty = Tx + tsz, *Tz = Ty + tsz;
-#pragma unroll
-                for (int ci = 0; ci < MAXC; ci++) {
-                    uint32_t w = idx[ci];
-                    if (w != 0xFFFFFFFFu) acc[ci] += Tx[w & 1023u] * Ty[(w >> 10) & 1023u] * Tz[(w >> 20) & 1023u];
-                }
-            }
-            __syncthreads();
-        }
-        if (QPW == 1 || live) {
-#pragma unroll
-            for (int ci = 0; ci < MAXC; ci++) {
-                int c = c0 + ci * GSZ + lane;
-                if (c < A.ncomp) wout[c] = acc[ci];
-            }
-        }
-    }
-}
-
-// The Rys phases of eri_rys_kernel for ONE quartet on ONE wave with the contracted [e0|f0] block written to LDS instead of the
-// hand-over buffer: the first half of the fused evaluation kernel (eri_fused_kernel).  `scratch` holds the recurrence tables and
-// the roots / weights of a batch ([PB n][3][tsz] + [PB][2 n] doubles), `out` the block ([ncomp] doubles, both in LDS).
-template <int MAXC>
-__device__ __forceinline__ void rys_core(const EriArgs &A, const PairRec &ab, const PairRec &cd, const int lane, double *scratch, double *out)
-{
-    const int n = A.nroots, tsz = A.tsz, M1 = A.mmax + 1;
-    const int ncd = cd.nprim, nPQ = ab.nprim * ncd;
-    const int PB = A.PB;
-    double *T0 = scratch;                              // [PB*n][3][tsz]
-    double *rw = scratch + (size_t)PB * n * 3 * tsz;   // [PB][2n]
-    const double *prim_b = A.prim + (size_t)ab.prim_off * 8, *prim_k = A.prim + (size_t)cd.prim_off * 8;
-    for (int c0 = 0; c0 < A.ncomp; c0 += 64 * MAXC) {
-        double acc[MAXC];
-        uint32_t idx[MAXC];
-#pragma unroll
-        for (int ci = 0; ci < MAXC; ci++) {
-            acc[ci] = 0.0;
-            const int c = c0 + ci * 64 + lane;
-            idx[ci] = (c < A.ncomp) ? A.comp[c] : 0xFFFFFFFFu;
-        }
-        for (int pq0 = 0; pq0 < nPQ; pq0 += PB) {
-            const int npq = min(PB, nPQ - pq0);
-            if (lane < npq * 2 * n) {                  // roots and weights
-                const int pql = lane / (2 * n), f = lane - pql * 2 * n;
-                const int pq = pq0 + pql, ip = pq / ncd, jp = pq - ip * ncd;
-                const double *b = prim_b + (size_t)ip * 8, *k = prim_k + (size_t)jp * 8;
-                const double p = b[0], q = k[0];
-                const double dx = b[1] - k[1], dy = b[2] - k[2], dz = b[3] - k[3];
-                const double rho = p * q / (p + q), x = rho * (dx * dx + dy * dy + dz * dz);
-                if (A.omega > 0.0) rw[pql * 2 * n + f] = rys_attenuate(A.rys, n, f, rho, x, A.omega);
-                else rw[pql * 2 * n + f] = rys_eval(A.rys, n, f, p * q / (p + q) * (dx * dx + dy * dy + dz * dz));
-            }
-            __syncthreads();
-            if (lane < npq * n * 3) {                  // 2-D recurrence tables
-                const int pql = lane / (3 * n), rem = lane - pql * 3 * n, r = rem / 3, d = rem - r * 3;
-                const int pq = pq0 + pql, ip = pq / ncd, jp = pq - ip * ncd;
-                const double *b = prim_b + (size_t)ip * 8, *k = prim_k + (size_t)jp * 8;
-                const double p = b[0], q = k[0], pq1 = 1.0 / (p + q);
-                const double u = rw[pql * 2 * n + r];
-                const double PQd = b[1 + d] - k[1 + d];
-                const double b00 = 0.5 * u * pq1, b10 = 0.5 / p * (1.0 - u * q * pq1), b01 = 0.5 / q * (1.0 - u * p * pq1);
-                const double c00 = b[4 + d] - u * q * pq1 * PQd, c01 = k[4 + d] + u * p * pq1 * PQd;
-                double *T = T0 + ((size_t)(pql * n + r) * 3 + d) * tsz;
-                double t00 = 1.0;
-                if (d == 2) t00 = rw[pql * 2 * n + n + r] * b[7] * k[7] * 34.986836655249725 /* 2 pi^2.5 */ * pq1 * sqrt(p + q) / (p * q);
-                T[0] = t00;
-                double tm = 0.0, tc = t00;
-                for (int i = 0; i < A.nmax; i++) {
-                    const double tn = c00 * tc + i * b10 * tm;
-                    T[(i + 1) * M1] = tn;
-                    tm = tc; tc = tn;
-                }
-                for (int m = 0; m < A.mmax; m++)
-                    for (int i = 0; i <= A.nmax; i++) {
-                        double v = c01 * T[i * M1 + m];
-                        if (m > 0) v += m * b01 * T[i * M1 + m - 1];
-                        if (i > 0) v += i * b00 * T[(i - 1) * M1 + m];
-                        T[i * M1 + m + 1] = v;
-                    }
-            }
-            __syncthreads();
-            const int nslot = npq * n;                 // component products
-            for (int s_ = 0; s_ < nslot; s_++) {
-                const double *Tx = T0 + (size_t)s_ * 3 * tsz, *Ty = Tx + tsz, *Tz = Ty + tsz;
-#pragma unroll
-                for (int ci = 0; ci < MAXC; ci++) {
-                    const uint32_t w = idx[ci];
-                    if (w != 0xFFFFFFFFu) acc[ci] += Tx[w & 1023u] * Ty[(w >> 10) & 1023u] * Tz[(w >> 20) & 1023u];
-                }
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int ci = 0; ci < MAXC; ci++) {
-            const int c = c0 + ci * 64 + lane;
-            if (c < A.ncomp) out[c] = acc[ci];
-        }
-    }
+    double *wout = A.work + (size_t)tl * A.ncomp;   // the hand-over buffer
+    rys_quartet_body<MAXC, GSZ>(A, prim_b, prim_k, cd.nprim, nPQ, nPQ_all, lane, lds, [&](int c, double v) { wout[c] = v; });
 }
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
@@ -1814,7 +1784,7 @@ __device__ inline void put_tile_at(const XfArgs &A, int64_t base, int i, int j, 
 }
 
 // FMAXC = 0: the [e0|f0] block comes from the hand-over buffer (A.work) of a preceding eri_rys_kernel launch.
-// FMAXC > 0 (GSZ = 64 only): FUSED evaluation -- the Rys phases (rys_core<FMAXC>, arguments *R) run first in this wave and leave
+// FMAXC > 0 (GSZ = 64 only): FUSED evaluation -- the Rys phases (rys_quartet_body<FMAXC, 64>, arguments *R) run first in this wave and leave
 // the block in LDS: no hand-over buffer (51.8 of the 139.8 GB written by an evaluation of ibuprofen/def2-TZVP), one launch
 // and one task look-up per quartet instead of two.
 template <bool MFMA, int GSZ, int FMAXC>
@@ -1850,8 +1820,10 @@ __device__ __forceinline__ void xf_body(const XfArgs &A, const EriArgs *R)
         Mab = ML; Mcd = ML + na;
     }
     const double *MabT = Mab + A.nsab * A.ne, *McdT = Mcd + A.nscd * A.nf;   // [e][r], [f][c]
-    if (FMAXC > 0) rys_core<(FMAXC > 0 ? FMAXC : 1)>(*R, ab, cd, lane, X /* tables over the not yet used X block */, E0);
-    else if (live)
+    if (FMAXC > 0) {   // (one quartet per wave and live here; the tables lie over the not yet used X block)
+        rys_quartet_body<(FMAXC > 0 ? FMAXC : 1), 64>(*R, R->prim + (size_t)ab.prim_off * 8, R->prim + (size_t)cd.prim_off * 8, cd.nprim, ab.nprim * cd.nprim,
+                                                       ab.nprim * cd.nprim, lane, X, [&](int c, double v) { E0[c] = v; });
+    } else if (live)
         for (int c = lane; c < A.ne * A.nf; c += GSZ) E0[c] = E0g[c];
     // symmetry images: role of (a0,a1,a2,a3) = (ab.i, ab.j, cd.i, cd.j) in (i,j,k,l); bit 0 swaps the bra pair, bit 1 the ket
     // pair, bit 2 exchanges bra and ket.  Which images can land in a canonical tile (I >= J, K >= L) at all is decided once per
@@ -2115,6 +2087,16 @@ __device__ __forceinline__ void tpq_pair_transform(const double *in, double *out
 }
 
 #define TPQ_BLOCK 128
+static size_t tpq_cheb_bytes(int nr) { return sizeof(double) * (size_t)RYS_NINT_H[nr] * 2 * nr * (RYS_DEG + 1); }
+// Chebyshev coefficients of the 2 NR root / weight functions, all intervals, staged in LDS by the workgroup (ends in a barrier)
+template <int NR>
+__device__ __forceinline__ void tpq_stage_cheb(const RysDev &rys, double *cheb)
+{
+    const int ntab = rys.nint[NR] * 2 * NR * (RYS_DEG + 1);
+    const double *src = rys.cheb + rys.off[NR];
+    for (int q = threadIdx.x; q < ntab; q += TPQ_BLOCK) cheb[q] = src[q];
+    __syncthreads();
+}
 template <int LA, int LB, int LC, int LD>
 __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_kernel(TpqArgs A)
 {
@@ -2122,14 +2104,9 @@ __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_kernel(TpqArgs A)
     constexpr int NMAX = LA + LB, MMAX = LC + LD;
     constexpr int NE = c_ne(LA, LB), NF = c_ne(LC, LD);
     constexpr int NSAB = (2 * LA + 1) * (2 * LB + 1), NSCD = (2 * LC + 1) * (2 * LD + 1);
-    extern __shared__ double cheb[];   // Chebyshev coefficients of the 2 NR root/weight functions, all intervals
+    extern __shared__ double cheb[];
     const int nint = A.rys.nint[NR];
-    {
-        const int ntab = nint * 2 * NR * (RYS_DEG + 1);
-        const double *src = A.rys.cheb + A.rys.off[NR];
-        for (int q = threadIdx.x; q < ntab; q += TPQ_BLOCK) cheb[q] = src[q];
-    }
-    __syncthreads();
+    tpq_stage_cheb<NR>(A.rys, cheb);
     const int64_t tl = (int64_t)xcd_block(blockIdx.x, A.xcd) * TPQ_BLOCK + threadIdx.x;
     if (tl >= A.ntask) return;
     int ib, ik;
@@ -2140,17 +2117,7 @@ __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_kernel(TpqArgs A)
     // block ranges of the four shells: which index images can land in a canonical tile, and is anything resident here
     const int lo[4] = {ab.ao_i >> 3, ab.ao_j >> 3, cd.ao_i >> 3, cd.ao_j >> 3};
     const int hi[4] = {(ab.ao_i + ni - 1) >> 3, (ab.ao_j + nj - 1) >> 3, (cd.ao_i + nk - 1) >> 3, (cd.ao_j + nl - 1) >> 3};
-    if (A.check_owner) {
-        bool hit = false;
-        for (int q = 0; q < 16; q++) {
-            int I = (q & 1) ? hi[0] : lo[0], J = (q & 2) ? hi[1] : lo[1], K = (q & 4) ? hi[2] : lo[2], L = (q & 8) ? hi[3] : lo[3];
-            int h1 = max(I, J), l1 = min(I, J), bij = h1 * (h1 + 1) / 2 + l1;
-            int h2 = max(K, L), l2 = min(K, L), bkl = h2 * (h2 + 1) / 2 + l2;
-            int bmax = max(bij, bkl), bmin = min(bij, bkl);
-            hit = hit || A.X.tile_table[(size_t)bmax * (bmax + 1) / 2 + bmin] >= 0;
-        }
-        if (!hit) return;
-    }
+    if (A.check_owner && !quartet_has_resident_tile_thread(A.X.tile_table, ab.ao_i, ni, ab.ao_j, nj, cd.ao_i, nk, cd.ao_j, nl)) return;
 
     double acc[NE * NF];
 #pragma unroll
@@ -2434,6 +2401,9 @@ static int64_t class_prefix(const PairClass &B, const PairClass &Kc, bool same, 
 // the 16-lane groups need more primitive batches / passes than they win by overlapping four latency chains).
 static bool eri_small_class(const EriArgs &E) { return E.nroots <= 2 && E.ncomp <= 18; }
 
+// LDS bytes of one quartet in eri_rys_kernel: its Rys block and the staged primitive records
+static size_t eri_rys_lds_bytes(const EriArgs &E) { return sizeof(double) * (RysLds{E.PB, E.nroots, E.tsz}.doubles() + (size_t)E.prim_lds * 8); }
+
 static int launch_eri(mi_ctx *c, EriArgs &E, int nblocks, hipStream_t st)
 {
     // E.ntask tasks; the low angular classes run four quartets per wave (16 lanes each) unless their contraction depth
@@ -2448,7 +2418,7 @@ static int launch_eri(mi_ctx *c, EriArgs &E, int nblocks, hipStream_t st)
         if (cost16 < cost64) {
             EriArgs G = E;
             G.PB = pb16;
-            size_t shm = 4 * sizeof(double) * ((size_t)G.PB * G.nroots * 3 * G.tsz + (size_t)G.PB * 2 * G.nroots + (size_t)G.prim_lds * 8);
+            const size_t shm = 4 * eri_rys_lds_bytes(G);
             hipLaunchKernelGGL((eri_rys_kernel<2, 16>), dim3(eri_grid((nblocks + 3) / 4, G.xcd)), dim3(64), shm, st, G);
             HIPCHK(hipGetLastError());
             return 0;
@@ -2460,7 +2430,7 @@ static int launch_eri(mi_ctx *c, EriArgs &E, int nblocks, hipStream_t st)
         E.h_shared_np * E.h_vary_max4 <= c->opt_rys_qpw_maxprim) {
         EriArgs G = E;
         G.PB = std::max(1, 16 / (3 * E.nroots));
-        const size_t shm = 4 * sizeof(double) * ((size_t)G.PB * G.nroots * 3 * G.tsz + (size_t)G.PB * 2 * G.nroots + (size_t)G.prim_lds * 8);
+        const size_t shm = 4 * eri_rys_lds_bytes(G);
         const dim3 grid(eri_grid((nblocks + 3) / 4, G.xcd));
         const int per16 = (E.ncomp + 15) / 16;
         if (shm <= 64 * 1024) {
@@ -2471,7 +2441,7 @@ static int launch_eri(mi_ctx *c, EriArgs &E, int nblocks, hipStream_t st)
             return 0;
         }
     }
-    size_t shm = sizeof(double) * ((size_t)E.PB * E.nroots * 3 * E.tsz + (size_t)E.PB * 2 * E.nroots + (size_t)E.prim_lds * 8);
+    const size_t shm = eri_rys_lds_bytes(E);
     if (perlane <= 1) hipLaunchKernelGGL((eri_rys_kernel<1, 64>), dim3(eri_grid(nblocks, E.xcd)), dim3(64), shm, st, E);
     else if (perlane <= 2 && c->opt_rys_fine) hipLaunchKernelGGL((eri_rys_kernel<2, 64>), dim3(eri_grid(nblocks, E.xcd)), dim3(64), shm, st, E);
     else if (perlane <= 4) hipLaunchKernelGGL((eri_rys_kernel<4, 64>), dim3(eri_grid(nblocks, E.xcd)), dim3(64), shm, st, E);
@@ -2497,8 +2467,7 @@ static void setup_eri_dims(EriArgs &E, int la, int lb, int lc, int ld)
 template <int LA, int LB, int LC, int LD>
 static int launch_eri_tpq_t(const TpqArgs &Q, hipStream_t st)
 {
-    constexpr int NR = (LA + LB + LC + LD) / 2 + 1;
-    const size_t shm = sizeof(double) * (size_t)RYS_NINT_H[NR] * 2 * NR * (RYS_DEG + 1);
+    const size_t shm = tpq_cheb_bytes((LA + LB + LC + LD) / 2 + 1);
     const int64_t MAXB = (int64_t)1 << 24;
     for (int64_t t0 = 0; t0 < Q.ntask; t0 += MAXB * TPQ_BLOCK) {   // grid.x stays well below 2^31 (also after the XCD-map rounding)
         TpqArgs P = Q;
@@ -2512,11 +2481,12 @@ static int launch_eri_tpq_t(const TpqArgs &Q, hipStream_t st)
     return 1;
 }
 
-static bool tpq_has_class(int la, int lb, int lc, int ld);
-static int launch_eri_tpq(int la, int lb, int lc, int ld, const TpqArgs &Q, hipStream_t st)
+// returns 1 if the class has a thread-per-quartet kernel (and it was launched), 0 if not, -1 on error.  dry: only answers the question
+static int launch_eri_tpq(int la, int lb, int lc, int ld, const TpqArgs &Q, hipStream_t st, bool dry = false)
 {
+    if (la > 3 || lb > 3 || lc > 3 || ld > 3) return 0;
     const int key = ((la * 4 + lb) * 4 + lc) * 4 + ld;
-#define TPQ_CASE(a, b, c_, d) case (((a) * 4 + (b)) * 4 + (c_)) * 4 + (d): return launch_eri_tpq_t<a, b, c_, d>(Q, st)
+#define TPQ_CASE(a, b, c_, d) case (((a) * 4 + (b)) * 4 + (c_)) * 4 + (d): return dry ? 1 : launch_eri_tpq_t<a, b, c_, d>(Q, st)
     switch (key) {
         TPQ_CASE(0, 0, 0, 0); TPQ_CASE(1, 0, 0, 0); TPQ_CASE(1, 0, 1, 0); TPQ_CASE(1, 1, 0, 0); TPQ_CASE(1, 1, 1, 0);
         TPQ_CASE(2, 0, 0, 0); TPQ_CASE(2, 0, 1, 0); TPQ_CASE(2, 0, 1, 1); TPQ_CASE(2, 0, 2, 0); TPQ_CASE(2, 1, 0, 0);
@@ -2530,11 +2500,8 @@ static int launch_eri_tpq(int la, int lb, int lc, int ld, const TpqArgs &Q, hipS
 }
 static bool tpq_has_class(int la, int lb, int lc, int ld)
 {
-    static const int keys[][4] = {{0,0,0,0},{1,0,0,0},{1,0,1,0},{1,1,0,0},{1,1,1,0},{2,0,0,0},{2,0,1,0},{2,0,1,1},{2,0,2,0},{2,1,0,0},
-                                  {2,1,1,0},{2,2,0,0},{3,0,0,0},{3,0,1,0},{3,0,2,0},{3,1,0,0},{3,2,0,0},{2,1,2,0},{2,2,1,0},{3,3,0,0},
-                                  {3,1,1,0},{3,0,1,1},{3,0,3,0}};
-    for (const auto &k : keys) if (k[0] == la && k[1] == lb && k[2] == lc && k[3] == ld) return true;
-    return false;
+    TpqArgs none{};
+    return launch_eri_tpq(la, lb, lc, ld, none, nullptr, true) == 1;
 }
 
 // Sharding plan of the resident tile store: enumerate the (J,K,L) runs that survive the block-pair
@@ -3163,7 +3130,7 @@ static int prepare_evaluate_class_pair(PrepareState &S, PairClass &B, PairClass 
     const int64_t *d_prefix = S.d_prefix;
     ClassPairEval P{};
     P.B = &B; P.Kc = &Kc; P.ntask = ntask;
-    const bool tpq_class = c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= 32768 &&
+    const bool tpq_class = c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= c->opt_tpq_min_tasks &&
                            tpq_has_class(B.la, B.lb, Kc.la, Kc.lb);
     const TaskIdx *d_tasks = nullptr;
     if (c->opt_task_table && !tpq_class && ntask >= 65536) {   // the wave-per-quartet pair walks the task list twice
@@ -3222,7 +3189,7 @@ static int eval_route_tpq(PrepareState &S, const ClassPairEval &P)
     const PairClass &B = *P.B, &Kc = *P.Kc;
     const EriArgs &E = P.E;
     const int64_t ntask = P.ntask;
-    if (!(c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= 32768)) return 0;
+    if (!(c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= c->opt_tpq_min_tasks)) return 0;
     TpqArgs Q{};
     Q.bra = B.d_recs; Q.ket = Kc.d_recs; Q.prim = c->d_prim; Q.prefix = E.prefix; Q.nbra = E.nbra; Q.t0 = 0; Q.ntask = ntask;
     Q.c2s = c->d_c2s;
@@ -3256,7 +3223,7 @@ static int eval_route_fused(PrepareState &S, const ClassPairEval &P)
     F.R.PB = std::max(1, std::min(E.PB, B.max_np * Kc.max_np));   // uncontracted d / f shells: one primitive quartet per batch
     F.R.prim_lds = 0; F.R.own_table = nullptr; F.R.qtol = 0.0; F.R.scr.dmax = nullptr;   // (the transform half screens: check_owner, qtol)
     F.X.m_lds = 0;
-    const size_t scratch = (size_t)F.R.PB * E.nroots * 3 * E.tsz + (size_t)F.R.PB * 2 * E.nroots;
+    const size_t scratch = RysLds{F.R.PB, E.nroots, E.tsz}.doubles();
     const size_t shmf = sizeof(double) * ((size_t)X.ne * X.nf + std::max((size_t)X.nsab * X.nf, scratch));
     if (shmf > 160 * 1024) return 0;
     const int perlane = (E.ncomp + 63) / 64;
@@ -7078,8 +7045,8 @@ __global__ __launch_bounds__(GSZ > 64 ? GSZ : 64) void eri_grad_contract(GradXfA
 // derivative variants (rows 0 .. ne_p-1: the (l1+1, l2) block, rows ne_p .. ne_p+ne_m-1: the (l1-1, l2) block; ROWS rows per
 // lane) and keeps its NF = ne(LC, LD) elements in REGISTERS; the other pair (LC, LD) is a template parameter, so the NF
 // products of a row per primitive quartet and root are straight-line code over 3 (LC+LD+1) table values the lane reads from
-// LDS once.  Roots, weights and the 2-D recurrence tables are computed by the wave exactly as in eri_rys_kernel (runtime l1,
-// l2); the (l1-1) rows share them -- same Gaussian product, the factor K-/K+ = 1 / (2 alpha) is applied per primitive pair.
+// LDS once.  Roots, weights and the 2-D recurrence tables come from the phase functions of eri_rys_kernel (rys_phase_roots,
+// rys_phase_tables; runtime l1, l2, the other pair's degree a constant); the (l1-1) rows share them -- same Gaussian product, the factor K-/K+ = 1 / (2 alpha) is applied per primitive pair.
 // The gradient is LINEAR in the block, so the row is contracted where it lives:
 //     Yk[c]  = sum_f E0[e][f] Mcd[c][f]                       (ket HRR + cart->sph, matrix in LDS)
 //     t_r    = sum_c Yk[c] G[r][c]                            (two-particle density block in LDS)
@@ -7100,6 +7067,9 @@ struct FTab {
                 for (int b = f - a; b >= 0; b--) { fx[n] = a; fy[n] = b; fz[n] = f - a - b; n++; }
     }
 };
+
+// LDS doubles of a quartet behind its Rys block (RysLds): K- / K+ per primitive quartet of a batch, the ket matrix, the density block
+__host__ __device__ inline size_t grad_rows_lds_extra(int PB, int nscd, int nf, int nsab) { return (size_t)PB + (size_t)nscd * nf + (size_t)nsab * nscd; }
 
 struct GradRowsArgs {
     const PairRec *dplus, *dminus, *ket;
@@ -7145,10 +7115,10 @@ __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
     int m_prim = dp.prim_off, m_off_m = 0;
     if (has_m) { const PairRec dm = A.dminus[ib]; m_prim = dm.prim_off; m_off_m = dm.m_off; }
     const int n = A.nroots, tsz = A.tsz, PB = A.PB, nsab = A.nsab;
-    const size_t lds_per = (size_t)PB * n * 3 * tsz + (size_t)PB * 2 * n + PB + NSCD * NF + (size_t)nsab * NSCD;
-    double *T0 = lds_all + (size_t)grp * lds_per;          // [PB n][3][tsz]
-    double *rw = T0 + (size_t)PB * n * 3 * tsz;            // [PB][2 n]
-    double *rho = rw + (size_t)PB * 2 * n;                 // [PB]   K- / K+ of the bra primitive pair
+    const RysLds L{PB, n, tsz};
+    double *T0 = lds_all + (size_t)grp * (L.doubles() + grad_rows_lds_extra(PB, NSCD, NF, nsab));   // [PB n][3][tsz], then rw [PB][2 n]
+    double *rw = T0 + L.rw();
+    double *rho = T0 + L.doubles();                        // [PB]   K- / K+ of the bra primitive pair
     double *McdL = rho + PB;                               // [NSCD][NF]
     double *G = McdL + NSCD * NF;                          // [nsab][NSCD]
     // ket matrix and two-particle density block (used after the Rys loop: its barriers order these writes)
@@ -7187,47 +7157,14 @@ __global__ __launch_bounds__(64) void eri_grad_rows_kernel(GradRowsArgs A)
     const double *prim_m = A.prim + (size_t)m_prim * 8;
     for (int pq0 = 0; pq0 < nPQ_all; pq0 += PB) {
         const int npq = max(0, min(PB, nPQ - pq0));
-        for (int idx = lane; idx < npq * 2 * n; idx += GSZ) {   // roots and weights
-            const int pql = idx / (2 * n), f = idx - pql * 2 * n;
-            const int pq = pq0 + pql, ip = pq / ncd, jp = pq - ip * ncd;
-            const double *b = prim_b + (size_t)ip * 8, *k = prim_k + (size_t)jp * 8;
-            const double p = b[0], q = k[0];
-            const double dx = b[1] - k[1], dy = b[2] - k[2], dz = b[3] - k[3];
-            rw[pql * 2 * n + f] = rys_eval(A.rys, n, f, p * q / (p + q) * (dx * dx + dy * dy + dz * dz));
-        }
+        rys_phase_roots<GSZ, false>(A.rys, 0.0, n, prim_b, prim_k, ncd, pq0, npq, lane, rw);
         if (has_m)
             for (int idx = lane; idx < npq; idx += GSZ) {       // K- / K+ of the primitive pairs of this batch
                 const int ip = (pq0 + idx) / ncd;
                 rho[idx] = prim_m[(size_t)ip * 8 + 7] / prim_b[(size_t)ip * 8 + 7];
             }
         __syncthreads();
-        for (int idx = lane; idx < npq * n * 3; idx += GSZ) {    // 2-D recurrence tables
-            const int pql = idx / (3 * n), rem = idx - pql * 3 * n, r = rem / 3, d = rem - r * 3;
-            const int pq = pq0 + pql, ip = pq / ncd, jp = pq - ip * ncd;
-            const double *b = prim_b + (size_t)ip * 8, *k = prim_k + (size_t)jp * 8;
-            const double p = b[0], q = k[0], pq1 = 1.0 / (p + q);
-            const double u = rw[pql * 2 * n + r];
-            const double PQd = b[1 + d] - k[1 + d];
-            const double b00 = 0.5 * u * pq1, b10 = 0.5 / p * (1.0 - u * q * pq1), b01 = 0.5 / q * (1.0 - u * p * pq1);
-            const double c00 = b[4 + d] - u * q * pq1 * PQd, c01 = k[4 + d] + u * p * pq1 * PQd;
-            double *T = T0 + ((size_t)(pql * n + r) * 3 + d) * tsz;
-            double t00 = 1.0;
-            if (d == 2) t00 = rw[pql * 2 * n + n + r] * b[7] * k[7] * 34.986836655249725 /* 2 pi^2.5 */ * pq1 * sqrt(p + q) / (p * q);
-            T[0] = t00;
-            double tm = 0.0, tc = t00;
-            for (int i = 0; i < A.nmax; i++) {
-                const double tn = c00 * tc + i * b10 * tm;
-                T[(i + 1) * M1] = tn;
-                tm = tc; tc = tn;
-            }
-            for (int m = 0; m < MMAX; m++)
-                for (int i = 0; i <= A.nmax; i++) {
-                    double v = c01 * T[i * M1 + m];
-                    if (m > 0) v += m * b01 * T[i * M1 + m - 1];
-                    if (i > 0) v += i * b00 * T[(i - 1) * M1 + m];
-                    T[i * M1 + m + 1] = v;
-                }
-        }
+        rys_phase_tables<GSZ, false>(n, A.nmax, MMAX, tsz, prim_b, prim_k, ncd, pq0, npq, lane, rw, T0);
         __syncthreads();
         const int nslot = npq * n;
         for (int s_ = 0; s_ < nslot; s_++) {
@@ -7658,8 +7595,7 @@ __global__ __launch_bounds__(TPQ_BLOCK) void eri_tpq_grad_kernel(TpqGradArgs A)
 template <int L1, int L2, int LC, int LD>
 static int launch_eri_tpq_grad_t(const TpqGradArgs &Q, hipStream_t st)
 {
-    constexpr int NR = (L1 + 1 + L2 + LC + LD) / 2 + 1;
-    const size_t shm = sizeof(double) * (size_t)RYS_NINT_H[NR] * 2 * NR * (RYS_DEG + 1);
+    const size_t shm = tpq_cheb_bytes((L1 + 1 + L2 + LC + LD) / 2 + 1);
     if (Q.ntask <= 0) return 1;   // nothing in this rank's share of the class (the class is still "handled")
     const dim3 grid((unsigned)((Q.ntask + TPQ_BLOCK - 1) / TPQ_BLOCK));
     return with_grad_terms(QuartetDensity{Q.D, Q.Dm, Q.ld, Q.hyb, Q.pt, Q.xt}, [&](auto terms) {
@@ -7873,7 +7809,7 @@ static int grad_route_tpq(GradState &G, GradClassPair &CP, const GradPerm &M)
     hipStream_t st = G.st;
     const PairClass &B = *CP.B, &Kc = *CP.Kc, &Dc = *M.Dc, &Oc = *M.Oc;
     const int64_t ntask = CP.ntask;
-    if (!(c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= 32768)) return 0;
+    if (!(c->opt_eri_tpq && B.mean_np * Kc.mean_np <= c->opt_tpq_maxprim && ntask >= c->opt_tpq_min_tasks)) return 0;
     TpqGradArgs Q{};
     Q.dplus = Dc.d_g_recs[M.orient][0]; Q.dminus = M.l1 >= 1 ? Dc.d_g_recs[M.orient][1] : nullptr; Q.ket = Oc.d_recs;
     Q.prim = c->d_prim; Q.prefix = G.d_prefix; Q.nbra = (int)B.recs.size();
@@ -7928,8 +7864,7 @@ static int grad_route_rows(GradState &G, const GradClassPair &CP, const GradPerm
     R.inv_from_second = M.swap ? 0 : 1;
     R.dens = G.dens; R.scr = G.screen(Dc, Oc, M.dmax_w);
     const int nscd_ = Oc.nsab, nf_ = Oc.ne;
-    const size_t shm_q = sizeof(double) * ((size_t)R.PB * R.nroots * 3 * R.tsz + (size_t)R.PB * 2 * R.nroots + (size_t)R.PB +
-                                           (size_t)nscd_ * nf_ + (size_t)R.nsab * nscd_);
+    const size_t shm_q = sizeof(double) * (RysLds{R.PB, R.nroots, R.tsz}.doubles() + grad_rows_lds_extra(R.PB, nscd_, nf_, R.nsab));
     if (!(R.ntask < ((int64_t)1 << 31))) return 0;
     const bool dbgr = getenv("MI355_DEBUG") != nullptr;
     auto tr0 = std::chrono::steady_clock::now();

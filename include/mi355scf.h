@@ -57,6 +57,8 @@ void mi_release_cache(void);
  *   "ao_order", "ket_cluster"  tile AO order (1 = angular-momentum major, 0 = caller's) / ket order inside Schwarz clusters
  *   "xf_mfma_min" transform kernel: FP64-MFMA tiles for spherical blocks of at least this many elements
  *   "eri_tpq", "tpq_maxprim"  thread-per-quartet kernels for the low angular classes / their contraction-depth limit
+ *   "tpq_min_tasks"  ... and the fewest quartets of a class pair that they take (default 32768; the gradient reads it at each
+ *                 call).  Smaller class pairs run on the wave-per-quartet kernels; tests set 1 to put every class on them
  *   "omega"       > 0: the store holds long-range integrals (ij|erf(omega r12)/r12|kl) instead of (ij|kl) (range-separated
  *                 hybrids: CAM-B3LYP's K_LR).  Every evaluation path (Rys pair, fused, thread-per-quartet) uses theta = omega^2 /
  *                 (omega^2 + rho), rho = pq/(p+q): Rys argument theta x, roots u theta, prefactor sqrt(theta).  Screening keeps

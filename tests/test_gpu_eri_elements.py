@@ -5,7 +5,13 @@ integral by integral -- not only through J/K contractions -- and the Schwarz fac
     shell quartets read back with `mi_eri_read_quartet`, stratified over the angular classes incl. (ff|ff) / (dd|dd).
 Tolerance 1e-10 absolute (FP64; integrals are O(1e-3 .. 1)).
 The plain Coulomb store is also evaluated under every option that selects another evaluation route, launch shape or layout
-(`test_coulomb_store_under_evaluation_options*`): whole tensor and Schwarz table again, same bounds."""
+(`test_coulomb_store_under_evaluation_options*`): whole tensor and Schwarz table again, same bounds.
+`test_every_tpq_class_*`: a synthetic s..f molecule at two geometries with `tpq_min_tasks = 1`, so that every class of the
+thread-per-quartet switch -- the f-shell ones included -- is compared element by element, inside the Chebyshev table of the
+Rys roots, beyond it and at x = 0 (`rys_branch_coverage` asserts that from the exponents and centres)."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -59,9 +65,10 @@ def _dense_ref(name, basis):
     return _DENSE[(name, basis)]
 
 
-def _check_store(name, basis, opts):
+def _check_store(name, basis, opts, min_kept=0.9, ref=None):
+    """`ref`: the (mol, oracle tensor, oracle Schwarz table) triple, where it is not one of conftest's molecules."""
     from mi355scf.engine import Engine
-    mol, ref, qo = _dense_ref(name, basis)
+    mol, ref, qo = ref or _dense_ref(name, basis)
     eng = Engine(mol)
     for k, v in opts.items():
         eng.set_option(k, v)
@@ -74,7 +81,7 @@ def _check_store(name, basis, opts):
     print(f"{name}/{basis} {opts}: max|eri - oracle| = {err:.3e}, max|q - oracle| = {qerr:.3e}, {st['n_quartets']} quartets")
     assert got.shape == ref.shape and np.isfinite(got).all()
     assert err < 1e-10, err
-    assert kept.sum() > 0.9 * q.size
+    assert kept.sum() > min_kept * q.size
     assert qerr < 1e-11
     assert (qo[~kept] * qo.max() < 1e-13).all()
     eng.close()
@@ -121,6 +128,132 @@ def test_coulomb_store_under_evaluation_options_h2o_ccpvtz(opts):
 def test_coulomb_store_under_evaluation_options_h2co_631gd(opts):
     """H2CO/6-31G(d) (N = 32: no ragged block, d shells, no f)."""
     _check_store("h2co", "6-31g(d)", opts)
+
+
+# --- every class of the thread-per-quartet switch, every branch of the root evaluation ----------------------------------
+# Geometry "near": the synthetic s..f molecule with its ghost centre (one two-primitive s, p, d and f shell on each of four
+# centres, 16 shells, 64 AOs); the largest Rys argument is about 12, inside the tables.  Geometry "far": the ghost moved to
+# (9, -5, 3) Bohr; the quartets of a one-centre pair there and a one-centre pair on He have arguments 57 .. 204, beyond the
+# table end (40 .. 70 for 1 .. 7 roots), and integrals of order 0.09, far above every screen.
+FAR_GHOST = "9.0 -5.0 3.0"
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "computational-chemistry-ai_amd", "csrc")
+_SYNTH = {}
+_SYNTH_REF = {}
+
+
+def synthetic_mol(which):
+    """"near": test_gpu_pcm_kernels._synthetic_with_ghost(); "far": the same atoms and basis, ghost centre at FAR_GHOST."""
+    import test_gpu_pcm_kernels as pk
+    if which not in _SYNTH:
+        if which == "near":
+            _SYNTH[which] = pk._synthetic_with_ghost()
+        else:
+            basis = pk._synthetic_basis()
+            basis["Ghost:C"] = basis["C"]
+            _SYNTH[which] = pk._mol(pk.SYNTH_ATOMS + "; Ghost:C " + FAR_GHOST, basis, unit="Bohr")
+        mol = _SYNTH[which]
+        assert mol.nbas == 16 and mol.nao == 64 and sorted(mol._bas[:, 1]) == sorted(4 * [0, 1, 2, 3])
+    return _SYNTH[which]
+
+
+def switch_classes(macro):
+    """The (a, b, c, d) tuples of a class switch of the engine source (`TPQ_CASE`, `TPQG_CASE`, `ROWS_CASE`): the tests ask for
+    what the switch holds instead of keeping a list of their own."""
+    src = open(os.path.join(CSRC, "mi355scf.hip")).read()
+    out = {tuple(int(x) for x in m.group(1).split(",")) for m in re.finditer(macro + r"\(([0-9, ]+)\)", src)}
+    assert out
+    return out
+
+
+def rys_table_ends():
+    """x beyond which the kernels use the asymptotic roots, per root count: RYS_NINT_H[n] * RYS_H of the generated tables."""
+    src = open(os.path.join(CSRC, "rys_tables.h")).read()
+    h = float(re.search(r"#define RYS_H ([0-9.]+)", src).group(1))
+    nint = [int(x) for x in re.search(r"RYS_NINT_H\[RYS_NMAX \+ 1\] = \{([0-9, ]+)\}", src).group(1).split(",")]
+    return {n: nint[n] * h for n in range(1, len(nint))}
+
+
+def rys_branch_coverage(mols, extra=0, omega=0.0, require=True):
+    """Asserts that the primitive quartets of `mols` together reach, for every root count n = (la + lb + lc + ld + extra) / 2 + 1
+    that occurs, all three cases of the root evaluation: x = pq/(p+q) |P - Q|^2 inside the Chebyshev table, beyond its end, and
+    x = 0 (all four shells on one centre).  omega > 0: the argument the attenuated kernels evaluate the roots at, theta x with
+    theta = omega^2 / (omega^2 + pq/(p+q)).  (One-centre
+    products of unequal exponents give x of rounding size, 1e-33; `x = 0` means exactly 0.)  Returns {n: (smallest x > 1e-3, largest x)};
+    require = False only reports."""
+    ends = rys_table_ends()
+    seen = {}
+    for mol in mols:
+        sh = [(int(b[1]), mol._env[b[5]:b[5] + b[2]], mol._env[mol._atm[b[0], 1]:mol._atm[b[0], 1] + 3]) for b in mol._bas]
+        pl, pp, pP = [], [], []
+        for la, ea, A in sh:
+            for lb, eb, B in sh:
+                for a in ea:
+                    for b in eb:
+                        pl.append(la + lb); pp.append(a + b); pP.append((a * A + b * B) / (a + b))
+        pl, pp, pP = np.array(pl), np.array(pp), np.array(pP)
+        x = pp[:, None] * pp[None, :] / (pp[:, None] + pp[None, :]) * ((pP[:, None, :] - pP[None, :, :]) ** 2).sum(-1)
+        if omega > 0.0:
+            x = x * omega ** 2 / (omega ** 2 + pp[:, None] * pp[None, :] / (pp[:, None] + pp[None, :]))
+        n = (pl[:, None] + pl[None, :] + extra) // 2 + 1
+        for nr in np.unique(n):
+            xs = x[n == nr]
+            c = seen.setdefault(int(nr), [False, False, False, np.inf, 0.0])
+            c[0] |= bool(((xs > 1e-3) & (xs < ends[nr])).any()); c[1] |= bool((xs > ends[nr]).any()); c[2] |= bool((xs == 0.0).any())
+            c[3] = min(c[3], xs[xs > 1e-3].min()); c[4] = max(c[4], xs.max())
+    assert sorted(seen) == list(range(1, 8)), sorted(seen)
+    for nr, c in seen.items():
+        assert not require or (c[0] and c[1] and c[2]), (nr, c, ends[nr])
+    return {nr: (c[3], c[4]) for nr, c in seen.items()}
+
+
+def _synthetic_ref(which):
+    """(mol, oracle tensor, oracle Schwarz table) of a synthetic geometry, once per module."""
+    if which not in _SYNTH_REF:
+        from oracle import oracle as orc
+        mol = synthetic_mol(which)
+        o = orc.Oracle(mol)
+        _SYNTH_REF[which] = (mol, o.eri_full(), o.schwarz())
+    return _SYNTH_REF[which]
+
+
+_EVAL_LINE = re.compile(r"\[mi355\] eri class \((\d)(\d)\|(\d)(\d)\): \d+ quartets, ([a-z+-]+(?: [a-z+-]+)*) ")
+FORCED_TPQ = {"tpq_min_tasks": 1, "tpq_maxprim": 1e9}
+# Shell pairs the Schwarz table must keep (`min_kept`).  Far geometry: most of the 96 pairs of a shell on the far ghost with a
+# shell 10 Bohr away are negligible and dropped (that they are is asserted); the 9 x 16 pairs among the three near centres and the
+# 16 on the ghost itself, 160 of 256, must stay.
+MIN_KEPT = {"near": 0.9, "far": 159.5 / 256}
+
+
+def _eval_routes(err):
+    """{class (la, lb, lc, ld): first words of its route} from the MI355_DEBUG=2 lines of a prepare."""
+    return {tuple(int(m.group(i)) for i in range(1, 5)): m.group(5) for m in map(_EVAL_LINE.search, err.splitlines()) if m}
+
+
+@pytest.mark.parametrize("which", ["near", "far"])
+def test_every_tpq_class_whole_tensor(which, monkeypatch, capfd):
+    """All 64^4 elements and the Schwarz table with every class of the evaluation switch on the thread-per-quartet kernels."""
+    cover = rys_branch_coverage([synthetic_mol("near"), synthetic_mol("far")])
+    ref = _synthetic_ref(which)
+    monkeypatch.setenv("MI355_DEBUG", "2")
+    capfd.readouterr()
+    _check_store(which, "synthetic", FORCED_TPQ, MIN_KEPT[which], ref)
+    routes = _eval_routes(capfd.readouterr().err)
+    on_tpq = {k for k, v in routes.items() if v.startswith("thread-per-quartet fused kernel")}
+    print(f"{which}: {len(on_tpq)} of {len(routes)} class pairs on the thread-per-quartet kernels; x range per root count {cover}")
+    assert len(routes) == 55 and on_tpq == switch_classes("TPQ_CASE"), sorted(switch_classes("TPQ_CASE") ^ on_tpq)
+
+
+@pytest.mark.parametrize("opts", [{"eri_tpq": 0}, {"eri_fused": 1, "eri_tpq": 0}], ids=["pair", "fused"])
+def test_wave_per_quartet_beyond_the_root_tables(opts, monkeypatch, capfd):
+    """The far geometry on the wave-per-quartet pair and on its fused caller: the asymptotic branch of the LDS-table body."""
+    rys_branch_coverage([synthetic_mol("near"), synthetic_mol("far")])
+    ref = _synthetic_ref("far")
+    monkeypatch.setenv("MI355_DEBUG", "2")
+    capfd.readouterr()
+    _check_store("far", "synthetic", opts, MIN_KEPT["far"], ref)
+    routes = _eval_routes(capfd.readouterr().err)
+    want = "fused rys" if opts.get("eri_fused") else "rys "
+    assert len(routes) == 55 and all((v + " ").startswith(want) for v in routes.values()), routes
 
 
 def _sample_quartets(mol, n, seed, classes):

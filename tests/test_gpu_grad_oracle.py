@@ -99,7 +99,7 @@ def test_grad_eri_matches_exact_oracle(system, spin):
 
 # --- every route of mi_grad_eri on benzene/cc-pVDZ (114 AOs, 54 shells, class pairs up to 251k tasks) ----------------------
 DEFAULTS = {"eri_tpq": 1, "tpq_maxprim": 32, "grad_rows": 1, "grad_rows_min": 20, "grad_rows_g32": 1, "grad_live": 1,
-            "task_table": 1, "grad_work_mb": 1024}
+            "task_table": 1, "grad_work_mb": 1024, "tpq_min_tasks": 32768}
 # (name, options on top of DEFAULTS, hyb): the routes each one must show are asserted in _check_routes
 ROUTES = [
     ("default", {}, 1.0),
@@ -195,6 +195,77 @@ def test_grad_eri_every_route_matches_exact_oracle(monkeypatch, capfd):
         eng.set_option("grad_rows_g32", 1)     # process-wide, not per context
     print("\n".join(report))
     print(f"routes: worst |g - g_ref| / max(1, |g_ref|) = {worst:.2e}")
+
+
+# --- every class of every route, inside and beyond the Rys root tables ----------------------------------------------------
+def _ne(la, lb):
+    return sum((e + 1) * (e + 2) // 2 for e in range(la, la + lb + 1))
+
+
+def test_grad_eri_every_class_on_every_route_beyond_the_root_tables(monkeypatch, capfd):
+    """The synthetic s..f molecule with its ghost centre at (9, -5, 3) Bohr (test_gpu_eri_elements.synthetic_mol("far"): every
+    derivative class (l1 l2|lc ld), l <= 3, that mi_grad_eri can launch, Rys arguments from 0 to 260, see rys_branch_coverage): every class of the
+    thread-per-quartet switch on that kernel (`tpq_min_tasks = 1`), every class with a row kernel there (with and without two
+    quartets per wave), and all of them on the Rys -> hand-over -> contraction pipeline.
+
+    Observed on the MI355X: |g - g_ref| = 7.3e-11 .. 7.9e-11 of |g_ref|max 283 on the four routes (bound 2.8e-8)."""
+    from mi355scf.engine import Engine
+    from test_gpu_eri_elements import rys_branch_coverage, switch_classes, synthetic_mol
+    mol = synthetic_mol("far")
+    cover = rys_branch_coverage([synthetic_mol("near"), mol], extra=1)
+    n = mol.nao
+    D, M = _sym(n, 71), _sym(n, 72)
+    # The derivative classes (l1 l2|lc ld) a molecule can show: class pairs (B | Kc), B >= Kc in the order of the pair classes,
+    # derivative on B's second shell, on Kc's first and on Kc's second (the fourth force follows from the other three).  131 of
+    # the 160 ordered classes, all of them here.  Nine classes of the thread-per-quartet switch are not among them -- (ps|ss),
+    # (ds|ss), (ds|ps), (ds|pp), (dp|ss), (dp|ps), (fs|ss), (fs|ps), (fp|ss) never get a launch from mi_grad_eri.
+    pairs = [(a, b) for a in range(4) for b in range(a + 1)]
+    every = set()
+    for i, B in enumerate(pairs):
+        for Kc in pairs[:i + 1]:
+            every |= {(B[1], B[0]) + Kc, Kc + B, (Kc[1], Kc[0]) + B}
+    switch = switch_classes("TPQG_CASE")
+    tpq = switch & every
+    rows = {k for k in every if k[2:] in switch_classes("ROWS_CASE") and _ne(k[0] + 1, k[1]) + (_ne(k[0] - 1, k[1]) if k[0] else 0) <= 192}
+    assert len(every) == 131 and len(switch - every) == 9 and len(tpq) == 28 and len(rows) == 99
+    as_key = lambda ks: {(f"{a}{b}", f"{c}{d}") for a, b, c, d in ks}
+    forced = {"tpq_min_tasks": 1, "tpq_maxprim": 1e9}
+    routes = [("thread per quartet", forced),
+              ("rows, g32", {"eri_tpq": 0, "grad_rows_min": 1, "grad_rows_g32": 1}),
+              ("rows, no g32", {"eri_tpq": 0, "grad_rows_min": 1, "grad_rows_g32": 0}),
+              ("pipeline", {"eri_tpq": 0, "grad_rows": 0})]
+    # _ref's bound at hyb = 1 with the spin density, from ONE oracle call (4 s) instead of _oracle_eri's three
+    from oracle import oracle as orc
+    ref, dropped = orc.Oracle(mol).grad_eri(D, M, hyb=1.0, qtol=QTOL)
+    tol = 1e-10 * max(1.0, np.abs(ref).max()) + 2 * np.abs(dropped).max()
+    eng = Engine(mol)
+    eng.prepare_eri(QTOL)
+    monkeypatch.setenv("MI355_DEBUG", "1")
+    report = []
+    try:
+        for name, opts in routes:
+            for k, v in {**DEFAULTS, **opts, "grad_dtol": DTOL}.items():
+                eng.set_option(k, v)
+            capfd.readouterr()
+            g = _grad_eri(eng, mol, D, M, 1.0)
+            r = _routes(capfd.readouterr().err)
+            err = np.abs(g - ref).max()
+            report.append(f"route '{name}': classes on tpq {len(r['tpq'])}, rows {len(r['rows'])} (g32 {len(r['rows32'])}), pipeline "
+                          f"{len(r['pipeline'])}; |g - g_ref| = {err:.2e} of {np.abs(ref).max():.1f} (tol {tol:.1e})")
+            assert err < tol, (name, err, tol)
+            assert r["tpq"] | r["rows"] | r["pipeline"] == as_key(every), name
+            if name == "thread per quartet":
+                assert r["tpq"] == as_key(tpq), sorted(r["tpq"] ^ as_key(tpq))
+            elif name.startswith("rows"):
+                assert not r["tpq"] and r["rows"] == as_key(rows), sorted(r["rows"] ^ as_key(rows))
+                assert bool(r["rows32"]) == (name == "rows, g32")
+            else:
+                assert not r["tpq"] and not r["rows"] and r["pipeline"] == as_key(every)
+    finally:
+        for k, v in DEFAULTS.items():
+            eng.set_option(k, v)                   # grad_rows_g32 is process-wide, not per context
+    print("\n".join(report))
+    print(f"x range per root count: {cover}")
 
 
 # --- one-electron -----------------------------------------------------------------------------------------------------

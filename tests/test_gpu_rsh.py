@@ -105,6 +105,77 @@ def test_lr_store_thread_per_quartet_kernels():
         eng.close()
 
 
+def _synthetic_sample(seed):
+    """{"near" / "far": shell quartets} of the synthetic s..f molecule (test_gpu_eri_elements.synthetic_mol; shell 4 c + l is the
+    l shell of centre c, centre 0 = He, 3 = the ghost): for every angular class one all-one-centre quartet, one quartet of a
+    one-centre pair on the far ghost and a one-centre pair on He (far geometry: Rys argument 57 .. 204, beyond the root tables),
+    one four-centre quartet, and a seeded random one (three quartets per class on the near geometry, four on the far one)."""
+    rng = np.random.default_rng(seed)
+    out = {"near": [], "far": []}
+    for la in range(4):
+        for lb in range(la + 1):
+            for lc in range(la + 1):
+                for ld in range(lc + 1):
+                    if (lc, ld) > (la, lb):
+                        continue
+                    ls = (la, lb, lc, ld)
+                    at = lambda cs: tuple(4 * c + l for c, l in zip(cs, ls))
+                    one, fn, four = int(rng.integers(4)), (3, 3, 0, 0), tuple(int(c) for c in rng.permutation(4))
+                    rand = [tuple(int(c) for c in rng.integers(0, 4, 4)) for _ in range(2)]
+                    out["near"] += [at(c) for c in [(one,) * 4, four] + rand[:1]]
+                    out["far"] += [at(c) for c in [(one,) * 4, fn, four] + rand[1:]]
+    return out
+
+
+LR_OMEGA_LARGE = 2.0
+
+
+def test_lr_store_every_tpq_class_inside_and_beyond_the_root_tables(monkeypatch, capfd):
+    """The long-range store with every class of the thread-per-quartet switch on those kernels (`tpq_min_tasks = 1`; the f-shell
+    classes included, asserted from the MI355_DEBUG lines), and the same quartets on the wave-per-quartet pair, against
+    MDEri.shell_block.  The sample holds, per angular class, an all-one-centre quartet (x = 0), a far/near one-centre x
+    one-centre quartet and a four-centre one.
+
+    The attenuated kernels evaluate the roots at theta x, theta = omega^2 / (omega^2 + rho).  With omega = CAM_OMEGA theta is
+    about 0.05 .. 0.2 and NO quartet of either geometry leaves the root tables (asserted: the largest theta x stays below every
+    table end), so that case covers the Chebyshev branch and x = 0 only.  The asymptotic branch under omega > 0 is reached by the
+    far geometry at omega = LR_OMEGA_LARGE (theta 0.7 .. 0.9): rys_branch_coverage asserts all three cases on theta x for every
+    root count there, and the same sample is compared again.
+
+    Observed on the MI355X: worst block 2.0e-14 (near) and 1.9e-14 (far) at CAM_OMEGA, the same on both routes."""
+    from test_gpu_eri_elements import FORCED_TPQ, _eval_routes, rys_branch_coverage, rys_table_ends, switch_classes, synthetic_mol
+    mols = {w: synthetic_mol(w) for w in ("near", "far")}
+    rys_branch_coverage(list(mols.values()))                               # the un-attenuated arguments, as the issue states them
+    ends = rys_table_ends()
+    cam = rys_branch_coverage(list(mols.values()), omega=CAM_OMEGA, require=False)
+    assert all(hi < ends[n] for n, (_lo, hi) in cam.items()), cam       # CAM_OMEGA: nothing beyond the tables (see above)
+    cover = rys_branch_coverage(list(mols.values()), omega=LR_OMEGA_LARGE)
+    assert all(hi > ends[n] for n, (_lo, hi) in cover.items())
+    sample = _synthetic_sample(seed=23)
+    classes = {tuple(s % 4 for s in q) for q in sample["far"]}
+    assert len(classes) == 55 and switch_classes("TPQ_CASE") <= classes
+    monkeypatch.setenv("MI355_DEBUG", "2")
+    for which, omega in (("near", CAM_OMEGA), ("far", CAM_OMEGA), ("far", LR_OMEGA_LARGE)):
+        mol = mols[which]
+        md = MDEri(mol, omega)
+        ref = {q: md.shell_block(*q) for q in sample[which]}
+        if which == "far":
+            assert (12, 12, 0, 0) in ref and np.abs(ref[(12, 12, 0, 0)]).max() > 0.05       # nothing screens the far/near quartets
+        report = []
+        for opts in (FORCED_TPQ, dict(eri_tpq=0)):
+            capfd.readouterr()
+            eng = _engine(mol, omega, **opts)
+            routes = _eval_routes(capfd.readouterr().err)
+            on_tpq = {k for k, v in routes.items() if v.startswith("thread-per-quartet fused kernel")}
+            assert on_tpq == (switch_classes("TPQ_CASE") if opts is FORCED_TPQ else set()), (which, omega, opts, sorted(on_tpq))
+            err = {q: np.abs(eng.eri_read_quartet(*q) - ref[q]).max() for q in sample[which]}
+            eng.close()
+            worst = max(err, key=err.get)
+            report.append(f"{which} omega={omega} {opts}: {len(err)} quartets, worst {worst} {err[worst]:.2e}")
+            assert err[worst] < 1e-10, (which, omega, opts, worst, err[worst])
+        print("\n".join(report))
+
+
 def test_huge_omega_is_the_full_store():
     """omega = 1e8: theta = 1 - O(rho / omega^2) for every primitive pair, the store equals the full-Coulomb one."""
     mol = _mol(MOLECULES["h2o"], "cc-pvtz")
