@@ -148,6 +148,25 @@ def ref_ccsd_t(cc):
     return float(et)
 
 
+def numpy_cc_energy_terms(t1, t2, ovov):
+    """The terms of E = sum_ijab (t2[i,j,a,b] + t1[i,a] t1[j,b]) (2 (ia|jb) - (ib|ja)), ovov[i,a,j,b] = (ia|jb), as [o,o,v,v]."""
+    g = 2.0 * ovov.transpose(0, 2, 1, 3) - ovov.transpose(0, 2, 3, 1)
+    return (t2 + t1[:, None, :, None] * t1[None, :, None, :]) * g
+
+
+def numpy_amp_update(num, told, ovov, eo, ev):
+    """`cc_amp_update_kernel` (csrc/cc_kernels.h) restated: on the stacked vector [t1 (o v) | t2 (o o v v)]
+    new = num / D with D = e_i - e_a and e_i + e_j - e_a - e_b, err = new - old, and the TERMS of the two sums the kernel
+    returns, |err|^2 and the correlation energy of the new amplitudes.  Returns (new, err, err^2 terms, energy terms), all flat."""
+    o, v = len(eo), len(ev)
+    n1 = o * v
+    t1 = num[:n1].reshape(o, v) / (eo[:, None] - ev[None, :])
+    t2 = num[n1:].reshape(o, o, v, v) / (eo[:, None, None, None] + eo[None, :, None, None] - ev[None, None, :, None] - ev[None, None, None, :])
+    new = np.concatenate([t1.ravel(), t2.ravel()])
+    err = new - told
+    return new, err, err * err, numpy_cc_energy_terms(t1, t2, ovov).ravel()
+
+
 # =================================================================================================
 # the reference against independent facts
 # =================================================================================================
@@ -191,6 +210,32 @@ def test_ref_zeroth_iteration_is_mp2():
     # amplitudes keep the antisymmetry the equations preserve
     t2 = cc["t2"]
     assert np.abs(t2 + t2.transpose(1, 0, 2, 3)).max() < 1e-13 and np.abs(t2 + t2.transpose(0, 1, 3, 2)).max() < 1e-13
+
+
+def test_closed_shell_energy_expression_reproduces_the_spin_orbital_energy():
+    """The closed-shell blocks of the converged spin-orbital amplitudes (alpha t1; the alpha-beta block of t2; (ia|jb) is the
+    alpha-beta block of <ij||ab>, whose exchange part vanishes by spin) in the energy expression of `numpy_amp_update`.  What
+    it leaves out is sum f_ia t_ia, zero for the converged RHF orbitals (f_ov is printed)."""
+    mol, r, h, eri = _oracle_case(MOLECULES["h2o"], "sto-3g")
+    cc = ref_ccsd(h, eri, r["mo_coeff"], mol.energy_nuc(), mol.nelectron // 2)
+    no = cc["nocc_so"]
+    t1 = cc["t1"][0::2, 0::2]
+    t2 = cc["t2"][0::2, 1::2, 0::2, 1::2]
+    ovov = cc["anti"][:no, :no, no:, no:][0::2, 1::2, 0::2, 1::2].transpose(0, 2, 1, 3)
+    e = float(np.sum(numpy_cc_energy_terms(t1, t2, ovov)))
+    fov = np.abs(cc["fock"][:no, no:]).max()
+    print(f"H2O/STO-3G: closed-shell expression - E_corr = {e - cc['e_corr']:.2e} (E_corr = {cc['e_corr']:.10f}, |f_ov|max = {fov:.1e})")
+    assert t1.shape == (5, 2) and ovov.shape == (5, 2, 5, 2) and abs(e - cc["e_corr"]) <= 1e-10
+
+    # the update itself on these amplitudes: with num = D t the division gives them back and err vanishes
+    eps = np.diag(cc["fock"])[0::2]
+    eo, ev = eps[:5], eps[5:]
+    told = np.concatenate([t1.ravel(), t2.ravel()])
+    D = np.concatenate([(eo[:, None] - ev[None, :]).ravel(),
+                        (eo[:, None, None, None] + eo[None, :, None, None] - ev[None, None, :, None] - ev[None, None, None, :]).ravel()])
+    new, err, dt, et = numpy_amp_update(told * D, told, ovov, eo, ev)
+    assert np.abs(new - told).max() <= 1e-15 and np.abs(err).max() <= 1e-15 and dt.shape == told.shape
+    assert abs(float(np.sum(et)) - cc["e_corr"]) <= 1e-10
 
 
 # =================================================================================================

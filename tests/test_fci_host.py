@@ -9,6 +9,7 @@ one elementary a+ / a at a time with its Jordan-Wigner sign (-1)^(occupied spin 
 The reference is validated here against facts that do not depend on it; then the product's host tables are checked against it.
 """
 import ctypes
+import functools
 import itertools
 import os
 import re
@@ -114,6 +115,80 @@ def ref_rdm12(cbra, cket, norb, nelec):
     return dm1, dm2
 
 
+# =================================================================================================
+# the matrix-free reference (sectors the dense H cannot reach)
+# =================================================================================================
+# With creators ordered (alpha ascending)(beta ascending), a+_p a_q of one spin carries the sign of its own string only, so on
+# the coefficient matrix C[nsa, nsb] the spin-summed operator is E_pq C = Ea_pq @ C + C @ Eb_pq^T with Ea, Eb the operators of
+# the single-spin spaces (n, 0) and (0, n) -- still `RefSpace.apply`, one elementary a+ / a at a time.
+@functools.lru_cache(maxsize=None)
+def ref_spin_E(norb, n, spin):
+    """E[p][q] = a+_p a_q of `spin` on the strings of n electrons in norb orbitals, sparse [target string, source string]."""
+    S = RefSpace(norb, (n, 0) if spin == 0 else (0, n))
+    return [[S.E(p, q, spin) for q in range(norb)] for p in range(norb)]
+
+
+def _ref_D(norb, nelec, c):
+    """D[r * norb + s] = E_rs c, as [norb^2, nsa, nsb]."""
+    Ea, Eb = ref_spin_E(norb, nelec[0], 0), ref_spin_E(norb, nelec[1], 1)
+    c = np.asarray(c, dtype=np.float64).reshape(Ea[0][0].shape[0], Eb[0][0].shape[0])
+    return np.stack([Ea[r][s] @ c + (Eb[r][s] @ c.T).T for r in range(norb) for s in range(norb)])
+
+
+def ref_sigma(h, eri, norb, nelec, c):
+    """H c of the module docstring's H without forming it: D_rs = E_rs c, F_pq = 1/2 sum_rs (pq|rs) D_rs + h~_pq c,
+    sigma = sum_pq E_pq F_pq."""
+    n2 = norb * norb
+    D = _ref_D(norb, nelec, c)
+    shape = D.shape[1:]
+    ht = h - 0.5 * np.einsum("prrq->pq", eri)
+    F = (0.5 * eri.reshape(n2, n2)) @ D.reshape(n2, -1) + ht.reshape(n2, 1) * np.asarray(c, dtype=np.float64).reshape(1, -1)
+    del D
+    Ea, Eb = ref_spin_E(norb, nelec[0], 0), ref_spin_E(norb, nelec[1], 1)
+    out = np.zeros(shape)
+    for p in range(norb):
+        for q in range(norb):
+            f = F[p * norb + q].reshape(shape)
+            out += Ea[p][q] @ f + (Eb[p][q] @ f.T).T
+    return out
+
+
+def _occupations(norb, n):
+    return ((ref_strings(norb, n)[:, None] >> np.arange(norb)[None, :]) & 1).astype(np.float64)
+
+
+def ref_hdiag(h, eri, norb, nelec):
+    """<I|H|I> in closed form from the occupation lists: sum_P h_PP + 1/2 sum_{P,Q occupied spin orbitals} (J_PQ - delta_spin K_PQ),
+    J_pq = (pp|qq), K_pq = (pq|qp) (the P = Q terms cancel).  [nsa, nsb]."""
+    oa, ob = _occupations(norb, nelec[0]), _occupations(norb, nelec[1])
+    hd, J, K = np.diag(h), np.einsum("ppqq->pq", eri), np.einsum("pqqp->pq", eri)
+    same = lambda x: x @ hd + 0.5 * np.einsum("ip,pq,iq->i", x, J - K, x)
+    return same(oa)[:, None] + same(ob)[None, :] + oa @ J @ ob.T
+
+
+def ref_rdm12_large(cbra, cket, norb, nelec):
+    """(dm1, dm2) in the convention of `ref_rdm12` (PySCF's `trans_rdm12`): E1[r,s] = <bra|E_rs|ket>,
+    EE[p,q,r,s] = <bra|E_pq E_rs|ket> = <E_qp bra|E_rs ket>, dm2 = EE - delta_qr E1[p,s], dm1[p,q] = E1[q,p]."""
+    n2 = norb * norb
+    Dk = _ref_D(norb, nelec, cket).reshape(n2, -1)
+    Db = Dk if cbra is cket else _ref_D(norb, nelec, cbra).reshape(n2, -1)
+    E1 = (Dk @ np.ravel(cbra)).reshape(norb, norb)
+    dm2 = (Db @ Dk.T).reshape((norb,) * 4).transpose(1, 0, 2, 3).copy()
+    for q in range(norb):
+        dm2[:, q, q, :] -= E1
+    return E1.T.copy(), dm2
+
+
+def ref_spin_square_large(c, norb, nelec):
+    """<S^2> = S_z (S_z + 1) + N_b - sum_rs <Ea_rs C, C Eb_rs^T> / <C, C>   (S_- S_+ = N_b - sum_rs Ea_rs Eb_sr, and
+    <C|Ea_rs Eb_sr|C> = <Ea_sr C|Eb_sr C>)."""
+    Ea, Eb = ref_spin_E(norb, nelec[0], 0), ref_spin_E(norb, nelec[1], 1)
+    c = np.asarray(c, dtype=np.float64).reshape(Ea[0][0].shape[0], Eb[0][0].shape[0])
+    x = sum(np.sum((Ea[r][s] @ c) * (Eb[r][s] @ c.T).T) for r in range(norb) for s in range(norb))
+    sz = 0.5 * (nelec[0] - nelec[1])
+    return sz * (sz + 1.0) + nelec[1] - x / np.sum(c * c)
+
+
 def random_integrals(norb, seed, scale=1.0):
     """Random h1 (symmetric) and eri with the full 8-fold symmetry, O(1) entries."""
     rng = np.random.default_rng(seed)
@@ -187,6 +262,51 @@ def test_ref_s2_eigenvalues_are_s_s_plus_1(norb, nelec):
 
 
 # =================================================================================================
+# the matrix-free reference against the dense one
+# =================================================================================================
+SMALL_SECTORS = [(5, (3, 2)), (6, (1, 3)), (5, (2, 0)), (5, (0, 2)), (6, (3, 3)), (4, (0, 0))]
+
+
+@pytest.mark.parametrize("norb,nelec", SMALL_SECTORS)
+def test_matrix_free_sigma_and_diagonal_equal_the_dense_hamiltonian(norb, nelec):
+    h, e = random_integrals(norb, 21 + norb)
+    H = ref_hamiltonian(h, e, norb, nelec)
+    shape = (comb(norb, nelec[0]), comb(norb, nelec[1]))
+    c = np.random.default_rng(3).standard_normal(shape)
+    ref = (H @ c.reshape(-1)).reshape(shape)
+    err = np.abs(ref_sigma(h, e, norb, nelec, c) - ref).max()
+    errd = np.abs(ref_hdiag(h, e, norb, nelec).reshape(-1) - np.diag(H)).max()
+    tol, told = 1e-12 * max(1.0, np.abs(ref).max()), 1e-12 * max(1.0, np.abs(np.diag(H)).max())
+    print(f"({norb},{nelec}): sigma {err:.2e} (bound {tol:.2e}), diagonal {errd:.2e} (bound {told:.2e})")
+    assert err <= tol and errd <= told
+
+
+@pytest.mark.parametrize("norb,nelec", [(4, (2, 2)), (5, (3, 2)), (4, (1, 3)), (5, (2, 0)), (5, (0, 2))])
+def test_matrix_free_density_matrices_equal_the_operator_ones(norb, nelec):
+    rng = np.random.default_rng(4)
+    shape = (comb(norb, nelec[0]), comb(norb, nelec[1]))
+    bra, ket = rng.standard_normal(shape), rng.standard_normal(shape)
+    worst = 0.0
+    for b in (ket, bra):
+        r1, r2 = ref_rdm12(b, ket, norb, nelec)
+        g1, g2 = ref_rdm12_large(b, ket, norb, nelec)
+        scale = max(1.0, np.abs(r1).max(), np.abs(r2).max())
+        worst = max(worst, np.abs(g1 - r1).max() / scale, np.abs(g2 - r2).max() / scale)
+    print(f"({norb},{nelec}): worst error / max(1, |ref|max) {worst:.2e}")
+    assert worst <= 1e-12
+
+
+@pytest.mark.parametrize("norb,nelec", SMALL_SECTORS)
+def test_matrix_free_spin_square_equals_the_operator_one(norb, nelec):
+    S2 = ref_s2(norb, nelec)
+    c = np.random.default_rng(5).standard_normal(S2.shape[0])
+    ref = c @ S2 @ c / (c @ c)
+    got = ref_spin_square_large(c, norb, nelec)
+    print(f"({norb},{nelec}): <S^2> {got:.12f}, operator {ref:.12f}")
+    assert abs(got - ref) <= 1e-12 * max(1.0, abs(ref))
+
+
+# =================================================================================================
 # the product's host tables
 # =================================================================================================
 @pytest.mark.parametrize("norb,n", [(1, 1), (4, 2), (6, 0), (6, 6), (7, 3), (16, 8)])
@@ -227,6 +347,40 @@ def test_link_tables_reproduce_the_reference_excitation_operators(norb, na, nb):
                 src = np.nonzero(t)[0]
                 got2[np.abs(t[src]) - 1, src] = np.sign(t[src])
                 assert np.array_equal(got2, ref), (spin, p, q)
+
+
+@pytest.mark.parametrize("norb,n", [(9, 4), (13, 6), (16, 8)])
+def test_strings_and_link_tables_beyond_a_byte(norb, n):
+    """norb > 8: the occupied orbitals "between p and q" span more than a byte of the mask.  Every (cre, ann) plane of the dense
+    table and of the link list, rebuilt as a sparse [target, source] matrix of signs, equals the single-spin reference operator
+    of either spin entry by entry -- sign, target, and nothing where the reference has no link (a link listed twice would
+    add up to +-2)."""
+    from mi355scf import fci
+    strs = fci.make_strings(norb, n)
+    nstr = comb(norb, n)
+    assert strs.dtype == np.int64 and np.array_equal(strs, ref_strings(norb, n))
+    dense, lt = fci.dense_link_table(norb, n), fci.link_table(norb, n)
+    assert dense.shape == (norb * norb, nstr) and dense.dtype == np.int32
+    assert lt.shape == (nstr, n * (norb - n) + n, 4) and lt.dtype == np.int32
+    J = np.repeat(np.arange(nstr), lt.shape[1])
+    cre, ann, tgt, sgn = (lt[:, :, k].reshape(-1) for k in range(4))
+    assert tgt.min() >= 0 and tgt.max() < nstr and set(np.unique(sgn)) <= {-1, 1}
+    checked = 0
+    for spin in (0, 1):
+        E = ref_spin_E(norb, n, spin)
+        for p in range(norb):
+            for q in range(norb):
+                ref = E[p][q]
+                t = dense[q * norb + p]
+                src = np.nonzero(t)[0]
+                got = sp.csr_matrix((np.sign(t[src]).astype(np.float64), (np.abs(t[src]) - 1, src)), shape=(nstr, nstr))
+                assert (got != ref).nnz == 0, ("dense", spin, p, q)
+                m = (cre == p) & (ann == q)
+                got = sp.csr_matrix((sgn[m].astype(np.float64), (tgt[m], J[m])), shape=(nstr, nstr))
+                assert (got != ref).nnz == 0, ("list", spin, p, q)
+                checked += ref.nnz
+    assert checked == 2 * nstr * lt.shape[1]                 # the reference has exactly the links the list has room for
+    print(f"norb {norb}, n {n}: {nstr} strings, {checked // 2} links per spin checked in both tables")
 
 
 def test_nelec_splitting_and_packed_integrals():

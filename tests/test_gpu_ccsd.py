@@ -3,6 +3,7 @@ converged orbitals with the CPU oracle's integrals (as `test_gpu_casci._referenc
 engine-versus-oracle margin `test_gpu_rsh.py` and `test_gpu_casci.py` use.  SCF conv_tol 1e-11, CCSD conv_tol 1e-10 and
 conv_tol_normt 1e-8.  Molecules come from `conftest.MOLECULES`; H2 (not in that table) is 0.74 Angstrom along z."""
 import functools
+import math
 
 import numpy as np
 import pytest
@@ -125,10 +126,93 @@ def _numpy_t_energy(raw, ijk, wt, t1, ovov, eo, ev):
     return out
 
 
-@pytest.mark.parametrize("v", [2, 13, 17])
+def _amp_inputs(o, v):
+    """Random numerators, old amplitudes and (ia|jb); e_occ in [-2, -1], e_vir in [0.5, 1.5]: every denominator is below -1.5."""
+    rng = np.random.default_rng(1000 * o + v)
+    n = o * v + (o * v) ** 2
+    return rng.standard_normal(n), rng.standard_normal(n), rng.standard_normal((o, v, o, v)), -1.0 - rng.random(o), 0.5 + rng.random(v)
+
+
+def _check_amp_sums(name, got_dt2, got_e, dt_terms, e_terms):
+    """The two sums against `math.fsum` of the reference terms with the a-priori bound of ANY summation order,
+    (N + 8) 2^-53 sum |terms| (N - 1 additions of relative error 2^-53 each; the 8 covers the few roundings inside a term,
+    contracted or not)."""
+    from test_gpu_dense_kernels import U, record
+    for what, got, terms in (("|err|^2", got_dt2, dt_terms), ("energy", got_e, e_terms)):
+        bound = (terms.size + 8) * U * math.fsum(np.abs(terms))
+        record(f"cc_amp_update {name} {what} ({terms.size} terms)", abs(got - math.fsum(terms)) / bound)
+
+
+@pytest.mark.parametrize("o,v", [(1, 1), (2, 3), (5, 13), (8, 64), (10, 80)])
+def test_amp_update_kernel_against_numpy(o, v):
+    """`mi_cc_amp_update` against `numpy_amp_update`.  The kernel is a grid-stride loop of at most 1024 blocks x 256 threads:
+    (8,64) has 262 656 elements, 512 past one trip; (10,80) has 640 800, 2.44 trips with a ragged last one.  New amplitudes within
+    2 ulp (one correctly rounded division on both sides), err = new - old exactly for the kernel's own new amplitudes, the
+    two sums within the any-order bound, and everything bit-identical on a repeat.
+    MI355X: new amplitudes bit-identical (0 ulp) in all five cases.  Sum error / bound, |err|^2 and energy: (1,1) 0, 0; (2,3) 0, 0;
+    (5,13) 4.2e-4, 0; (8,64) 4.4e-5, 3.3e-8; (10,80) 9.8e-6, 1.4e-8."""
+    import torch
+    from mi355scf import ccsd
+    from test_cc_host import numpy_amp_update
+    num, told, ovov, eo, ev = _amp_inputs(o, v)
+    new, err, dt_terms, e_terms = numpy_amp_update(num, told, ovov, eo, ev)
+    T = lambda a: torch.as_tensor(a, dtype=torch.float64, device="cuda").contiguous()
+    args = [T(a) for a in (num, told, ovov, eo, ev)]
+    tnew, terr, dt2, e = ccsd.amp_update_native(*args)
+    tnew2, terr2, dt2_again, e_again = ccsd.amp_update_native(*args)
+    tnew, terr = tnew.cpu().numpy(), terr.cpu().numpy()
+    ulps = np.abs(tnew - new) / np.spacing(np.abs(new))
+    print(f"o = {o}, v = {v}: {new.size} amplitudes, worst new-amplitude error {ulps.max():.1f} ulp, "
+          f"{int((terr != tnew - told).sum())} err elements differ from new - old")
+    assert tnew.shape == new.shape and ulps.max() <= 2.0
+    assert np.array_equal(terr, tnew - told)
+    _check_amp_sums(f"({o},{v})", dt2, e, dt_terms, e_terms)
+    assert np.array_equal(tnew2.cpu().numpy(), tnew) and np.array_equal(terr2.cpu().numpy(), terr)
+    assert dt2 == dt2_again and e == e_again                # fixed-order sums
+
+
+def test_amp_update_c_entry_writes_only_its_outputs():
+    """(8,64) through `mi_cc_amp_update` itself: `tnew`, `err`, `part` and `out` start as NaN, each followed by a guard band.
+    Every element of the four is written (2 x 1024 block partials, 2 results), nothing beyond them.
+    MI355X: all guards intact, no NaN left, sum error / bound 4.4e-5 (|err|^2) and 3.3e-8 (energy)."""
+    import ctypes
+    import torch
+    from mi355scf import engine
+    from test_cc_host import numpy_amp_update
+    from test_gpu_dense_kernels import assert_guard, guarded
+    o, v = 8, 64
+    num, told, ovov, eo, ev = _amp_inputs(o, v)
+    new, err, dt_terms, e_terms = numpy_amp_update(num, told, ovov, eo, ev)
+    n = new.size
+    L = engine.lib()
+    nblk = min(-(-n // 256), int(L.mi_cc_amp_blocks()))
+    assert nblk == 1024 and n == 262656
+    T = lambda a: torch.as_tensor(a, dtype=torch.float64, device="cuda").contiguous()
+    d_num, d_told, d_ovov, d_eo, d_ev = (T(a) for a in (num, told, ovov, eo, ev))
+    sizes = dict(tnew=n, err=n, part=2 * nblk, out=2)
+    bufs = {k: guarded(m) for k, m in sizes.items()}
+    for k, m in sizes.items():
+        bufs[k][:m] = float("nan")
+    engine._check(L.mi_cc_amp_update(d_num.data_ptr(), d_told.data_ptr(), bufs["tnew"].data_ptr(), bufs["err"].data_ptr(), d_ovov.data_ptr(),
+                                     d_eo.data_ptr(), d_ev.data_ptr(), o, v, bufs["part"].data_ptr(), bufs["out"].data_ptr(),
+                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+    host = {k: bufs[k][:m].cpu().numpy() for k, m in sizes.items()}
+    for k, m in sizes.items():
+        assert_guard(bufs[k], m, f"cc_amp_update {k}")
+        assert not np.isnan(host[k]).any(), f"{k}: {int(np.isnan(host[k]).sum())} elements not written"
+    assert (np.abs(host["tnew"] - new) <= 2.0 * np.spacing(np.abs(new))).all() and np.array_equal(host["err"], host["tnew"] - told)
+    part = host["part"].reshape(nblk, 2)
+    assert host["out"][0] == np.add.accumulate(part[:, 0])[-1] and host["out"][1] == np.add.accumulate(part[:, 1])[-1]   # block order
+    _check_amp_sums("(8,64) C entry", host["out"][0], host["out"][1], dt_terms, e_terms)
+
+
+@pytest.mark.parametrize("v", [2, 8, 13, 16, 17, 25])
 def test_t_energy_kernel_against_numpy(v):
     """Random raw cubes: a wrong permutation shows here, whatever the GEMM operands were.  1e-12 relative is FP64
-    summation-order noise over at most 17^3 terms with a margin of a few hundred ulp."""
+    summation-order noise over at most 25^3 terms with a margin of a few hundred ulp.  v = 8 and 16 are whole tiles (no
+    masked lane), v = 25 has four blocks (the block decode walks to A = 3); the third triple is also run alone (ntrip = 1).
+    MI355X: worst per-triple relative error 6.0e-16 (v = 2), 3.7e-16 at v = 25; the lone triple is bit-identical to its batched value."""
     import torch
     from mi355scf import ccsd
     rng = np.random.default_rng(100 + v)
@@ -149,6 +233,9 @@ def test_t_energy_kernel_against_numpy(v):
     assert np.all(np.abs(ref) > 1e-3)                    # random cubes: no triple's sum is accidentally tiny
     assert rel.max() <= 1e-12 and (np.abs(alt - ref) / np.abs(ref)).max() <= 1e-12
     assert np.array_equal(got, again)
+    lone = ccsd.t_energy_native(T(raw[:, 2:3]), T(ijk[2:3], torch.int32), T(wt[2:3]), T(t1), T(ovov), T(eo), T(ev)).cpu().numpy()
+    print(f"ntrip = 1: relative error {abs(lone[0] - ref[2]) / abs(ref[2]):.2e}, batched - lone {got[2] - lone[0]:.1e}")
+    assert lone.shape == (1,) and abs(lone[0] - ref[2]) <= 1e-12 * abs(ref[2]) and lone[0] == got[2]
 
 
 def test_restart_from_converged_amplitudes():
