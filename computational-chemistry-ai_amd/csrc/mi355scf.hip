@@ -9414,6 +9414,313 @@ extern "C" int mi_pcm_fock(mi_ctx *c, const double *d_B, int npts, int64_t ld, c
 }
 
 // =================================================================================================
+// Point-charge embedding (mi355scf/qmmm.py): the attraction integrals of the C-PCM section against an explicit environment of
+// 10^4 .. 10^5 sites, formed, contracted and discarded in one pass -- nothing of size pairs x points is ever stored.
+//
+//   pts[k] = (x, y, z, zeta) in Bohr: zeta <= 0 a point charge (1/r, the nuclear body), zeta > 0 a Gaussian charge
+//   (erf(zeta r)/r, the PCM body); both run the attenuated table, which reproduces the plain one exactly at theta = 1 (pc_eta).
+//
+//   pc_fock_kernel<LA,LB>   workgroup = (shell pair i >= j, chunk of points); the lanes stride over the chunk's points with the
+//                           cartesian block in registers, one butterfly per block, cart -> sph by the first NSA NSB lanes and
+//                           a write into part[chunk][packed column]; pcm_fock_finalize_kernel adds the chunks in index order
+//   pc_grad_kernel<LA,LB>   workgroup = (chunk of ordered pairs, block of 64 .. PC_GRAD_POINTS sites); per pair the density block goes
+//                           to LDS once, each lane walks its points; the bra derivative is summed over the block's points per
+//                           pair (butterfly -> apart[pair][block][3], the share of the atom of shell i) and over the chunk's
+//                           pairs per point (lane-owned LDS slots -> ppart[pair chunk][point][3], the point's share is minus it)
+//   pc_grad_atoms_kernel, pc_grad_points_kernel   the two partial arrays summed in fixed order (no atomics anywhere)
+// =================================================================================================
+#define PC_FOCK_POINTS 256   /* smallest chunk of mi_pc_fock: four points per lane */
+#define PC_FOCK_CHUNKS 64    /* most chunks of mi_pc_fock: beyond PC_FOCK_POINTS * PC_FOCK_CHUNKS points the chunks grow */
+#define PC_GRAD_POINTS 512   /* largest point block of mi_pc_grad: 12 KB of lane-owned LDS accumulators */
+
+struct PcArgs : BasisDev {
+    const int *pairs;      // [n][2] shell pairs of one class (la, lb) = template arguments
+    const double *pts;     // [npts][4]: x, y, z, zeta
+    const double *q;       // [npts]
+    int npts;
+    int per, nchunk;       // Fock: points per chunk, chunks
+    int64_t ld;
+    double *part;          // Fock: [nchunk][ld]
+    const double *D;       // gradient: density [nao][nao]
+    int npair, kpairs, nblk, pblk;   // gradient: pairs of the class, pairs per pair chunk, point blocks, sites per block
+    double *apart;         // gradient: [pairs of the class][nblk][3] at the class' offset
+    double *ppart;         // gradient: [pair chunks of the class][npts][3] at the class' offset
+};
+
+// eta of a site for attraction_table<.., true>: zeta^2, and for a point charge a value so large that theta = eta / (p + eta)
+// rounds to exactly 1 for every exponent p -- the attenuated body then IS the plain one bit for bit (x 1, sqrt(1), u 1), and
+// the two kinds share one instruction stream instead of a divergent branch around two copies of the recurrences
+#define PC_POINT_ETA 1e300
+__device__ __forceinline__ double pc_eta(double zeta) { return zeta > 0.0 ? zeta * zeta : PC_POINT_ETA; }
+
+template <int LA, int LB>
+__global__ __launch_bounds__(64) void pc_fock_kernel(PcArgs A)
+{
+    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2, NSA = 2 * LA + 1, NSB = 2 * LB + 1;
+    constexpr int NR = (LA + LB) / 2 + 1, NI = LA + LB + 1;
+    const int pidx = blockIdx.x / A.nchunk, k = blockIdx.x - pidx * A.nchunk;
+    const int g0 = k * A.per, g1 = min(A.npts, g0 + A.per);
+    const int ish = A.pairs[2 * pidx], jsh = A.pairs[2 * pidx + 1];
+    const int32_t *bi = A.bas + ish * BAS_SLOTS, *bj = A.bas + jsh * BAS_SLOTS;
+    const double *ra = A.env + A.atm[bi[0] * ATM_SLOTS + 1], *rb = A.env + A.atm[bj[0] * ATM_SLOTS + 1];
+    const double AB[3] = {ra[0] - rb[0], ra[1] - rb[1], ra[2] - rb[2]};
+    double acc[NCA * NCB];
+#pragma unroll
+    for (int e = 0; e < NCA * NCB; e++) acc[e] = 0.0;
+    for (int g = g0 + (int)threadIdx.x; g < g1; g += 64) {
+        const double C[3] = {A.pts[4 * g], A.pts[4 * g + 1], A.pts[4 * g + 2]};
+        const double eta = pc_eta(A.pts[4 * g + 3]), qg = A.q[g];
+        for (int ip = 0; ip < bi[2]; ip++)
+            for (int jp = 0; jp < bj[2]; jp++) {
+                PrimPair q = prim_pair(A.env, bi, bj, ip, jp, ra, rb, AB);
+                q.cc = qg * q.cc;   // the point's charge rides on the prefactor
+#pragma unroll
+                for (int r = 0; r < NR; r++) {
+                    double gt[3][NI][LB + 1];
+                    const double f = attraction_table<LB, NI, true>(gt, q, C, eta, AB, NR, r, A.rys);
+                    attraction_accumulate<LA, LB>(acc, gt, f);
+                }
+            }
+    }
+    // butterfly over the wave: every lane ends with the same fixed-order sum of the chunk (no atomics)
+#pragma unroll
+    for (int e = 0; e < NCA * NCB; e++)
+        for (int o = 32; o > 0; o >>= 1) acc[e] += __shfl_xor(acc[e], o);
+    if ((int)threadIdx.x >= NSA * NSB) return;
+    const int i = threadIdx.x / NSB, j = threadIdx.x - i * NSB;
+    int m = A.shell_ao[ish] + i, n = A.shell_ao[jsh] + j;
+    if (ish == jsh && n > m) return;
+    const double v = block_to_spherical<LA, LB>(acc, A.c2s + A.c2s_off[LA], A.c2s + A.c2s_off[LB], i, j);
+    if (m < n) { const int s_ = m; m = n; n = s_; }
+    A.part[(int64_t)k * A.ld + (int64_t)m * (m + 1) / 2 + n] = v;
+}
+
+template <int LA, int LB>
+__global__ __launch_bounds__(64) void pc_grad_kernel(PcArgs A)
+{
+    constexpr int NCA = (LA + 1) * (LA + 2) / 2, NCB = (LB + 1) * (LB + 2) / 2;
+    constexpr int NR = (LA + LB + 1) / 2 + 1, NI = LA + LB + 2;
+    constexpr int ROOT_UNROLL = LA + LB >= 5 ? 1 : NR;   // the three heaviest classes keep one table alive (below)
+    __shared__ double Dc[NCA * NCB];
+    __shared__ double gp[3][PC_GRAD_POINTS];   // slot s belongs to lane s % 64 alone: no synchronisation, fixed order
+    __shared__ double ga[3][64];               // the pair's sum over the lane's sites, kept out of the registers
+    const int cidx = blockIdx.x / A.nblk, b = blockIdx.x - cidx * A.nblk;
+    const int g0 = b * A.pblk, g1 = min(A.npts, g0 + A.pblk);
+    const int p0 = cidx * A.kpairs, p1 = min(A.npair, p0 + A.kpairs);
+    for (int s = threadIdx.x; s < A.pblk; s += 64) gp[0][s] = gp[1][s] = gp[2][s] = 0.0;
+#pragma nounroll
+    for (int p = p0; p < p1; p++) {
+        const int ish = A.pairs[2 * p], jsh = A.pairs[2 * p + 1];
+        const int32_t *bi = A.bas + ish * BAS_SLOTS, *bj = A.bas + jsh * BAS_SLOTS;
+        const int ao_i = A.shell_ao[ish], ao_j = A.shell_ao[jsh];
+        const double *ca = A.c2s + A.c2s_off[LA], *cb = A.c2s + A.c2s_off[LB];
+        __syncthreads();   // the previous pair's block has been read by every lane
+        for (int e = threadIdx.x; e < NCA * NCB; e += 64)   // density block back-transformed to cartesian components, once per pair
+            Dc[e] = density_block_to_cartesian<LA, LB>(A.D, A.nao, ao_i, ao_j, ca, cb, e / NCB, e % NCB);
+        __syncthreads();
+        const double *ra = A.env + A.atm[bi[0] * ATM_SLOTS + 1], *rb = A.env + A.atm[bj[0] * ATM_SLOTS + 1];
+        const double AB[3] = {ra[0] - rb[0], ra[1] - rb[1], ra[2] - rb[2]};
+        ga[0][threadIdx.x] = ga[1][threadIdx.x] = ga[2][threadIdx.x] = 0.0;
+#pragma nounroll
+        for (int s = threadIdx.x; g0 + s < g1; s += 64) {
+            const int g = g0 + s;
+            const double C[3] = {A.pts[4 * g], A.pts[4 * g + 1], A.pts[4 * g + 2]};
+            const double eta = pc_eta(A.pts[4 * g + 3]), qg = A.q[g];
+            double gc[3] = {0.0, 0.0, 0.0};
+            // <2,3>, <3,2>, <3,3>: no unrolling of the root loop -- unrolled, <3,3> keeps four tables alive and spills 1.9 KB per lane
+#pragma nounroll
+            for (int ip = 0; ip < bi[2]; ip++)
+#pragma nounroll
+                for (int jp = 0; jp < bj[2]; jp++) {
+                    PrimPair q = prim_pair(A.env, bi, bj, ip, jp, ra, rb, AB);
+                    q.cc = qg * q.cc;   // the point's charge rides on the prefactor
+#pragma unroll ROOT_UNROLL
+                    for (int r = 0; r < NR; r++) {
+                        double gt[3][NI][LB + 1];
+                        const double f = attraction_table<LB, NI, true>(gt, q, C, eta, AB, NR, r, A.rys);
+                        attraction_bra_gradient<LA, LB>(gc, gt, f, q.a, Dc);
+                    }
+                }
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                ga[d][threadIdx.x] += gc[d];
+                gp[d][s] += gc[d];
+            }
+        }
+        // butterfly over the wave: a fixed-order sum of the block's sites (no atomics)
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            double t = ga[d][threadIdx.x];
+            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+            if (threadIdx.x == 0) A.apart[((int64_t)p * A.nblk + b) * 3 + d] = t;
+        }
+    }
+    for (int s = threadIdx.x; g0 + s < g1; s += 64)
+        for (int d = 0; d < 3; d++) A.ppart[((int64_t)cidx * A.npts + g0 + s) * 3 + d] = gp[d][s];
+}
+
+// out[a] = 2 sum over the ordered pairs whose first shell sits on atom a, over the point blocks: thread t takes pairs t, t + 256, ..
+// in order, then a fixed tree over the threads
+__global__ __launch_bounds__(256) void pc_grad_atoms_kernel(const double *apart, const int *pairs, const int32_t *bas, int npair, int nblk,
+                                                            double *out)
+{
+    __shared__ double sh[3][256];
+    const int a = blockIdx.x;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int p = threadIdx.x; p < npair; p += 256) {
+        if (bas[pairs[2 * p] * BAS_SLOTS] != a) continue;
+        const double *row = apart + (int64_t)p * nblk * 3;
+        for (int b = 0; b < nblk; b++)
+            for (int d = 0; d < 3; d++) s[d] += row[3 * b + d];
+    }
+    for (int d = 0; d < 3; d++) sh[d][threadIdx.x] = s[d];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o)
+            for (int d = 0; d < 3; d++) sh[d][threadIdx.x] += sh[d][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) out[3 * a + threadIdx.x] = 2.0 * sh[threadIdx.x][0];
+}
+
+// out[g][d] = -2 sum_c ppart[c][g][d], pair chunks in index order
+__global__ __launch_bounds__(256) void pc_grad_points_kernel(const double *ppart, int nchunk, int64_t n3, double *out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n3) return;
+    double s = 0.0;
+    for (int c = 0; c < nchunk; c++) s += ppart[(int64_t)c * n3 + i];
+    out[i] = -2.0 * s;
+}
+
+// points per chunk of mi_pc_fock: PC_FOCK_POINTS until there would be more than PC_FOCK_CHUNKS chunks, then whole waves more
+static int pc_fock_points(int npts)
+{
+    const int per = (npts + PC_FOCK_CHUNKS - 1) / PC_FOCK_CHUNKS;
+    return std::max(PC_FOCK_POINTS, (per + 63) / 64 * 64);
+}
+
+extern "C" int mi_pc_fock_chunks(int npts, int64_t ld)
+{
+    (void)ld;   // the chunking depends on the points alone; the row stride is the caller's to size the scratch with
+    if (npts <= 0) return 1;
+    const int per = pc_fock_points(npts);
+    return (npts + per - 1) / per;
+}
+
+// every coordinate, width and charge finite (one copy to the host: these entry points run once per geometry)
+static int pc_check_points(const char *who, const double *d_pts, const double *d_q, int npts, hipStream_t st)
+{
+    std::vector<double> h((size_t)npts * 5);
+    HIPCHK(hipMemcpyAsync(h.data(), d_pts, sizeof(double) * (size_t)npts * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h.data() + (size_t)npts * 4, d_q, sizeof(double) * (size_t)npts, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (size_t k = 0; k < h.size(); k++)
+        if (!std::isfinite(h[k]))
+            return fail("%s: %s %lld is not finite", who, k < (size_t)npts * 4 ? "coordinate or width of point" : "charge of point",
+                        (long long)(k < (size_t)npts * 4 ? k / 4 : k - (size_t)npts * 4));
+    return 0;
+}
+
+extern "C" int mi_pc_fock(mi_ctx *c, const double *d_pts, const double *d_q, int npts, double scale, int accumulate, double *d_work,
+                          double *d_V, void *stream)
+{
+    if (!c || !d_pts || !d_q || !d_work || !d_V) return fail("mi_pc_fock: null argument");
+    if (check_orbital_lmax(c, "mi_pc_fock")) return -1;
+    if (npts < 0) return fail("mi_pc_fock: npts = %d", npts);
+    if (npts == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (pc_check_points("mi_pc_fock", d_pts, d_q, npts, st)) return -1;
+    PcArgs A{basis_dev(c)};
+    const int64_t nn2 = (int64_t)c->nao * (c->nao + 1) / 2;
+    A.pts = d_pts; A.q = d_q; A.npts = npts; A.ld = nn2 + (nn2 & 1); A.part = d_work;
+    A.per = pc_fock_points(npts);
+    A.nchunk = (npts + A.per - 1) / A.per;
+    const int rc = launch_pair_classes<false>(c, A.nchunk, "mi_pc_fock", [&](auto la, auto lb, int first, int count) {
+        PcArgs B = A;
+        B.pairs = c->pair_classes[0].d_pairs + 2 * first;
+        hipLaunchKernelGGL((pc_fock_kernel<decltype(la)::value, decltype(lb)::value>), dim3((unsigned)((int64_t)count * A.nchunk)), dim3(64),
+                           0, st, B);
+    });
+    if (rc) return rc;
+    const size_t nn = (size_t)c->nao * c->nao;
+    hipLaunchKernelGGL(pcm_fock_finalize_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, d_work, A.nchunk, A.ld, c->nao, scale,
+                       accumulate, d_V);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The gradient's chunking.  Point blocks: whole waves of sites, one site per lane for few sites and up to PC_GRAD_POINTS for
+// many (apart = pairs x blocks x 24 B stays at pairs x 64 x 24 B until 32 768 sites).  Pair chunks: a budget for all classes of
+// about 32 768 / blocks workgroups' worth, at most 1024, at most what keeps ppart = chunks x sites x 24 B within 128 MB, at
+// least 64; every class gets a sixteenth of it, so that a class of few, expensive pairs (f f) is spread as widely as one of many
+// cheap ones instead of running its pairs one after the other in a handful of workgroups.
+struct PcGradPlan { int pblk, nblk, kpairs[16], chunk_start[17]; };
+
+static PcGradPlan pc_grad_plan(const mi_ctx *c, int npts)
+{
+    PcGradPlan P;
+    const mi_ctx::PairClasses &pc = c->pair_classes[1];
+    P.pblk = std::min(PC_GRAD_POINTS, std::max(64, ((npts + 63) / 64 + 63) / 64 * 64));
+    P.nblk = std::max(1, (npts + P.pblk - 1) / P.pblk);
+    const int64_t by_memory = ((int64_t)1 << 27) / (24 * (int64_t)std::max(npts, 1));
+    const int budget = (int)std::max<int64_t>(64, std::min<int64_t>({1024, 32768 / P.nblk, by_memory}));
+    P.chunk_start[0] = 0;
+    for (int k = 0; k < 16; k++) {
+        const int count = pc.start[k + 1] - pc.start[k];
+        P.kpairs[k] = std::max(1, (count + budget / 16 - 1) / (budget / 16));
+        P.chunk_start[k + 1] = P.chunk_start[k] + (count + P.kpairs[k] - 1) / P.kpairs[k];
+    }
+    return P;
+}
+
+extern "C" int64_t mi_pc_grad_work(mi_ctx *c, int npts)
+{
+    if (!c || npts < 0) return fail("mi_pc_grad_work: bad arguments");
+    const PcGradPlan P = pc_grad_plan(c, npts);
+    return 3 * ((int64_t)c->pair_classes[1].start[16] * P.nblk + (int64_t)P.chunk_start[16] * npts);
+}
+
+extern "C" int mi_pc_grad(mi_ctx *c, const double *d_pts, const double *d_q, int npts, const double *d_D, double *d_work, double *d_grad_atoms,
+                          double *d_grad_pts, void *stream)
+{
+    if (!c || !d_pts || !d_q || !d_D || !d_work || !d_grad_atoms || !d_grad_pts) return fail("mi_pc_grad: null argument");
+    if (check_orbital_lmax(c, "mi_pc_grad")) return -1;
+    if (npts < 0) return fail("mi_pc_grad: npts = %d", npts);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (npts == 0) {
+        HIPCHK(hipMemsetAsync(d_grad_atoms, 0, sizeof(double) * 3 * (size_t)c->natm, st));
+        return 0;
+    }
+    if (pc_check_points("mi_pc_grad", d_pts, d_q, npts, st)) return -1;
+    const PcGradPlan P = pc_grad_plan(c, npts);
+    const mi_ctx::PairClasses &pc = c->pair_classes[1];
+    PcArgs A{basis_dev(c)};
+    A.pts = d_pts; A.q = d_q; A.npts = npts; A.D = d_D; A.nblk = P.nblk; A.pblk = P.pblk;
+    double *apart = d_work, *ppart = d_work + 3 * (int64_t)pc.start[16] * P.nblk;
+    const int rc = launch_pair_classes<true>(c, P.nblk, "mi_pc_grad", [&](auto la, auto lb, int first, int count) {
+        constexpr int K = decltype(la)::value * 4 + decltype(lb)::value;
+        PcArgs B = A;
+        B.pairs = pc.d_pairs + 2 * first;
+        B.npair = count;
+        B.kpairs = P.kpairs[K];
+        B.apart = apart + 3 * (int64_t)first * P.nblk;
+        B.ppart = ppart + 3 * (int64_t)P.chunk_start[K] * npts;
+        const int64_t nwg = (int64_t)(P.chunk_start[K + 1] - P.chunk_start[K]) * P.nblk;
+        hipLaunchKernelGGL((pc_grad_kernel<decltype(la)::value, decltype(lb)::value>), dim3((unsigned)nwg), dim3(64), 0, st, B);
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(pc_grad_atoms_kernel, dim3((unsigned)c->natm), dim3(256), 0, st, apart, pc.d_pairs, c->d_bas, pc.start[16], P.nblk,
+                       d_grad_atoms);
+    const int64_t n3 = 3 * (int64_t)npts;
+    hipLaunchKernelGGL(pc_grad_points_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, ppart, P.chunk_start[16], n3, d_grad_pts);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// =================================================================================================
 // Determinant full CI inside an active space (mi_fci_*): gather / GEMM / gather over string link tables.
 // =================================================================================================
 #include "fci_kernels.h"

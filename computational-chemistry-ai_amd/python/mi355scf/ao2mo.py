@@ -23,6 +23,9 @@ def check_rhf_reference(mf, who, unrestricted="UHF / UKS references are not supp
         raise NotImplementedError(f"{who}: density-fitted references are not supported")
     if getattr(mf, "_pcm", False) or getattr(mf, "with_solvent", None) is not None:
         raise NotImplementedError(f"{who}: PCM-solvated references are not supported")
+    if getattr(mf, "_qmmm", False):
+        from .qmmm import refuse_embedded
+        refuse_embedded(mf, who)
     if getattr(mf, "_nranks", 1) > 1:
         raise NotImplementedError(f"{who}: sharded references are not supported (one GPU, unsharded ERI store)")
     if not all(hasattr(type(mf), a) for a in ("_jk", "_setup_once", "engine")) or not hasattr(mf, "mo_coeff"):    # (`engine`: a property that opens the GPU)

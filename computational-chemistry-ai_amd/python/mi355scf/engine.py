@@ -137,6 +137,11 @@ def lib():
         L.mi_pcm_potential.argtypes = [vp, vp, ctypes.c_int, i64, vp, vp, vp, vp, vp]
         L.mi_pcm_fock_chunks.argtypes = [ctypes.c_int, i64]
         L.mi_pcm_fock.argtypes = [vp, vp, ctypes.c_int, i64, vp, ctypes.c_double, ctypes.c_int, vp, vp, vp]
+        L.mi_pc_fock_chunks.argtypes = [ctypes.c_int, i64]
+        L.mi_pc_fock.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, vp, vp, vp]
+        L.mi_pc_grad_work.restype = i64
+        L.mi_pc_grad_work.argtypes = [vp, ctypes.c_int]
+        L.mi_pc_grad.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp]
         ci = ctypes.c_int
         L.mi_fci_gather_d.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, vp, vp]
         L.mi_fci_gather_sigma.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp]
@@ -734,6 +739,63 @@ class Engine:
         assert part.numel() >= self.pcm_fock_chunks(n, ld) * ld
         _check(lib().mi_pcm_fock(self._h, B.data_ptr(), n, int(ld), q.data_ptr(), float(scale), int(bool(accumulate)),
                                  part.data_ptr(), V.data_ptr(), self._stream()))
+
+    # --- point-charge embedding (qmmm.py): fused integral-and-contract passes over 10^4 .. 10^5 sites ------------------------
+    @staticmethod
+    def pc_fock_chunks(npts, ld):
+        """Point chunks of `pc_fock` (its scratch is this many rows of ld doubles)."""
+        return int(lib().mi_pc_fock_chunks(int(npts), int(ld)))
+
+    def _pc_points(self, pts, q):
+        assert pts.is_contiguous() and pts.dtype == torch.float64 and pts.dim() == 2 and pts.shape[1] == 4
+        assert q.is_contiguous() and q.dtype == torch.float64 and q.numel() == pts.shape[0]
+        if pts.shape[0] == 0:      # empty tensors have no address: any valid one serves, nothing is read through it
+            pts = q = torch.zeros(4, dtype=torch.float64, device=q.device)
+        return pts.data_ptr(), q.data_ptr()
+
+    def pc_fock(self, pts, q, V, scale=1.0, accumulate=False, work=None):
+        """V (+)= scale sum_k q_k (m| g_k |n) for the sites pts [n, 4] = (x, y, z, zeta) in Bohr: zeta <= 0 a point charge
+        (g = 1/r), zeta > 0 a Gaussian one (g = erf(zeta r)/r).  `work`: pc_fock_chunks(n, ld) * ld doubles, ld the packed
+        size nao (nao + 1) / 2 rounded up to even (allocated here when None)."""
+        ppts, pq = self._pc_points(pts, q)
+        assert V.is_contiguous() and V.dtype == torch.float64 and V.shape == (self.nao, self.nao)
+        n = pts.shape[0]
+        ld = self.nao * (self.nao + 1) // 2
+        ld += ld & 1
+        need = self.pc_fock_chunks(n, ld) * ld
+        if work is None:
+            work = torch.empty(need, dtype=torch.float64, device=self.device)
+        assert work.is_contiguous() and work.numel() >= need
+        with torch.cuda.device(self.device):
+            _check(lib().mi_pc_fock(self._h, ppts, pq, n, float(scale), int(bool(accumulate)), work.data_ptr(),
+                                    V.data_ptr(), self._stream()))
+        return V
+
+    def pc_grad_work(self, npts):
+        n = int(lib().mi_pc_grad_work(self._h, int(npts)))
+        _check(0 if n >= 0 else n)
+        return n
+
+    def pc_grad(self, pts, q, D, work=None, out=None):
+        """(g_atoms [natm, 3], g_pts [n, 3]): the derivatives of sum_k q_k sum_mn D_mn (m| g_k |n) with respect to the basis
+        centres and to the sites, for a symmetric D (the kernels put the derivative on the first shell of every ordered pair and
+        double it).  `work`: pc_grad_work(n) doubles; `out`: the pair of output tensors (both allocated here when None)."""
+        ppts, pq = self._pc_points(pts, q)
+        assert D.is_contiguous() and D.dtype == torch.float64 and D.shape == (self.nao, self.nao)
+        n = pts.shape[0]
+        need = self.pc_grad_work(n)
+        if work is None:
+            work = torch.empty(max(need, 1), dtype=torch.float64, device=self.device)
+        if out is None:
+            out = (torch.empty(self.mol.natm, 3, dtype=torch.float64, device=self.device),
+                   torch.empty(n, 3, dtype=torch.float64, device=self.device))
+        ga, gp = out
+        assert work.is_contiguous() and work.numel() >= need
+        assert ga.is_contiguous() and ga.numel() == 3 * self.mol.natm and gp.is_contiguous() and gp.numel() == 3 * n
+        with torch.cuda.device(self.device):
+            _check(lib().mi_pc_grad(self._h, ppts, pq, n, D.data_ptr(), work.data_ptr(), ga.data_ptr(),
+                                    gp.data_ptr() if n else work.data_ptr(), self._stream()))
+        return ga, gp
 
     # --- row a11: SP2 purification helpers ------------------------------------------------------
     def sp2_init(self, f_orth, X, work):

@@ -231,6 +231,10 @@ def optimize(mf, maxsteps=100, callback=None, coordsys="internal", **kw):
     log = lambda msg: mf._log(3, msg)
     log("Step    Energy (Ha)        dE         RMS grad    max grad    RMS disp(A)  max disp(A)")
     res = None
+    if getattr(mf, "_qmmm", False):
+        # fixed external charges (qmmm.mm_charge) pull on the molecule as a whole: the primitive internals span 3N - 6 motions and
+        # leave that net force and torque standing, so the gradient criteria could never be met -> Cartesian coordinates
+        coordsys = "cart"
     if coordsys.lower() in ("internal", "ric", "tric", "prim", "dlc"):
         res = optimize_internal(gs, mol, maxsteps, log, callback)
     if res is None:

@@ -27,6 +27,8 @@ class Hessian:
     def __init__(self, mf):
         from .dft import require_no_rsh
         require_no_rsh(mf, "Hessian")
+        from .qmmm import refuse_embedded
+        refuse_embedded(mf, "Hessian")
         self.base = mf
         self.mol = mf.mol
         self.verbose = mf.verbose

@@ -17,6 +17,8 @@ class Infrared:
     def __init__(self, mf):
         from .dft import require_no_rsh
         require_no_rsh(mf, "infrared spectrum")
+        from .qmmm import refuse_embedded
+        refuse_embedded(mf, "infrared spectrum")
         self.base = mf
         self.mol = mf.mol
         self.verbose = mf.verbose

@@ -448,6 +448,8 @@ def PCM(mf, **params):
     mf's state).  Closed shells (RHF / RKS), one rank."""
     if getattr(mf, "_pcm", False):
         return mf
+    if getattr(mf, "_qmmm", False):
+        raise NotImplementedError("solvent.PCM on a point-charge-embedded SCF (qmmm.mm_charge) is not supported")
     if not getattr(mf, "_spin_restricted", True):
         raise NotImplementedError("PCM with UHF / UKS is not implemented (closed-shell RHF / RKS only)")
     if getattr(mf, "_nranks", 1) > 1:

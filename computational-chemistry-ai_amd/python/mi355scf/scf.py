@@ -612,7 +612,7 @@ class SCF:
             from . import parallel
             parallel.broadcast0(dm, self._pg)
         self._fgraph = self._fgraph_seen = None     # captured heads belong to one SCF (its CDIIS history buffers)
-        st = {"nocc": mol.nelectron // 2, "enuc": mol.energy_nuc(), "cycle": 0, "diis": DeviceDIIS(eng, self.diis_space)}
+        st = {"nocc": mol.nelectron // 2, "enuc": self.energy_nuc(), "cycle": 0, "diis": DeviceDIIS(eng, self.diis_space)}
         st["dmo"] = self._L.T @ dm @ self._L
         self._after_density(st, dm, e_last=None, next_cycle=0)
         self.timing["first_fock_seconds"] = time.time() - t0
@@ -1006,10 +1006,10 @@ class SCF:
         d = torch.as_tensor(np.asarray(dm), dtype=torch.float64, device=self.engine.device)
         self._setup_once()
         _, e2 = self._veff(d)
-        return float(torch.sum(d * self._h1) + e2) + self.mol.energy_nuc()
+        return float(torch.sum(d * self._h1) + e2) + self.energy_nuc()
 
     def energy_elec(self, dm=None, h1e=None, vhf=None):
-        e = self.energy_tot(dm) - self.mol.energy_nuc()
+        e = self.energy_tot(dm) - self.energy_nuc()
         return e, None
 
     # --- properties the templates read (calculate_energy.py:244-254) ----------------------------

@@ -191,6 +191,8 @@ class _TDBase:
 
     def __init__(self, mf):
         from .dft import parse_xc, rsh_coeff
+        from .qmmm import refuse_embedded
+        refuse_embedded(mf, "TDA/TDDFT")
         if not getattr(mf, "_spin_restricted", True):
             raise NotImplementedError("TDA/TDDFT: only closed-shell RHF/RKS references are supported (UHF/UKS are not)")
         if getattr(mf, "with_df", None) is not None:

@@ -122,7 +122,7 @@ class UHF(SCF):
             return self.e_tot
         self._setup_once()
         d = torch.as_tensor(np.asarray(dm), dtype=torch.float64, device=self.engine.device)
-        return float(self._fock_pair(d)[1]) + self.mol.energy_nuc()
+        return float(self._fock_pair(d)[1]) + self.energy_nuc()
 
     def spin_square(self, mo_coeff=None, s=None):
         """<S^2> and 2S+1 of the UHF determinant: S_z(S_z+1) + n_beta - sum_ij |<i_a|j_b>|^2."""
@@ -436,7 +436,7 @@ class UHF(SCF):
     def _plain_start(self, dm0):
         """State of the plain loop after the first Fock build (`self.nelec` set)."""
         dm = self._udm0(dm0)
-        enuc = self.mol.energy_nuc()
+        enuc = self.energy_nuc()
         # sharded runs: the all-reduced J/K(/Vxc) are identical on every rank and the replicated algebra below is made of
         # deterministic library reductions, so the ranks stay bit-identical without broadcasting control scalars;
         # `sync_control` (auto-on for sharded runs, see scf.SCF) makes rank 0's Gram row / scalars authoritative
@@ -532,7 +532,7 @@ class UHF(SCF):
         n = eng.nao
         na, nb = self.nelec
         dm = self._udm0(dm0)
-        st = {"plain": False, "nocc": (na, nb), "enuc": self.mol.energy_nuc(), "cycle": 0,
+        st = {"plain": False, "nocc": (na, nb), "enuc": self.energy_nuc(), "cycle": 0,
               "diis": DeviceDIIS(eng, self.diis_space, nmat=2), "spin": self._spin_states(n),
               "nvo": max(na * (n - na) + nb * (n - nb), 1), "e_tot": None}
         dmo0 = torch.stack([L.T @ dm[0] @ L, L.T @ dm[1] @ L])

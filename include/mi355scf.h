@@ -468,6 +468,30 @@ int mi_pcm_fock(mi_ctx *ctx, const double *d_B, int npts, int64_t ld, const doub
 int mi_pcm_grad(mi_ctx *ctx, const double *d_pts, int npts, const int32_t *d_blk, int nblk, const double *d_D, const double *d_q,
                 double *d_part, void *stream);
 
+/* ---- point-charge embedding (additions; ABI version unchanged) --------------------------------------------------------------
+ * Sites d_pts[npts][4] = (x, y, z, zeta) in Bohr with charges d_q[npts]: zeta <= 0 a point charge g(r) = 1/r, zeta > 0 a
+ * Gaussian charge g(r) = erf(zeta r)/r (the C-PCM convention).  The integrals are formed, contracted and discarded in one pass:
+ * no buffer of size pairs x points exists, every sum has a fixed order (no atomics; two calls give identical bits).  Null
+ * arguments, npts < 0 and non-finite coordinates, widths or charges are refused; npts == 0 is a no-op (mi_pc_grad: zero d_grad_atoms).
+ * mi_pc_fock:        d_V[nao][nao] (accumulate ? += : =) scale * sum_k q_k (m| g_k |n).  d_work holds
+ *                    mi_pc_fock_chunks(npts, ld) * ld doubles with ld = nao (nao + 1) / 2 rounded up to even: one packed
+ *                    partial matrix per chunk of points, added in index order.
+ * mi_pc_fock_chunks: the number of point chunks, at most 64; chunk k holds the points [k per, (k + 1) per), per = 256 up to
+ *                    16 384 points and ceil(npts / 64) rounded up to a multiple of 64 beyond (ld does not enter).
+ * mi_pc_grad:        the derivative of sum_k q_k sum_mn D_mn (m| g_k |n), D symmetric, with respect to the basis centres,
+ *                    d_grad_atoms[natm][3], and to the sites, d_grad_pts[npts][3] (minus the sum of the bra derivatives of the
+ *                    ordered pairs: translational invariance).  d_work holds mi_pc_grad_work(ctx, npts) doubles:
+ *                    [ordered pairs][site blocks][3] for the atoms (blocks of 64 sites, growing to 512 beyond 32 768 sites) and
+ *                    [pair chunks][npts][3] for the sites (at most 1024 chunks and, beyond 5 461 sites, at most 128 MB).
+ * Both entry points copy the sites to the host and synchronise the stream once per call (the finiteness check): they belong in
+ * the per-geometry set-up, not in a captured graph. */
+int mi_pc_fock_chunks(int npts, int64_t ld);
+int mi_pc_fock(mi_ctx *ctx, const double *d_pts, const double *d_q, int npts, double scale, int accumulate, double *d_work, double *d_V,
+               void *stream);
+int64_t mi_pc_grad_work(mi_ctx *ctx, int npts);
+int mi_pc_grad(mi_ctx *ctx, const double *d_pts, const double *d_q, int npts, const double *d_D, double *d_work, double *d_grad_atoms,
+               double *d_grad_pts, void *stream);
+
 /* ---- determinant full CI in an active space (additions; ABI version unchanged; no context: nothing depends on the molecule) ----
  * `mcscf.CASCI(mf, ncas, nelecas).kernel()` -> fcisolver.kernel (templates/calculate_casscf.py:126-131); stands in for
  * pyscf.fci.direct_spin1's FCIcontract_2e_spin1 / FCImake_hdiag_uhf / FCIrdm12kern_sf of libfci [MEM].
