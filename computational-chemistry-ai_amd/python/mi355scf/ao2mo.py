@@ -1,41 +1,20 @@
-"""What the post-HF methods (`mp2`, `tdscf`, `casci`, `ccsd`, `casscf`) share on top of the resident ERI tile store: the checks
-of the reference, the AO -> MO integral transformation (`transform`: one `Engine.eri_qtrans` pass and three FP64 GEMMs) with
-its work-space plan, the symmetrisation of transformed integrals and the frozen-core Fock matrix.  Plain functions; each
-method module keeps its own algorithm and the wording of its own refusals."""
+"""What the post-HF methods (`mp2`, `tdscf`, `casci`, `ccsd`, `casscf`) share on top of the resident ERI tile store: the store
+guard (`resident_engine`), the AO -> MO integral transformation (`transform`: one `Engine.eri_qtrans` pass and three FP64 GEMMs)
+with its work-space plan, the symmetrisation of transformed integrals and the frozen-core Fock matrix.  Plain functions; each
+method module keeps its own algorithm.  Which references a method takes is its row of `reference.SUPPORT`."""
 import time
 
 import numpy as np
 import torch
 
+from .reference import traits
+
 
 # ---- the reference --------------------------------------------------------------------------------------------------------------
-def check_rhf_reference(mf, who, unrestricted="UHF / UKS references are not supported (closed-shell RHF only)", rohf=False):
-    """Refuse every reference but a closed-shell RHF of this engine on one GPU, without touching the GPU; `rohf`: an engine ROHF
-    (one orbital set, occupations 2 / 1 / 0) passes too."""
-    if getattr(mf, "_rohf", False):
-        if not rohf:
-            raise NotImplementedError(f"{who}: restricted open-shell (ROHF / ROKS) references are not supported")
-    elif not getattr(mf, "_spin_restricted", True):
-        raise NotImplementedError(f"{who}: {unrestricted}")
-    if getattr(mf, "xc", None) is not None:
-        raise NotImplementedError(f"{who}: Kohn-Sham references (xc = {mf.xc!r}) are not supported (closed-shell RHF only)")
-    if getattr(mf, "with_df", None) is not None:
-        raise NotImplementedError(f"{who}: density-fitted references are not supported")
-    if getattr(mf, "_pcm", False) or getattr(mf, "with_solvent", None) is not None:
-        raise NotImplementedError(f"{who}: PCM-solvated references are not supported")
-    if getattr(mf, "_qmmm", False):
-        from .qmmm import refuse_embedded
-        refuse_embedded(mf, who)
-    if getattr(mf, "_nranks", 1) > 1:
-        raise NotImplementedError(f"{who}: sharded references are not supported (one GPU, unsharded ERI store)")
-    if not all(hasattr(type(mf), a) for a in ("_jk", "_setup_once", "engine")) or not hasattr(mf, "mo_coeff"):    # (`engine`: a property that opens the GPU)
-        raise NotImplementedError(f"{who}: {type(mf).__name__} is not an RHF object of this engine")
-
-
 def resident_engine(mf, who):
     """The engine of `mf` with the resident, unsharded ERI store of one GPU ready; sharded and direct-mode references are refused.
     Whether a reference runs in the direct mode is known only after its set-up, which therefore runs first."""
-    if getattr(mf, "_nranks", 1) > 1:
+    if traits(mf).nranks > 1:
         raise NotImplementedError(f"{who}: sharded references are not supported (one GPU, unsharded ERI store)")
     mf._setup_once()
     if getattr(mf, "_stream_groups", 1) > 1:

@@ -16,6 +16,8 @@ import re
 
 import numpy as np
 
+from .reference import require
+
 
 def avas_algebra(C, mo_occ, S, S12, S22, F=None, threshold=0.2, canonicalize=True):
     """-> (ncas, nelecas, mo_coeff, (n_occ_kept, n_vir_kept)).  C [N, nmo]: orbitals with occupations mo_occ (2 / 0);
@@ -104,7 +106,8 @@ def avas(mf, ao_labels, threshold=0.2, minao="sto-3g", with_iao=False, openshell
     or indices of reference AOs."""
     if with_iao or ncore:
         raise NotImplementedError("avas: with_iao and ncore are not implemented")
-    if getattr(mf, "_rohf", False) or not getattr(mf, "_spin_restricted", True) or int(getattr(mf.mol, "spin", 0)):
+    require(mf, "avas")
+    if int(getattr(mf.mol, "spin", 0)):
         raise NotImplementedError("avas: closed-shell RHF references only")
     if mf.mo_coeff is None:
         raise NotImplementedError("avas: the reference has no orbitals; run mf.kernel() first")

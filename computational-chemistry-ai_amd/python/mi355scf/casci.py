@@ -13,8 +13,8 @@ and `ci` a list.  `natorb = True` rotates the active block to the natural orbita
 CI again in them (so `ci` belongs to the returned `mo_coeff`) and fills `mo_occ`.  There is no canonicalisation: `mo_energy` is
 the diagonal of the reference's Fock matrix in the returned orbitals.
 
-Not implemented (refused with NotImplementedError, never approximated): RKS / ROKS / UHF / UKS references, an open-shell core, density fitting, PCM,
-sharded or direct-mode references.  Orbital optimisation and state averaging are `casscf.CASSCF` (re-exported here).
+Not implemented (refused with NotImplementedError, never approximated): the references of row "CASCI" of `reference.SUPPORT`, an
+open-shell core, direct-mode references.  Orbital optimisation and state averaging are `casscf.CASSCF` (re-exported here).
 """
 import sys
 
@@ -22,14 +22,15 @@ import numpy as np
 import torch
 
 from . import fci
-from .ao2mo import check_rhf_reference, core_fock, resident_engine, symmetrize8, transform
+from .ao2mo import core_fock, resident_engine, symmetrize8, transform
+from .reference import require
 
 
 class CASCI:
     natorb = False
 
     def __init__(self, mf, ncas, nelecas, ncore=None):
-        check_rhf_reference(mf, "CASCI", rohf=True)
+        ref = require(mf, "CASCI")
         self._scf = mf
         self.mol = mf.mol
         self.verbose = mf.verbose
@@ -58,7 +59,7 @@ class CASCI:
             raise NotImplementedError(f"CASCI: ncas = {self.ncas}; the FCI solver holds at most {fci.MAX_NORB} orbitals")
         if nmo is not None and self.ncore + self.ncas > nmo:
             raise NotImplementedError(f"CASCI: ncore + ncas = {self.ncore + self.ncas} exceeds the {nmo} molecular orbitals")
-        if getattr(mf, "_rohf", False):
+        if ref.spin == "rohf":
             na, nb = self.mol.nelec
             for i in range(nb, na):          # the core density is built closed-shell: no singly occupied orbital may fall outside
                 if not self.ncore <= i < self.ncore + self.ncas:

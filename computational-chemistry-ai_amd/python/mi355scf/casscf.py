@@ -34,8 +34,8 @@ averages, `e_tot` the weighted energy, `e_states` the per-state energies, `ci` t
 
 The gradient, rotation and step algebra are plain functions of NumPy arrays (tests/test_casscf_host.py drives them on a CPU).
 
-Not implemented (refused with NotImplementedError): everything `ao2mo.check_rhf_reference` refuses, ROHF / ROKS references
-(ROHF-based CASSCF), references that have not been run, direct-mode stores, state-specific excited states (`fcisolver.nroots > 1`
+Not implemented (refused with NotImplementedError): the references of row "CASSCF" of `reference.SUPPORT` (ROHF / ROKS among them:
+no ROHF-based CASSCF), references that have not been run, direct-mode stores, state-specific excited states (`fcisolver.nroots > 1`
 without `state_average`).  Nuclear gradients (`nuc_grad_method()`, casscf_grad.py) exist for the state-specific wavefunction only:
 state-averaged objects are refused there.
 """
@@ -44,8 +44,9 @@ import copy
 import numpy as np
 import torch
 
-from .ao2mo import check_rhf_reference, core_fock, resident_engine, symmetrize8
+from .ao2mo import core_fock, resident_engine, symmetrize8
 from .casci import CASCI
+from .reference import require
 
 RISE_NOISE = 1e-11        # Hartree: an energy "rise" below this is the CI eigenvalue's noise, not a rise
 HDIAG_FLOOR = 0.05        # smallest diagonal Hessian element the preconditioner divides by
@@ -237,10 +238,7 @@ class CASSCF(CASCI):
     stability_probe = 1e-3     # |kappa| of the central-difference gradient probes
 
     def __init__(self, mf, ncas, nelecas, ncore=None):
-        if getattr(mf, "_rohf", False):
-            raise NotImplementedError("CASSCF: restricted open-shell (ROHF / ROKS) references are not supported yet: ROHF-based "
-                                      "CASSCF is not implemented (mcscf.CASCI takes an ROHF reference)")
-        check_rhf_reference(mf, "CASSCF")
+        require(mf, "CASSCF")
         if mf.mo_coeff is None:
             raise NotImplementedError("CASSCF: the reference has no orbitals; run mf.kernel() first")
         super().__init__(mf, ncas, nelecas, ncore)

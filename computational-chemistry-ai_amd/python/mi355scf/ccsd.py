@@ -26,8 +26,8 @@ per-workgroup then fixed-order reduction into one number per triple); no v^3 per
 Settings keep PySCF's names; the defaults (conv_tol 1e-7, conv_tol_normt 1e-5, max_cycle 50, diis_space 6, diis_start_cycle 0)
 and the `frozen` convention (`ao2mo.active_mask`) are written from memory, not pinned against PySCF.
 
-Not implemented (refused with NotImplementedError, never approximated): UHF / UKS references (UCCSD), Kohn-Sham references,
-density fitting, PCM, sharded or direct-mode references, frozen natural orbitals, gradients, lambda equations.
+Not implemented (refused with NotImplementedError, never approximated): the references of row "CCSD" of `reference.SUPPORT`,
+direct-mode references, frozen natural orbitals, gradients, lambda equations.
 """
 import ctypes
 import sys
@@ -37,8 +37,9 @@ import numpy as np
 import torch
 
 from . import engine
-from .ao2mo import (active_mask, check_rhf_reference, free_hbm, plan_qtrans_batch, qtrans_work_bytes, resident_engine, symmetrize8,
+from .ao2mo import (active_mask, free_hbm, plan_qtrans_batch, qtrans_work_bytes, resident_engine, symmetrize8,
                     transform)
+from .reference import require
 
 PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))     # lexicographic, as in csrc/cc_kernels.h
 _Z_COEFF = (4.0, -2.0, -2.0, 1.0, 1.0, -2.0)                                   # identity, transpositions, 3-cycles
@@ -204,7 +205,7 @@ class CCSD:
     t_batch = None          # (T): occupied triples per launch (None: from free HBM)
 
     def __init__(self, mf, frozen=None):
-        check_rhf_reference(mf, "CCSD", unrestricted="UCCSD is not implemented (UHF / UKS references; closed-shell RHF only)")
+        require(mf, "CCSD")
         self._scf = mf
         self.mol = mf.mol
         self.verbose = mf.verbose

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .grids import Grids, _grid_generation
+from .reference import require
 from .scf import RHF
 
 XC_IDS = {"slater": 1, "b88": 2, "vwn_rpa": 3, "vwn5": 4, "lyp": 5, "pbe_x": 6, "pbe_c": 7,
@@ -87,25 +88,12 @@ def xc_params(name):
     return [omega if k in ids else 0.0 for _c, k in terms]
 
 
-def require_no_rsh(mf, what):
-    """NotImplementedError for paths that have no long-range exchange (K_LR) and would silently drop it."""
-    xc = getattr(mf, "xc", None)
-    if is_rsh(xc):
-        raise NotImplementedError(f"{what}: not implemented for the range-separated hybrid {xc} (no long-range exchange "
-                                  "integrals on this path)")
-
-
 def check_rsh_scf(mf):
     """Configurations a range-separated-hybrid SCF refuses instead of running without K_LR."""
     xc = mf.xc
     if getattr(mf, "omega", None) is not None:
         raise NotImplementedError(f"{xc}: mf.omega overrides are not implemented (the functional's own omega is used)")
-    if getattr(mf, "with_df", None) is not None:
-        raise NotImplementedError(f"{xc}: density fitting is not implemented for range-separated hybrids")
-    if getattr(mf, "with_solvent", None) is not None:
-        raise NotImplementedError(f"{xc}: PCM solvation is not implemented for range-separated hybrids")
-    if mf._nranks > 1:
-        raise NotImplementedError(f"{xc}: sharded runs are not implemented for range-separated hybrids")
+    require(mf, "RSH SCF")
     if mf._stream_groups > 1:
         raise NotImplementedError(f"{xc}: the ERI store does not fit (direct mode); not implemented for range-separated hybrids")
 

@@ -17,6 +17,7 @@ import numpy as np
 
 from .internals import Internals
 from .mole import BOHR
+from .reference import traits
 
 CONV = dict(energy=1e-6, grms=3e-4, gmax=4.5e-4, drms=1.2e-3, dmax=1.8e-3)
 _COV = {1: 0.31, 2: 0.28, 3: 1.28, 4: 0.96, 5: 0.84, 6: 0.76, 7: 0.71, 8: 0.66, 9: 0.57, 10: 0.58,
@@ -207,6 +208,13 @@ def optimize_internal(energy_grad, mol, maxsteps=100, log=lambda m: None, callba
     return mol, converged, step
 
 
+def choose_coordsys(mf, coordsys="internal"):
+    """"internal" or "cart", the coordinates `optimize(mf, coordsys=...)` works in.  Fixed external charges (qmmm.mm_charge) pull on
+    the molecule as a whole: the primitive internals span 3N - 6 motions and leave that net force and torque standing, so the
+    gradient criteria could never be met -> Cartesian coordinates."""
+    return "internal" if coordsys.lower() in ("internal", "ric", "tric", "prim", "dlc") and not traits(mf).qmmm else "cart"
+
+
 def optimize(mf, maxsteps=100, callback=None, coordsys="internal", **kw):
     """Drop-in for `pyscf.geomopt.geometric_solver.optimize(mf, maxsteps=...)`: returns a `Mole` at the
     optimised geometry.  `coordsys="internal"` (default; redundant primitive internals, Cartesian fallback) or
@@ -231,11 +239,7 @@ def optimize(mf, maxsteps=100, callback=None, coordsys="internal", **kw):
     log = lambda msg: mf._log(3, msg)
     log("Step    Energy (Ha)        dE         RMS grad    max grad    RMS disp(A)  max disp(A)")
     res = None
-    if getattr(mf, "_qmmm", False):
-        # fixed external charges (qmmm.mm_charge) pull on the molecule as a whole: the primitive internals span 3N - 6 motions and
-        # leave that net force and torque standing, so the gradient criteria could never be met -> Cartesian coordinates
-        coordsys = "cart"
-    if coordsys.lower() in ("internal", "ric", "tric", "prim", "dlc"):
+    if choose_coordsys(mf, coordsys) == "internal":
         res = optimize_internal(gs, mol, maxsteps, log, callback)
     if res is None:
         res = optimize_cartesian(gs, mol, maxsteps, log, callback)

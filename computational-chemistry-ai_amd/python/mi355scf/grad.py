@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .mole import Mole
+from .reference import require
 
 
 def grad_nuc(mol):
@@ -150,8 +151,7 @@ class Gradients:
     grid_response = False
 
     def __init__(self, mf):
-        from .dft import require_no_rsh
-        require_no_rsh(mf, "nuclear gradients")
+        require(mf, "nuclear gradients")
         self.base = mf
         self.mol = mf.mol
         self.de = None
@@ -241,8 +241,7 @@ class FDGradients:
     step = 2.0e-3  # Bohr
 
     def __init__(self, mf):
-        from .dft import require_no_rsh
-        require_no_rsh(mf, "nuclear gradients")
+        require(mf, "nuclear gradients")
         self.base = mf
         self.mol = mf.mol
         self.de = None

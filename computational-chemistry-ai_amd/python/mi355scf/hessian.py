@@ -16,6 +16,8 @@ small molecules.  Returns the PySCF layout `hess[i, j, x, y] = d2E / dR_ix dR_jy
 """
 import numpy as np
 
+from .reference import require
+
 
 class Hessian:
     step = 5.0e-3   # Bohr
@@ -25,10 +27,7 @@ class Hessian:
     grid_response = False
 
     def __init__(self, mf):
-        from .dft import require_no_rsh
-        require_no_rsh(mf, "Hessian")
-        from .qmmm import refuse_embedded
-        refuse_embedded(mf, "Hessian")
+        require(mf, "Hessian")
         self.base = mf
         self.mol = mf.mol
         self.verbose = mf.verbose

@@ -7,6 +7,7 @@ import numpy as np
 
 from . import thermo
 from .hessian import Hessian
+from .reference import require
 
 KM_PER_MOL = 974.8801   # (e^2/amu) -> km/mol  [= 42.2561 km/mol per (D/A)^2/amu * (4.80320 D/A per e)^2]
 
@@ -15,10 +16,7 @@ class Infrared:
     grid_response = False   # forwarded to the Hessian's displaced gradients (`hessian.Hessian.grid_response`)
 
     def __init__(self, mf):
-        from .dft import require_no_rsh
-        require_no_rsh(mf, "infrared spectrum")
-        from .qmmm import refuse_embedded
-        refuse_embedded(mf, "infrared spectrum")
+        require(mf, "infrared spectrum")
         self.base = mf
         self.mol = mf.mol
         self.verbose = mf.verbose

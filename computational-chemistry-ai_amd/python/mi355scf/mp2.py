@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from .ao2mo import active_mask as _active, plan_qtrans_batch, qtrans_work_bytes, resident_engine, transform
+from .reference import require
 
 MAX_NAO = 220   # dense path: 8 * 220^4 = 18.7 GB tensor
 T2_MAX_BYTES = 8 * (MAX_NAO // 2) ** 4   # 1.17 GB: the largest n_occ^2 n_vir^2 amplitude tensor of any N <= MAX_NAO basis
@@ -38,8 +39,7 @@ class MP2:
     occ_batch = None        # occupied orbitals per batch of the streaming path (None: from free HBM)
 
     def __init__(self, mf, frozen=None):
-        if getattr(mf, "_rohf", False):
-            raise NotImplementedError("MP2: restricted open-shell (ROHF / ROKS) references are not supported (RHF -> RMP2, UHF -> UMP2)")
+        require(mf, "MP2")
         self._scf = mf
         self.mol = mf.mol
         self.verbose = mf.verbose

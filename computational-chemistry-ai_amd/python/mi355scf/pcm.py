@@ -21,6 +21,7 @@ import torch
 
 from .grids import lebedev
 from .mole import BOHR
+from .reference import require, wrap
 
 # ---- the defaults, all [MEM] (entered from memory; not checked against PySCF or the papers) -------------------------------
 DEFAULTS = {
@@ -412,11 +413,6 @@ class _PCMMixin:
 
     TDHF = TDDFT = TDA
 
-    def shard(self, rank, nranks, process_group=None):
-        if nranks > 1:
-            raise NotImplementedError("PCM runs on one rank")
-        return super().shard(rank, nranks, process_group)
-
     def PCM(self):
         return self
 
@@ -446,23 +442,10 @@ _CLASSES = {}
 def PCM(mf, **params):
     """`solvent.PCM(mf)`: the SCF object wrapped for C-PCM (an instance of a subclass of mf's class made at run time, sharing
     mf's state).  Closed shells (RHF / RKS), one rank."""
-    if getattr(mf, "_pcm", False):
+    if isinstance(mf, _PCMMixin):
         return mf
-    if getattr(mf, "_qmmm", False):
-        raise NotImplementedError("solvent.PCM on a point-charge-embedded SCF (qmmm.mm_charge) is not supported")
-    if not getattr(mf, "_spin_restricted", True):
-        raise NotImplementedError("PCM with UHF / UKS is not implemented (closed-shell RHF / RKS only)")
-    if getattr(mf, "_nranks", 1) > 1:
-        raise NotImplementedError("PCM runs on one rank")
-    from .dft import require_no_rsh
-    require_no_rsh(mf, "PCM")
-    base = mf.__class__
-    cls = _CLASSES.get(base)
-    if cls is None:
-        cls = _CLASSES[base] = type("PCM" + base.__name__, (_PCMMixin, base), {})
-    new = cls.__new__(cls)
-    new.__dict__.update(mf.__dict__)
-    new.with_solvent = PCMSolvent(mf.mol)
+    require(mf, "PCM")
+    new = wrap(mf, _PCMMixin, "PCM", _CLASSES, with_solvent=PCMSolvent(mf.mol))
     for k, v in params.items():
         setattr(new.with_solvent, k, v)
     _method(new.with_solvent.method)

@@ -16,11 +16,12 @@ available when this was written, so parity with it has not been checked.
 
 The embedding is part of h1, so the SCF cycle, its captured graph and the purification see an ordinary core Hamiltonian.  One
 rank, no density fitting, no PCM on top; the post-SCF methods that were not checked with an embedded reference refuse it
-(`refuse_embedded`), MP2 reads only the orbitals and their energies and is allowed."""
+(the "qmmm" entries of `reference.SUPPORT`), MP2 reads only the orbitals and their energies and is allowed."""
 import numpy as np
 import torch
 
 from .mole import BOHR
+from .reference import require, traits, wrap
 
 NEAR = 1e-8        # Bohr: a point charge this close to a nucleus makes the energy diverge
 _TSP = 2.0 / np.sqrt(np.pi)
@@ -102,13 +103,6 @@ def grad_nuc_mm(atom_coords, atom_charges, coords, charges, zeta):
     return t.sum(axis=1), -t.sum(axis=0)
 
 
-def refuse_embedded(mf, who):
-    """NotImplementedError for a method that was not checked with a point-charge-embedded reference."""
-    if getattr(mf, "_qmmm", False):
-        raise NotImplementedError(f"{who}: point-charge-embedded references (qmmm.mm_charge) are not supported: the method "
-                                  "was not verified with an embedded core Hamiltonian")
-
-
 # ---- the embedded SCF object ---------------------------------------------------------------------------------------------------
 class MMSites:
     """`mf.mm_mol`: the sites in Bohr (`atom_coords()`), their charges (`atom_charges()`) and widths (`zeta`, 0 = point)."""
@@ -142,12 +136,7 @@ class _QMMMMixin:
         return self.mm_mol.charges
 
     def _check_embedding(self):
-        if getattr(self, "_nranks", 1) > 1:
-            raise NotImplementedError("qmmm.mm_charge runs on one rank")
-        if getattr(self, "with_df", None) is not None:
-            raise NotImplementedError("qmmm.mm_charge: density-fitted SCF objects are not supported")
-        if getattr(self, "with_solvent", None) is not None:
-            raise NotImplementedError("qmmm.mm_charge: PCM solvation on top of the embedding is not supported")
+        require(self, "embedded SCF")
         mm = self.mm_mol
         check_sites(self.mol.atom_coords(), self.mol.atom_charges(), mm.coords, mm.zeta)
 
@@ -178,14 +167,6 @@ class _QMMMMixin:
 
     Gradients = nuc_grad_method
 
-    def shard(self, rank, nranks, process_group=None):
-        if nranks > 1:
-            raise NotImplementedError("qmmm.mm_charge runs on one rank")
-        return super().shard(rank, nranks, process_group)
-
-    def density_fit(self, *a, **kw):
-        raise NotImplementedError("qmmm.mm_charge: density fitting of an embedded SCF is not supported")
-
 
 _CLASSES = {}
 
@@ -193,25 +174,10 @@ _CLASSES = {}
 def mm_charge(mf, coords, charges, radii=None, unit=None):
     """`qmmm.mm_charge(mf, coords, charges)`: mf embedded in the charges (an instance of a subclass of mf's class made at run
     time, sharing mf's state).  RHF / UHF / ROHF / RKS / UKS / ROKS on one rank."""
-    if not all(hasattr(type(mf), a) for a in ("_setup", "_setup_once", "engine", "energy_nuc")):
-        raise NotImplementedError(f"qmmm.mm_charge: {type(mf).__name__} is not an SCF object of this engine")
-    if getattr(mf, "_pcm", False) or getattr(mf, "with_solvent", None) is not None:
-        raise NotImplementedError("qmmm.mm_charge on a PCM-solvated SCF is not supported")
-    if getattr(mf, "with_df", None) is not None:
-        raise NotImplementedError("qmmm.mm_charge: density-fitted SCF objects are not supported")
-    if getattr(mf, "_nranks", 1) > 1:
-        raise NotImplementedError("qmmm.mm_charge runs on one rank")
+    require(mf, "qmmm.mm_charge")
     sites = MMSites(*mm_sites(mf.mol, coords, charges, radii, unit))
     check_sites(mf.mol.atom_coords(), mf.mol.atom_charges(), sites.coords, sites.zeta)
-    if getattr(mf, "_qmmm", False):
-        new = mf            # embedding again replaces the sites (one set of charges per object)
-    else:
-        base = mf.__class__
-        cls = _CLASSES.get(base)
-        if cls is None:
-            cls = _CLASSES[base] = type("QMMM" + base.__name__, (_QMMMMixin, base), {})
-        new = cls.__new__(cls)
-        new.__dict__.update(mf.__dict__)
+    new = mf if isinstance(mf, _QMMMMixin) else wrap(mf, _QMMMMixin, "QMMM", _CLASSES)   # (again: the sites are replaced)
     new.mm_mol = sites
     new._h1 = None          # the core Hamiltonian of the bare molecule is no longer this object's
     return new
@@ -220,6 +186,7 @@ def mm_charge(mf, coords, charges, radii=None, unit=None):
 # ---- gradients -------------------------------------------------------------------------------------------------------------------
 class _QMMMGradMixin:
     """What a gradient object of an embedded SCF gains: the MM terms on the QM atoms and the derivatives on the sites."""
+    _qmmm = True
 
     def _total_density(self, dm=None):
         mf = self.base
@@ -263,24 +230,17 @@ _GRAD_CLASSES = {}
 
 
 def _embedded_gradients(g, sites):
-    if getattr(g, "_qmmm", False):
+    if isinstance(g, _QMMMGradMixin):
         g.mm_mol = sites
         return g
-    base = g.__class__
-    cls = _GRAD_CLASSES.get(base)
-    if cls is None:
-        cls = _GRAD_CLASSES[base] = type("QMMM" + base.__name__, (_QMMMGradMixin, base), {"_qmmm": True})
-    new = cls.__new__(cls)
-    new.__dict__.update(g.__dict__)
-    new.mm_mol = sites
-    return new
+    return wrap(g, _QMMMGradMixin, "QMMM", _GRAD_CLASSES, mm_mol=sites)
 
 
 def mm_charge_grad(grad_obj, coords, charges, radii=None, unit=None):
     """`qmmm.mm_charge_grad(mf.nuc_grad_method(), coords, charges)` [MEM]: the gradient object with the MM terms.  Its SCF
     must be embedded in the same charges (the energy-weighted density needs the embedded Fock matrix)."""
     mf = grad_obj.base
-    if not getattr(mf, "_qmmm", False):
+    if not traits(mf).qmmm:
         raise NotImplementedError("qmmm.mm_charge_grad: the SCF object behind the gradient is not embedded (use qmmm.mm_charge first)")
     if not all(hasattr(grad_obj, a) for a in ("_densities", "kernel")):
         raise NotImplementedError(f"qmmm.mm_charge_grad: {type(grad_obj).__name__} is not an analytic SCF gradient of this engine")

@@ -18,8 +18,8 @@ like F n - n F) with the partial sums of |G|^2.  The loop is UHF's plain loop (`
 `eigh` of it per cycle in the Cholesky-orthogonalised basis.  The two nested densities are not purified (DESIGN.md section 14 names
 that as the follow-up).
 
-Refused (NotImplementedError, never approximated): range-separated hybrids, density fitting, sharded runs; PCM, TDA / TDDFT, MP2
-and CCSD refuse an ROHF reference themselves.  `mcscf.CASCI` accepts ROHF (not ROKS).
+Refused (NotImplementedError, never approximated): rows "ROHF / ROKS", "density_fit()" and "shard()" of `reference.SUPPORT`; the
+"rohf" entries of the other rows are the methods that do not take an ROHF reference.  `mcscf.CASCI` accepts ROHF (not ROKS).
 """
 import ctypes
 
@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import engine as _engine
+from .reference import require
 from .uhf import UHF
 from .uks import UKS
 
@@ -69,14 +70,6 @@ class ROHF(UHF):
     _purify_spins = False    # one `eigh` of F_eff per cycle at every size: the two nested densities are not purified
     # (`_spin_restricted` stays False as for UHF: every consumer that needs a closed shell -- PCM, TDA / TDDFT, CCSD -- refuses)
 
-    def shard(self, rank, nranks, process_group=None):
-        if nranks > 1:
-            raise NotImplementedError("ROHF / ROKS: sharded runs are not implemented")
-        return UHF.shard(self, rank, nranks, process_group)
-
-    def density_fit(self, *a, **kw):
-        raise NotImplementedError("ROHF / ROKS: density fitting is not implemented")
-
     # --- densities and occupations --------------------------------------------------------------
     def _classes(self):
         """(ncore, nopen) = (n_beta, n_alpha - n_beta)."""
@@ -101,11 +94,7 @@ class ROHF(UHF):
 
     # --- the plain loop's hooks -----------------------------------------------------------------
     def kernel(self, dm0=None, **kw):
-        from .dft import is_rsh
-        if is_rsh(getattr(self, "xc", None)):
-            raise NotImplementedError(f"ROKS: the range-separated hybrid {self.xc} is not implemented (RKS / UKS only)")
-        if getattr(self, "with_df", None) is not None or getattr(self, "with_solvent", None) is not None:
-            raise NotImplementedError("ROHF / ROKS: density fitting and PCM solvation are not implemented")
+        require(self, "ROHF / ROKS")
         return self._run(dm0, fast=False)
 
     scf = kernel

@@ -19,6 +19,7 @@ import torch
 from . import engine as _engine
 from .mole import Mole
 from .purify import HEAD_MAX, Purifier
+from .reference import require
 
 AU2DEBYE = 2.541746473  # e*a0 -> Debye [MEM: pyscf.data.nist.AU2DEBYE]
 
@@ -184,10 +185,11 @@ class SCF:
     def shard(self, rank, nranks, process_group=None):
         """Shard the resident-ERI tile runs over `nranks` GPUs; J/K partial sums are all-reduced over
         RCCL each Fock build."""
-        self._rank, self._nranks, self._pg = rank, nranks, process_group
         if nranks > 1:
+            require(self, "shard()")
             from . import parallel
             parallel.blas_atomics_off()
+        self._rank, self._nranks, self._pg = rank, nranks, process_group
         return self
 
     def _sync_control_on(self):
@@ -1036,8 +1038,7 @@ class SCF:
         set, or a {element: shells} dict.  Returns `self` (PySCF returns a DF-decorated copy; the templates' idiom
         `mf = mf.density_fit()` works with both)."""
         from . import df
-        from .dft import require_no_rsh
-        require_no_rsh(self, "density_fit()")
+        require(self, "density_fit()")
         self.with_df = with_df if with_df is not None else df.DF(self.mol, auxbasis)
         self._eng_df_ready = False
         return self

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .ao2mo import resident_engine
+from .reference import require
 
 HARTREE2EV = 27.211386245988
 HARTREE2NM = 45.56335252907954   # nm * Hartree: lambda = 45.563... / E
@@ -191,13 +192,7 @@ class _TDBase:
 
     def __init__(self, mf):
         from .dft import parse_xc, rsh_coeff
-        from .qmmm import refuse_embedded
-        refuse_embedded(mf, "TDA/TDDFT")
-        if not getattr(mf, "_spin_restricted", True):
-            raise NotImplementedError("TDA/TDDFT: only closed-shell RHF/RKS references are supported (UHF/UKS are not)")
-        if getattr(mf, "with_df", None) is not None:
-            raise NotImplementedError("TDA/TDDFT: density-fitted references are not supported")
-        xc = getattr(mf, "xc", None)
+        xc = require(mf, "TDA/TDDFT").xc
         self._omega, self._alpha = 0.0, 0.0
         if xc is None:
             self._hyb, self._dft = 1.0, False

@@ -30,7 +30,7 @@ rotations) and W (orthonormality).  In the order of `relaxed_state`:
      wv0 the ground-state potential, wv1[M] = f_xc rho_M (`xc_fxc_apply`), wv2 the third-order term.
   8. third order: wv2[U, U] = (wv1_{rho0 + e rho_U}[U] - wv1_{rho0 - e rho_U}[U]) / (2 e), e = `xc3_step` / max |U|.
 
-Refused (NotImplementedError): triplets, range-separated hybrids (no long-range derivative integrals), PCM, sharded or direct-mode
+Refused (NotImplementedError): triplets, the references of row "TDA/TDDFT gradients" of `reference.SUPPORT`, sharded or direct-mode
 engines, a state above nstates, unconverged roots.
 """
 import time
@@ -40,6 +40,7 @@ import numpy as np
 import torch
 
 from .grad import _GradScanner, _add_xc_force, assemble, log_gradient, xc_force
+from .reference import require
 
 ALGORITHMS = ("onepass", "loop")
 FOLLOW_MIN_OVERLAP = 0.7   # the scanner warns when the followed state overlaps the previous one by less than this
@@ -217,14 +218,9 @@ def relaxed_state(td, x, y, conv_tol=1e-9, max_cycle=60, xc3_step=1e-3, log=None
 
 # ---- driver -----------------------------------------------------------------------------------------------------------------------
 def _refuse(td):
-    mf = td._scf
     if not td.singlet:
         raise NotImplementedError("TDA/TDDFT gradients: triplet states are not implemented (closed-shell singlets only)")
-    if td._omega != 0.0:
-        raise NotImplementedError(f"TDA/TDDFT gradients: not implemented for the range-separated hybrid {mf.xc} (no long-range "
-                                  "derivative integrals)")
-    if getattr(mf, "_pcm", False) or getattr(mf, "with_solvent", None) is not None:
-        raise NotImplementedError("TDA/TDDFT gradients: PCM-wrapped references are not implemented")
+    require(td._scf, "TDA/TDDFT gradients")
 
 
 class Gradients:

@@ -1,13 +1,11 @@
 """`pyscf.tdscf` (templates/calculate_uv_spectrum.py:92-158): closed-shell TDA / TDHF / TDDFT on the MI355X engine.
 Imported on its own (`from pyscf import tdscf`), not by `import pyscf`."""
+from mi355scf.reference import require
 from . import rhf, rks  # noqa: F401
 
 
 def _check(mf):
-    if not getattr(mf, "_spin_restricted", True):
-        raise NotImplementedError("tdscf: UHF/UKS references are not supported (closed-shell RHF/RKS only)")
-    if getattr(mf, "_pcm", False):
-        raise NotImplementedError("tdscf: excited states with PCM solvation are not implemented")
+    require(mf, "tdscf")
     return mf
 
 
