@@ -5052,6 +5052,12 @@ struct BeckeArgs {
     double *w;
 };
 
+// One step f(x) = (3 - x^2) x / 2 of the Becke polynomial, written as x + x (1 - x^2) / 2 with 1 - x^2 from one fma (the product is
+// not rounded).  From anywhere within 2^-27 of +-1 this lands on +-1 exactly, so a point on a nucleus or on an interatomic axis
+// (mu = +-1 up to the rounding of rsqrt) gets cell functions of exactly 0 and 1.  (3.0 - x * x) * x * 0.5 does not: at
+// x = 1 - 2^-53 the difference 3 - x^2 rounds to 2, the step returns x, and the cell function stays at 2^-54.
+__device__ __forceinline__ double becke_step(double x) { return fma(0.5 * x, fma(-x, x, 1.0), x); }
+
 // One thread per grid point.  P_i = prod_{j != i} s(mu_ij), 3x iterated Becke polynomial, with
 // mu' = mu + a_ij (1 - mu^2); w = vol * P_owner / sum_i P_i.
 __global__ __launch_bounds__(256) void becke_weights_kernel(BeckeArgs A)
@@ -5075,9 +5081,7 @@ __global__ __launch_bounds__(256) void becke_weights_kernel(BeckeArgs A)
             double ax = sh[3 * i] - sh[3 * j], ay = sh[3 * i + 1] - sh[3 * j + 1], az = sh[3 * i + 2] - sh[3 * j + 2];
             double mu = (ri - rj) * rsqrt(ax * ax + ay * ay + az * az);
             mu = mu + A.adj[i * A.natm + j] * (1.0 - mu * mu);
-            mu = (3.0 - mu * mu) * mu * 0.5;
-            mu = (3.0 - mu * mu) * mu * 0.5;
-            mu = (3.0 - mu * mu) * mu * 0.5;
+            mu = becke_step(becke_step(becke_step(mu)));
             p *= 0.5 * (1.0 - mu);
         }
         psum += p;
@@ -5089,7 +5093,10 @@ __global__ __launch_bounds__(256) void becke_weights_kernel(BeckeArgs A)
 extern "C" int mi_grid_becke(mi_ctx *c, const double *d_coords, const int32_t *d_atom_of, const double *d_vol, int64_t ng,
                              const double *d_adjust, double *d_weights, void *stream)
 {
-    if (!c || !d_coords || !d_atom_of || !d_vol || !d_adjust || !d_weights) return fail("mi_grid_becke: null argument");
+    if (!c) return fail("mi_grid_becke: null context");
+    if (ng < 0) return fail("mi_grid_becke: negative number of grid points");
+    if (ng == 0) return 0;   // nothing to write (a zero-sized grid would be a launch error)
+    if (!d_coords || !d_atom_of || !d_vol || !d_adjust || !d_weights) return fail("mi_grid_becke: null argument");
     if (c->natm > MAXATM_LDS) return fail("mi_grid_becke: too many atoms");
     HIPCHK(hipSetDevice(c->device));
     std::vector<double> xyz(c->natm * 3);
@@ -5159,9 +5166,7 @@ __global__ __launch_bounds__(256) void becke_grad_kernel(BeckeGradArgs A)
             double ax = sh[3 * i] - sh[3 * j], ay = sh[3 * i + 1] - sh[3 * j + 1], az = sh[3 * i + 2] - sh[3 * j + 2];
             double mu = (ri - rj) * rsqrt(ax * ax + ay * ay + az * az);
             mu = mu + A.adj[i * natm + j] * (1.0 - mu * mu);
-            mu = (3.0 - mu * mu) * mu * 0.5;
-            mu = (3.0 - mu * mu) * mu * 0.5;
-            mu = (3.0 - mu * mu) * mu * 0.5;
+            mu = becke_step(becke_step(becke_step(mu)));
             p *= 0.5 * (1.0 - mu);
         }
         psum += p;
@@ -5189,9 +5194,7 @@ __global__ __launch_bounds__(256) void becke_grad_kernel(BeckeGradArgs A)
             const double mu = (rc - rj) * rinv;
             const double a = A.adj[C * natm + j];
             const double nu = mu + a * (1.0 - mu * mu);
-            const double f1 = (3.0 - nu * nu) * nu * 0.5;
-            const double f2 = (3.0 - f1 * f1) * f1 * 0.5;
-            const double f3 = (3.0 - f2 * f2) * f2 * 0.5;
+            const double f1 = becke_step(nu), f2 = becke_step(f1), f3 = becke_step(f2);
             const double sp = -1.6875 * (1.0 - f2 * f2) * (1.0 - f1 * f1) * (1.0 - nu * nu);   // s'(nu) = -1/2 (3/2)^3 prod (1 - f_k^2)
             const double sCj = 0.5 * (1.0 - f3), sjC = 0.5 * (1.0 + f3);
             const double qj = ((j == own ? qo : 0.0) - qz) * (live ? cell[(int64_t)j * A.ldc] : 0.0);
@@ -5385,13 +5388,17 @@ __global__ __launch_bounds__(256) void eval_ao_kernel(AoArgs A)
 
 extern "C" int mi_eval_ao(mi_ctx *c, const double *d_coords, int64_t ng, int deriv, double *d_ao, void *stream)
 {
-    if (c && check_orbital_lmax(c, "mi_eval_ao")) return -1;
-    if (!c || !d_coords || !d_ao) return fail("mi_eval_ao: null argument");
+    if (!c) return fail("mi_eval_ao: null context");
+    if (check_orbital_lmax(c, "mi_eval_ao")) return -1;
+    if (ng < 0) return fail("mi_eval_ao: negative number of grid points");
+    if (deriv < 0 || deriv > 2) return fail("mi_eval_ao: deriv must be 0, 1 or 2 (got %d)", deriv);
+    if (ng == 0) return 0;   // nothing to write (a zero-sized grid would be a launch error)
+    if (!d_coords || !d_ao) return fail("mi_eval_ao: null argument");
     HIPCHK(hipSetDevice(c->device));
     AoArgs A{basis_dev(c)};
     A.deriv = deriv; A.coords = d_coords; A.ng = ng; A.ao = d_ao;
     const dim3 grid((unsigned)((ng + 255) / 256)), block(256);
-    if (deriv <= 0) hipLaunchKernelGGL(eval_ao_kernel<0>, grid, block, 0, (hipStream_t)stream, A);
+    if (deriv == 0) hipLaunchKernelGGL(eval_ao_kernel<0>, grid, block, 0, (hipStream_t)stream, A);
     else if (deriv == 1) hipLaunchKernelGGL(eval_ao_kernel<1>, grid, block, 0, (hipStream_t)stream, A);
     else hipLaunchKernelGGL(eval_ao_kernel<2>, grid, block, 0, (hipStream_t)stream, A);
     HIPCHK(hipGetLastError());
@@ -5421,7 +5428,10 @@ __global__ __launch_bounds__(256) void xc_rho_kernel(const double *ao, const dou
 
 extern "C" int mi_xc_rho(mi_ctx *c, const double *d_ao, const double *d_C, int64_t ng, int deriv, double *d_rho, void *stream)
 {
-    if (!c || !d_ao || !d_C || !d_rho) return fail("mi_xc_rho: null argument");
+    if (!c) return fail("mi_xc_rho: null context");
+    if (ng < 0) return fail("mi_xc_rho: negative number of grid points");
+    if (ng == 0) return 0;   // nothing to write (a zero-sized grid would be a launch error)
+    if (!d_ao || !d_C || !d_rho) return fail("mi_xc_rho: null argument");
     hipLaunchKernelGGL(xc_rho_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_ao, d_C, c->nao, ng, deriv, d_rho);
     HIPCHK(hipGetLastError());
     return 0;
@@ -5610,7 +5620,11 @@ extern "C" int mi_nystrom_warm(mi_ctx *c, const double *d_Zt, const int *d_info,
 
 extern "C" int mi_xc_rho_mo(mi_ctx *c, const double *d_psi, int nocc, int64_t ng, int deriv, double *d_rho, double *d_tau, void *stream)
 {
-    if (!c || !d_psi || !d_rho || nocc < 1 || (d_tau && !deriv)) return fail("mi_xc_rho_mo: bad argument");
+    if (!c) return fail("mi_xc_rho_mo: null context");
+    if (ng < 0) return fail("mi_xc_rho_mo: negative number of grid points");
+    if (nocc < 1 || (d_tau && !deriv)) return fail("mi_xc_rho_mo: bad argument");
+    if (ng == 0) return 0;   // nothing to write (a zero-sized grid would be a launch error)
+    if (!d_psi || !d_rho) return fail("mi_xc_rho_mo: null argument");
     hipLaunchKernelGGL(xc_rho_mo_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_psi, nocc, ng, deriv, d_rho, d_tau);
     HIPCHK(hipGetLastError());
     return 0;

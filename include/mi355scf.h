@@ -284,7 +284,9 @@ int mi_commutator_norm(mi_ctx *ctx, const double *d_M, double *d_E, double *d_pa
 /* Becke fuzzy-cell weights for `ng` atom-centred grid points: d_coords[ng][3] (Bohr), d_atom_of[ng]
  * (owning atom), d_vol[ng] (radial x angular volume element), d_adjust[natm][natm] (Treutler radius
  * adjustment a_ij, device) -> d_weights[ng].  Replaces libdft VXCgen_grid [MEM], reached from
- * dft.RKS(mol) -> Grids.build (templates/calculate_energy.py:148,163; optimize_geometry.py:72,86). */
+ * dft.RKS(mol) -> Grids.build (templates/calculate_energy.py:148,163; optimize_geometry.py:72,86).
+ * Sizes, here and in mi_eval_ao / mi_xc_rho / mi_xc_rho_mo (the convention of mi_xc_aow): ng == 0 returns 0 without a
+ * launch and leaves the output untouched; ng < 0 is an error ("negative"). */
 int mi_grid_becke(mi_ctx *ctx, const double *d_coords, const int32_t *d_atom_of, const double *d_vol,
                   int64_t ng, const double *d_adjust, double *d_weights, void *stream);
 
@@ -297,7 +299,7 @@ int mi_grid_becke_grad(mi_ctx *ctx, const double *d_coords, const int32_t *d_ato
                        int64_t ng, const double *d_adjust, double *d_out, void *stream);
 
 /* AO values (deriv=0), +gradient (deriv=1), +second derivatives xx,xy,xz,yy,yz,zz (deriv=2, for the XC
- * nuclear gradient) on grid points: d_ao[(1|4|10)][nao][ng].
+ * nuclear gradient) on grid points: d_ao[(1|4|10)][nao][ng]; any other deriv is an error.
  * Replaces libdft GTOval_sph_deriv1 / gpu4pyscf GDFTeval_gto [MEM] (numint.eval_ao). */
 int mi_eval_ao(mi_ctx *ctx, const double *d_coords, int64_t ng, int deriv, double *d_ao, void *stream);
 
