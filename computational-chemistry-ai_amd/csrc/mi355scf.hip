@@ -4897,10 +4897,13 @@ extern "C" int mi_diis_dots_dev(mi_ctx *c, const double *d_hist_e, const double 
 // CDIIS without the host: one small workgroup adds the Gram-row partials of the newest error vector in index order, updates the
 // device-resident B matrix (row and column `slot` of [space][space]) and solves Pulay's (m+1) x (m+1) system
 //   [0 1^T; 1 B] [lambda; c] = [1; 0]
-// by Gaussian elimination with partial pivoting (what LAPACK's dgesv behind numpy.linalg.solve does in PySCF's
-// scf.diis -> lib.diis [MEM]); c[0..m) goes to d_coef for diis_combine_dev_kernel.  A singular or non-finite system (error
-// vectors exactly zero) falls back to c = e_slot, i.e. no extrapolation.  Same instruction sequence on every rank of a
-// sharded run, so the coefficients are bit-identical there.
+// by Gaussian elimination with partial pivoting on the rows (the largest |entry| of the column, the first row on ties; row
+// updates are fused multiply-adds), then back substitution; c[0..m) goes to d_coef for diis_combine_dev_kernel.  There is no
+// rank guard: the only fallback, c = e_slot (no extrapolation), is taken when a pivot is exactly zero or not finite or a
+// back-substituted value is not finite -- error vectors exactly zero, a history holding the same pair twice to the bit, a NaN
+// or Inf among the partials.  A merely ill-conditioned history is solved as it stands, backward stably (the
+// contract B1-B5 and what tests/test_gpu_diis_chain.py measured).  Same instruction sequence on every rank of a sharded run,
+// so the coefficients are bit-identical there.
 #define DIIS_MAXM 16
 // value of `x` on lane `l` (wave-uniform l) through v_readlane: no LDS crossbar trip, unlike __shfl with a runtime lane
 __device__ __forceinline__ double lane_bcast(double x, int l)

@@ -3,6 +3,8 @@
 import numpy as np
 import pytest
 
+import diis_reference as dr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -37,7 +39,9 @@ def test_diis_solve_matches_numpy_and_updates_the_gram_matrix():
         assert abs(got.sum() - 1.0) < 1e-9
         worst = max(worst, np.abs(got - ref).max() / max(1.0, np.abs(ref).max()) / max(1.0, np.linalg.cond(A) * 1e-16 / 1e-9))
         Bn = Bd.cpu().numpy()
-        assert np.allclose(Bn[:m, slot], Bfull[:m, slot], rtol=1e-13, atol=0) and np.allclose(Bn[slot, :m], Bfull[slot, :m], rtol=1e-13, atol=0)
+        want = dr.sequential_sum(part[:m])                   # the 16 partials added in index order: equal to the bit
+        assert np.array_equal(Bn[:m, slot], want) and np.array_equal(Bn[slot, :m], want)
+        assert np.allclose(want, Bfull[:m, slot], rtol=1e-13, atol=0)
     assert worst < 1e-9, worst
     # singular system (all error vectors zero): no extrapolation, the newest Fock matrix alone
     Bd = torch.zeros(space, space, dtype=torch.float64, device="cuda")
